@@ -2,6 +2,16 @@
 """bench.py -- count+solve hot path on synthetic MRF reads, one process per GPU.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c1|c5s|c5] [--mode strong|weak]
+                    [--dump-outputs DIR] [--full]
+
+A plain run does what the headline figure needs and nothing else: it writes the job's files, ingests them, warms up,
+times K steps and prints the JSON line (`metric`, `value`, `unit`, `ms_per_step`, ... and a short `config`).
+--dump-outputs DIR: after the timed steps, the tables that the last timed step handed over -- per-class read counts and
+bases, theta per isoform, log-likelihood per event, as lsq_gathered_unpack returns them -- go to DIR/<name>.npy as
+float64 (the inputs are deterministic in the seed, so two builds can be compared output for output).
+--full: everything below as well -- kernel durations and the roofline, the EM-placement and wide-record legs, the
+end-to-end legs, the live HBM-traffic measurement, the checks of the step's tables against the first count, the
+`cpu_baseline`, and with N > 1 the configs[4] leg.
 
 The job: BASELINE.json configs[2] (default workload c3: 100 M synthetic 100-bp MRF reads over 50 k mixed local
 events on 24 chromosomes).  Rank 0 writes the job's files once (annotation + MRF text, deterministic in the
@@ -84,6 +94,27 @@ def shared_dir(tag):
     return os.path.join(base, "lsq_bench_%s_%s%s" % (os.environ.get("USER", "u"), tag, os.environ.get("LSQ_BENCH_TAG", "")))
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, arrays):
+    """arrays {name: ndarray} -> d/<name>.npy as float64 (u64 counters are exact there below 2^53).  Above DUMP_LIMIT_BYTES in
+    all, every array keeps its share of the limit as a fixed, seeded sample of its flattened entries, in index order, with the
+    indices beside it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    arrays = {k: np.asarray(v).astype(np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, DUMP_LIMIT_BYTES * v.size // total // 2)        # (half: the indices take the other half)
+            if keep < v.size:
+                idx = np.sort(np.random.default_rng(12345).choice(v.size, keep, replace=False))
+                np.save(os.path.join(d, name + "_index.npy"), idx.astype(np.float64))
+                v = v.reshape(-1)[idx]
+        np.save(os.path.join(d, name + ".npy"), v)
+
+
 def measure_traffic_live(wl_name, timeout=300):
     """HBM bytes per launch of the count kernel, measured now: two short child runs of this script under `rocprofv3 --pmc`
     (FETCH_SIZE, then WRITE_SIZE: separate passes, counters only, no trace domain), corrected as MI355X_MICROARCH.md's HBM section
@@ -101,7 +132,7 @@ def measure_traffic_live(wl_name, timeout=300):
         for ctr in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(base, ctr)
             cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", d, "--", sys.executable, os.path.abspath(__file__),
-                   "--workload", wl_name, "--steps", "5", "--warmup", "1", "--no-e2e", "--cpu-sample", "0", "--no-traffic"]
+                   "--workload", wl_name, "--steps", "5", "--warmup", "1", "--full", "--no-e2e", "--cpu-sample", "0", "--no-traffic"]
             try:
                 p = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, timeout=timeout)
             except subprocess.TimeoutExpired:
@@ -143,7 +174,11 @@ def main():
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end legs")
     ap.add_argument("--no-c5", action="store_true", help="N > 1: skip the configs[4] leg (config.c5_*)")
     ap.add_argument("--no-traffic", action="store_true", help="skip the live HBM-traffic measurement (two short child runs under rocprofv3 --pmc)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the tables of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--full", action="store_true", help="also every figure and check beyond the headline (see the module docstring)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     # stdout carries the one JSON line and nothing else: libraries that greet on stdout (RCCL's version banner, gloo's
     # connection notes) are sent to stderr for the duration
@@ -185,7 +220,7 @@ def main():
     out = run_workload(env, a, a.workload, True)
     # N > 1, default job: the same measurement on BASELINE configs[4] (1 B reads: a millisecond of count work per step on one
     # GPU) rides along under config.c5_* -- strong scaling of the 0.13 ms c3 job is bounded by the fixed terms of a step
-    if strong and a.workload == "c3" and not a.no_c5:
+    if strong and a.workload == "c3" and not a.no_c5 and a.full:
         # The parsed line is c3's and must come out whatever the c5 leg does: a watchdog per rank ends the process after
         # LSQ_BENCH_C5_LIMIT seconds (default 300) -- rank 0 prints the c3 line with c5_error first -- and an exception on one
         # rank (which leaves the others inside a collective) is reported the same way.
@@ -295,7 +330,8 @@ def setup_lsq_comm(env):
 
 def run_workload(env, a, wl_name, primary):
     """One workload, measured as the module docstring says; returns the JSON line as a dict on rank 0 (None elsewhere).
-    primary: the run's own workload (end-to-end legs, cpu_baseline); otherwise only the timed loop and what describes it."""
+    primary: the run's own workload (end-to-end legs, cpu_baseline); otherwise only the timed loop and what describes it.
+    Without --full only the job's files, the ingest, the timed loop and the headline (the module docstring)."""
     import numpy as np
     import torch
     import torch.distributed as dist
@@ -308,8 +344,9 @@ def run_workload(env, a, wl_name, primary):
     if scale != 1:
         W["n_reads"], W["n_events"] = max(1000, int(W["n_reads"] * scale)), max(10, int(W["n_events"] * scale))
         W["desc"] += " -- SCALED by %g for a rehearsal" % scale
-    no_e2e = a.no_e2e or not primary
-    cpu_sample = a.cpu_sample if primary else 0
+    full = a.full
+    no_e2e = a.no_e2e or not primary or not full
+    cpu_sample = a.cpu_sample if primary and full else 0
     types = W["types"] or L.EVENT_TYPES
     job_rank = 0 if (strong or world == 1) else rank            # weak mode: a job of its own per rank
     spec = L.SynthSpec(W["seed"] + 1000 * job_rank, W["n_events"], W["n_reads"], W["R"], W["n_chrom"], types, W.get("zipf", False))
@@ -441,7 +478,7 @@ def run_workload(env, a, wl_name, primary):
         e2e["e2e_from_text_table_matches_cli"] = hashlib.sha256(table.encode()).hexdigest() == e2e.get("e2e_cli_solve_table_sha256")
     bounds = [(0, n_ev)]
     n1_same_box = None
-    if strong:
+    if strong and full:
         # N > 1: the whole job is resident on every GPU at this point (the pre-pass count that weighs the slices).  Twenty unsharded
         # steps of it -- count + EM + pack, no gather -- give the one-GPU step time of THIS box, so the line's speed-up does not
         # rest on another box's one-GPU run (boxes differ by ~5 %).  Every rank runs them (same work everywhere); rank 0's counts.
@@ -604,6 +641,53 @@ def run_workload(env, a, wl_name, primary):
     fence()
     elapsed = time.perf_counter() - t0
     last = (a.steps - 1) & 1
+    if primary and rank == 0 and a.dump_outputs:
+        # what the last timed step handed over: its packed records (gathered over the ranks when the loop gathers), unpacked
+        src = gathered[last] if in_loop_gather else blocks[last]
+        tables = ev.gathered_unpack(bounds if strong else [(0, n_ev)], src.cpu().numpy().view(np.uint64), stride)
+        dump_outputs(a.dump_outputs, dict(zip(("class_counts", "class_bases", "theta", "loglik"), tables)))
+
+    if not full:
+        out = None
+        tmax = torch.tensor([elapsed], dtype=torch.float64, device="cpu" if on_host else dev)
+        retained = torch.tensor([float(job_retained), float(job_blocks)], dtype=torch.float64, device="cpu" if on_host else dev)
+        if world > 1:
+            dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+            if not strong:
+                dist.all_reduce(retained, op=dist.ReduceOp.SUM)      # weak: a job per rank
+        elapsed = float(tmax.item())
+        total_retained, total_blocks = (float(x) for x in retained.cpu().numpy())
+        if rank == 0:
+            out = {
+                "metric": "MRF reads/sec through count+solve",
+                "value": total_retained * a.steps / elapsed,
+                "unit": "reads/s",
+                "n_gpus": world,
+                "steps": a.steps,
+                "warmup": a.warmup,
+                "ms_per_step": 1e3 * elapsed / a.steps,
+                "higher_is_better": True,
+                "scaling": "strong" if strong else "weak",
+                "vs_baseline": None,
+                "dtype": "int32 coordinates / u64 counters (count), f64 (EM)",
+                "data": "synthetic",
+                "config": {
+                    "workload": W["desc"] + ("; BASELINE configs[3]: the same job sharded by event index over %d GPUs" % world if strong and wl_name == "c3" else ""),
+                    "events": n_ev * (1 if strong or world == 1 else world),
+                    "mrf_reads": float(W["n_reads"] * (1 if strong or world == 1 else world)),
+                    "retained_reads": total_retained, "retained_blocks": total_blocks,
+                    "generate_s": t_gen, "ingest_from_text_s": t_ingest,
+                    "gather_through": (None if not in_loop_gather else "liblesseq_rccl lsq_gather" if use_lsq_gather else "torch.distributed all_gather_into_tensor"),
+                    "note": "plain run: the timed loop only; --full adds kernel durations, roofline, end-to-end legs, checks and cpu_baseline",
+                },
+            }
+        ctx.synchronize()
+        ctx.close()
+        if world > 1:
+            dist.barrier()
+        if writer:
+            shutil.rmtree(tmp, ignore_errors=True)
+        return out
 
     # Kernel durations, right after the timed loop, with the library's HIP events switched on (the
     # event records of a step cost ~25 us of queue time, so the timed loop runs without them).
