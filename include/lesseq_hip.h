@@ -419,7 +419,7 @@ int lsq_format_solve(const lsq_events *e, int n_methods, const uint64_t *class_c
 void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
- * "count", "solve" or "classify".  stdout text is returned in *out_text (malloc'd), the
+ * "count", "solve", "classify" or "test_as" (bin/Test_AS.r; lsq_as_* below).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -428,6 +428,53 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
  * teardown of several gigabytes of HBM takes (0.1-0.2 s of a 0.7 s run); LSQ_CLI_TEARDOWN=1 in the environment keeps
  * the orderly way.  Not for use inside a host process: call lsq_cli_run there. */
 int lsq_cli_main(const char *tool, int argc, const char *const *argv);
+
+/* ------------------------------------------------------------------------------------
+ * Differential splicing tests: step 4 of the pipeline, bin/Test_AS.r ("Differential splicing tests")
+ * ------------------------------------------------------------------------------------ */
+
+/* Device group (HIP, FP64).  Host arrays in and out; NaN stands for R's NA.  Each call allocates its device buffers on
+ * the context's device, runs on the context's stream and frees them before it returns. */
+/* Replaces Test_AS.r:34-47: fisher.test(two.sided) per 2x2 table, cells [n][4] = A B C D (R's matrix(c(A,B,C,D), 2)),
+ * rounded half-to-even.  A table with an NA, negative, infinite or above-2^40 cell gets p = NA (R stops the script). */
+int lsq_as_fisher(lsq_ctx *c, uint64_t n_tables, const double *cells /* [n][4]: A B C D */, double *p);
+/* Replaces Test_AS.r:89-131: per row the Poisson glm log(mu) ~ tissue + rep + offset and ~ rep + offset (tissue, rep
+ * numeric; y = round(count) + 1, offset = log(round(total) + 1)), lrtest's statistic and chi-square p.  NA in a cell
+ * (the first: the script's own rule; any other, or a negative or infinite one: a divergence) gives stat = p = NA; a
+ * non-finite log-likelihood stat = 0, p = 1.  count / total: [n][n1+n2], condition 1 first.  1 <= n1, n2 <= 4096. */
+int lsq_as_lrt(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count, const double *total /* [n][n1+n2] each */,
+               double *stat, double *p);
+/* Replaces Test_AS.r:162-175: diff = mean(condition 1) - mean(condition 2), p = wilcox.test(x, y)'s (two-sided,
+ * correct = TRUE; non-finite values dropped; an empty group gives NA, the script's try-error).  value: [n][n1+n2]. */
+int lsq_as_wilcox(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *value /* [n][n1+n2] */, double *diff, double *p);
+/* Replaces Test_AS.r:45,129,173: p.adjust(p, "bonferroni") and p.adjust(p, "BH") over the non-NA values (NA stays NA;
+ * with at most one non-NA value p comes back unchanged).  LSQ_E_ARG for a negative p-value. */
+int lsq_as_adjust(lsq_ctx *c, uint64_t n, const double *p, double *p_bonferroni, double *p_bh);
+
+/* Host-only: the inputs of one test ("fisher", "lrt", "wilcox"), read and checked (no GPU touched).
+ * lsq_as_read_matrix reads the script's own files -- a header line, then an ID and the same number of values per line;
+ * a value is a number, NA / NaN / nan / -nan or Inf / -Inf / inf / -inf: "fisher" one file of 2 value columns, rows
+ * taken in pairs (the ID is the second row's, an odd last row is ignored); "lrt" the count_one and count_all files of
+ * n1+n2 columns with the same IDs in the same order; "wilcox" one file of n1+n2 columns.
+ * lsq_as_read_tables reads this project's tables, one per sample: count tables for "fisher" (two) and "lrt", solve
+ * tables for "wilcox" (n1+n2 each).  With M read files a count table has M+3 columns and a solve table M+5; the form ID
+ * is column M+2, the event total the sum of columns 2..M+1, the value column M+3.  "fisher" takes the events (runs of
+ * one gene name) with exactly two forms, cells as above with the second form's ID (lsq_as_input_left_out: the others).
+ * Input errors (LSQ_E_IO, LSQ_E_PARSE, LSQ_E_ARG) name the file and line: a ragged row, a duplicate ID, a field that is
+ * not a number, mismatched IDs, n1+n2 not the number of columns or tables, a negative count for "fisher" or "lrt". */
+typedef struct lsq_as_input lsq_as_input;
+int lsq_as_read_matrix(const char *test, int n_paths, const char *const *paths, int n1, int n2, lsq_as_input **out);
+int lsq_as_read_tables(const char *test, int n_paths, const char *const *paths, int n1, int n2, lsq_as_input **out);
+void lsq_as_input_free(lsq_as_input *in);
+uint64_t lsq_as_input_rows(const lsq_as_input *in);
+int lsq_as_input_columns(const lsq_as_input *in);                 /* 4 for "fisher", n1+n2 otherwise */
+const char *lsq_as_input_id(const lsq_as_input *in, uint64_t row);
+const double *lsq_as_input_values(const lsq_as_input *in);        /* [rows][columns]: cells, counts or values */
+const double *lsq_as_input_totals(const lsq_as_input *in);        /* "lrt": [rows][columns] totals; NULL otherwise */
+uint64_t lsq_as_input_left_out(const lsq_as_input *in);
+/* R's as.character(v): 15 significant digits, trailing zeros dropped, fixed unless scientific is strictly shorter
+ * ("1e-04", "0.001", "1e+05", "123456"), NaN as "NA".  32 bytes always suffice. */
+int lsq_as_format_number(double v, char *buf, size_t cap);
 
 /* ------------------------------------------------------------------------------------
  * Synthetic workload; deterministic in (seed, sizes).  Host-only.

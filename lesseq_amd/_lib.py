@@ -151,6 +151,20 @@ _sig("lsq_format_count", C.c_int, vp, C.c_int, P(u64), P(vp))
 _sig("lsq_format_solve", C.c_int, vp, C.c_int, P(u64), P(u64), P(C.c_double), P(C.c_double), P(C.c_double), P(vp))
 _sig("lsq_cli_run", C.c_int, cs, C.c_int, P(cs), P(vp))
 _sig("lsq_synth_write", C.c_int, P(SynthSpecStruct), cs, cs, C.c_int)
+_sig("lsq_as_fisher", C.c_int, vp, u64, P(C.c_double), P(C.c_double))
+_sig("lsq_as_lrt", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_as_wilcox", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_as_adjust", C.c_int, vp, u64, P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_as_read_matrix", C.c_int, cs, C.c_int, P(cs), C.c_int, C.c_int, P(vp))
+_sig("lsq_as_read_tables", C.c_int, cs, C.c_int, P(cs), C.c_int, C.c_int, P(vp))
+_sig("lsq_as_input_free", None, vp)
+_sig("lsq_as_input_rows", u64, vp)
+_sig("lsq_as_input_columns", C.c_int, vp)
+_sig("lsq_as_input_id", cs, vp, u64)
+_sig("lsq_as_input_values", P(C.c_double), vp)
+_sig("lsq_as_input_totals", P(C.c_double), vp)
+_sig("lsq_as_input_left_out", u64, vp)
+_sig("lsq_as_format_number", C.c_int, C.c_double, C.c_char_p, C.c_size_t)
 _sig("lsq_synth_reads", C.c_int, P(SynthSpecStruct), vp, C.c_int, P(vp))
 
 

@@ -479,7 +479,7 @@ def format_solve(events, cnt, bases, theta, logll, total_read_bases):
 
 
 def cli_run(tool, argv):
-    """Runs count / solve / classify in-process with the reference's argv (without argv[0]).
+    """Runs count / solve / classify / test_as in-process with the reference's argv (without argv[0]).
     Returns (exit_status, stdout_text).  The log goes to this process's stderr."""
     full = [b"lsq"] + [_b(a) for a in argv]
     arr = (cs * len(full))(*full)

@@ -1,0 +1,629 @@
+// Differential splicing tests (step 4 of the pipeline, bin/Test_AS.r) on the device: Fisher's exact test per 2x2 table, the
+// Poisson log-linear model + likelihood-ratio test per form, the Wilcoxon rank-sum test per form, and the Bonferroni / BH
+// corrections (R's p.adjust).  FP64 throughout; NaN stands for R's NA.  The rules each kernel follows are spelled out in
+// DESIGN.md ("Differential splicing tests"); the host side (readers, formatter, the test_as executable) is lsq_as.cpp.
+//
+//   lsq_as_fisher_kernel   one wave per table: the hypergeometric pmf walked outward from its mode, 64 terms a step
+//   lsq_as_lrt_kernel      one lane per row: two IRLS fits (R's glm.fit), normal equations in registers, Cholesky
+//   lsq_as_wilcox_kernel   one lane per row: W and the tie groups by counting over the row; exact tables from the host
+//   correction             NA compaction (lsq_scan.hpp, flag mode), stable LSD radix sort of (p bits, index), reverse min-scan
+#include <cfloat>
+
+#include "lsq_device.hpp"
+#include "lsq_scan.hpp"
+
+namespace {
+
+constexpr double FISHER_REL_ERR = 1.0 + 1e-7;   // fisher.test's relErr
+constexpr double LOG_FLOOR = -746.0;            // exp() of anything below is 0 in double
+constexpr double AS_MAX_CELL = 1099511627776.0; // 2^40
+constexpr int GLM_MAXIT = 25;                   // glm.control()
+constexpr double GLM_EPS = 1e-8;
+constexpr int WILCOX_EXACT_MAX = 50;            // wilcox.test: exact when both groups have fewer values, and no ties
+
+__device__ inline double wave_incl_sum(double v) {
+	const unsigned lane = threadIdx.x & 63u;
+#pragma unroll
+	for (unsigned d = 1; d < 64; d <<= 1) {
+		const double o = __shfl_up(v, d);
+		if (lane >= d) v += o;
+	}
+	return v;
+}
+
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) v += __shfl_xor(v, d);
+	return v;
+}
+
+// ---- Fisher ---------------------------------------------------------------------------------------------------------
+
+struct Hyper {
+	long long m, n, k, lo, hi, mode;
+	// log d(s+1)/d(s) for lo <= s < hi: one log per term (lgamma differences lose ~1e-8 at counts of 10^6)
+	__device__ double step(long long s) const {
+		return log(((double)(m - s) / (double)(s + 1)) * ((double)(k - s) / (double)(n - k + s + 1)));
+	}
+};
+
+// floor((k+1)(m+1)/(m+n+2)) exactly: a double estimate, corrected with 128-bit products (no 128-bit division)
+__device__ inline long long hyper_mode(long long m, long long n, long long k) {
+	typedef unsigned __int128 u128;
+	const unsigned long long a = (unsigned long long)(k + 1), b = (unsigned long long)(m + 1), N = (unsigned long long)(m + n + 2);
+	const u128 P = (u128)a * b;
+	long long q = (long long)floor(((double)a * (double)b) / (double)N);
+	if (q < 0) q = 0;
+	while ((u128)(unsigned long long)q * N > P) --q;
+	while ((u128)(unsigned long long)(q + 1) * N <= P) ++q;
+	return q;
+}
+
+// One wave per table (grid-stride over tables).  Every branch below is uniform over the wave.
+__global__ void __launch_bounds__(256) lsq_as_fisher_kernel(const double *cells, unsigned long long n_tables, double *p_out) {
+	const unsigned lane = threadIdx.x & 63u;
+	const unsigned long long waves = (unsigned long long)gridDim.x * (blockDim.x >> 6);
+	for (unsigned long long t = (unsigned long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); t < n_tables; t += waves) {
+		double c[4];
+		bool na = false;
+#pragma unroll
+		for (int q = 0; q < 4; ++q) {
+			c[q] = rint(cells[t * 4 + q]);
+			if (!(c[q] >= 0.0 && c[q] <= AS_MAX_CELL)) na = true;     // NA, negative, infinite or beyond 2^40
+		}
+		if (na) { if (lane == 0) p_out[t] = NAN; continue; }
+		Hyper h;
+		const long long A = (long long)c[0], B = (long long)c[1], C = (long long)c[2], D = (long long)c[3];
+		h.m = A + B; h.n = C + D; h.k = A + C;
+		const long long x = A;
+		h.lo = h.k - h.n > 0 ? h.k - h.n : 0;
+		h.hi = h.k < h.m ? h.k : h.m;
+		h.mode = hyper_mode(h.m, h.n, h.k);
+		if (h.mode < h.lo) h.mode = h.lo;
+		if (h.mode > h.hi) h.mode = h.hi;
+		if (h.lo == h.hi) { if (lane == 0) p_out[t] = 1.0; continue; }
+
+		// log d(x)/d(mode), walking from the mode towards x; below LOG_FLOOR d(x) is 0, as in R, and so is p
+		double Lx = 0.0;
+		bool x_zero = false;
+		if (x != h.mode) {
+			const long long dir = x > h.mode ? 1 : -1, dist = x > h.mode ? x - h.mode : h.mode - x;
+			double carry = 0.0;
+			for (long long j0 = 0;; j0 += 64) {
+				const long long j = j0 + lane + 1, s = h.mode + dir * j;
+				const double term = j <= dist ? (dir > 0 ? h.step(s - 1) : -h.step(s)) : 0.0;
+				const double L = carry + wave_incl_sum(term);
+				if (dist <= j0 + 64) { Lx = __shfl(L, (int)(dist - j0 - 1)); break; }
+				carry = __shfl(L, 63);
+				if (__all(L < LOG_FLOOR)) { x_zero = true; break; }
+			}
+		}
+		if (x_zero) { if (lane == 0) p_out[t] = 0.0; continue; }
+
+		// both sums over the window around the mode where terms are non-zero (the pmf is log-concave: once a whole chunk
+		// is below LOG_FLOOR every term further out is too)
+		const double thr = exp(Lx) * FISHER_REL_ERR;
+		double total = 0.0, num = 0.0;
+		for (int side = 0; side < 2; ++side) {
+			const long long dir = side == 0 ? 1 : -1, limit = side == 0 ? h.hi - h.mode : h.mode - h.lo;
+			double carry = 0.0;
+			for (long long j0 = 0; j0 < limit; j0 += 64) {
+				const long long j = j0 + lane + 1, s = h.mode + dir * j;
+				const bool valid = j <= limit;
+				const double term = valid ? (dir > 0 ? h.step(s - 1) : -h.step(s)) : 0.0;
+				const double L = carry + wave_incl_sum(term);
+				const double e = valid ? exp(L) : 0.0;
+				total += e;
+				if (e <= thr) num += e;
+				carry = __shfl(L, 63);
+				if (__all(!valid || L < LOG_FLOOR)) break;
+			}
+		}
+		total = 1.0 + wave_sum(total);
+		num = (1.0 <= thr ? 1.0 : 0.0) + wave_sum(num);
+		if (lane == 0) p_out[t] = num / total;
+	}
+}
+
+// ---- Poisson log-linear model + LRT -----------------------------------------------------------------------------------
+
+// Columns of a design: the intercept, then tissue (if TISSUE), then rep while columns remain.
+template <int P, bool TISSUE>
+__device__ inline void design_row(double tissue, double rep, double *x) {
+	x[0] = 1.0;
+	if (P >= 2) x[1] = TISSUE ? tissue : rep;
+	if (P >= 3) x[2] = rep;
+}
+
+// A x = b for a symmetric positive definite P x P matrix in packed lower storage (a[i*(i+1)/2 + j], j <= i).
+// false when a pivot is not positive.
+template <int P>
+__device__ inline bool cholesky_solve(const double *a, const double *b, double *x) {
+	double l[P * (P + 1) / 2];
+#pragma unroll
+	for (int i = 0; i < P; ++i) {
+#pragma unroll
+		for (int j = 0; j <= i; ++j) {
+			double s = a[i * (i + 1) / 2 + j];
+#pragma unroll
+			for (int q = 0; q < j; ++q) s -= l[i * (i + 1) / 2 + q] * l[j * (j + 1) / 2 + q];
+			if (i == j) {
+				if (!(s > 0.0)) return false;
+				l[i * (i + 1) / 2 + i] = sqrt(s);
+			} else {
+				l[i * (i + 1) / 2 + j] = s / l[j * (j + 1) / 2 + j];
+			}
+		}
+	}
+	double y[P];
+#pragma unroll
+	for (int i = 0; i < P; ++i) {
+		double s = b[i];
+#pragma unroll
+		for (int q = 0; q < i; ++q) s -= l[i * (i + 1) / 2 + q] * y[q];
+		y[i] = s / l[i * (i + 1) / 2 + i];
+	}
+#pragma unroll
+	for (int i = P - 1; i >= 0; --i) {
+		double s = y[i];
+#pragma unroll
+		for (int q = i + 1; q < P; ++q) s -= l[q * (q + 1) / 2 + i] * x[q];
+		x[i] = s / l[i * (i + 1) / 2 + i];
+	}
+	return true;
+}
+
+// R's glm.fit for family = poisson(log) with an offset: start at mu = y + 0.1, WLS by the normal equations, stop on the
+// relative deviance change or after GLM_MAXIT solves.  y and o lie sample-major (y[j * stride]).  Returns
+// sum(y log mu - mu) at the last iterate (the log-likelihood without its lgamma terms), NaN when a solve fails.
+template <int P, bool TISSUE>
+__device__ double glm_poisson(const double *y, const double *o, unsigned long long stride, int n1, int n) {
+	double a[P * (P + 1) / 2], b[P], beta[P], x[P];
+#pragma unroll
+	for (int q = 0; q < P * (P + 1) / 2; ++q) a[q] = 0.0;
+#pragma unroll
+	for (int q = 0; q < P; ++q) b[q] = 0.0;
+	double dev_old = 0.0;
+	for (int j = 0; j < n; ++j) {
+		const double yj = y[(unsigned long long)j * stride], oj = o[(unsigned long long)j * stride];
+		const double eta = log(yj + 0.1), mu = fmax(exp(eta), DBL_EPSILON);
+		dev_old += 2.0 * (yj * log(yj / mu) - (yj - mu));
+		design_row<P, TISSUE>(j < n1 ? 1.0 : 2.0, (double)(j < n1 ? j + 1 : j - n1 + 1), x);
+		const double z = (eta - oj) + (yj - mu) / mu;
+#pragma unroll
+		for (int r = 0; r < P; ++r) {
+			b[r] += mu * x[r] * z;
+#pragma unroll
+			for (int s = 0; s <= r; ++s) a[r * (r + 1) / 2 + s] += mu * x[r] * x[s];
+		}
+	}
+	for (int it = 0; it < GLM_MAXIT; ++it) {
+		if (!cholesky_solve<P>(a, b, beta)) return NAN;
+		double dev = 0.0;
+#pragma unroll
+		for (int q = 0; q < P * (P + 1) / 2; ++q) a[q] = 0.0;
+#pragma unroll
+		for (int q = 0; q < P; ++q) b[q] = 0.0;
+		for (int j = 0; j < n; ++j) {
+			const double yj = y[(unsigned long long)j * stride], oj = o[(unsigned long long)j * stride];
+			design_row<P, TISSUE>(j < n1 ? 1.0 : 2.0, (double)(j < n1 ? j + 1 : j - n1 + 1), x);
+			double lin = 0.0;
+#pragma unroll
+			for (int r = 0; r < P; ++r) lin += x[r] * beta[r];
+			const double eta = lin + oj, mu = fmax(exp(eta), DBL_EPSILON);
+			dev += 2.0 * (yj * log(yj / mu) - (yj - mu));
+			const double z = (eta - oj) + (yj - mu) / mu;
+#pragma unroll
+			for (int r = 0; r < P; ++r) {
+				b[r] += mu * x[r] * z;
+#pragma unroll
+				for (int s = 0; s <= r; ++s) a[r * (r + 1) / 2 + s] += mu * x[r] * x[s];
+			}
+		}
+		if (fabs(dev - dev_old) / (fabs(dev) + 0.1) < GLM_EPS) break;
+		dev_old = dev;
+	}
+	double ll = 0.0;
+	for (int j = 0; j < n; ++j) {
+		const double yj = y[(unsigned long long)j * stride], oj = o[(unsigned long long)j * stride];
+		design_row<P, TISSUE>(j < n1 ? 1.0 : 2.0, (double)(j < n1 ? j + 1 : j - n1 + 1), x);
+		double lin = 0.0;
+#pragma unroll
+		for (int r = 0; r < P; ++r) lin += x[r] * beta[r];
+		const double mu = fmax(exp(lin + oj), DBL_EPSILON);
+		ll += yj * log(mu) - mu;
+	}
+	return ll;
+}
+
+// One lane per row.  count / total arrive sample-major ([sample][row]) and are turned in place into y = round(count) + 1
+// and the offset log(round(total) + 1) -- each lane rewrites its own column only.
+__global__ void __launch_bounds__(256) lsq_as_lrt_kernel(double *count, double *total, unsigned long long n_rows, int n1, int n2,
+                                                          double *stat_out, double *p_out) {
+	const int n = n1 + n2;
+	const bool aliased = n1 == 1 && n2 == 1;      // rep is constant: R drops it (ranks 2 and 1)
+	for (unsigned long long r = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (unsigned long long)gridDim.x * blockDim.x) {
+		bool na = false;
+		for (int j = 0; j < n; ++j) {
+			const double c = rint(count[(unsigned long long)j * n_rows + r]), tt = rint(total[(unsigned long long)j * n_rows + r]);
+			if (!(c >= 0.0 && c < INFINITY) || !(tt >= 0.0 && tt < INFINITY)) na = true;
+			count[(unsigned long long)j * n_rows + r] = c + 1.0;
+			total[(unsigned long long)j * n_rows + r] = log(tt + 1.0);
+		}
+		if (na) { stat_out[r] = NAN; p_out[r] = NAN; continue; }
+		const double *y = count + r, *o = total + r;
+		double lf, lr;
+		if (aliased) {
+			lf = glm_poisson<2, true>(y, o, n_rows, n1, n);
+			lr = glm_poisson<1, false>(y, o, n_rows, n1, n);
+		} else {
+			lf = glm_poisson<3, true>(y, o, n_rows, n1, n);
+			lr = glm_poisson<2, false>(y, o, n_rows, n1, n);
+		}
+		const double stat = 2.0 * fabs(lf - lr);
+		if (!isfinite(lf) || !isfinite(lr) || isnan(stat)) { stat_out[r] = 0.0; p_out[r] = 1.0; continue; }   // Test_AS.r:112-114
+		stat_out[r] = stat;
+		p_out[r] = erfc(sqrt(stat / 2.0));      // upper chi-square tail, one degree of freedom
+	}
+}
+
+// ---- Wilcoxon rank-sum --------------------------------------------------------------------------------------------------
+
+// mean() of R: the sum over n, then the mean of the residuals added (in double here; R sums in long double)
+__device__ inline double r_mean(const double *v, unsigned long long stride, int first, int cnt) {
+	double s = 0.0;
+	for (int j = first; j < first + cnt; ++j) s += v[(unsigned long long)j * stride];
+	s /= cnt;
+	if (isfinite(s)) {
+		double t = 0.0;
+		for (int j = first; j < first + cnt; ++j) t += v[(unsigned long long)j * stride] - s;
+		s += t / cnt;
+	}
+	return s;
+}
+
+// One lane per row, values sample-major.  exact_off[nx * WILCOX_EXACT_MAX + ny]: where the lower CDF of W for (nx, ny)
+// starts in exact_cdf (nx*ny + 1 values), -1 when the host built none.
+__global__ void __launch_bounds__(256) lsq_as_wilcox_kernel(const double *value, unsigned long long n_rows, int n1, int n2,
+                                                             const long long *exact_off, const double *exact_cdf,
+                                                             double *diff_out, double *p_out) {
+	const int n = n1 + n2;
+	for (unsigned long long r = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; r < n_rows; r += (unsigned long long)gridDim.x * blockDim.x) {
+		const double *v = value + r;
+		bool any_nan = false;
+		int nx = 0, ny = 0;
+		for (int j = 0; j < n; ++j) {
+			const double a = v[(unsigned long long)j * n_rows];
+			any_nan |= isnan(a);
+			if (isfinite(a)) { if (j < n1) ++nx; else ++ny; }
+		}
+		diff_out[r] = any_nan ? NAN : r_mean(v, n_rows, 0, n1) - r_mean(v, n_rows, n1, n2);
+		if (nx == 0 || ny == 0) { p_out[r] = NAN; continue; }
+		// 2W = sum over pairs (x_i > y_j: 2, x_i == y_j: 1); ties = sum over tie groups of t^3 - t = sum over values of c^2 - 1
+		long long w2 = 0, ties = 0;
+		for (int i = 0; i < n; ++i) {
+			const double a = v[(unsigned long long)i * n_rows];
+			if (!isfinite(a)) continue;
+			long long same = 0;
+			for (int j = 0; j < n; ++j) {
+				const double bj = v[(unsigned long long)j * n_rows];
+				if (!isfinite(bj)) continue;
+				same += bj == a;
+				if (i < n1 && j >= n1) w2 += a > bj ? 2 : (a == bj ? 1 : 0);
+			}
+			ties += same * same - 1;
+		}
+		const long long mn = (long long)nx * ny;
+		double p;
+		if (nx < WILCOX_EXACT_MAX && ny < WILCOX_EXACT_MAX && ties == 0) {
+			const long long off = exact_off[nx * WILCOX_EXACT_MAX + ny], w = w2 / 2;
+			if (off < 0) { p = NAN; }
+			else {
+				const double P = 2 * w > mn ? exact_cdf[off + (mn - w)] : exact_cdf[off + w];
+				p = fmin(1.0, 2.0 * P);
+			}
+		} else {
+			const double N = (double)(nx + ny);
+			double z = 0.5 * (double)w2 - (double)mn / 2.0;
+			const double sigma = sqrt(((double)mn / 12.0) * ((N + 1.0) - (double)ties / (N * (N - 1.0))));
+			if (!(sigma > 0.0)) { p = NAN; }
+			else {
+				const double corr = z > 0.0 ? 0.5 : (z < 0.0 ? -0.5 : 0.0);
+				z = (z - corr) / sigma;
+				p = fmin(erfc(-z / M_SQRT2), erfc(z / M_SQRT2));   // 2 min(pnorm(z), pnorm(z, lower.tail = FALSE))
+			}
+		}
+		p_out[r] = p;
+	}
+}
+
+// ---- correction -----------------------------------------------------------------------------------------------------
+
+__global__ void __launch_bounds__(256) lsq_as_flag_kernel(const double *p, unsigned long long n, unsigned *flag, double *bon, double *bh) {
+	for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
+		const double v = p[i];
+		flag[i] = isnan(v) ? 0u : 1u;
+		if (isnan(v)) { bon[i] = v; bh[i] = v; }
+	}
+}
+
+__global__ void __launch_bounds__(256) lsq_as_compact_kernel(const double *p, unsigned long long n, const unsigned *flag, const unsigned long long *pos,
+                                                              unsigned long long *key, unsigned *idx) {
+	for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
+		if (!flag[i]) continue;
+		const double v = p[i];
+		key[pos[i]] = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);     // -0 sorts as +0
+		idx[pos[i]] = (unsigned)i;
+	}
+}
+
+constexpr unsigned RADIX_TILE = 256;      // values per workgroup of a radix pass: one per lane
+
+// per tile the count of each 8-bit digit, digit-major: hist[digit * n_tiles + tile]
+__global__ void __launch_bounds__(256) lsq_as_radix_hist_kernel(const unsigned long long *key, unsigned long long n, unsigned shift,
+                                                                 unsigned *hist, unsigned n_tiles) {
+	__shared__ unsigned h[256];
+	h[threadIdx.x] = 0;
+	__syncthreads();
+	const unsigned long long i = (unsigned long long)blockIdx.x * RADIX_TILE + threadIdx.x;
+	if (i < n) atomicAdd(&h[(unsigned)(key[i] >> shift) & 255u], 1u);
+	__syncthreads();
+	hist[(unsigned long long)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
+}
+
+// stable scatter: a value goes to the exclusive prefix of (digit, tile) plus the values of its digit ahead of it in the tile
+// (lanes of its wave with the same digit, found by eight ballots, then the earlier waves' counts)
+__global__ void __launch_bounds__(256) lsq_as_radix_scatter_kernel(const unsigned long long *key_in, const unsigned *idx_in, unsigned long long n,
+                                                                    unsigned shift, const unsigned long long *off, unsigned n_tiles,
+                                                                    unsigned long long *key_out, unsigned *idx_out) {
+	__shared__ unsigned wave_cnt[4][256];
+	const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	for (unsigned q = threadIdx.x; q < 4 * 256; q += blockDim.x) (&wave_cnt[0][0])[q] = 0;
+	__syncthreads();
+	const unsigned long long i = (unsigned long long)blockIdx.x * RADIX_TILE + threadIdx.x;
+	const bool valid = i < n;
+	const unsigned long long k = valid ? key_in[i] : 0ull;
+	const unsigned d = (unsigned)(k >> shift) & 255u;
+	unsigned long long peers = __ballot(valid);
+#pragma unroll
+	for (unsigned b = 0; b < 8; ++b) {
+		const unsigned long long bb = __ballot((d >> b) & 1u);
+		peers &= ((d >> b) & 1u) ? bb : ~bb;
+	}
+	const unsigned long long lt = lane ? (~0ull >> (64u - lane)) : 0ull;
+	const unsigned ahead = (unsigned)__popcll(peers & lt);
+	if (valid && ahead == 0) wave_cnt[w][d] = (unsigned)__popcll(peers);
+	__syncthreads();
+	if (valid) {
+		unsigned before = 0;
+		for (unsigned q = 0; q < w; ++q) before += wave_cnt[q][d];
+		const unsigned long long dst = off[(unsigned long long)d * n_tiles + blockIdx.x] + before + ahead;
+		key_out[dst] = k;
+		idx_out[dst] = idx_in[i];
+	}
+}
+
+constexpr unsigned MIN_BLOCK = 4096;      // values per workgroup of the reverse min-scan: 256 lanes x 16
+
+__device__ inline double bh_value(const unsigned long long *key, unsigned long long k, double nd) {
+	return (nd / (double)(k + 1)) * __longlong_as_double((long long)key[k]);     // p.adjust: n/i * p[o]
+}
+
+__global__ void __launch_bounds__(256) lsq_as_minblock_kernel(const unsigned long long *key, unsigned long long n, double *bmin) {
+	__shared__ double lds[4];
+	const unsigned long long b0 = (unsigned long long)blockIdx.x * MIN_BLOCK;
+	const double nd = (double)n;
+	double m = INFINITY;
+	for (unsigned q = 0; q < MIN_BLOCK / 256; ++q) {
+		const unsigned long long k = b0 + q * 256u + threadIdx.x;
+		if (k < n) m = fmin(m, bh_value(key, k, nd));
+	}
+#pragma unroll
+	for (int d = 32; d >= 1; d >>= 1) m = fmin(m, __shfl_xor(m, d));
+	if ((threadIdx.x & 63u) == 0) lds[threadIdx.x >> 6] = m;
+	__syncthreads();
+	if (threadIdx.x == 0) bmin[blockIdx.x] = fmin(fmin(lds[0], lds[1]), fmin(lds[2], lds[3]));
+}
+
+// one lane: bmin[b] <- the minimum over the blocks after b (exclusive suffix minimum; a few hundred blocks per million values)
+__global__ void lsq_as_minspine_kernel(double *bmin, unsigned long long n_blocks) {
+	if (threadIdx.x != 0 || blockIdx.x != 0) return;
+	double run = INFINITY;
+	for (unsigned long long b = n_blocks; b-- > 0;) { const double v = bmin[b]; bmin[b] = run; run = fmin(run, v); }
+}
+
+// the sorted values again: BH = min(1, running minimum from the largest down), Bonferroni = min(1, n p), scattered back
+__global__ void __launch_bounds__(256) lsq_as_minapply_kernel(const unsigned long long *key, const unsigned *idx, unsigned long long n,
+                                                               const double *bcarry, double *bon, double *bh) {
+	__shared__ double lds[4];
+	const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+	const unsigned long long k0 = (unsigned long long)blockIdx.x * MIN_BLOCK + threadIdx.x * 16ull;
+	const double nd = (double)n;
+	double m = INFINITY;
+	for (unsigned q = 0; q < 16; ++q) if (k0 + q < n) m = fmin(m, bh_value(key, k0 + q, nd));
+	// inclusive suffix minimum over the lanes of the wave, then over the waves after this one
+	double suf = m;
+#pragma unroll
+	for (unsigned d = 1; d < 64; d <<= 1) {
+		const double o = __shfl_down(suf, d);
+		if (lane + d < 64) suf = fmin(suf, o);
+	}
+	if (lane == 0) lds[w] = suf;
+	__syncthreads();
+	double run = bcarry[blockIdx.x];
+	for (unsigned q = w + 1; q < 4; ++q) run = fmin(run, lds[q]);
+	const double after = __shfl_down(suf, 1);
+	if (lane < 63) run = fmin(run, after);
+	for (int q = 15; q >= 0; --q) {
+		const unsigned long long k = k0 + (unsigned)q;
+		if (k >= n) continue;
+		const double pv = __longlong_as_double((long long)key[k]);
+		run = fmin(run, bh_value(key, k, nd));
+		const unsigned i = idx[k];
+		bh[i] = fmin(1.0, run);
+		bon[i] = fmin(1.0, nd * pv);
+	}
+}
+
+unsigned grid_for(const lsq_ctx *c, unsigned long long items, unsigned per_block, unsigned per_cu) {
+	const unsigned long long want = (items + per_block - 1) / per_block, cap = (unsigned long long)c->n_cu * per_cu;
+	return (unsigned)std::max<unsigned long long>(1, std::min(want, cap));
+}
+
+// [n][cols] row-major (the ABI's layout) -> [cols][n] sample-major, so that lane r reading sample j is a coalesced load
+std::vector<double> sample_major(const double *a, unsigned long long n, int cols) {
+	std::vector<double> t((size_t)n * (size_t)cols);
+	for (unsigned long long r = 0; r < n; ++r)
+		for (int j = 0; j < cols; ++j) t[(size_t)j * n + r] = a[(size_t)r * cols + j];
+	return t;
+}
+
+int finish(lsq_ctx *c) {
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return LSQ_OK;
+}
+
+// Lower CDF of the Wilcoxon statistic W for (nx, ny): cwilcox's counts built by f(w; a, b) = f(w - b; a - 1, b) + f(w; a, b - 1)
+// in doubles, then summed over choose(nx + ny, nx) in order, as pwilcox sums them.
+std::vector<double> wilcox_cdf(int nx, int ny) {
+	const size_t W = (size_t)nx * ny + 1;
+	// F[a][w] over b = 0 .. ny (in place: F[a] holds b - 1's counts until a's turn)
+	std::vector<std::vector<double>> F((size_t)nx + 1, std::vector<double>(W, 0.0));
+	for (int a = 0; a <= nx; ++a) F[(size_t)a][0] = 1.0;         // b = 0: only W = 0
+	for (int b = 1; b <= ny; ++b)
+		for (int a = 1; a <= nx; ++a)
+			for (size_t w = W; w-- > (size_t)b;) F[(size_t)a][w] += F[(size_t)a - 1][w - (size_t)b];
+	double c = 1.0;          // choose(nx + ny, nx)
+	for (int q = 1; q <= nx; ++q) c = c * (double)(ny + q) / (double)q;
+	c = std::round(c);
+	std::vector<double> cdf(W);
+	double s = 0.0;
+	for (size_t w = 0; w < W; ++w) { s += F[(size_t)nx][w] / c; cdf[w] = s; }
+	return cdf;
+}
+
+} // namespace
+
+extern "C" {
+
+// Test_AS.r:34-47 (fisher.test per pair of rows)
+int lsq_as_fisher(lsq_ctx *c, uint64_t n_tables, const double *cells, double *p) LSQ_API_TRY {
+	if (!c || (n_tables && (!cells || !p))) return fail(LSQ_E_ARG, "null argument");
+	if (n_tables == 0) return LSQ_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf<double> d_cells, d_p;
+	int rc;
+	if ((rc = d_cells.upload(cells, (size_t)n_tables * 4, c->stream)) || (rc = d_p.alloc((size_t)n_tables))) return rc;
+	hipLaunchKernelGGL(lsq_as_fisher_kernel, dim3(grid_for(c, n_tables, 4, 32)), dim3(256), 0, c->stream, d_cells.p, (unsigned long long)n_tables, d_p.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_tables * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	return finish(c);
+} LSQ_API_CATCH
+
+// Test_AS.r:89-131 (glm + lrtest per row)
+int lsq_as_lrt(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count, const double *total, double *stat, double *p) LSQ_API_TRY {
+	if (!c || (n_rows && (!count || !total || !stat || !p))) return fail(LSQ_E_ARG, "null argument");
+	if (n1 < 1 || n2 < 1 || n1 > 4096 || n2 > 4096) return fail(LSQ_E_ARG, "replicates per condition must lie in [1, 4096] (n1 = %d, n2 = %d)", n1, n2);
+	if (n_rows == 0) return LSQ_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	const int n = n1 + n2;
+	DevBuf<double> d_count, d_total, d_stat, d_p;
+	int rc;
+	const std::vector<double> hc = sample_major(count, n_rows, n), ht = sample_major(total, n_rows, n);
+	if ((rc = d_count.upload(hc.data(), hc.size(), c->stream)) || (rc = d_total.upload(ht.data(), ht.size(), c->stream)) ||
+	    (rc = d_stat.alloc((size_t)n_rows)) || (rc = d_p.alloc((size_t)n_rows))) return rc;
+	hipLaunchKernelGGL(lsq_as_lrt_kernel, dim3(grid_for(c, n_rows, 256, 8)), dim3(256), 0, c->stream, d_count.p, d_total.p, (unsigned long long)n_rows, n1, n2, d_stat.p, d_p.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(stat, d_stat.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	return finish(c);
+} LSQ_API_CATCH
+
+// Test_AS.r:162-175 (mean difference + wilcox.test per row)
+int lsq_as_wilcox(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *value, double *diff, double *p) LSQ_API_TRY {
+	if (!c || (n_rows && (!value || !diff || !p))) return fail(LSQ_E_ARG, "null argument");
+	if (n1 < 1 || n2 < 1 || n1 > 4096 || n2 > 4096) return fail(LSQ_E_ARG, "replicates per condition must lie in [1, 4096] (n1 = %d, n2 = %d)", n1, n2);
+	if (n_rows == 0) return LSQ_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	const int n = n1 + n2;
+	// exact tables for every (nx, ny) that a row can have after its non-finite values are dropped
+	std::vector<long long> off((size_t)WILCOX_EXACT_MAX * WILCOX_EXACT_MAX, -1);
+	std::vector<double> cdf;
+	for (uint64_t r = 0; r < n_rows; ++r) {
+		int nx = 0, ny = 0;
+		for (int j = 0; j < n; ++j) if (std::isfinite(value[(size_t)r * n + j])) { if (j < n1) ++nx; else ++ny; }
+		if (nx == 0 || ny == 0 || nx >= WILCOX_EXACT_MAX || ny >= WILCOX_EXACT_MAX) continue;
+		long long &o = off[(size_t)nx * WILCOX_EXACT_MAX + ny];
+		if (o >= 0) continue;
+		o = (long long)cdf.size();
+		const std::vector<double> t = wilcox_cdf(nx, ny);
+		cdf.insert(cdf.end(), t.begin(), t.end());
+	}
+	DevBuf<double> d_value, d_cdf, d_diff, d_p;
+	DevBuf<long long> d_off;
+	int rc;
+	const std::vector<double> hv = sample_major(value, n_rows, n);
+	if ((rc = d_value.upload(hv.data(), hv.size(), c->stream)) || (rc = d_off.upload(off.data(), off.size(), c->stream)) ||
+	    (rc = d_cdf.upload(cdf.data(), cdf.size(), c->stream)) || (rc = d_diff.alloc((size_t)n_rows)) || (rc = d_p.alloc((size_t)n_rows))) return rc;
+	hipLaunchKernelGGL(lsq_as_wilcox_kernel, dim3(grid_for(c, n_rows, 256, 8)), dim3(256), 0, c->stream, d_value.p, (unsigned long long)n_rows, n1, n2,
+	                   (const long long *)d_off.p, (const double *)d_cdf.p, d_diff.p, d_p.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(diff, d_diff.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	return finish(c);
+} LSQ_API_CATCH
+
+// Test_AS.r:45,129,173 (p.adjust, "bonferroni" and "BH")
+int lsq_as_adjust(lsq_ctx *c, uint64_t n, const double *p, double *p_bonferroni, double *p_bh) LSQ_API_TRY {
+	if (!c || (n && (!p || !p_bonferroni || !p_bh))) return fail(LSQ_E_ARG, "null argument");
+	if (n >= 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 - 2 p-values");
+	uint64_t n_valid = 0;
+	for (uint64_t i = 0; i < n; ++i) {
+		if (std::isnan(p[i])) continue;
+		if (p[i] < 0.0) return fail(LSQ_E_ARG, "p-value %llu is negative (%g)", (unsigned long long)i, p[i]);
+		++n_valid;
+	}
+	if (n_valid <= 1) {          // p.adjust returns p unchanged
+		if (n) { memmove(p_bonferroni, p, (size_t)n * sizeof(double)); memmove(p_bh, p, (size_t)n * sizeof(double)); }
+		return LSQ_OK;
+	}
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	const unsigned n_tiles = (unsigned)((n_valid + RADIX_TILE - 1) / RADIX_TILE);
+	const unsigned long long n_hist = (unsigned long long)n_tiles * 256ull;
+	DevBuf<double> d_p, d_bon, d_bh, d_bmin;
+	DevBuf<unsigned> d_flag, d_idx[2], d_hist;
+	DevBuf<unsigned long long> d_pos, d_key[2], d_off;
+	ScanScratch S;
+	int rc;
+	if ((rc = d_p.upload(p, (size_t)n, st)) || (rc = d_bon.alloc((size_t)n)) || (rc = d_bh.alloc((size_t)n)) || (rc = d_flag.alloc((size_t)n)) ||
+	    (rc = d_pos.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n_valid)) || (rc = d_key[1].alloc((size_t)n_valid)) ||
+	    (rc = d_idx[0].alloc((size_t)n_valid)) || (rc = d_idx[1].alloc((size_t)n_valid)) || (rc = d_hist.alloc((size_t)n_hist)) ||
+	    (rc = d_off.alloc((size_t)n_hist + 1)) || (rc = d_bmin.alloc((size_t)((n_valid + MIN_BLOCK - 1) / MIN_BLOCK))) ||
+	    (rc = S.reserve(std::max<unsigned long long>(n, n_hist)))) return rc;
+	const unsigned g = grid_for(c, n, 256, 16);
+	hipLaunchKernelGGL(lsq_as_flag_kernel, dim3(g), dim3(256), 0, st, (const double *)d_p.p, (unsigned long long)n, d_flag.p, d_bon.p, d_bh.p);
+	if ((rc = device_scan<1, true>(S, d_flag.p, n, d_pos.p, st))) return rc;
+	hipLaunchKernelGGL(lsq_as_compact_kernel, dim3(g), dim3(256), 0, st, (const double *)d_p.p, (unsigned long long)n, (const unsigned *)d_flag.p,
+	                   (const unsigned long long *)d_pos.p, d_key[0].p, d_idx[0].p);
+	// stable LSD radix sort, 8 bits a pass; non-negative doubles sort as their bit patterns
+	for (unsigned pass = 0; pass < 8; ++pass) {
+		const unsigned a = pass & 1u, shift = 8u * pass;
+		hipLaunchKernelGGL(lsq_as_radix_hist_kernel, dim3(n_tiles), dim3(256), 0, st, (const unsigned long long *)d_key[a].p, (unsigned long long)n_valid, shift, d_hist.p, n_tiles);
+		if ((rc = device_scan<1, false>(S, d_hist.p, n_hist, d_off.p, st))) return rc;
+		hipLaunchKernelGGL(lsq_as_radix_scatter_kernel, dim3(n_tiles), dim3(256), 0, st, (const unsigned long long *)d_key[a].p, (const unsigned *)d_idx[a].p,
+		                   (unsigned long long)n_valid, shift, (const unsigned long long *)d_off.p, n_tiles, d_key[a ^ 1u].p, d_idx[a ^ 1u].p);
+	}
+	const unsigned nb = (unsigned)((n_valid + MIN_BLOCK - 1) / MIN_BLOCK);
+	hipLaunchKernelGGL(lsq_as_minblock_kernel, dim3(nb), dim3(256), 0, st, (const unsigned long long *)d_key[0].p, (unsigned long long)n_valid, d_bmin.p);
+	hipLaunchKernelGGL(lsq_as_minspine_kernel, dim3(1), dim3(64), 0, st, d_bmin.p, (unsigned long long)nb);
+	hipLaunchKernelGGL(lsq_as_minapply_kernel, dim3(nb), dim3(256), 0, st, (const unsigned long long *)d_key[0].p, (const unsigned *)d_idx[0].p,
+	                   (unsigned long long)n_valid, (const double *)d_bmin.p, d_bon.p, d_bh.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(p_bonferroni, d_bon.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(p_bh, d_bh.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
+	return finish(c);
+} LSQ_API_CATCH
+
+} // extern "C"

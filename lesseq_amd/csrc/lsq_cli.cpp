@@ -793,6 +793,8 @@ std::string format_events_parallel(size_t n, F &&one) {
 
 } // namespace
 
+void lsq::cli_log(int level, const char *text) { logf(level, "%s", text); }
+
 extern "C" {
 
 int lsq_format_count(const lsq_events *E, int M, const uint64_t *cnt, char **out_text) LSQ_API_TRY {
@@ -876,6 +878,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	if (tool && strcmp(tool, "count") == 0) rc = run_count_solve(false, argc, argv, out);
 	else if (tool && strcmp(tool, "solve") == 0) rc = run_count_solve(true, argc, argv, out);
 	else if (tool && strcmp(tool, "classify") == 0) rc = run_classify(argc, argv);
+	else if (tool && strcmp(tool, "test_as") == 0) rc = run_test_as(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -292,5 +292,7 @@ namespace lsq {
 
 int plan_device(lsq_events &E);
 int host_threads(int requested);
+void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
+int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
 
 } // namespace lsq

@@ -1,5 +1,6 @@
 // count / solve / classify executables: the reference's argv, stdout, stderr log and exit
-// status (count/count.cpp:88-129, solve/solve.cpp:102-146, classify/classify.cpp:51-79).
+// status (count/count.cpp:88-129, solve/solve.cpp:102-146, classify/classify.cpp:51-79);
+// test_as, the differential splicing tests of bin/Test_AS.r (lsq_as.cpp).
 // The tool is chosen by the program name.
 #include <cstdio>
 #include <cstdlib>
@@ -10,6 +11,6 @@
 int main(int argc, char **argv) {
 	const char *base = strrchr(argv[0], '/');
 	base = base ? base + 1 : argv[0];
-	const char *tool = strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
+	const char *tool = strstr(base, "test_as") ? "test_as" : strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
 	return lsq_cli_main(tool, argc, argv);
 }
