@@ -419,7 +419,7 @@ int lsq_format_solve(const lsq_events *e, int n_methods, const uint64_t *class_c
 void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
- * "count", "solve", "classify" or "test_as" (bin/Test_AS.r; lsq_as_* below).  stdout text is returned in *out_text (malloc'd), the
+ * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below) or "events" (bin/Events.r; lsq_le_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -475,6 +475,47 @@ uint64_t lsq_as_input_left_out(const lsq_as_input *in);
 /* R's as.character(v): 15 significant digits, trailing zeros dropped, fixed unless scientific is strictly shorter
  * ("1e-04", "0.001", "1e+05", "123456"), NaN as "NA".  32 bytes always suffice. */
 int lsq_as_format_number(double v, char *buf, size_t cap);
+
+/* ------------------------------------------------------------------------------------
+ * Local events: step 2 of the pipeline, bin/Events.r
+ * ------------------------------------------------------------------------------------ */
+
+/* Host-only: the splicing graphs of the genes Events.r walks, in its order, read and checked (no GPU touched).
+ * lsq_le_load_matrices reads the gene list (group_path, UCSC_GENE2ISOFORM; read.table + table(): ids convert to
+ * integers or doubles when all of them do, and sort numerically then, strings sort in byte order; the ids with more
+ * than one line are taken) and <matrix_prefix><id>.matrix for each (classify's files; prefix pasted on as it is).
+ * lsq_le_load_annotation does classify in memory instead: every gene with two or more isoforms, named and ordered as
+ * the map's ids are.  Input errors (LSQ_E_IO, LSQ_E_PARSE, LSQ_E_ARG, LSQ_E_FORMAT) name the file and line: a missing
+ * matrix, a malformed header or row, a coordinate beyond R's integer, an id R reads as NA / logical / hexadecimal, no
+ * gene with more than one line.  A gene of fewer than 3 columns is kept (its line is printed) and gives no events. */
+typedef struct lsq_le_graphs lsq_le_graphs;
+typedef struct lsq_le_result lsq_le_result;
+int lsq_le_load_matrices(const char *matrix_prefix, const char *group_path, lsq_le_graphs **out);
+int lsq_le_load_annotation(const char *isoform_format, const char *isoforms_path, const char *g2i_format, const char *g2i_path,
+                           lsq_le_graphs **out);
+void lsq_le_graphs_free(lsq_le_graphs *g);
+int64_t lsq_le_num_genes(const lsq_le_graphs *g);
+const char *lsq_le_gene_name(const lsq_le_graphs *g, int64_t gene);          /* as Events.r prints it */
+int lsq_le_gene_shape(const lsq_le_graphs *g, int64_t gene, int *n_columns, int *n_isoforms);
+/* The gene's pos[1..2N] (Events.r:53, the header's digit runs) at *pos; returns 2N (0 for a gene of < 3 columns) */
+int64_t lsq_le_gene_positions(const lsq_le_graphs *g, int64_t gene, const int32_t **pos);
+/* Device group: Events.r:57-156 for every gene (one wave per gene; any number of columns and isoforms).  The result
+ * refers to g, which must outlive it. */
+int lsq_le_detect(lsq_ctx *c, const lsq_le_graphs *g, lsq_le_result **out);
+void lsq_le_result_free(lsq_le_result *r);
+/* type: 0 ES, 1 RI, 2 A5SS, 3 A3SS, 4 MXE, 5 AFE, 6 ALE, 7 T3.  Event q of a type has counter q + 1 and writes two
+ * lines to each file; *code is the script's column i (ES .. MXE), the block (AFE / ALE: 0 first-exon, 1 last-exon) or
+ * the form (T3: 0 +, 1 -). */
+const char *lsq_le_type_name(int type);
+int64_t lsq_le_num_events(const lsq_le_result *r, int type);
+int lsq_le_event(const lsq_le_result *r, int type, int64_t event, int64_t *gene, int32_t *code);
+/* Milliseconds of the detection by HIP events: ms[0] upload, [1] count kernel + scan, [2] emit kernel, [3] download
+ * (0 where no event was found and the emit pass did not run) */
+int lsq_le_result_times(const lsq_le_result *r, double *ms /* [4] */);
+/* The text Events.r appends to <out_prefix><TYPE>.interval and <TYPE>.map (malloc'd; lsq_free) */
+int lsq_le_format(const lsq_le_result *r, int type, char **interval_text, char **map_text);
+/* Appends both files of every type that has events (none: no file), as the script's write(..., append = T) does */
+int lsq_le_write(const lsq_le_result *r, const char *out_prefix);
 
 /* ------------------------------------------------------------------------------------
  * Synthetic workload; deterministic in (seed, sizes).  Host-only.

@@ -166,6 +166,21 @@ _sig("lsq_as_input_totals", P(C.c_double), vp)
 _sig("lsq_as_input_left_out", u64, vp)
 _sig("lsq_as_format_number", C.c_int, C.c_double, C.c_char_p, C.c_size_t)
 _sig("lsq_synth_reads", C.c_int, P(SynthSpecStruct), vp, C.c_int, P(vp))
+_sig("lsq_le_load_matrices", C.c_int, cs, cs, P(vp))
+_sig("lsq_le_load_annotation", C.c_int, cs, cs, cs, cs, P(vp))
+_sig("lsq_le_graphs_free", None, vp)
+_sig("lsq_le_num_genes", i64, vp)
+_sig("lsq_le_gene_name", cs, vp, i64)
+_sig("lsq_le_gene_shape", C.c_int, vp, i64, P(C.c_int), P(C.c_int))
+_sig("lsq_le_gene_positions", i64, vp, i64, P(P(i32)))
+_sig("lsq_le_detect", C.c_int, vp, vp, P(vp))
+_sig("lsq_le_result_free", None, vp)
+_sig("lsq_le_type_name", cs, C.c_int)
+_sig("lsq_le_num_events", i64, vp, C.c_int)
+_sig("lsq_le_event", C.c_int, vp, C.c_int, i64, P(i64), P(i32))
+_sig("lsq_le_format", C.c_int, vp, C.c_int, P(vp), P(vp))
+_sig("lsq_le_result_times", C.c_int, vp, P(C.c_double))
+_sig("lsq_le_write", C.c_int, vp, cs)
 
 
 def _warn_on_runtime_mismatch():

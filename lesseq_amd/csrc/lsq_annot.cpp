@@ -869,7 +869,9 @@ int compile_events(const lsq_annotation *a, int n_methods, const char *const *re
 		// segment masks are 64 bits wide; a gene's compatibility classes are kept as a dense table of 2^K - 1 counters.
 		// Genes beyond the kernels' limits (LSQ_MAX_SEGMENTS, LSQ_MAX_ISOFORMS) are not refused: plan_device puts them
 		// into host buckets, which lsq_count / lsq_solve evaluate on the host (lsq_replay.hip).
-		if (e.N > 64) return fail(LSQ_E_UNSUPPORTED, "gene %s has %d segments (limit 64)", g.name.c_str(), e.N);
+		// classify (device_plan = false) takes genes of any size: their masks are kept in iso_wide alone
+		if (device_plan && e.N > 64) return fail(LSQ_E_UNSUPPORTED, "gene %s has %d segments (limit 64)", g.name.c_str(), e.N);
+		const size_t nw = ((size_t)e.N + 63) / 64;
 		if (device_plan && e.K > LSQ_HOST_MAX_ISOFORMS) return fail(LSQ_E_UNSUPPORTED, "gene %s has %d isoforms (limit %d: the class table of a gene has 2^K - 1 entries)", g.name.c_str(), e.K, LSQ_HOST_MAX_ISOFORMS);
 		for (const Seg &s : segs) { e.seg_s.push_back(s.start); e.seg_e.push_back(s.end); }
 		// build_isoform_array (splicing_graph.h:318-361): per isoform walk the segments in order;
@@ -879,10 +881,13 @@ int compile_events(const lsq_annotation *a, int n_methods, const char *const *re
 			uint64_t mask = 0, len = 0;
 			uint64_t from = 0;
 			std::vector<uint64_t> seg_len;
+			const size_t w0 = e.iso_wide.size();
+			if (!device_plan) e.iso_wide.resize(w0 + nw, 0);
 			for (int n = 0; n < e.N; ++n) {
 				for (uint64_t i = from; i < r->exonCount; ++i) {
 					if (r->exonStarts[i] <= e.seg_s[n] && e.seg_e[n] <= r->exonEnds[i]) {
-						mask |= 1ull << n;
+						if (n < 64) mask |= 1ull << n;
+						if (!device_plan) e.iso_wide[w0 + (size_t)n / 64] |= 1ull << (n % 64);
 						uint64_t l = (uint64_t)(e.seg_e[n] - e.seg_s[n]);
 						len += l;
 						seg_len.push_back(l);

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "lsq_internal.hpp"
+#include "lsq_localev.hpp"
 
 using namespace lsq;
 
@@ -151,8 +152,9 @@ int run_classify(int argc, const char *const *argv) {
 		fprintf(f, "%s\t%s\t", e.chrom.c_str(), e.strand.c_str());
 		for (int n = 0; n < e.N; ++n) fprintf(f, "[%lld,%lld)-", (long long)e.seg_s[n], (long long)e.seg_e[n]);
 		fputc('\n', f);
+		const size_t nw = ((size_t)e.N + 63) / 64;        // any N: compile_events keeps the masks in iso_wide here
 		for (int k = 0; k < e.K; ++k) {
-			for (int n = 0; n < e.N; ++n) fprintf(f, "%d\t", (int)(e.iso_mask[k] >> n & 1));
+			for (int n = 0; n < e.N; ++n) fprintf(f, "%d\t", (int)(e.iso_wide[(size_t)k * nw + (size_t)n / 64] >> (n % 64) & 1));
 			fputc('\n', f);
 		}
 		fclose(f);
@@ -879,6 +881,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "solve") == 0) rc = run_count_solve(true, argc, argv, out);
 	else if (tool && strcmp(tool, "classify") == 0) rc = run_classify(argc, argv);
 	else if (tool && strcmp(tool, "test_as") == 0) rc = run_test_as(argc, argv, out);
+	else if (tool && strcmp(tool, "events") == 0) rc = run_events(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

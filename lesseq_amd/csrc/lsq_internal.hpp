@@ -93,6 +93,8 @@ struct Event {
 	std::vector<int64_t> seg_s, seg_e;             // atomic segments, ascending
 	std::vector<std::string> iso_names;
 	std::vector<uint64_t> iso_mask;                // bit n: isoform holds segment n (N <= 64)
+	// classify's path only (compile_events, device_plan = false): the same bits for any N, [iso][ceil(N/64)] words
+	std::vector<uint64_t> iso_wide;
 	std::vector<uint64_t> iso_len;                 // total segment length per isoform
 	int64_t gene_start = 0, gene_end = 0;          // first start / last end of the merged exon list
 	std::vector<std::vector<uint64_t>> ars;        // [method][iso]
