@@ -409,23 +409,12 @@ __device__ inline bool fast_trip(const FastCtx &C, const int4 v, const int total
 // Each wave streams its own part of the workgroup's range straight from HBM into registers
 // (next words in flight while the current ones are processed) and owns its parking area: no
 // workgroup barrier inside the stream, a slow wave never holds up the others.
-#ifndef LSQ_STREAM_WORDS_P2
-#define LSQ_STREAM_WORDS_P2 2
-#endif
-#ifndef LSQ_STREAM_WORDS
-#define LSQ_STREAM_WORDS 2
-#endif
 #ifndef LSQ_P2_COMPACT_WORDS
 #define LSQ_P2_COMPACT_WORDS 2         // two-block reads a lane takes per step from a compact pool (2 or 4; 4 -- one table look for four reads -- measured 3 % slower: the one-block path of the same kernel loses more registers than the look saves)
 #endif
 #ifndef LSQ_P2_COMPACT_WORDS_W5
 #define LSQ_P2_COMPACT_WORDS_W5 4      // the same in the five-wave kernel: with 96 registers the one look for four reads pays (C3, developer builds, same box: 0.1401 -> 0.1364 ms per step)
 #endif
-constexpr int STREAM_WORDS = LSQ_STREAM_WORDS;                // 16-byte words per lane in flight
-#ifndef LSQ_GROUP_WORDS
-#define LSQ_GROUP_WORDS 2
-#endif
-constexpr int GROUP_WORDS = LSQ_GROUP_WORDS;                  // words per lane looked up together (independent chains)
 constexpr unsigned WAVE_QUEUE_WORDS = 256;                    // 16-byte words of parking per wave (4 KiB): 63 left over + what is pushed between two walks
 constexpr unsigned WAVES = COUNT_BLOCK / 64;
 
@@ -524,23 +513,16 @@ __device__ inline void walk_parked(const FastCtx &C, Ring<(NB == 1 || PACKED2) ?
 	}
 }
 
-// RPW = reads per 16-byte word of a wide pool: 2 (pool 1: one block) or 1 (pool 2: two blocks); a lane's words are
-// numbered that way for compact pools too (the fetch unpacks one compact word into two of them)
-// P1W: words a lane takes from the one-block pool per step, all of them settled by one look at the tables (2 or 4, i.e. four
-// or eight reads: the pool's cell groups are padded to eight)
-template <int RPW, bool COMPACT, int P1W>
-__device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uint4 *cells, const uint4 *cellx, const unsigned n_cells, const BucketDesc &d,
+// The streaming loop of the wide pools ((start, end) pairs, 8 bytes a block): what lsq_count_fast_kernel<false, 2> runs.
+// RPW = reads per 16-byte word: 2 (pool 1: one block) or 1 (pool 2: two blocks).  A lane takes two words per step -- four
+// one-block reads, settled by one look at the tables, or two two-block reads.
+template <int RPW>
+__device__ inline void stream_pool_wide(FastCtx &C, const uint4 *bins, const uint4 *cells, const uint4 *cellx, const unsigned n_cells, const BucketDesc &d,
                                         const CountArgs &A, uint4 *queue, const uint4 *src_generic,
                                         const unsigned long long g0, const unsigned long long g1) {
 	constexpr int NB = RPW == 2 ? 1 : 2;
-	// Words (16 bytes of a wide pool: two one-block reads, one two-block read) per lane in flight, and looked up together:
-	// two-block reads take the whole step as one group -- two of them with wide records, four with compact ones (one table
-	// look serves the four: the pool's junction groups are padded to quadruples)
-	constexpr int SW = RPW == 2 ? P1W : (COMPACT ? (P1W == 4 ? LSQ_P2_COMPACT_WORDS_W5 : LSQ_P2_COMPACT_WORDS) : LSQ_STREAM_WORDS_P2), GW = RPW == 2 ? (P1W == STREAM_WORDS ? GROUP_WORDS : P1W) : SW;
+	constexpr int SW = 2;                      // words per lane in flight, and looked up together
 	static_assert(RPW != 2 || (unsigned)(SW * RPW) <= P1_GROUP_PAD, "a lane's reads of a step lie in one cell group");
-	constexpr int CW = COMPACT ? SW / 2 : SW;          // 16-byte loads a lane issues per step
-	constexpr bool PACKED2 = COMPACT && RPW == 1;      // two-block reads are parked as their compact records
-	constexpr int RW = (NB == 1 || PACKED2) ? 1 : 2;   // ring words per parked read
 	constexpr unsigned TILE = 64u * SW;        // words per wave step
 	C.pool = RPW == 2 ? 0u : 1u;
 	C.slot0 = g0;
@@ -550,34 +532,20 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 	// words [w0, w1) of the workgroup, dealt to its waves a step at a time (wave, wave + 4, ...): the
 	// reads that need the general walk sit together in the start-ordered pool, and a contiguous
 	// quarter per wave would leave three waves waiting for the one that got them
-	// (the range starts on a multiple of a lane's words: they are one of the octuples / quadruples the pools' groups are padded
-	// to, and whole 16-byte words of a compact pool)
+	// (the range starts on a multiple of a lane's words: they lie in one of the octuples / quadruples the pools' groups are padded to)
 	const unsigned long long w0 = (g0 / RPW) & ~(unsigned long long)(SW - 1), w1 = (g1 + RPW - 1) / RPW;
 	const unsigned n_words = (unsigned)(w1 - w0);                                   // a workgroup's range stays below 2^21 reads
 	const unsigned ww0 = min(wave * TILE, n_words), ww1 = n_words;                   // relative to w0
-	const unsigned first_rel = (unsigned)(g0 - w0 * RPW);                            // reads of word w0 (and, compact, w0 + 1) before the range
+	const unsigned first_rel = (unsigned)(g0 - w0 * RPW);                            // reads of word w0 before the range
 	const unsigned n_rel = (unsigned)(g1 - g0);
 	uint4 nxt[SW];
-	static_assert(!COMPACT || (SW & 1) == 0, "a compact 16-byte word unpacks into two words of a lane");
-	const int base = d.lo - lsq::COMPACT_BIAS;
-	auto fetch_into = [&](uint4 (&dst)[SW], unsigned wt) {
-		if (COMPACT) {
-			// one 16-byte load per lane and step: four one-block records or two two-block ones; unpacked when the
-			// step that uses them begins (not here: the load is to stay in flight during the step before)
-#pragma unroll
-			for (int cq = 0; cq < CW; ++cq) {
-				const unsigned w = min((wt >> 1) + lane * (unsigned)CW + (unsigned)cq, (ww1 - 1u) >> 1);
-				const u32x4 t = src[(w0 >> 1) + w];
-				dst[cq] = make_uint4(t.x, t.y, t.z, t.w);
-			}
-			return;
-		}
+	auto fetch = [&](unsigned wt) {
 		if (ABL(A, RPW == 2 ? 131072u : 262144u)) {      // developer switch: half the words loaded (what a pool of half-size records would cost to stream)
 			const unsigned w = min((wt >> 1) + lane, ww1 - 1u);
 			const u32x4 t = src[w0 + w];
-			dst[0] = make_uint4(t.x, t.y, t.z, t.w);
+			nxt[0] = make_uint4(t.x, t.y, t.z, t.w);
 #pragma unroll
-			for (int k = 1; k < SW; ++k) dst[k] = make_uint4(t.x + 1u, t.y + 1u, t.z + 1u, t.w + 1u);
+			for (int k = 1; k < SW; ++k) nxt[k] = make_uint4(t.x + 1u, t.y + 1u, t.z + 1u, t.w + 1u);
 			return;
 		}
 #pragma unroll
@@ -586,10 +554,9 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 			// (no predication: every read is tested against the range before it counts)
 			const unsigned w = min(wt + lane * (unsigned)SW + (unsigned)k, ww1 - 1u);
 			const u32x4 t = src[w0 + w];
-			dst[k] = make_uint4(t.x, t.y, t.z, t.w);
+			nxt[k] = make_uint4(t.x, t.y, t.z, t.w);
 		}
 	};
-	auto fetch = [&](unsigned wt) { fetch_into(nxt, wt); };
 	// bin record of position p -> (the last cell that starts at or before p, first event of the bin).  The record
 	// names the bin's first cell and the ends of it and of the next two; in a bin with more cells the search goes on
 	// through the cell table (rare: bins are laid out for about one event each).
@@ -603,25 +570,24 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 			while (cell + 1u < n_cells && p >= (int)cells[cell + 1u].x) ++cell;
 		}
 	};
-	Ring<RW> R;
+	Ring<NB> R;
 	R.q = queue;
 
 	// one step of the wave over the words in `cur` (the step's words, fetched a step ahead)
-	uint4 raw2[PACKED2 ? CW : 1];        // the step's two-block records as loaded (what is parked of them)
 	auto do_step = [&](const uint4 (&cur)[SW], const unsigned wt) {
-#pragma unroll
-		for (int k0 = 0; k0 < SW; k0 += GW) {
 		if (ABL(A, 512u)) {      // developer switch: stream only
 #pragma unroll
-			for (int kg = 0; kg < GW; ++kg) asm volatile("" ::"v"(cur[k0 + kg].x), "v"(cur[k0 + kg].y), "v"(cur[k0 + kg].z), "v"(cur[k0 + kg].w));
-			continue;
+			for (int k = 0; k < SW; ++k) asm volatile("" ::"v"(cur[k].x), "v"(cur[k].y), "v"(cur[k].z), "v"(cur[k].w));
+			return;
 		}
 		// the reads of a group are looked up first (independent chains), parking comes after
-		constexpr int N_READS = GW * RPW;
+		constexpr int N_READS = SW * RPW;
 		bool park[N_READS];
 		uint4 pe0[N_READS], pe1[N_READS];
+		// (one look per step, in the loop's first turn; the second is empty.  The loop stays: without it the compiler lays this
+		// kernel out differently, and the code that the figures in these comments were measured with is kept)
 #pragma unroll
-		for (int kg = 0; kg < GW; ++kg) {
+		for (int kg = 0; kg < SW; ++kg) {
 			if (RPW == 2) {
 				// One look at the tables per lane and group: the lane's reads are neighbours in the
 				// start-ordered pool, so the cell of the first one is the cell of (nearly) all of
@@ -630,28 +596,26 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 				// once.  Everything else (a different cell, no cell, a longer run) is parked -- and only
 				// then is anything built for the ring: most steps park nothing in any lane.
 				if (kg == 0) {
-					// the loop's coordinates: the records' offsets from `base` (compact) or the reads' own (wide)
-					const int ws = COMPACT ? base : 0;
 					unsigned ci, evf;
-					locate((int)cur[k0].x + ws, ci, evf);
+					locate((int)cur[0].x, ci, evf);
 					const unsigned cc = min(ci, n_cells - 1u);
 					const uint4 cw = cells[cc];           // lo, hi, e1, e2
 					const uint4 cx = cellx[cc];           // slots, info, flags, owner event
 					const bool has = ci < n_cells && !ABL(A, 8u);
-					const int lo = (int)cw.x - ws, e1 = (int)cw.z - ws, e2 = (int)cw.w - ws;
+					const int lo = (int)cw.x, e1 = (int)cw.z, e2 = (int)cw.w;
 					const unsigned width = has ? (unsigned)((int)cw.y - (int)cw.x) : 0u;
 					// all but the first and last steps of a workgroup's range lie wholly inside it: no per-read range test there
 					const bool interior = wt + TILE <= ww1 && (wt > 0u || first_rel == 0u) && (wt + TILE) * 2u - first_rel <= n_rel;
 					auto in_range = [&](const int j, unsigned &rel) {
-						const unsigned wj = wt + lane * (unsigned)SW + (unsigned)(k0 + j / 2);
+						const unsigned wj = wt + lane * (unsigned)SW + (unsigned)(j / 2);
 						rel = wj * 2u + (unsigned)(j & 1) - first_rel;      // position in the range (wraps above n_rel when outside)
 						return wj < ww1 && rel < n_rel;
 					};
-					// read j of the lane: first base (in the loop's coordinates) and length
+					// read j of the lane: first base and length
 					auto read_of = [&](const int j, int &s, unsigned &len) {
-						const int kk = k0 + j / 2;
+						const int kk = j / 2;
 						const unsigned a = (j & 1) ? cur[kk].z : cur[kk].x, b = (j & 1) ? cur[kk].w : cur[kk].y;
-						s = (int)a; len = COMPACT ? b : b - a;
+						s = (int)a; len = b - a;
 					};
 					// Reads that end inside the owner's segment (A) and reads that end inside it or the segment that abuts it (L):
 					// count and matched bases of each kind in one word (count << 24 | bases: four reads of < 2^18 bases); the run
@@ -710,13 +674,13 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 								open |= op ? 1u << (j - h) : 0u;
 								// in a one-owner cell: that owner; in a two-owner cell and inside the farther segment: the owner of the
 								// nearer one (the loop has counted the read for the other); else from the first event of the bin
-								en[j - h] = make_uint4((unsigned)(s + ws), (unsigned)(s + ws) + len, (m && (!both || e <= e2)) ? (cx.w | PARK_ONE_EVENT) : PARK_EVENT_UNKNOWN, rel);
+								en[j - h] = make_uint4((unsigned)s, (unsigned)s + len, (m && (!both || e <= e2)) ? (cx.w | PARK_ONE_EVENT) : PARK_EVENT_UNKNOWN, rel);
 								if (ABL(A, 256u) && op) { atomicAdd(&A.dbg[5 + (m ? (both ? 2 : 1) : 0)], 1ull); atomicAdd(&A.dbg[0], 1ull); }
 							}
 							R.push2(open, lane, en[0], en[1]);
 							// the ring holds what one walk leaves behind (< 64) plus these 128 entries
 							if (R.live() >= 64u) {             // wave-uniform
-								if (!ABL(A, 32u)) walk_parked<NB, PACKED2>(C, R, false, base);
+								if (!ABL(A, 32u)) walk_parked<NB>(C, R, false);
 								else R.head = R.tail;
 							}
 						}
@@ -778,9 +742,9 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 					if (ABL(A, 256u) && L.park) atomicAdd(&A.dbg[8 + (v1 ? 1 : 0)], 1ull);       // parked: block 1 in no one-owner cell / in one
 					return L;
 				};
-				const uint4 u = cur[k0];
+				const uint4 u = cur[0];
 				const int4 rd = make_int4((int)u.x, (int)u.y, (int)u.z, (int)u.w);
-				const unsigned w0i = wt + lane * (unsigned)SW + (unsigned)k0;
+				const unsigned w0i = wt + lane * (unsigned)SW;
 				const unsigned rel = w0i - first_rel;
 				const bool in = w0i < ww1 && rel < n_rel;
 				const Look L1 = look2(rd, in);
@@ -788,14 +752,15 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 				// second, when it crosses the first one's junction, to the junction's)
 				unsigned n_add = L1.add ? 1u : 0u, s_add = L1.add ? L1.matched : 0u, n_add2 = 0, s_add2 = 0;
 				park[0] = L1.park && !ABL(A, 17u | 1048576u);
-				// a parked read: its blocks and (event to look at, position) -- or, PACKED2, its compact record with those two in one word
-				pe0[0] = PACKED2 ? make_uint4(raw2[0].x, raw2[0].y, L1.hint, rel) : u;
+				// a parked read: its blocks and (event to look at, position).  (Spelt as copies, uint4(u) here and uint4(v) of a
+				// reference below: with plain `= u` the compiler moves this kernel's register copies about -- 28 bytes more code)
+				pe0[0] = uint4(u);
 				pe1[0] = make_uint4(L1.hint, rel, 0u, 0u);
 #pragma unroll
 				for (int j = 1; j < N_READS; ++j) {
-					const uint4 v = cur[k0 + j];
+					const uint4 &v = cur[j];
 					const int4 r2 = make_int4((int)v.x, (int)v.y, (int)v.z, (int)v.w);
-					const unsigned wj = wt + lane * (unsigned)SW + (unsigned)(k0 + j);
+					const unsigned wj = wt + lane * (unsigned)SW + (unsigned)j;
 					const unsigned rel2 = wj - first_rel;
 					const bool in2 = wj < ww1 && rel2 < n_rel;
 					// same junction: block 1 ends and block 2 starts where the first read's do; then only the outer ends matter
@@ -808,8 +773,7 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 					// read, in the steps that hold such pairs only, was measured twice: 0.246 against 0.253 ms before the groups,
 					// 0.1627 against 0.1677 with them -- it costs more than the walk it saves.)
 					park[j] = in2 && !same && r2.y != r2.x && !ABL(A, 17u | 1048576u | 2097152u);
-					const uint4 rq = raw2[PACKED2 ? j / 2 : 0];
-					pe0[j] = PACKED2 ? make_uint4((j & 1) ? rq.z : rq.x, (j & 1) ? rq.w : rq.y, PARK_EVENT_UNKNOWN, rel2) : v;
+					pe0[j] = uint4(v);
 					pe1[j] = make_uint4(PARK_EVENT_UNKNOWN, rel2, 0u, 0u);
 				}
 				if (!ABL(A, 1u)) {
@@ -819,22 +783,8 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 				} else asm volatile("" ::"v"(n_add), "v"(s_add), "v"(n_add2), "v"(s_add2));
 			}
 		}
-		if (RPW == 1 && PACKED2) {
-			static_assert(!PACKED2 || N_READS == 4 || N_READS == 2, "two or four parked entries a step, two per push");
-#pragma unroll 1
-			for (int h = 0; h < N_READS / 2; ++h) {
-				const bool pa = h ? park[N_READS - 2] : park[0], pb = h ? park[N_READS - 1] : park[1];
-				const uint4 qa = h ? pe0[N_READS - 2] : pe0[0], qb = h ? pe0[N_READS - 1] : pe0[1];
-				if (ABL(A, 256u)) atomicAdd(&A.dbg[NB - 1], (pa ? 1ull : 0ull) + (pb ? 1ull : 0ull));
-				R.push2((pa ? 1u : 0u) | (pb ? 2u : 0u), lane, qa, qb);
-				// the ring holds what one walk leaves behind (< 64) plus these 128 one-word entries
-				if (R.live() >= 64u) {             // wave-uniform
-					if (!ABL(A, 32u)) walk_parked<NB, PACKED2>(C, R, false, base);
-					else R.head = R.tail;
-				}
-			}
-		} else if (RPW == 1) {
-			static_assert(RPW != 1 || PACKED2 || N_READS == 2, "two parked entries a step");
+		if (RPW == 1) {
+			static_assert(RPW != 1 || N_READS == 2, "two parked entries a step");
 			// (written out twice: as a loop over q the compiler kept the entries in scratch memory and indexed them there)
 #pragma unroll
 			for (int q = 0; q < 2; ++q) {
@@ -844,49 +794,27 @@ __device__ inline void stream_pool_fast(FastCtx &C, const uint4 *bins, const uin
 				R.push(pq, lane, q0, q1);
 				// the ring holds what one walk leaves behind (< 64) plus 64 two-block entries
 				if (R.live() >= 64u) {             // wave-uniform
-					if (!ABL(A, 32u)) walk_parked<NB, PACKED2>(C, R, false, base);
+					if (!ABL(A, 32u)) walk_parked<NB>(C, R, false);
 					else R.head = R.tail;
 				}
 			}
-		}
 		}
 	};
 	if (ww0 < ww1) fetch(ww0);
 	for (unsigned wt = ww0; wt < ww1; wt += WAVES * TILE) {
 		uint4 cur[SW];
-		if (COMPACT) {
-			if (RPW == 2) {
-				// one-block reads stay in the records' own terms: (offset from `base`, length); the loop compares there
 #pragma unroll
-				for (int cq = 0; cq < CW; ++cq) {
-					const uint4 t = nxt[cq];
-					cur[2 * cq] = make_uint4(t.x & lsq::COMPACT_OFF_MASK, t.x >> lsq::COMPACT_OFF_BITS, t.y & lsq::COMPACT_OFF_MASK, t.y >> lsq::COMPACT_OFF_BITS);
-					cur[2 * cq + 1] = make_uint4(t.z & lsq::COMPACT_OFF_MASK, t.z >> lsq::COMPACT_OFF_BITS, t.w & lsq::COMPACT_OFF_MASK, t.w >> lsq::COMPACT_OFF_BITS);
-				}
-			} else {
-#pragma unroll
-				for (int cq = 0; cq < CW; ++cq) {
-					const uint4 tq = nxt[cq];
-					const int4 a = unpack_two_block(tq.x, tq.y, base), b = unpack_two_block(tq.z, tq.w, base);
-					cur[2 * cq] = make_uint4((unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w);
-					cur[2 * cq + 1] = make_uint4((unsigned)b.x, (unsigned)b.y, (unsigned)b.z, (unsigned)b.w);
-					raw2[cq] = tq;
-				}
-			}
-		} else {
-#pragma unroll
-			for (int k = 0; k < SW; ++k) cur[k] = nxt[k];
-		}
+		for (int k = 0; k < SW; ++k) cur[k] = nxt[k];
 		if (wt + WAVES * TILE < ww1) fetch(wt + WAVES * TILE);
 		do_step(cur, wt);
 	}
 	// (the waves drain their own rings: handing the leftovers of four waves to one, so that fewer partly filled walk steps
 	// run, was measured -- 116 000 -> 87 000 walk steps on C3 -- and lost more at the two barriers it needs: 0.174 -> 0.180 ms)
-	if (R.live() && !ABL(A, 32u)) walk_parked<NB, PACKED2>(C, R, true, base);
+	if (R.live() && !ABL(A, 32u)) walk_parked<NB>(C, R, true);
 }
 
 // ---- compact pools: the streaming loops proper ---------------------------------------------------------------------
-// The two loops below are what lsq_count_fast_kernel<true, *> runs (the generic stream_pool_fast above keeps the wide
+// The two loops below are what lsq_count_fast_kernel<true, *> runs (stream_pool_wide above keeps the wide
 // records).  They lean on the pools' layout, which the ingest establishes with the kernel's own look at the tables and
 // lsq_debug_check_pool_layout verifies in the tests:
 //   one-block pool: the records of an aligned group of eight (P1_GROUP_PAD) start in ONE cell -- the cell of the group's
@@ -1306,7 +1234,8 @@ __device__ inline void pool_n_worker(const CountArgs &A, const unsigned long lon
 #ifndef LSQ_FAST_WAVES
 #define LSQ_FAST_WAVES 6
 #endif
-// <COMPACT, 2>: four one-block reads per lane and look, six waves a SIMD (80 registers); <true, 4>: eight, five waves (96
+// COMPACT: the pools hold compact records (stream_pool1_compact, stream_pool2_compact) or wide ones (stream_pool_wide; P1W = 2 only).
+// <*, 2>: four one-block reads per lane and look, six waves a SIMD (80 registers); <true, 4>: eight, five waves (96
 // registers) -- for the launches that are held to five workgroups a compute unit anyway (run_count), where the longer
 // step of a lane costs no occupancy and the look is shared by twice the reads
 template <bool COMPACT, int P1W>
@@ -1378,13 +1307,13 @@ __global__ void __launch_bounds__(COUNT_BLOCK, P1W == 4 ? 5 : LSQ_FAST_WAVES) ls
 		// ---- pool 1
 		if (l0 < n1 && !ABL(A, 1024u)) {
 			if constexpr (COMPACT) stream_pool1_compact<2 * P1W>(C, bins, cells, cellx, n_cells, d, A, wave_queue, A.p1, p1o + l0, p1o + (l1 < n1 ? l1 : n1));
-			else stream_pool_fast<2, COMPACT, P1W>(C, bins, cells, cellx, n_cells, d, A, wave_queue, reinterpret_cast<const uint4 *>(A.p1), p1o + l0, p1o + (l1 < n1 ? l1 : n1));
+			else stream_pool_wide<2>(C, bins, cells, cellx, n_cells, d, A, wave_queue, reinterpret_cast<const uint4 *>(A.p1), p1o + l0, p1o + (l1 < n1 ? l1 : n1));
 		}
 		// ---- pool 2
 		if (l1 > n1 && l0 < n1 + n2 && !ABL(A, 2048u)) {
 			const unsigned long long q0 = p2o + ((l0 > n1 ? l0 : n1) - n1), q1 = p2o + ((l1 < n1 + n2 ? l1 : n1 + n2) - n1);
 			if constexpr (COMPACT) stream_pool2_compact<(P1W == 4 ? LSQ_P2_COMPACT_WORDS_W5 : LSQ_P2_COMPACT_WORDS)>(C, bins, cells, cellx, n_cells, d, A, wave_queue, A.p2, q0, q1);
-			else stream_pool_fast<1, COMPACT, P1W>(C, bins, cells, cellx, n_cells, d, A, wave_queue, reinterpret_cast<const uint4 *>(A.p2), q0, q1);
+			else stream_pool_wide<1>(C, bins, cells, cellx, n_cells, d, A, wave_queue, reinterpret_cast<const uint4 *>(A.p2), q0, q1);
 		}
 		// (reads with three or more blocks are the workers')
 		__syncthreads();
