@@ -419,7 +419,8 @@ int lsq_format_solve(const lsq_events *e, int n_methods, const uint64_t *class_c
 void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
- * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below) or "events" (bin/Events.r; lsq_le_*).  stdout text is returned in *out_text (malloc'd), the
+ * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -516,6 +517,47 @@ int lsq_le_result_times(const lsq_le_result *r, double *ms /* [4] */);
 int lsq_le_format(const lsq_le_result *r, int type, char **interval_text, char **map_text);
 /* Appends both files of every type that has events (none: no file), as the script's write(..., append = T) does */
 int lsq_le_write(const lsq_le_result *r, const char *out_prefix);
+
+/* ------------------------------------------------------------------------------------
+ * Annotation from GTF: what comes before step 2 of the pipeline, bin/parseGencode and bin/gencodeIsoformMap
+ * ------------------------------------------------------------------------------------ */
+
+/* Device group.  Replaces `cat annotation.gtf | parseGencode` (a prebuilt binary; its rules were probed): the
+ * GTF's bytes are copied to HBM and every per-byte and per-line step runs there -- the nine TAB-separated fields, the
+ * `exon` filter on field 3, atoi of fields 4 and 5, gene_id and transcript_id of field 9 -- and one record per `exon` line
+ * comes back; the host orders the transcripts (gene id, then transcript id, bytewise) and sorts each one's starts and
+ * ends.  LSQ_E_PARSE with the reference's own "PROBLEM: ..." line in lsq_last_error() for the first line (of any feature)
+ * without gene_id or transcript_id or with an unquoted one, and for a line of fewer than nine fields (the reference dies
+ * there); lines that are empty or begin with '#' are skipped with a warning (the reference dies there too).
+ * lsq_gtf_parse_text takes the bytes from memory (standard input of the executable).  A line may be of any length and the
+ * last one needs no newline. */
+typedef struct lsq_gtf lsq_gtf;
+int lsq_gtf_parse(lsq_ctx *c, const char *path, lsq_gtf **out);
+int lsq_gtf_parse_text(lsq_ctx *c, const void *bytes, uint64_t len, lsq_gtf **out);
+void lsq_gtf_free(lsq_gtf *g);
+int64_t lsq_gtf_num_transcripts(const lsq_gtf *g);        /* output lines of parseGencode: distinct (gene id, transcript id) */
+int64_t lsq_gtf_num_genes(const lsq_gtf *g);              /* distinct gene ids */
+int64_t lsq_gtf_num_exon_lines(const lsq_gtf *g);         /* `exon` lines of the GTF */
+/* Transcript i in output order: "<gene_id>|<transcript_id>", chromosome and strand of its first `exon` line in file order */
+const char *lsq_gtf_transcript_name(const lsq_gtf *g, int64_t i);
+const char *lsq_gtf_transcript_chrom(const lsq_gtf *g, int64_t i);
+const char *lsq_gtf_transcript_strand(const lsq_gtf *g, int64_t i);
+/* Its exon starts (field 4 minus 1) and ends (field 5), each list sorted on its own as parseGencode prints them; returns
+ * the number of exons (-1: no such transcript).  The arrays live as long as g. */
+int64_t lsq_gtf_transcript_exons(const lsq_gtf *g, int64_t i, const int32_t **starts, const int32_t **ends);
+/* Replaces parseGencode's output and `cut -f1 x.interval | gencodeIsoformMap`: the LH_GENE_TXT text and the
+ * UCSC_GENE2ISOFORM text (malloc'd; lsq_free; either pointer may be null) */
+int lsq_gtf_format(const lsq_gtf *g, char **interval_text, char **map_text);
+/* Milliseconds of the parse by HIP events: ms[0] copy of the text to HBM, [1] newline scan, [2] parse kernels, [3] download */
+int lsq_gtf_result_times(const lsq_gtf *g, double *ms /* [4] */);
+/* Host-only (no GPU touched).  Replaces bin/gencodeIsoformMap: every line of names_text behind a counter and a TAB; the
+ * counter starts at 1 and goes up where the text before the line's first '|' differs from the line before.  Empty lines
+ * are dropped, "\r\n" ends a line as "\n" does, the last line needs no newline.  LSQ_E_PARSE, naming the line, for a line
+ * without '|' among others (the reference dies there; it prints such a line when it is the only one, and so does this). */
+int lsq_gtf_isoform_map(const char *names_text, uint64_t len, char **map_text);
+/* GTF -> annotation -> classify, all in memory: the graphs lsq_le_load_annotation makes from the two files that
+ * parseGencode and gencodeIsoformMap write for the same GTF.  Device group (the parse). */
+int lsq_le_load_gtf(lsq_ctx *c, const char *path, lsq_le_graphs **out);
 
 /* ------------------------------------------------------------------------------------
  * Synthetic workload; deterministic in (seed, sizes).  Host-only.

@@ -181,6 +181,20 @@ _sig("lsq_le_event", C.c_int, vp, C.c_int, i64, P(i64), P(i32))
 _sig("lsq_le_format", C.c_int, vp, C.c_int, P(vp), P(vp))
 _sig("lsq_le_result_times", C.c_int, vp, P(C.c_double))
 _sig("lsq_le_write", C.c_int, vp, cs)
+_sig("lsq_gtf_parse", C.c_int, vp, cs, P(vp))
+_sig("lsq_gtf_parse_text", C.c_int, vp, cs, u64, P(vp))
+_sig("lsq_gtf_free", None, vp)
+_sig("lsq_gtf_num_transcripts", i64, vp)
+_sig("lsq_gtf_num_genes", i64, vp)
+_sig("lsq_gtf_num_exon_lines", i64, vp)
+_sig("lsq_gtf_transcript_name", cs, vp, i64)
+_sig("lsq_gtf_transcript_chrom", cs, vp, i64)
+_sig("lsq_gtf_transcript_strand", cs, vp, i64)
+_sig("lsq_gtf_transcript_exons", i64, vp, i64, P(P(i32)), P(P(i32)))
+_sig("lsq_gtf_format", C.c_int, vp, P(vp), P(vp))
+_sig("lsq_gtf_result_times", C.c_int, vp, P(C.c_double))
+_sig("lsq_gtf_isoform_map", C.c_int, cs, u64, P(vp))
+_sig("lsq_le_load_gtf", C.c_int, vp, cs, P(vp))
 
 
 def _warn_on_runtime_mismatch():

@@ -197,7 +197,18 @@ size_t split_ws(const std::string &line, std::string *tok, size_t max_tok) {
 }
 
 // `while (getline(ifs, line) && !ifs.eof())`: only newline-terminated lines are seen
-bool read_lines(const char *path, std::vector<std::string> &lines) {
+void text_lines(const std::string &data, std::vector<std::string> &lines) {
+	size_t pos = 0;
+	while (pos < data.size()) {
+		size_t nl = data.find('\n', pos);
+		if (nl == std::string::npos) break;
+		lines.emplace_back(data, pos, nl - pos);
+		pos = nl + 1;
+	}
+}
+// (text: the file's content when the caller holds it already -- the annotation made from a GTF in memory, lsq_le_load_gtf)
+bool read_lines(const char *path, std::vector<std::string> &lines, const std::string *text = nullptr) {
+	if (text) { text_lines(*text, lines); return true; }
 	FILE *f = fopen(path, "rb");
 	if (!f) return false;
 	std::string data;
@@ -241,13 +252,16 @@ int lsq_abi_version(void) { return LSQ_ABI_VERSION; }
 void lsq_set_log_level(int level) { lsq::set_log_level(level); }
 void lsq_free(void *p) { free(p); }
 
-// count/count.cpp:135-216; the formats beyond LH_GENE_TXT / UCSC_GENE2ISOFORM are solve's (solve/solve.cpp:152-329)
-int lsq_annotation_load(const char *isoform_format, const char *isoforms_path,
-                        const char *g2i_format, const char *g2i_path,
-                        uint64_t gene_begin_idx, uint64_t gene_end_idx, lsq_annotation **out) LSQ_API_TRY {
-	if (!isoform_format || !isoforms_path || !g2i_format || !g2i_path || !out) return fail(LSQ_E_ARG, "null argument");
+} // extern "C"
+
+// count/count.cpp:135-216; the formats beyond LH_GENE_TXT / UCSC_GENE2ISOFORM are solve's (solve/solve.cpp:152-329).
+// isoforms_text / g2i_text: the two files' content where the caller holds it in memory (the paths then only name it in messages)
+namespace lsq {
+int annotation_load(const char *isoform_format, const char *isoforms_path, const std::string *isoforms_text,
+                    const char *g2i_format, const char *g2i_path, const std::string *g2i_text,
+                    uint64_t gene_begin_idx, uint64_t gene_end_idx, lsq_annotation **out) {
 	std::vector<std::string> lines;
-	if (!read_lines(isoforms_path, lines)) return fail(LSQ_E_IO, "cannot open isoforms file %s", isoforms_path);
+	if (!read_lines(isoforms_path, lines, isoforms_text)) return fail(LSQ_E_IO, "cannot open isoforms file %s", isoforms_path);
 	std::unique_ptr<lsq_annotation> a(new lsq_annotation);
 	const std::string ifmt = isoform_format;
 	// isoforms given exon by exon (one line per exon, any order): name -> chromosome, strand and the
@@ -344,7 +358,7 @@ int lsq_annotation_load(const char *isoform_format, const char *isoforms_path,
 	for (auto &r : a->recs) by_name[r->name] = r.get();
 
 	lines.clear();
-	if (!read_lines(g2i_path, lines)) return fail(LSQ_E_IO, "cannot open gene->isoform file %s", g2i_path);
+	if (!read_lines(g2i_path, lines, g2i_text)) return fail(LSQ_E_IO, "cannot open gene->isoform file %s", g2i_path);
 	const std::string gfmt = g2i_format;
 	if (gfmt != "UCSC_GENE2ISOFORM" && gfmt != "WORMBASE_GENE2ISOFORMS") return fail(LSQ_E_FORMAT, "Unknown file format error: %s", g2i_format);
 	std::map<std::string, std::vector<const IsoRec *>> genes;   // std::map: bytewise key order == std::set<string>
@@ -385,6 +399,16 @@ int lsq_annotation_load(const char *isoform_format, const char *isoforms_path,
 	}
 	*out = a.release();
 	return LSQ_OK;
+}
+} // namespace lsq
+
+extern "C" {
+
+int lsq_annotation_load(const char *isoform_format, const char *isoforms_path,
+                        const char *g2i_format, const char *g2i_path,
+                        uint64_t gene_begin_idx, uint64_t gene_end_idx, lsq_annotation **out) LSQ_API_TRY {
+	if (!isoform_format || !isoforms_path || !g2i_format || !g2i_path || !out) return fail(LSQ_E_ARG, "null argument");
+	return annotation_load(isoform_format, isoforms_path, nullptr, g2i_format, g2i_path, nullptr, gene_begin_idx, gene_end_idx, out);
 } LSQ_API_CATCH
 void lsq_annotation_free(lsq_annotation *a) { delete a; }
 int64_t lsq_annotation_num_genes(const lsq_annotation *a) { return a ? (int64_t)a->selected.size() : 0; }

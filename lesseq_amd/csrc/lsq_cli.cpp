@@ -21,6 +21,7 @@
 
 #include "lsq_internal.hpp"
 #include "lsq_localev.hpp"
+#include "lsq_gtf.hpp"
 
 using namespace lsq;
 
@@ -882,6 +883,8 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "classify") == 0) rc = run_classify(argc, argv);
 	else if (tool && strcmp(tool, "test_as") == 0) rc = run_test_as(argc, argv, out);
 	else if (tool && strcmp(tool, "events") == 0) rc = run_events(argc, argv, out);
+	else if (tool && strcmp(tool, "parseGencode") == 0) rc = run_parse_gencode(argc, argv, out);
+	else if (tool && strcmp(tool, "gencodeIsoformMap") == 0) rc = run_isoform_map(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -315,4 +315,9 @@ int host_count(lsq_ctx *c);                          // lsq_replay.hip: host buc
 int host_solve(lsq_ctx *c);
 int replay_flagged(lsq_ctx *c, unsigned *n_done);    // lsq_replay.hip: the EM of guard-band events in the reference's per-read order
 void select_counter_set(lsq_ctx *c, int set);                           // lsq_em.hip
+// lsq_ingest.hip, for lsq_gtf.hip: a text in host memory staged as lsq_text_stage stages a file; its newline tiles (T.d_tile_base:
+// newlines ahead of every tile of text_tile_bytes() bytes, T.n_nl: all of them)
+int text_stage_buffer(lsq_ctx *c, const void *bytes, unsigned long long len, const char *label, lsq_text &T);
+int text_scan_newlines(lsq_ctx *c, lsq_text &T);
+unsigned text_tile_bytes();
 } // namespace lsq

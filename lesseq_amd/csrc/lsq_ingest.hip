@@ -1131,6 +1131,41 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 
 } // namespace
 
+// What the GTF parser (lsq_gtf.hip) shares with the loader: the staging of a text and its newline tiles.
+namespace lsq {
+
+// lsq_text_stage for bytes that are already in host memory (standard input of an executable, a mapped file): the same copy
+// paths as stage_text_file -- the runtime's own staging below a gigabyte, the context's two pinned buffers filled by
+// memcpy() above -- and the same 16 bytes of slack behind the text.
+int text_stage_buffer(lsq_ctx *c, const void *bytes, unsigned long long len, const char *label, lsq_text &T) {
+	hipStream_t st = c->stream;
+	T.path = label; T.len = len; T.offset = 0; T.h2d_ms = 0; T.scanned = false; T.n_nl = 0;
+	if (len == 0) return LSQ_OK;
+	int rc;
+	if ((rc = T.d_text.alloc(len + 16))) return rc;
+	unsigned long long pinned_min = 1ull << 30;
+	if (const char *e = getenv("LSQ_PINNED_COPY_MIN")) { const long long v = atoll(e); if (v >= 0) pinned_min = (unsigned long long)v; }   // tests
+	bool pinned = len >= pinned_min && len >= 2 * PIN_SLICE;
+	HIP_TRY(hipEventRecord(c->evt0, st));
+	if (pinned && ensure_pinned_buffers(c) != LSQ_OK) pinned = false;
+	const unsigned char *src = (const unsigned char *)bytes;
+	if (pinned) {
+		if ((rc = pinned_pipeline(c, T.d_text.p, (size_t)len, [&](unsigned char *dst, size_t off, size_t n) { memcpy(dst, src + off, n); return true; }, label))) return rc;
+	} else {
+		for (unsigned long long off = 0; off < len; off += PIN_SLICE)
+			HIP_TRY(hipMemcpyAsync(T.d_text.p + off, src + off, (size_t)std::min<unsigned long long>(PIN_SLICE, len - off), hipMemcpyHostToDevice, st));
+		HIP_TRY(hipStreamSynchronize(st));
+	}
+	HIP_TRY(hipEventRecord(c->evt1, st));
+	HIP_TRY(hipEventSynchronize(c->evt1));
+	(void)hipEventElapsedTime(&T.h2d_ms, c->evt0, c->evt1);
+	return LSQ_OK;
+}
+int text_scan_newlines(lsq_ctx *c, lsq_text &T) { return scan_newlines(c, T); }
+unsigned text_tile_bytes() { return MRF_TILE; }
+
+} // namespace lsq
+
 extern "C" {
 
 int lsq_reads_upload(lsq_ctx *c, int method, const lsq_reads *R) LSQ_API_TRY {

@@ -20,7 +20,10 @@
 using namespace lsq;
 
 namespace lsq { int compile_events(const lsq_annotation *a, int n_methods, const char *const *read_types,
-                                   const uint64_t *lens, bool device_plan, lsq_events **out); }
+                                   const uint64_t *lens, bool device_plan, lsq_events **out);
+int annotation_load(const char *isoform_format, const char *isoforms_path, const std::string *isoforms_text,
+                    const char *g2i_format, const char *g2i_path, const std::string *g2i_text,
+                    uint64_t gene_begin_idx, uint64_t gene_end_idx, lsq_annotation **out); }      // lsq_annot.cpp
 
 void lsq_le_graphs::add_gene(const std::string &name, const std::string &ch, const std::string &st, int n, int k) {
 	if (pos_off.empty()) { pos_off.push_back(0); bit_off.push_back(0); }
@@ -151,10 +154,15 @@ struct GeneList {
 	}
 };
 
+int gene_list_of(const char *path, const std::string &text, GeneList &G);
 int read_gene_list(const char *path, GeneList &G) {
 	std::string text;
 	int rc = read_file(path, text);
 	if (rc) return rc;
+	return gene_list_of(path, text, G);
+}
+// (path names the text in messages)
+int gene_list_of(const char *path, const std::string &text, GeneList &G) {
 	std::vector<std::string> ids;
 	std::vector<uint64_t> line_of;
 	std::vector<std::pair<size_t, size_t>> f;
@@ -282,14 +290,16 @@ int load_matrices(const char *prefix, const char *group, lsq_le_graphs &out) {
 
 // annotation mode: classify's genes and matrices (lsq_cli.cpp run_classify), in memory; named and ordered as Events.r
 // names and orders the map's ids
-int load_annotation(const char *iso_fmt, const char *iso_path, const char *g2i_fmt, const char *g2i_path, lsq_le_graphs &out) {
+// iso_text / g2i_text: the two files' content where it is held in memory (lsq_le_load_gtf; the paths then name it in messages)
+int load_annotation(const char *iso_fmt, const char *iso_path, const char *g2i_fmt, const char *g2i_path, lsq_le_graphs &out,
+                    const std::string *iso_text = nullptr, const std::string *g2i_text = nullptr) {
 	if (strcmp(iso_fmt, "LH_GENE_TXT") != 0 || strcmp(g2i_fmt, "UCSC_GENE2ISOFORM") != 0)
 		return fail(LSQ_E_FORMAT, "Unknown file format error: %s", strcmp(iso_fmt, "LH_GENE_TXT") ? iso_fmt : g2i_fmt);
 	GeneList G;
-	int rc = read_gene_list(g2i_path, G);
+	int rc = g2i_text ? gene_list_of(g2i_path, *g2i_text, G) : read_gene_list(g2i_path, G);
 	if (rc) return rc;
 	lsq_annotation *a = nullptr;
-	if ((rc = lsq_annotation_load(iso_fmt, iso_path, g2i_fmt, g2i_path, 0, UINT64_MAX, &a))) return rc;
+	if ((rc = annotation_load(iso_fmt, iso_path, iso_text, g2i_fmt, g2i_path, g2i_text, 0, UINT64_MAX, &a))) return rc;
 	std::unique_ptr<lsq_annotation, void (*)(lsq_annotation *)> ann(a, lsq_annotation_free);
 	lsq_events *e = nullptr;
 	if ((rc = compile_events(a, 0, nullptr, nullptr, false, &e))) return rc;
@@ -441,28 +451,50 @@ std::string processing_lines(const lsq_le_graphs &g) {
 const char *USAGE =
 	"Usage:\n"
 	"events <matrix_prefix> <group_file> <out_prefix>\n"
-	"events --annotation <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <out_prefix>";
+	"events --annotation <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <out_prefix>\n"
+	"events --gtf <gtf_path> <out_prefix>";
 
 } // namespace
 
 namespace lsq {
 
+// classify in memory on an annotation that is held as text: lsq_le_load_gtf (lsq_gtf.cpp)
+int le_graphs_from_texts(const std::string &interval_text, const std::string &map_text, const char *label, lsq_le_graphs &out) {
+	const std::string a = std::string(label) + " (as LH_GENE_TXT)", b = std::string(label) + " (as UCSC_GENE2ISOFORM)";
+	return load_annotation("LH_GENE_TXT", a.c_str(), "UCSC_GENE2ISOFORM", b.c_str(), out, &interval_text, &map_text);
+}
+
 // events (argv[0] ignored).  Exit status: 0, 1 for a usage or input error (reported before any HIP call), 2 otherwise.
 int run_events(int argc, const char *const *argv, std::string &out) {
-	const bool annot = argc >= 2 && strcmp(argv[1], "--annotation") == 0;
+	const bool annot = argc >= 2 && strcmp(argv[1], "--annotation") == 0, gtf = argc >= 2 && strcmp(argv[1], "--gtf") == 0;
 	if (annot ? argc != 7 : argc != 4) { cli_log(0, USAGE); return 1; }
+	int dev = 0;
+	if (const char *e = getenv("LSQ_DEVICE")) dev = atoi(e);
+	lsq_ctx *c = nullptr;
+	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(nullptr, lsq_ctx_destroy);
 	lsq_le_graphs *raw = nullptr;
-	int st = annot ? lsq_le_load_annotation(argv[2], argv[3], argv[4], argv[5], &raw) : lsq_le_load_matrices(argv[1], argv[2], &raw);
+	int st;
+	if (gtf) {
+		// the GTF is parsed on the device (lsq_gtf.hip), so the context comes first; the output directory is still checked before anything is written
+		if ((st = check_out_prefix(argv[3]))) { cli_log(0, lsq_last_error()); return 1; }
+		st = lsq_ctx_create(dev, &c);
+		ctx.reset(c);
+		if (st) { cli_log(0, lsq_last_error()); return 2; }
+		st = lsq_le_load_gtf(c, argv[2], &raw);
+		if (st == LSQ_E_PARSE && strncmp(lsq_last_error(), "PROBLEM:", 8) == 0) { fprintf(stderr, "%s\n", lsq_last_error()); fflush(stderr); return 1; }
+		if (st == LSQ_E_DEVICE) { cli_log(0, lsq_last_error()); return 2; }
+	} else {
+		st = annot ? lsq_le_load_annotation(argv[2], argv[3], argv[4], argv[5], &raw) : lsq_le_load_matrices(argv[1], argv[2], &raw);
+	}
 	if (st) { cli_log(0, lsq_last_error()); return st == LSQ_E_INTERNAL ? 2 : 1; }
 	std::unique_ptr<lsq_le_graphs, void (*)(lsq_le_graphs *)> g(raw, lsq_le_graphs_free);
 	const char *prefix = annot ? argv[6] : argv[3];
 	if ((st = check_out_prefix(prefix))) { cli_log(0, lsq_last_error()); return 1; }
-	int dev = 0;
-	if (const char *e = getenv("LSQ_DEVICE")) dev = atoi(e);
-	lsq_ctx *c = nullptr;
 	lsq_le_result *res = nullptr;
-	st = lsq_ctx_create(dev, &c);
-	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(c, lsq_ctx_destroy);
+	if (!c) {
+		st = lsq_ctx_create(dev, &c);
+		ctx.reset(c);
+	}
 	if (!st) st = lsq_le_detect(c, g.get(), &res);
 	std::unique_ptr<lsq_le_result, void (*)(lsq_le_result *)> r(res, lsq_le_result_free);
 	if (st) { cli_log(0, lsq_last_error()); return 2; }

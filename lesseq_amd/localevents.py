@@ -1,6 +1,7 @@
 """Local events of the pipeline's step 2 (bin/Events.r): the eight local-event annotations (ES RI A5SS A3SS MXE AFE ALE
 T3) detected on the device from classify's splicing graphs (include/lesseq_hip.h, lsq_le_*).  Loading -- from a
-directory of .matrix files plus the gene list, or from an annotation with classify done in memory -- is host-only."""
+directory of .matrix files plus the gene list, or from an annotation with classify done in memory -- is host-only;
+Graphs.from_gtf starts from the GTF itself, which is parsed on the device."""
 import ctypes as C
 
 from ._lib import lib, check, vp
@@ -102,6 +103,14 @@ class Graphs:
     def from_annotation(cls, isoforms_path, g2i_path, isoform_format="LH_GENE_TXT", g2i_format="UCSC_GENE2ISOFORM"):
         h = vp()
         check(lib.lsq_le_load_annotation(_b(isoform_format), _b(isoforms_path), _b(g2i_format), _b(g2i_path), C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_gtf(cls, ctx, gtf_path):
+        """GTF -> annotation (parsed on the device, lesseq_amd.gencode) -> classify, all in memory: the graphs
+        from_annotation makes from the two files parseGencode and gencodeIsoformMap write for the same GTF"""
+        h = vp()
+        check(lib.lsq_le_load_gtf(ctx.h, _b(gtf_path), C.byref(h)))
         return cls(h)
 
     def __len__(self):
