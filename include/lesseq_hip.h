@@ -135,6 +135,25 @@ int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *e,
  * optional intron).  Lines of one name make one read; its names decide span-start ties against gene
  * names (solve/solve.cpp:70-98).  `count` takes MRF_SINGLE only, as in the reference. */
 int lsq_reads_parse(const char *read_format, const char *path, lsq_events *e, int n_threads, lsq_reads **out);
+/* "SAM_SINGLE": alignments as an aligner writes them, taken wherever "MRF_SINGLE" is (lsq_reads_parse, lsq_reads_upload_mrf,
+ * lsq_reads_upload_text, lsq_reads_upload_text_at, lsq_mrf_parse_device, the read_format slot of count and solve).  The format
+ * is DEFINED by its MRF_SINGLE equivalent (lesseq_amd/csrc/lsq_sam_line.hpp is the one statement of the
+ * rules): SAM line k, every line counted, is the read "read-<k>"; '@' lines, records with FLAG & skip_flags, MAPQ <
+ * min_mapq, RNAME "*", POS 0, CIGAR "*" or no block make no read; M = X D extend a block, N splits, I S move the query
+ * only, H P do nothing; the strand is FLAG & 0x10.  Every record is a read of its own (mates are not paired).
+ * lsq_sam_parse replaces what a foreign sam2mrf run followed by count/count.cpp:279-336 does: the arrays lsq_mrf_parse
+ * gives for the equivalent MRF file.  LSQ_E_PARSE with "#<k>:<line>" for the first malformed line (fewer than six fields,
+ * FLAG / MAPQ / POS not an unsigned decimal in range, a CIGAR of another shape, a reference end beyond 2^31-1).
+ * lsq_reads_parse("SAM_SINGLE") calls it with the defaults below. */
+#define LSQ_SAM_DEFAULT_SKIP_FLAGS 0x904u   /* unmapped, secondary, supplementary */
+#define LSQ_SAM_DEFAULT_MIN_MAPQ 0u
+int lsq_sam_parse(const char *path, lsq_events *e, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out);
+/* Defines the equivalence: the MRF_SINGLE text of a SAM text -- "AlignmentBlocks", then one line per SAM line that ends
+ * in '\n': "#" for a line that makes no read, else its blocks RNAME:<strand>:<s>:<e>:<qs>:<qe> joined by ','.  The
+ * reference's count and solve on that text are what count and solve here print for the SAM file.  *mrf_text is malloc'd
+ * and NUL-terminated (lsq_free); *mrf_len (may be null) its length.  Status as lsq_sam_parse.  The sam2mrf executable
+ * wraps this call. */
+int lsq_sam_to_mrf(const void *sam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len);
 /* Wraps caller-made arrays as a read set without copying (the arrays must outlive it).
  * blk_off has n_reads+1 entries; blocks are 0-based half-open; chrom_id / strand_id index
  * lsq_events_chrom_id() / lsq_events_strand_id() dictionaries; line_no is the 1-based line
@@ -233,6 +252,13 @@ int lsq_last_mrf_timing(lsq_ctx *c, float *h2d_ms, float *parse_ms);
 int lsq_ingest_stage_count(void);
 const char *lsq_ingest_stage_name(int stage);
 int lsq_last_ingest_stages(const lsq_ctx *c, float *ms, uint64_t *bytes, int capacity);
+/* The name of pass `stage` as the latest lsq_reads_upload* of the context ran it: lsq_ingest_stage_name's, except that the
+ * routing pass over SAM_SINGLE text is "sam_route" (other kernels than "route": lsq_sam_device.hpp). */
+const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage);
+/* Which of the SAM parse's kernels the latest SAM_SINGLE text of the context went through: lines the tile kernel handed to
+ * the fall-back kernel (a head longer than the tile kernel's window), and whether the whole file went through the
+ * byte-walking form (the line list ran over, or LSQ_SAM_SLOW is set).  Either pointer may be null. */
+int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow);
 uint64_t lsq_reads_retained(const lsq_ctx *c, int method);      /* "loaded N reads" log line */
 uint64_t lsq_reads_retained_blocks(const lsq_ctx *c, int method);
 /* Of the retained reads, those kept in the pools: reads whose first base lies in the span of an event planned on this
@@ -291,7 +317,8 @@ int lsq_host_evaluated(const lsq_ctx *c, uint64_t *n_genes, uint64_t *n_reads);
  * workgroups a compute unit and the pools are compact, else four; 4; 8), "workgroups_per_cu" (resident workgroups of the count kernel per compute unit: 0 = as many as fit, default -1 = five
  * when the EM runs its one-lane-per-event kernel beside it and the read set is evenly deep, else as many as fit), "em_flat_min_events" (default 16 384: with at
  * least that many two-isoform events the ones that converged within 32 iterations last time are solved one lane per
- * event instead of four -- fewer instructions, longer passes), "em_closed_form" (default 0; 1: two-isoform events with one read
+ * event instead of four -- fewer instructions, longer passes), "sam_skip_flags" (default 0x904) and "sam_min_mapq" (default 0): which records of SAM_SINGLE
+ * read files uploaded afterwards make no read -- these two do decide results; the executables also take them from LSQ_SAM_SKIP_FLAGS and LSQ_SAM_MIN_MAPQ), "em_closed_form" (default 0; 1: two-isoform events with one read
  * file run six ordinary EM iterations and finish in the closed form of their EM map -- the step of read.h:592-618 is then a
  * Moebius map of theta_0, theta after m more iterations one exponential away, and the iteration at which read.h:659 stops
  * is found by search: the same iteration counts, theta within 1e-13; pays where the slowest events take hundreds of
@@ -583,6 +610,10 @@ int lsq_synth_write(const lsq_synth_spec *s, const char *dir, const char *stem, 
 /* Generates the reads directly as a read set against already compiled events made from
  * lsq_synth_write's annotation with the same spec (no text round trip). */
 int lsq_synth_reads(const lsq_synth_spec *s, lsq_events *e, int n_threads, lsq_reads **out);
+/* Writes <stem>.interval, <stem>.map and <stem>.sam: the reads of lsq_synth_write as SAM_SINGLE -- "@HD" / "@SQ" / "@PG" lines
+ * first (so read k of the MRF file is line k + 2 + n_chrom here), CIGARs of M and N, NH / NM tag columns, SEQ and QUAL of the
+ * read length. */
+int lsq_synth_write_sam(const lsq_synth_spec *s, const char *dir, const char *stem);
 
 #ifdef __cplusplus
 }

@@ -78,6 +78,8 @@ _sig("lsq_events_host_genes", i64, vp)
 _sig("lsq_events_set_shard", C.c_int, vp, u64, u64)
 _sig("lsq_mrf_parse", C.c_int, cs, cs, vp, C.c_int, P(vp))
 _sig("lsq_reads_parse", C.c_int, cs, cs, vp, C.c_int, P(vp))
+_sig("lsq_sam_parse", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
+_sig("lsq_sam_to_mrf", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
 _sig("lsq_reads_wrap", C.c_int, u64, P(u64), P(u32), P(i32), P(i32), P(u16), P(u8), P(vp))
 _sig("lsq_reads_free", None, vp)
 _sig("lsq_reads_count", u64, vp)
@@ -109,6 +111,8 @@ _sig("lsq_set_log_level", None, C.c_int)
 _sig("lsq_ingest_stage_count", C.c_int)
 _sig("lsq_ingest_stage_name", cs, C.c_int)
 _sig("lsq_last_ingest_stages", C.c_int, vp, P(C.c_float), P(u64), C.c_int)
+_sig("lsq_last_ingest_stage_name", cs, vp, C.c_int)
+_sig("lsq_last_sam_paths", C.c_int, vp, P(u32), P(u32))
 _sig("lsq_reads_retained", u64, vp, C.c_int)
 _sig("lsq_reads_retained_blocks", u64, vp, C.c_int)
 _sig("lsq_reads_pooled", u64, vp, C.c_int)
@@ -151,6 +155,7 @@ _sig("lsq_format_count", C.c_int, vp, C.c_int, P(u64), P(vp))
 _sig("lsq_format_solve", C.c_int, vp, C.c_int, P(u64), P(u64), P(C.c_double), P(C.c_double), P(C.c_double), P(vp))
 _sig("lsq_cli_run", C.c_int, cs, C.c_int, P(cs), P(vp))
 _sig("lsq_synth_write", C.c_int, P(SynthSpecStruct), cs, cs, C.c_int)
+_sig("lsq_synth_write_sam", C.c_int, P(SynthSpecStruct), cs, cs)
 _sig("lsq_as_fisher", C.c_int, vp, u64, P(C.c_double), P(C.c_double))
 _sig("lsq_as_lrt", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
 _sig("lsq_as_wilcox", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double))

@@ -165,6 +165,20 @@ class Events:
         return off
 
 
+SAM_DEFAULT_SKIP_FLAGS = 0x904      # unmapped, secondary, supplementary
+
+
+def sam_to_mrf(sam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0):
+    """the MRF_SINGLE text (bytes) that defines what a SAM_SINGLE text means (lsq_sam_to_mrf)"""
+    data = bytes(sam_bytes)
+    out, n = vp(), u64()
+    check(lib.lsq_sam_to_mrf(data, len(data), skip_flags, min_mapq, C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        lib.lsq_free(out)
+
+
 class Reads:
     """A parsed read set in file order: from an MRF file, caller arrays, or the synthetic generator"""
 
@@ -176,6 +190,13 @@ class Reads:
     def from_mrf(cls, path, events, n_threads=0, read_format="MRF_SINGLE"):
         h = vp()
         check(lib.lsq_reads_parse(_b(read_format), _b(path), events.h, n_threads, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_sam(cls, path, events, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0, n_threads=0):
+        """a SAM_SINGLE file through the host parser (lsq_sam_parse): the arrays from_mrf gives for its MRF equivalent"""
+        h = vp()
+        check(lib.lsq_sam_parse(_b(path), events.h, skip_flags, min_mapq, n_threads, C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -262,6 +283,21 @@ class Context:
         check(lib.lsq_mrf_parse_device(self.h, _b(read_format), _b(path), C.byref(h)))
         return Reads(h)
 
+    def upload_reads_sam(self, method, path):
+        """SAM text -> HBM -> parsed and ingested on the device (lsq_reads_upload_mrf with "SAM_SINGLE"; the records that
+        make no read: options sam_skip_flags / sam_min_mapq)"""
+        check(lib.lsq_reads_upload_mrf(self.h, method, b"SAM_SINGLE", _b(path)))
+
+    def parse_sam_device(self, path):
+        """the device SAM parser's blocks, copied back as a Reads (tests, tools)"""
+        return self.parse_mrf_device(path, read_format="SAM_SINGLE")
+
+    def sam_paths(self):
+        """(lines the tile kernel handed to the fall-back kernel, whole file through the byte-walking form) of the latest SAM ingest"""
+        a, b = u32(), u32()
+        check(lib.lsq_last_sam_paths(self.h, C.byref(a), C.byref(b)))
+        return {"lines_to_fall_back_kernel": a.value, "whole_file_byte_walking": bool(b.value)}
+
     def mrf_timing(self):
         a, b = C.c_float(), C.c_float()
         check(lib.lsq_last_mrf_timing(self.h, C.byref(a), C.byref(b)))
@@ -281,7 +317,7 @@ class Context:
         n = lib.lsq_ingest_stage_count()
         ms, by = (C.c_float * n)(), (C.c_uint64 * n)()
         check(lib.lsq_last_ingest_stages(self.h, ms, by, n))
-        return [{"stage": lib.lsq_ingest_stage_name(i).decode(), "ms": float(ms[i]), "bytes": int(by[i])} for i in range(n)]
+        return [{"stage": lib.lsq_last_ingest_stage_name(self.h, i).decode(), "ms": float(ms[i]), "bytes": int(by[i])} for i in range(n)]
 
     def retained(self, method):
         return lib.lsq_reads_retained(self.h, method)
@@ -457,6 +493,11 @@ class SynthSpec:
 
 def synth_write(spec, directory, stem, write_mrf=True):
     check(lib.lsq_synth_write(C.byref(spec.c), _b(directory), _b(stem), 1 if write_mrf else 0))
+
+
+def synth_write_sam(spec, directory, stem):
+    """<stem>.interval, <stem>.map and the reads of synth_write as <stem>.sam (lsq_synth_write_sam)"""
+    check(lib.lsq_synth_write_sam(C.byref(spec.c), _b(directory), _b(stem)))
 
 
 def format_count(events, cnt):

@@ -113,11 +113,14 @@ bool named_read_format(const char *fmt) {       // the read formats only `solve`
 	return strcmp(fmt, "UCSC_GFF") == 0 || strcmp(fmt, "UCSC_BED") == 0 || strcmp(fmt, "WORMBASE_GFF3") == 0;
 }
 
+// the read formats of one read per line that the device parses from the text itself (lsq_reads_upload_text)
+bool line_text_format(const char *fmt) { return strcmp(fmt, "MRF_SINGLE") == 0 || strcmp(fmt, "SAM_SINGLE") == 0; }
+
 int precheck_reads_file(const char *fmt, const char *path, bool solve) {
 	FILE *f = fopen(path, "rb");
 	if (!f) return fail(LSQ_E_IO, "cannot open reads file %s", path);
 	fclose(f);
-	if (strcmp(fmt, "MRF_SINGLE") != 0 && !(solve && named_read_format(fmt))) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", fmt);
+	if (!line_text_format(fmt) && !(solve && named_read_format(fmt))) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", fmt);
 	return LSQ_OK;
 }
 
@@ -182,6 +185,15 @@ struct PhaseTimer {
 
 // LSQ_OPTIONS="name=value,...": tuning knobs for lsq_ctx_set_option, read once per process
 int apply_env_options(lsq_ctx *c) {
+	// which records of SAM_SINGLE read files make no read (decimal, or 0x... / 0... as strtoul reads them)
+	for (const char *const *kv : {(const char *const[]){"LSQ_SAM_SKIP_FLAGS", "sam_skip_flags"}, (const char *const[]){"LSQ_SAM_MIN_MAPQ", "sam_min_mapq"}})
+		if (const char *e = getenv(kv[0])) {
+			char *end = nullptr;
+			const unsigned long v = strtoul(e, &end, 0);
+			if (end == e || *end) return fail(LSQ_E_ARG, "%s=%s is not a number", kv[0], e);
+			const int st = lsq_ctx_set_option(c, kv[1], (double)v);
+			if (st) return st;
+		}
 	const char *o = getenv("LSQ_OPTIONS");
 	if (!o) return LSQ_OK;
 	const std::string all(o);
@@ -452,7 +464,7 @@ int run_sharded_job(const ShardedJob &J, lsq_ctx *ctx0, lsq_events *ev0, std::ve
 		if ((s = lsq_events_set_shard(e, first[(size_t)r], count[(size_t)r])) || (s = lsq_events_upload(c, e))) return bad(s, lsq_last_error());
 		for (int m = 0; m < M; ++m) {
 			if (r == 0 && texts0[(size_t)m]) s = lsq_reads_upload_text(c, m, J.fmts[(size_t)m], texts0[(size_t)m]);
-			else if (strcmp(J.fmts[(size_t)m], "MRF_SINGLE") == 0 && (r > 0 || !texts0[(size_t)m])) s = lsq_reads_upload_mrf(c, m, J.fmts[(size_t)m], J.paths[(size_t)m]);
+			else if (line_text_format(J.fmts[(size_t)m]) && (r > 0 || !texts0[(size_t)m])) s = lsq_reads_upload_mrf(c, m, J.fmts[(size_t)m], J.paths[(size_t)m]);
 			else s = LSQ_E_UNSUPPORTED;
 			if (s == LSQ_E_UNSUPPORTED) {         // name-keyed formats, long strand strings: the host parser
 				lsq_reads *rd = nullptr;
@@ -594,7 +606,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 		ctx_ready.store(1, std::memory_order_release);
 		if (shard_reads) return;          // every GPU stages its own byte range later
 		for (int m = 0; m < M; ++m)
-			if (strcmp(fmts[m], "MRF_SINGLE") == 0 && lsq_text_stage(ctx_bg, paths[m], &texts[(size_t)m]) != LSQ_OK) texts[(size_t)m] = nullptr;
+			if (line_text_format(fmts[m]) && lsq_text_stage(ctx_bg, paths[m], &texts[(size_t)m]) != LSQ_OK) texts[(size_t)m] = nullptr;
 	};
 	// What the second thread made is released by this guard, which is declared BEFORE the thread group: on every way out
 	// of this function the group is destroyed first (it joins the thread, so nothing is being written any more), then the
@@ -885,6 +897,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "events") == 0) rc = run_events(argc, argv, out);
 	else if (tool && strcmp(tool, "parseGencode") == 0) rc = run_parse_gencode(argc, argv, out);
 	else if (tool && strcmp(tool, "gencodeIsoformMap") == 0) rc = run_isoform_map(argc, argv, out);
+	else if (tool && strcmp(tool, "sam2mrf") == 0) rc = run_sam2mrf(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

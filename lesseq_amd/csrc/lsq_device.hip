@@ -876,6 +876,12 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 		else if (n == "share_cost_hot") c->opt_share_cost_hot = value;
 		else c->opt_share_taper = value;
 		for (auto &r : c->reads) r.wg_grid = 0;
+	} else if (n == "sam_skip_flags") {
+		if (!(value >= 0 && value <= 65535)) return fail(LSQ_E_ARG, "sam_skip_flags must lie in 0..65535");
+		c->opt_sam_skip_flags = (unsigned)value;      // takes effect with the next upload of a SAM_SINGLE read set
+	} else if (n == "sam_min_mapq") {
+		if (!(value >= 0 && value <= 256)) return fail(LSQ_E_ARG, "sam_min_mapq must lie in 0..256");
+		c->opt_sam_min_mapq = (unsigned)value;
 	} else if (n == "compact_pools") {
 		c->opt_compact_pools = value != 0;        // takes effect with the next upload of a read set
 	} else if (n == "workgroups_per_cu") {

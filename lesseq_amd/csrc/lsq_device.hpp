@@ -281,6 +281,11 @@ struct lsq_ctx {
 	// how the latest device parse went (lsq_debug_last_parse_paths): tiles handed to the byte-walking kernel, lines handed to the shared
 	// splitter, and whether the whole file went through the byte-walking kernel
 	unsigned parse_tiles_handed = 0, parse_lines_listed = 0, parse_all_slow = 0;
+	// SAM_SINGLE read files (lsq_sam_device.hpp): which records make no read ("sam_skip_flags", "sam_min_mapq"), whether the
+	// latest text ingest was one, and what its kernels handed on (lsq_last_sam_paths)
+	unsigned opt_sam_skip_flags = 0x904u, opt_sam_min_mapq = 0u;
+	bool ing_sam = false;
+	unsigned sam_lines_listed = 0, sam_all_slow = 0;
 	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_mrf_device.hpp: pinned_pipeline)
 	unsigned char *pin_buf[2] = {nullptr, nullptr};
 	hipEvent_t pin_ev[2] = {nullptr, nullptr};

@@ -31,6 +31,7 @@
 
 #include "lsq_device.hpp"
 #include "lsq_mrf_line.hpp"
+#include "lsq_sam_line.hpp"
 
 namespace {
 
@@ -1046,9 +1047,12 @@ static void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_b
 // MRF text in HBM through the chain: newline counts, then the parse as the chain's routing pass
 static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text &T, unsigned has_header, unsigned long long first_line) {
 	if (!read_format) return fail(LSQ_E_ARG, "null argument");
-	if (strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
+	const bool sam = strcmp(read_format, "SAM_SINGLE") == 0;
+	if (!sam && strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
+	const SamOpts Q{c->opt_sam_skip_flags, c->opt_sam_min_mapq};
 	hipStream_t st = c->stream;
 	int rc;
+	c->ing_sam = sam;
 	c->mrf_h2d_ms = T.h2d_ms; c->mrf_parse_ms = 0;
 	stages_reset(c, T.scanned);
 	if (T.len && (rc = scan_newlines(c, T))) return rc;
@@ -1065,7 +1069,7 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 	// (at most one a tile begins ahead of its window; the rest is whatever the file holds -- when the list runs over, the
 	// whole file goes through the kernel that walks bytes)
 	unsigned long long list_cap = 1ull << 22;
-	if (const char *e = getenv("LSQ_MRF_LINE_LIST")) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }      // tests: the run-over path on a small file
+	if (const char *e = getenv(sam ? "LSQ_SAM_LINE_LIST" : "LSQ_MRF_LINE_LIST")) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }      // tests: the run-over path on a small file
 	const unsigned line_cap = (unsigned)std::min<unsigned long long>(n_lines, list_cap) + n_tiles + 1u;
 	DevBuf<MrfLongLine> d_lines;
 	DevBuf<unsigned> d_tiles, d_counts;
@@ -1094,7 +1098,7 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 		HIP_TRY(hipStreamSynchronize(st));
 		FD.ckey = d_ckey.p; FD.cid = d_cid.p; FD.usable = usable ? 1u : 0u;
 	}
-	bool all_slow = !FD.usable;
+	bool all_slow = sam ? getenv("LSQ_SAM_SLOW") != nullptr : !FD.usable;       // (LSQ_SAM_SLOW: the tests run the byte-walking form over whole files with it)
 	const unsigned side_grid = std::min(std::max(n_tiles, 1u), 4u * (unsigned)c->n_cu);
 	// a workgroup a tile: the kernel can also run as a grid of resident workgroups that stay for many tiles (LSQ_FAST_GRID workgroups a
 	// compute unit; developer aid) -- measured slower on C3: 7.4 ms at 6, 7.0 at 12, 6.7 at 24 against 6.1 with a workgroup a tile
@@ -1104,6 +1108,16 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 		int r2 = DD.reset_errors(s);
 		if (r2) return r2;
 		HIP_TRY(hipMemsetAsync(d_counts.p, 0, 16, s));
+		if (sam) {
+			// a workgroup a tile, as the MRF kernel is launched; the listed lines behind it
+			if (n_tiles && all_slow) hipLaunchKernelGGL(lsq_sam_route_kernel<true>, dim3(n_tiles), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H, n_tiles);
+			else if (n_tiles) {
+				hipLaunchKernelGGL(lsq_sam_route_kernel<false>, dim3(n_tiles), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H, n_tiles);
+				hipLaunchKernelGGL(lsq_sam_route_lines_kernel, dim3(std::min(line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H);
+			}
+			HIP_TRY(hipGetLastError());
+			return LSQ_OK;
+		}
 		if (!all_slow) {
 			hipLaunchKernelGGL(lsq_mrf_route_fast_kernel, dim3(std::min(n_tiles, fast_grid)), dim3(256), 0, s, X, DD.D, FD, RT, O, DD.d_err.p, H, n_tiles);
 			hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(std::min(side_grid, 256u)), dim3(256), 0, s, X, DD.D, RT, O, DD.d_err.p, H, n_tiles, 1u);
@@ -1118,7 +1132,8 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 		HIP_TRY(hipMemcpy(counts, d_counts.p, 16, hipMemcpyDeviceToHost));
 		if (counts[2] && !all_slow) { all_slow = true; return LSQ_RETRY; }
 		if (counts[2]) return fail(LSQ_E_INTERNAL, "the device parser's line list ran over");
-		c->parse_tiles_handed = all_slow ? 0u : counts[0]; c->parse_lines_listed = counts[1]; c->parse_all_slow = all_slow ? 1u : 0u;
+		if (sam) { c->sam_lines_listed = all_slow ? 0u : counts[1]; c->sam_all_slow = all_slow ? 1u : 0u; }
+		else { c->parse_tiles_handed = all_slow ? 0u : counts[0]; c->parse_lines_listed = counts[1]; c->parse_all_slow = all_slow ? 1u : 0u; }
 		return DD.settle(c, T, has_header, first_line, s);
 	};
 	c->reads[method].named = false;
@@ -1207,6 +1222,7 @@ int lsq_reads_upload(lsq_ctx *c, int method, const lsq_reads *R) LSQ_API_TRY {
 	SW.mark("upload: allocations, copies queued");
 	if (SW.on) { HIP_TRY(hipStreamSynchronize(st)); SW.mark("upload: copies done"); }
 	stages_reset(c, false);
+	c->ing_sam = false;
 	Front F;
 	front_of_raw(c, Rw, nblk, F);
 	if ((rc = ingest_device(c, method, F))) return rc;
@@ -1230,7 +1246,7 @@ int lsq_reads_upload_mrf(lsq_ctx *c, int method, const char *read_format, const 
 	if (rc) return rc;
 	lsq_text T;
 	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
-	rc = ingest_text(c, method, read_format, T, 1u, 1ull);
+	rc = ingest_text(c, method, read_format, T, text_has_header(read_format), 1ull);
 	SW.mark("upload_mrf: all");
 	return rc;
 } LSQ_API_CATCH
@@ -1257,7 +1273,7 @@ int lsq_text_lines(lsq_ctx *c, lsq_text *t, uint64_t *n_newlines) LSQ_API_TRY {
 void lsq_text_free(lsq_text *t) { delete t; }
 
 int lsq_reads_upload_text(lsq_ctx *c, int method, const char *read_format, lsq_text *t) LSQ_API_TRY {
-	return lsq_reads_upload_text_at(c, method, read_format, t, 1, 1);
+	return lsq_reads_upload_text_at(c, method, read_format, t, read_format ? (int)text_has_header(read_format) : 1, 1);
 } LSQ_API_CATCH
 
 int lsq_reads_upload_text_at(lsq_ctx *c, int method, const char *read_format, lsq_text *t, int has_header, uint64_t first_line) LSQ_API_TRY {
@@ -1277,7 +1293,7 @@ int lsq_mrf_parse_device(lsq_ctx *c, const char *read_format, const char *path, 
 	lsq_text T;
 	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
 	DevParsed P;
-	if ((rc = parse_staged_text(c, read_format, T, 1u, 1ull, P, &c->mrf_h2d_ms, &c->mrf_parse_ms))) return rc;
+	if ((rc = parse_staged_text(c, read_format, T, text_has_header(read_format), 1ull, P, &c->mrf_h2d_ms, &c->mrf_parse_ms))) return rc;
 	std::unique_ptr<lsq_reads> R(new lsq_reads);
 	R->o_blk_off.resize(P.n_reads + 1); R->o_line_no.resize(P.n_reads);
 	R->o_start.resize(P.n_blocks); R->o_end.resize(P.n_blocks); R->o_chrom.resize(P.n_blocks); R->o_strand.resize(P.n_blocks);
@@ -1314,6 +1330,13 @@ static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
 	"newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"};
 int lsq_ingest_stage_count(void) { return LSQ_INGEST_STAGES; }
 const char *lsq_ingest_stage_name(int stage) { return stage >= 0 && stage < LSQ_INGEST_STAGES ? INGEST_STAGE_NAMES[stage] : nullptr; }
+const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) { return c && c->ing_sam && stage == 1 ? "sam_route" : lsq_ingest_stage_name(stage); }
+int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {
+	if (!c) return LSQ_E_ARG;
+	if (lines_listed) *lines_listed = c->sam_lines_listed;
+	if (all_slow) *all_slow = c->sam_all_slow;
+	return LSQ_OK;
+}
 int lsq_last_ingest_stages(const lsq_ctx *c, float *ms, uint64_t *bytes, int capacity) LSQ_API_TRY {
 	if (!c) return fail(LSQ_E_ARG, "null context");
 	for (int s = 0; s < LSQ_INGEST_STAGES && s < capacity; ++s) {

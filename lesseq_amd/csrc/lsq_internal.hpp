@@ -296,5 +296,6 @@ int plan_device(lsq_events &E);
 int host_threads(int requested);
 void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
 int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
+int run_sam2mrf(int argc, const char *const *argv, std::string &out);        // lsq_sam.cpp: the sam2mrf executable
 
 } // namespace lsq

@@ -16,6 +16,7 @@
 
 #include "lsq_internal.hpp"
 #include "lsq_mrf_line.hpp"
+#include "lsq_sam_line.hpp"
 
 using namespace lsq;
 
@@ -48,7 +49,10 @@ struct Chunk {
 
 struct StrandCache { std::string s; int id = -1; };
 
-void parse_chunk(Chunk &ck, lsq_events *E) {
+struct SamOpts { unsigned skip_flags, min_mapq; };
+
+// sam == nullptr: MRF_SINGLE lines; otherwise SAM_SINGLE lines (lsq_sam_line.hpp) -- the blocks go the same way
+void parse_chunk(Chunk &ck, lsq_events *E, const SamOpts *sam) {
 	const int64_t LIM = (int64_t)1 << 30;
 	std::string last_chrom; int last_chrom_id = -2;
 	StrandCache sc[2];
@@ -60,10 +64,10 @@ void parse_chunk(Chunk &ck, lsq_events *E) {
 		MrfView line{p, (size_t)(nl - p)};
 		p = nl + 1;
 		++line_num;
-		if (mrf_line_is_skipped(line)) continue;
+		if (!sam && mrf_line_is_skipped(line)) continue;
 		uint64_t nb = 0;
 		int bad_status = LSQ_OK;
-		const bool ok = mrf_split_line(line, [&](MrfView chr, MrfView strand, int64_t start, int64_t end) {
+		auto take = [&](MrfView chr, MrfView strand, int64_t start, int64_t end) {
 			// chromosome: only names the events know can ever pass the containment filter
 			if (last_chrom_id == -2 || last_chrom.size() != chr.n || memcmp(last_chrom.data(), chr.p, chr.n) != 0) {
 				last_chrom.assign(chr.p, chr.n);
@@ -86,7 +90,16 @@ void parse_chunk(Chunk &ck, lsq_events *E) {
 			ck.bc.push_back(cid);
 			ck.bst.push_back((uint8_t)sid);
 			++nb;
-		});
+		};
+		bool ok;
+		if (sam) {
+			const size_t keep = ck.bs.size();
+			const int v = sam_split_line(line, sam->skip_flags, sam->min_mapq, [&](MrfView chr, bool minus, int64_t start, int64_t end, int64_t, int64_t) {
+				take(chr, MrfView{minus ? "-" : "+", 1}, start, end);
+			});
+			ok = v != SAM_MALFORMED;
+			if (ok && v != SAM_READ) { ck.bs.resize(keep); ck.be.resize(keep); ck.bc.resize(keep); ck.bst.resize(keep); continue; }
+		} else ok = mrf_split_line(line, take);
 		if (bad_status != LSQ_OK) { ck.status = bad_status; ck.err = "more than 256 distinct strand strings"; return; }
 		if (!ok) {
 			ck.status = LSQ_E_PARSE;
@@ -99,15 +112,8 @@ void parse_chunk(Chunk &ck, lsq_events *E) {
 	}
 }
 
-} // namespace
-
-extern "C" {
-
-int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *E, int n_threads, lsq_reads **out) LSQ_API_TRY {
-	if (!read_format || !path || !E || !out) return fail(LSQ_E_ARG, "null argument");
-	int fd = open(path, O_RDONLY);
-	if (fd < 0) return fail(LSQ_E_IO, "cannot open reads file %s", path);
-	if (strcmp(read_format, "MRF_SINGLE") != 0) { close(fd); return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format); }
+// a file of one read per line, parsed by a few threads over runs of whole lines (fd is closed here)
+int parse_line_file(int fd, const char *path, lsq_events *E, int n_threads, const SamOpts *sam, lsq_reads **out) {
 	struct stat st;
 	if (fstat(fd, &st) != 0) { close(fd); return fail(LSQ_E_IO, "cannot stat %s", path); }
 	size_t len = (size_t)st.st_size;
@@ -121,11 +127,11 @@ int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *E, int 
 		madvise((void *)data, len, MADV_SEQUENTIAL);
 	}
 	close(fd);
-	// first line skipped unconditionally (count/count.cpp:283); an unterminated tail is never seen (:285)
-	const char *body = data ? (const char *)memchr(data, '\n', len) : nullptr;
+	// MRF: first line skipped unconditionally (count/count.cpp:283); an unterminated tail is never seen (:285)
+	const char *body = !data ? nullptr : (sam ? data : (const char *)memchr(data, '\n', len));
 	const char *tail = nullptr;
 	if (body) {
-		++body;
+		if (!sam) ++body;
 		const char *e = data + len;
 		while (e > body && e[-1] != '\n') --e;
 		tail = e;
@@ -167,7 +173,7 @@ int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *E, int 
 		for (int t = 0; t < T; ++t) { chunks[t].first_line = ln; ln += nlines[t]; }
 		{
 			ThreadGroup th;
-			for (int t = 0; t < T; ++t) th.spawn([&, t] { parse_chunk(chunks[t], E); });
+			for (int t = 0; t < T; ++t) th.spawn([&, t] { parse_chunk(chunks[t], E, sam); });
 			th.join();
 			if (th.failed()) return fail(LSQ_E_INTERNAL, "a helper thread failed: %s", th.error().c_str());
 		}
@@ -195,6 +201,26 @@ int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *E, int 
 	R->adopt();
 	*out = R.release();
 	return LSQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int lsq_mrf_parse(const char *read_format, const char *path, lsq_events *E, int n_threads, lsq_reads **out) LSQ_API_TRY {
+	if (!read_format || !path || !E || !out) return fail(LSQ_E_ARG, "null argument");
+	int fd = open(path, O_RDONLY);
+	if (fd < 0) return fail(LSQ_E_IO, "cannot open reads file %s", path);
+	if (strcmp(read_format, "MRF_SINGLE") != 0) { close(fd); return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format); }
+	return parse_line_file(fd, path, E, n_threads, nullptr, out);
+} LSQ_API_CATCH
+
+int lsq_sam_parse(const char *path, lsq_events *E, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out) LSQ_API_TRY {
+	if (!path || !E || !out) return fail(LSQ_E_ARG, "null argument");
+	int fd = open(path, O_RDONLY);
+	if (fd < 0) return fail(LSQ_E_IO, "cannot open reads file %s", path);
+	const SamOpts sam{skip_flags, min_mapq};
+	return parse_line_file(fd, path, E, n_threads, &sam, out);
 } LSQ_API_CATCH
 
 // solve's name-keyed read formats (solve/solve.cpp:413-428 UCSC_GFF, :487-551 UCSC_BED, :552-634
@@ -207,6 +233,7 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 	if (!read_format || !path || !E || !out) return fail(LSQ_E_ARG, "null argument");
 	const std::string fmt = read_format;
 	if (fmt == "MRF_SINGLE") return lsq_mrf_parse(read_format, path, E, n_threads, out);
+	if (fmt == "SAM_SINGLE") return lsq_sam_parse(path, E, SAM_DEFAULT_SKIP_FLAGS, SAM_DEFAULT_MIN_MAPQ, n_threads, out);
 	FILE *fp = fopen(path, "rb");
 	if (!fp) return fail(LSQ_E_IO, "cannot open reads file %s", path);
 	if (fmt != "UCSC_GFF" && fmt != "UCSC_BED" && fmt != "WORMBASE_GFF3") { fclose(fp); return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format); }

@@ -703,6 +703,8 @@ __global__ void __launch_bounds__(256) lsq_mrf_write_kernel(MrfText X, const uns
 	});
 }
 
+#include "lsq_sam_device.hpp"
+
 struct DevParsed {
 	uint64_t n_reads = 0, n_blocks = 0;
 	DevBuf<unsigned long long> blk_off;
@@ -963,7 +965,9 @@ struct MrfDictDev {
 static int parse_staged_text(lsq_ctx *c, const char *read_format, lsq_text &T, unsigned has_header, unsigned long long first_line, DevParsed &out, float *h2d_ms, float *parse_ms) {
 	if (!read_format) return fail(LSQ_E_ARG, "null argument");
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	if (strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
+	const bool sam = strcmp(read_format, "SAM_SINGLE") == 0;
+	if (!sam && strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
+	const SamOpts Q{c->opt_sam_skip_flags, c->opt_sam_min_mapq};
 	hipStream_t st = c->stream;
 	int rc;
 	const unsigned long long zero_off = 0;
@@ -991,7 +995,8 @@ static int parse_staged_text(lsq_ctx *c, const char *read_format, lsq_text &T, u
 	MrfDictDev DD;
 	if ((rc = d_line_nb.alloc(n_lines)) || (rc = d_rd_idx.alloc(n_lines + 1)) || (rc = d_bk_off.alloc(n_lines + 1)) || (rc = SS.reserve(n_lines)) || (rc = DD.build(c, st))) return rc;
 	MrfText X{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines};
-	hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(n_tiles), dim3(256), 0, st, X, d_line_nb.p, DD.d_err.p);
+	if (sam) hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(n_tiles), dim3(256), 0, st, X, Q, d_line_nb.p, DD.d_err.p);
+	else hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(n_tiles), dim3(256), 0, st, X, d_line_nb.p, DD.d_err.p);
 	HIP_TRY(hipGetLastError());
 	if ((rc = device_scan<1, true>(SS, d_line_nb.p, n_lines, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, n_lines, d_bk_off.p, st))) return rc;
 	unsigned long long n_reads = 0, n_blocks = 0;
@@ -1002,7 +1007,9 @@ static int parse_staged_text(lsq_ctx *c, const char *read_format, lsq_text &T, u
 	    (rc = out.bc.alloc(n_blocks)) || (rc = out.bst.alloc(n_blocks))) return rc;
 	MrfOut O{};
 	O.blk_off = out.blk_off.p; O.line_no = out.line_no.p; O.blk_start = out.bs.p; O.blk_end = out.be.p; O.blk_chrom = out.bc.p; O.blk_strand = out.bst.p;
-	hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(n_tiles), dim3(256), 0, st, X, (const unsigned *)d_line_nb.p, (const unsigned long long *)d_rd_idx.p,
+	if (sam) hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(n_tiles), dim3(256), 0, st, X, Q, (const unsigned *)d_line_nb.p, (const unsigned long long *)d_rd_idx.p,
+	                            (const unsigned long long *)d_bk_off.p, DD.D, O, DD.d_err.p);
+	else hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(n_tiles), dim3(256), 0, st, X, (const unsigned *)d_line_nb.p, (const unsigned long long *)d_rd_idx.p,
 	                   (const unsigned long long *)d_bk_off.p, DD.D, O, DD.d_err.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->ev2, st));
@@ -1018,6 +1025,8 @@ static int check_mrf_file(const char *read_format, const char *path) {
 	FILE *f = fopen(path, "rb");
 	if (!f) return fail(LSQ_E_IO, "cannot open reads file %s", path);
 	fclose(f);
-	if (strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
+	if (strcmp(read_format, "MRF_SINGLE") != 0 && strcmp(read_format, "SAM_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
 	return LSQ_OK;
 }
+// a whole file: MRF's first line is its header; every line of a SAM file counts ("read-<k>", k from 1)
+static unsigned text_has_header(const char *read_format) { return strcmp(read_format, "SAM_SINGLE") == 0 ? 0u : 1u; }

@@ -339,6 +339,73 @@ int lsq_synth_write(const lsq_synth_spec *S, const char *dir, const char *stem, 
 	return LSQ_OK;
 } LSQ_API_CATCH
 
+// The reads of lsq_synth_write as SAM_SINGLE: header lines, then a record per read -- QNAME, FLAG (0 / 16), RNAME, POS, MAPQ 255,
+// a CIGAR of M and N, "*	0	0", SEQ and QUAL of the read's bases, NH and NM tags.  (A read whose second block does not lie behind
+// its first -- the generator's adversarial reads on a one-exon form -- has no CIGAR: its first block alone is written.)
+int lsq_synth_write_sam(const lsq_synth_spec *S, const char *dir, const char *stem) LSQ_API_TRY {
+	if (!S || !dir || !stem) return fail(LSQ_E_ARG, "null argument");
+	int rc = lsq_synth_write(S, dir, stem, 0);
+	if (rc) return rc;
+	SynModel Mo;
+	if ((rc = build_model(*S, Mo))) return rc;
+	const std::string base = std::string(dir) + "/" + stem;
+	FILE *fr = fopen((base + ".sam").c_str(), "w");
+	if (!fr) return fail(LSQ_E_IO, "cannot write under %s", dir);
+	fputs("@HD\tVN:1.6\tSO:unsorted\n", fr);
+	for (uint32_t c = 0; c < S->n_chrom; ++c) fprintf(fr, "@SQ\tSN:%s\tLN:%lld\n", chrom_name((int)c).c_str(), (long long)Mo.chrom_end[c] + 40000);
+	fputs("@PG\tID:lsq_synth\tPN:lsq_synth\n", fr);
+	const int T = host_threads(0);
+	const uint64_t CHUNK = 1u << 16;
+	std::vector<std::string> bufs((size_t)T);
+	std::vector<uint32_t> order;
+	if (S->sorted && (rc = sorted_order(*S, Mo, order))) { fclose(fr); return rc; }
+	auto put_int = [](std::string &o, long long v) {
+		char tmp[24]; int n = 0;
+		if (v < 0) { o.push_back('-'); v = -v; }
+		do { tmp[n++] = (char)('0' + v % 10); v /= 10; } while (v);
+		while (n) o.push_back(tmp[--n]);
+	};
+	bool io_ok = true;
+	for (uint64_t round0 = 0; round0 < S->n_reads && io_ok; round0 += CHUNK * (uint64_t)T) {
+		ThreadGroup th;
+		for (int t = 0; t < T; ++t) {
+			th.spawn([&, t] {
+				std::string &o = bufs[(size_t)t];
+				o.clear();
+				const uint64_t i0 = round0 + CHUNK * (uint64_t)t, i1 = std::min<uint64_t>(i0 + CHUNK, S->n_reads);
+				OneRead r;
+				for (uint64_t i = i0; i < i1; ++i) {
+					const uint64_t no = S->first_read + (order.empty() ? i : (uint64_t)order[i]);
+					gen_read(*S, Mo, no, r);
+					int nb = r.nb;
+					for (int b = 1; b < nb; ++b) if (r.bs[b] < r.be[b - 1]) nb = b;
+					o += "r"; put_int(o, (long long)no); o.push_back('\t');
+					o += r.strand == '-' ? "16" : "0";
+					o += "\tchr"; put_int(o, r.chrom + 1); o.push_back('\t');
+					put_int(o, (long long)r.bs[0] + 1); o += "\t255\t";
+					long long bases = 0;
+					for (int b = 0; b < nb; ++b) {
+						if (b) { put_int(o, (long long)r.bs[b] - r.be[b - 1]); o.push_back('N'); }
+						put_int(o, (long long)r.be[b] - r.bs[b]); o.push_back('M');
+						bases += r.be[b] - r.bs[b];
+					}
+					o += "\t*\t0\t0\t";
+					uint64_t x = no * 0x9E3779B97F4A7C15ull + S->seed;
+					for (long long k = 0; k < bases; ++k) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; o.push_back("ACGT"[x & 3]); }
+					o.push_back('\t');
+					for (long long k = 0; k < bases; ++k) { x ^= x << 13; x ^= x >> 7; x ^= x << 17; o.push_back((char)('#' + x % 40)); }      // '#' .. 'J': holds ',' ':' '@'
+					o += "\tNH:i:1\tNM:i:"; put_int(o, (long long)(x % 3)); o.push_back('\n');
+				}
+			});
+		}
+		th.join();
+		if (th.failed()) { fclose(fr); return fail(LSQ_E_INTERNAL, "a helper thread failed: %s", th.error().c_str()); }
+		for (int t = 0; t < T; ++t) if (!bufs[(size_t)t].empty() && fwrite(bufs[(size_t)t].data(), 1, bufs[(size_t)t].size(), fr) != bufs[(size_t)t].size()) io_ok = false;
+	}
+	if (fclose(fr) != 0 || !io_ok) return fail(LSQ_E_IO, "cannot write %s.sam", base.c_str());
+	return LSQ_OK;
+} LSQ_API_CATCH
+
 int lsq_synth_reads(const lsq_synth_spec *S, lsq_events *E, int n_threads, lsq_reads **out) LSQ_API_TRY {
 	if (!S || !E || !out) return fail(LSQ_E_ARG, "null argument");
 	SynModel Mo;

@@ -12,6 +12,6 @@
 int main(int argc, char **argv) {
 	const char *base = strrchr(argv[0], '/');
 	base = base ? base + 1 : argv[0];
-	const char *tool = strstr(base, "parseGencode") ? "parseGencode" : strstr(base, "gencodeIsoformMap") ? "gencodeIsoformMap" : strstr(base, "events") ? "events" : strstr(base, "test_as") ? "test_as" : strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
+	const char *tool = strstr(base, "sam2mrf") ? "sam2mrf" : strstr(base, "parseGencode") ? "parseGencode" : strstr(base, "gencodeIsoformMap") ? "gencodeIsoformMap" : strstr(base, "events") ? "events" : strstr(base, "test_as") ? "test_as" : strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
 	return lsq_cli_main(tool, argc, argv);
 }
