@@ -1,7 +1,8 @@
 // Shared by the HIP translation units of the device group (not part of the ABI): device buffers, the
 // per-read-file state, the context, and the entry points one unit offers the others.
 //   lsq_device.hip  context, event tables, result fetch         lsq_count.hip  count kernels
-//   lsq_ingest.hip  loader kernels (MRF parse, filter, pools)    lsq_em.hip     EM kernel
+//   lsq_ingest.hip  loader kernels (read parsers, filter, pools) lsq_em.hip     EM kernel
+//   lsq_text.hip    texts staged in HBM, their newline tiles
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -281,12 +282,12 @@ struct lsq_ctx {
 	// how the latest device parse went (lsq_debug_last_parse_paths): tiles handed to the byte-walking kernel, lines handed to the shared
 	// splitter, and whether the whole file went through the byte-walking kernel
 	unsigned parse_tiles_handed = 0, parse_lines_listed = 0, parse_all_slow = 0;
-	// SAM_SINGLE read files (lsq_sam_device.hpp): which records make no read ("sam_skip_flags", "sam_min_mapq"), whether the
-	// latest text ingest was one, and what its kernels handed on (lsq_last_sam_paths)
+	// SAM_SINGLE read files (lsq_sam_device.hpp): which records make no read ("sam_skip_flags", "sam_min_mapq") and what the
+	// kernels of the latest one handed on (lsq_last_sam_paths)
 	unsigned opt_sam_skip_flags = 0x904u, opt_sam_min_mapq = 0u;
-	bool ing_sam = false;
+	int ing_format = -1;                    // the read format of the latest ingest (lsq_ingest.hip: READ_FORMATS), -1: parsed blocks from the host
 	unsigned sam_lines_listed = 0, sam_all_slow = 0;
-	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_mrf_device.hpp: pinned_pipeline)
+	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_text.hip: pinned_pipeline)
 	unsigned char *pin_buf[2] = {nullptr, nullptr};
 	hipEvent_t pin_ev[2] = {nullptr, nullptr};
 	// device time and bytes of the stages of the latest ingest (lsq_ingest.hip: lsq_last_ingest_stages)
@@ -296,7 +297,7 @@ struct lsq_ctx {
 	bool ing_seen[LSQ_INGEST_STAGES] = {};
 };
 
-// MRF text of one file in HBM (lsq_text_stage).  Staging needs no event tables: the executables start it
+// The text of one file in HBM (lsq_text_stage).  Staging needs no event tables: the executables start it
 // on a second thread while the first is still reading the annotation.
 struct lsq_text {
 	std::string path;
@@ -305,7 +306,7 @@ struct lsq_text {
 	float h2d_ms = 0;
 	bool scanned = false;                           // newlines counted (lsq_text_lines or the parse)
 	unsigned long long n_nl = 0;
-	lsq::DevBuf<unsigned long long> d_tile_base;    // per 8 KiB tile of the text: newlines ahead of it (n_tiles + 1)
+	lsq::DevBuf<unsigned long long> d_tile_base;    // per tile of the text (lsq_text.hpp: TEXT_TILE bytes): newlines ahead of it (n_tiles + 1)
 };
 
 namespace lsq {
@@ -320,9 +321,4 @@ int host_count(lsq_ctx *c);                          // lsq_replay.hip: host buc
 int host_solve(lsq_ctx *c);
 int replay_flagged(lsq_ctx *c, unsigned *n_done);    // lsq_replay.hip: the EM of guard-band events in the reference's per-read order
 void select_counter_set(lsq_ctx *c, int set);                           // lsq_em.hip
-// lsq_ingest.hip, for lsq_gtf.hip: a text in host memory staged as lsq_text_stage stages a file; its newline tiles (T.d_tile_base:
-// newlines ahead of every tile of text_tile_bytes() bytes, T.n_nl: all of them)
-int text_stage_buffer(lsq_ctx *c, const void *bytes, unsigned long long len, const char *label, lsq_text &T);
-int text_scan_newlines(lsq_ctx *c, lsq_text &T);
-unsigned text_tile_bytes();
 } // namespace lsq

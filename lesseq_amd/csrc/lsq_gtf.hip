@@ -1,9 +1,9 @@
 // GTF annotation parsed on the device: what bin/parseGencode does per byte and per line (the host side --
-// sorting the transcripts, formatting, the executables -- is lsq_gtf.cpp).  The text is staged in HBM as the loader stages
-// MRF text and its newline tiles are the loader's (lsq_ingest.hip: text_stage_buffer, text_scan_newlines).
+// sorting the transcripts, formatting, the executables -- is lsq_gtf.cpp).  The text is staged in HBM and its newline tiles
+// are counted by the text layer the read parsers use (lsq_text.hip: text_stage_buffer, scan_newlines).
 //
 //   lsq_gtf_lines_kernel   one workgroup per tile of the newline scan.  The tile and GTF_AHEAD bytes behind it go to LDS with
-//                          16-byte loads; the tile's newlines are listed in order (zero-byte tests, a workgroup scan), so
+//                          16-byte loads; the tile's newlines are listed in order (lsq_text.hpp: TextTileNl), so
 //                          that line j that STARTS in the tile has the number tile base + j.  A wave takes a line: the 64
 //                          lanes look at 64 bytes at a time and ballots find the TABs, the end of the line, the first
 //                          "gene_id" / "transcript_id", the ';' around it and the quotes inside -- every branch is the same
@@ -17,8 +17,7 @@
 //   device_scan + lsq_gtf_emit_heads_kernel   the run heads, compacted
 // Only the run heads (one per transcript, more where a transcript's lines are scattered), the (start, end) pairs and three
 // words of status come back; the text does not.
-#include "lsq_device.hpp"
-#include "lsq_scan.hpp"
+#include "lsq_text.hpp"
 #include "lsq_gtf.hpp"
 
 #include <fcntl.h>
@@ -30,15 +29,13 @@ using namespace lsq;
 
 namespace {
 
-constexpr unsigned GTF_MAX_TILE = 7680;         // the newline scan's tile (text_tile_bytes()); nlpos holds a tile of empty lines
 constexpr unsigned GTF_AHEAD = 2560;            // bytes behind the tile that are staged with it: lines that start in the tile end here, mostly
-constexpr unsigned GTF_WINDOW = GTF_MAX_TILE + GTF_AHEAD;
+static_assert(TEXT_TILE % 16u == 0 && GTF_AHEAD % 16u == 0, "the window is staged in 16-byte words");
 constexpr unsigned long long GTF_NONE = ~0ull;
 
 struct GtfLds {
-	__align__(16) unsigned char text[GTF_WINDOW];
-	unsigned short nlpos[GTF_MAX_TILE];
-	unsigned long long scan16[16];
+	__align__(16) unsigned char text[TEXT_TILE + GTF_AHEAD];
+	TextNlLds nl;
 };
 
 // the text as a wave reads it: LDS inside the window [w0, w1), HBM elsewhere
@@ -51,15 +48,6 @@ struct GtfView {
 
 __device__ inline unsigned gtf_lane() { return threadIdx.x & 63u; }
 __device__ inline unsigned gtf_ctz(unsigned long long m) { return (unsigned)__ffsll((long long)m) - 1u; }
-
-// bit j set iff byte j of the 16 is '\n' (the first `valid` bytes count)
-__device__ inline unsigned gtf_newline_bits(const uint4 v, unsigned valid) {
-	const unsigned w[4] = {v.x, v.y, v.z, v.w};
-	unsigned bits = 0;
-#pragma unroll
-	for (unsigned j = 0; j < 16; ++j) bits |= (((w[j >> 2] >> (8u * (j & 3u))) & 0xFFu) == 0x0Au ? 1u : 0u) << j;
-	return valid >= 16u ? bits : (bits & ((1u << valid) - 1u));
-}
 
 // first position in [from, to) that holds ch, or `to`.  to <= len.
 __device__ inline unsigned long long gtf_find_first(const GtfView &V, unsigned char ch, unsigned long long from, unsigned long long to) {
@@ -187,37 +175,31 @@ __device__ inline void gtf_line(const GtfView &V, unsigned long long s, unsigned
 	}
 }
 
-__global__ void __launch_bounds__(256) lsq_gtf_lines_kernel(const unsigned char *text, unsigned long long len, const unsigned long long *tile_base, unsigned tile,
+__global__ void __launch_bounds__(256) lsq_gtf_lines_kernel(const unsigned char *text, unsigned long long len, const unsigned long long *tile_base,
                                                             GtfRec *rec, unsigned *keep, GtfStatus *status) {
 	__shared__ GtfLds L;
-	const unsigned long long t0 = (unsigned long long)blockIdx.x * tile;
-	// the window: 16 bytes a lane and round (the buffer holds 16 bytes of slack behind the text; t0 is a multiple of 16)
-	const unsigned long long w1 = min(len, t0 + tile + GTF_AHEAD);
-	for (unsigned off = threadIdx.x * 16u; t0 + off < w1; off += 256u * 16u)
+	const unsigned long long t0 = (unsigned long long)blockIdx.x * TEXT_TILE;
+	// the window: the tile, its newlines found on the way, and GTF_AHEAD bytes behind it, 16 bytes a lane and round (the buffer
+	// holds 16 bytes of slack behind the text; t0 is a multiple of 16)
+	const unsigned long long w1 = min(len, t0 + TEXT_TILE + GTF_AHEAD);
+	TextTileNl N;
+	N.load(L.text, text, len, t0);
+	for (unsigned off = TEXT_TILE + threadIdx.x * 16u; t0 + off < w1; off += 256u * 16u)
 		*reinterpret_cast<uint4 *>(L.text + off) = *reinterpret_cast<const uint4 *>(text + t0 + off);
-	// the tile's newlines, in order
-	unsigned n_nl = 0;
-	for (unsigned r0 = 0; r0 < tile; r0 += 256u * 16u) {
-		const unsigned off = r0 + threadIdx.x * 16u;
-		unsigned bits = 0;
-		if (off < tile && t0 + off < len) {
-			const unsigned valid = (unsigned)min((unsigned long long)min(16u, tile - off), len - (t0 + off));
-			bits = gtf_newline_bits(*reinterpret_cast<const uint4 *>(text + t0 + off), valid);
-		}
-		unsigned long long total;
-		unsigned at = n_nl + (unsigned)scan_block_excl((unsigned long long)__popc(bits), L.scan16, total);
-		while (bits) { L.nlpos[at++] = (unsigned short)(off + (unsigned)__ffs((int)bits) - 1u); bits &= bits - 1u; }
-		n_nl += (unsigned)total;
-	}
-	__syncthreads();
+	N.number(L.nl);                                  // (its barriers also publish L.text)
 	const GtfView V{text, L.text, len, t0, w1};
 	const unsigned long long base = tile_base[blockIdx.x];      // newlines ahead of the tile: line `base` is the one that holds t0 (or starts at it)
-	// the lines that start in the tile: behind each of its newlines, and at byte 0 of the text
-	const int first = blockIdx.x == 0 ? -1 : 0;
-	for (int j = first + (int)(threadIdx.x >> 6); j < (int)n_nl; j += 4) {
-		const unsigned long long s = j < 0 ? 0ull : t0 + L.nlpos[j] + 1ull;
-		if (s >= len) continue;               // the text ends with this newline
-		gtf_line(V, s, j < 0 ? 0ull : base + (unsigned long long)j + 1ull, rec, keep, status);
+	// the lines that start in the tile: at byte 0 of the text, and behind each of the tile's newlines; a wave takes every fourth
+	const unsigned wave = threadIdx.x >> 6;
+	if (blockIdx.x == 0 && wave == 0) gtf_line(V, 0ull, 0ull, rec, keep, status);
+	for (unsigned rb = 0; rb < N.nt; rb += TEXT_NLCAP) {
+		N.round(L.nl, rb);
+		const unsigned r_end = min(N.nt, rb + TEXT_NLCAP);
+		for (unsigned j = rb + wave; j < r_end; j += 4u) {
+			const unsigned long long s = t0 + L.nl.nlpos[j - rb] + 1ull;
+			if (s >= len) continue;               // the text ends with this newline
+			gtf_line(V, s, base + (unsigned long long)j + 1ull, rec, keep, status);
+		}
 	}
 }
 
@@ -271,19 +253,17 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 	if (len == 0) { *out = G.release(); return LSQ_OK; }
 	HIP_TRY(hipSetDevice(c->device));
 	hipStream_t st = c->stream;
-	const unsigned tile = text_tile_bytes();
-	if (tile > GTF_MAX_TILE || tile % 16u) return fail(LSQ_E_INTERNAL, "the newline scan's tile of %u bytes does not fit the GTF kernel", tile);
 	lsq_text T;
 	int rc;
 	Ev ev[5];
 	for (Ev &x : ev) HIP_TRY(hipEventCreate(&x.e));
 	if ((rc = text_stage_buffer(c, bytes, len, label, T))) return rc;
 	HIP_TRY(hipEventRecord(ev[0].e, st));
-	if ((rc = text_scan_newlines(c, T))) return rc;
+	if ((rc = scan_newlines(c, T))) return rc;
 	HIP_TRY(hipEventRecord(ev[1].e, st));
 	const unsigned long long n_lines = T.n_nl + 1;                 // lines that may exist (the last one may be empty: the text ends in a newline)
 	if (n_lines >= 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "%s: more than 2^32 lines", label);
-	const unsigned long long n_tiles = (len + tile - 1) / tile;
+	const unsigned long long n_tiles = (len + TEXT_TILE - 1) / TEXT_TILE;
 	DevBuf<GtfRec> d_rec, d_out, d_heads;
 	DevBuf<int2> d_se;
 	DevBuf<unsigned> d_keep, d_head;
@@ -296,7 +276,7 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 	HIP_TRY(hipMemcpyAsync(d_status.p, &clean, sizeof clean, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(d_keep.p, 0, n_lines * sizeof(unsigned), st));
 	const unsigned lb = (unsigned)((n_lines + 255) / 256);
-	hipLaunchKernelGGL(lsq_gtf_lines_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, (const unsigned char *)T.d_text.p, len, (const unsigned long long *)T.d_tile_base.p, tile,
+	hipLaunchKernelGGL(lsq_gtf_lines_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, (const unsigned char *)T.d_text.p, len, (const unsigned long long *)T.d_tile_base.p,
 	                   d_rec.p, d_keep.p, d_status.p);
 	if ((rc = device_scan<1, true>(S, d_keep.p, n_lines, d_kplace.p, st))) return rc;
 	hipLaunchKernelGGL(lsq_gtf_compact_kernel, dim3(lb), dim3(256), 0, st, (const GtfRec *)d_rec.p, (const unsigned *)d_keep.p, (const unsigned long long *)d_kplace.p, n_lines, d_out.p, d_se.p);

@@ -20,32 +20,13 @@
 // 10 ms + 6 ms of one-workgroup scans per C3 file, >= 56 GB of HBM traffic for 3.7 GB of text.
 // This replaces the reference's load-time filter and its read index (count/count.cpp:348-364).
 #include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
-#include <atomic>
-#include <chrono>
-#include <functional>
-#include <thread>
-
-#include "lsq_device.hpp"
+#include "lsq_text.hpp"
 #include "lsq_mrf_line.hpp"
 #include "lsq_sam_line.hpp"
 
 namespace {
-
-// developer aid: LSQ_CLI_TIMING=1 prints host-side seconds of the loader's steps on stderr
-struct HostStopwatch {
-	bool on = getenv("LSQ_CLI_TIMING") != nullptr;
-	std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
-	void mark(const char *what) {
-		if (!on) return;
-		const auto n = std::chrono::steady_clock::now();
-		fprintf(stderr, "[timing]     %-32s %.3f s\n", what, std::chrono::duration<double>(n - t).count());
-		t = n;
-	}
-};
 
 constexpr int INGEST_MAX_BLOCKS = 16;                  // merged blocks per read the device ingest handles
 constexpr int LSQ_RETRY = 1;                           // a front end's settle(): route the file again (it has changed its own mode)
@@ -286,18 +267,7 @@ struct ReadAcc {
 	}
 };
 
-// ---- device time of the chain's stages (lsq_last_ingest_stages): events around each stage's launches
-struct StageClock {
-	lsq_ctx *c; hipStream_t st; int s;
-	StageClock(lsq_ctx *c_, hipStream_t st_, int s_) : c(c_), st(st_), s(s_) {
-		for (int q = 0; q < 2; ++q) if (!c->ing_ev[2 * s + q]) (void)hipEventCreate(&c->ing_ev[2 * s + q]);
-		if (c->ing_ev[2 * s]) (void)hipEventRecord(c->ing_ev[2 * s], st);
-	}
-	void end(unsigned long long bytes) {
-		if (c->ing_ev[2 * s + 1]) (void)hipEventRecord(c->ing_ev[2 * s + 1], st);
-		c->ing_bytes[s] = bytes; c->ing_seen[s] = true;
-	}
-};
+// ---- device time of the chain's stages (lsq_last_ingest_stages; StageClock, lsq_text.hpp, records them)
 static void stages_reset(lsq_ctx *c, bool keep_text_stage) {
 	for (int s = keep_text_stage ? 1 : 0; s < LSQ_INGEST_STAGES; ++s) { c->ing_seen[s] = false; c->ing_ms[s] = 0; c->ing_bytes[s] = 0; }
 }
@@ -310,13 +280,71 @@ static void stages_collect(lsq_ctx *c) {          // (the stream has been waited
 	(void)hipGetLastError();
 }
 
-} // namespace
+// the reads of one file as the routing pass meets them
+struct Front {
+	unsigned long long n = 0;                 // reads of the pass (text: data lines, skipped ones among them)
+	const unsigned *line_no = nullptr;        // per read (device), or null: first_line + index
+	unsigned long long first_line = 0;
+	unsigned long long in_bytes = 0;          // what the routing pass reads
+	std::function<int(const RouteTables &, const RouteOut &, hipStream_t)> launch;   // runs the routing kernel
+	std::function<int(hipStream_t)> settle;   // once the stream has been waited for: the front end's own verdict (the first failing line)
+};
 
-#include "lsq_scan.hpp"
+// ---- what the chain hands a read format's device parser (lsq_mrf_device.hpp, lsq_sam_device.hpp): the staged text, the dictionaries,
+// the lists of work a tile kernel hands on, the parsed arrays of lsq_mrf_parse_device
+struct MrfText {
+	const unsigned char *text;
+	unsigned long long len;
+	const unsigned long long *tile_base;
+	unsigned has_header;
+	unsigned long long first_line;            // the number of data line 0 in the whole file (read name "read-<L>")
+	unsigned long long n_lines;
+};
 
-namespace {
+struct MrfDict {
+	const unsigned *chrom_hash;             // open addressing, 0 = empty; 32-bit FNV-1a of the name
+	const unsigned *chrom_id;
+	const unsigned *name_off;               // per chromosome id, into names
+	const char *names;
+	unsigned mask, n_chrom, names_bytes;
+	unsigned long long *strand_tab;         // 256 slots
+};
+
+// A line that began more than MRF_LB bytes ahead of its tile: its data line index, first byte and length.  At most one per tile.
+struct MrfLongLine { unsigned long long i, start, n; };
+
+// lists of work the fast kernel hands on: counts[0] tiles, counts[1] lines, counts[2] set when the line list ran over
+struct MrfHandOff {
+	unsigned *counts;
+	unsigned *tiles; unsigned tile_cap;
+	MrfLongLine *lines; unsigned line_cap;
+};
+
+struct MrfOut {
+	unsigned long long *blk_off;
+	unsigned *line_no;
+	int *blk_start, *blk_end;
+	unsigned short *blk_chrom;
+	unsigned char *blk_strand;
+};
+
+// What ingest_text hands a read format's front end, and parse_staged_text the format's count / write launches: the
+// text, the dictionaries and the error words, the hand-off lists.
+struct TextJob {
+	lsq_ctx *c;
+	MrfText X;
+	MrfDict D;
+	unsigned long long *err;
+	MrfHandOff H;
+	unsigned n_tiles;
+	bool all_slow;                          // every tile through the format's byte-walking kernel: the front end's choice, or the line list ran over
+	unsigned counts[4];                     // H.counts as the routing pass left them (the front end's record reads them)
+	DevBuf<unsigned long long> tab64;       // tables of the format's own, made by its prepare (MRF: the fast kernel's dictionary)
+	DevBuf<unsigned short> tab16;
+};
 
 #include "lsq_mrf_device.hpp"
+
 
 // ---- routing of parsed blocks that came from the host (lsq_reads_upload: file order) -------------------------------------
 struct IngestRaw {
@@ -737,16 +765,6 @@ __global__ void __launch_bounds__(256) lsq_ingest_pad_kernel(const BucketDesc *b
 }
 
 // ---- the chain on the host ---------------------------------------------------------------------------------------------
-// the reads of one file as the routing pass meets them
-struct Front {
-	unsigned long long n = 0;                 // reads of the pass (text: data lines, skipped ones among them)
-	const unsigned *line_no = nullptr;        // per read (device), or null: first_line + index
-	unsigned long long first_line = 0;
-	unsigned long long in_bytes = 0;          // what the routing pass reads
-	std::function<int(const RouteTables &, const RouteOut &, hipStream_t)> launch;   // runs the routing kernel
-	std::function<int(hipStream_t)> settle;   // once the stream has been waited for: the front end's own verdict (the first failing line)
-};
-
 static RouteTables route_tables(lsq_ctx *c) {
 	RouteTables T{};
 	T.chrom = c->route_chrom.p; T.cov = c->cov.p; T.clu = c->clu.p; T.loc = c->loc.p; T.loc_shift = c->loc_shift; T.n_chrom = c->n_chrom_tables;
@@ -1044,15 +1062,196 @@ static void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_b
 	F.settle = nullptr;
 }
 
-// MRF text in HBM through the chain: newline counts, then the parse as the chain's routing pass
-static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text &T, unsigned has_header, unsigned long long first_line) {
-	if (!read_format) return fail(LSQ_E_ARG, "null argument");
-	const bool sam = strcmp(read_format, "SAM_SINGLE") == 0;
-	if (!sam && strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
-	const SamOpts Q{c->opt_sam_skip_flags, c->opt_sam_min_mapq};
+// The dictionaries of a parse: the events' chromosome names behind a hash table, the strand table seeded with the strands
+// already known.  The events' strand dictionary grows by the strings the file introduces (as it does under lsq_mrf_parse).
+struct MrfDictDev {
+	DevBuf<unsigned> d_hash, d_id, d_off;
+	DevBuf<unsigned long long> d_strand, d_err;
+	DevBuf<char> d_names;
+	size_t n_seed = 0;
+	MrfDict D{};
+	int build(lsq_ctx *c, hipStream_t st) {
+		lsq_events &E = *c->E;
+		int rc;
+		const size_t nc = E.covered.size();
+		size_t tab = 2;
+		while (tab < 4 * nc) tab <<= 1;
+		std::vector<unsigned> h_hash(tab, 0), h_id(tab, 0), h_off(nc + 1, 0);
+		std::string h_names;
+		for (size_t id = 0; id < nc; ++id) {
+			const std::string &nm = E.chroms.names[id];
+			const unsigned h = mrf_fnv32(nm.data(), nm.size());
+			size_t i = (size_t)(h & (unsigned)(tab - 1));
+			while (h_hash[i] != 0) i = (i + 1) & (tab - 1);
+			h_hash[i] = h; h_id[i] = (unsigned)id;
+			h_names += nm;
+			h_off[id + 1] = (unsigned)h_names.size();
+		}
+		if (E.strands.names.size() > 256) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
+		n_seed = E.strands.names.size();
+		std::vector<unsigned long long> h_strand(256, STRAND_EMPTY);
+		for (size_t i = 0; i < n_seed; ++i) {
+			const std::string &s = E.strands.names[i];
+			h_strand[i] = s.size() <= 7 ? mrf_strand_key(s.data(), s.size()) : STRAND_UNMATCHABLE;
+		}
+		const unsigned long long err[4] = {MRF_NO_ERR, 0, 0, 0};
+		if ((rc = d_hash.upload(h_hash.data(), tab, st)) || (rc = d_id.upload(h_id.data(), tab, st)) || (rc = d_off.upload(h_off.data(), nc + 1, st)) ||
+		    (rc = d_names.upload(h_names.data(), h_names.size(), st)) || (rc = d_strand.upload(h_strand.data(), 256, st)) || (rc = d_err.upload(err, 4, st))) return rc;
+		HIP_TRY(hipStreamSynchronize(st));            // the host vectors go out of scope
+		D.chrom_hash = d_hash.p; D.chrom_id = d_id.p; D.name_off = d_off.p; D.names = d_names.p; D.mask = (unsigned)(tab - 1);
+		D.n_chrom = (unsigned)nc; D.names_bytes = (unsigned)h_names.size(); D.strand_tab = d_strand.p;
+		return LSQ_OK;
+	}
+	int reset_errors(hipStream_t st) {
+		static const unsigned long long err0[4] = {MRF_NO_ERR, 0, 0, 0};
+		HIP_TRY(hipMemcpyAsync(d_err.p, err0, sizeof(err0), hipMemcpyHostToDevice, st));
+		return LSQ_OK;
+	}
+	// after the parse kernels have run and the stream has been waited for: the first failing line, strand strings out of range, new strands
+	int settle(lsq_ctx *c, const lsq_text &T, unsigned has_header, unsigned long long first_line, hipStream_t st) {
+		lsq_events &E = *c->E;
+		unsigned long long err[4];
+		std::vector<unsigned long long> h_strand(256);
+		HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(h_strand.data(), d_strand.p, 256 * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (err[0] != MRF_NO_ERR) {
+			// the text of the failing line, from the file: between the newline that ends the line before it and its own
+			const unsigned long long want = err[0] - first_line + has_header;      // ordinal of the newline that ends the failing line
+			std::string text;
+			const int fd = open(T.path.c_str(), O_RDONLY);
+			if (fd >= 0) {
+				// walk the file's range for the want-th newline (an error path: speed does not matter, bounded memory does)
+				std::vector<char> buf(1 << 20);
+				unsigned long long seen = 0, pos = 0;
+				bool in_line = want == 0, done = false;
+				while (!done && pos < T.len) {
+					const size_t ask = (size_t)std::min<unsigned long long>(buf.size(), T.len - pos);
+					const ssize_t got = pread(fd, buf.data(), ask, (off_t)(T.offset + pos));
+					if (got <= 0) break;
+					for (ssize_t q = 0; q < got && !done; ++q) {
+						if (buf[(size_t)q] == '\n') {
+							if (in_line) done = true;
+							else if (++seen == want) in_line = true;
+						} else if (in_line) text.push_back(buf[(size_t)q]);
+					}
+					pos += (unsigned long long)got;
+				}
+				close(fd);
+			}
+			return fail(LSQ_E_PARSE, "#%llu:%s", err[0], text.c_str());
+		}
+		if (err[1]) return fail(LSQ_E_UNSUPPORTED, "a strand string longer than 7 bytes: outside the device parser's range (lsq_mrf_parse handles it)");
+		if (err[2]) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
+		for (size_t i = n_seed; i < 256 && h_strand[i] != STRAND_EMPTY; ++i) {
+			const unsigned long long k = h_strand[i];
+			std::string s;
+			for (unsigned j = 0; j < (unsigned)(k & 0xFF); ++j) s.push_back((char)(k >> (56 - 8 * j)));
+			const int id = E.strands.intern(s);
+			if (id != (int)i) return fail(LSQ_E_STATE, "strand dictionary changed while a reads file was being parsed");
+		}
+		n_seed = E.strands.names.size();
+		return LSQ_OK;
+	}
+};
+
+struct DevParsed {
+	uint64_t n_reads = 0, n_blocks = 0;
+	DevBuf<unsigned long long> blk_off;
+	DevBuf<unsigned> line_no;
+	DevBuf<int> bs, be;
+	DevBuf<unsigned short> bc;
+	DevBuf<unsigned char> bst;
+};
+
+// ---- the read formats: the one place that names them.  Per format: whether a whole file's first line is a header (MRF; every
+// line of a SAM file counts: "read-<k>", k from 1), the switch that shortens its line list (tests: the run-over path on a small
+// file), the routing stage's name, its front end for the chain (prepare once; launch the routing kernels, once more with
+// J.all_slow set if the line list ran over; record what they handed on), and its count / write launches for parse_staged_text
+struct ReadFormat {
+	const char *name;
+	unsigned has_header;
+	const char *line_list_env, *stage;
+	int (*prepare)(TextJob &);
+	void (*launch)(const TextJob &, const RouteTables &, const RouteOut &, hipStream_t);
+	void (*record)(const TextJob &);
+	void (*count)(const TextJob &, hipStream_t, unsigned *);
+	void (*write)(const TextJob &, hipStream_t, const unsigned *, const unsigned long long *, const unsigned long long *, const MrfOut &);
+};
+static const ReadFormat READ_FORMATS[] = {
+	{"MRF_SINGLE", 1u, "LSQ_MRF_LINE_LIST", "route", mrf_prepare, mrf_launch, mrf_record,
+	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, J.err); },
+	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
+		 hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, rd, bk, J.D, O, J.err); }},
+	{"SAM_SINGLE", 0u, "LSQ_SAM_LINE_LIST", "sam_route", sam_prepare, sam_launch, sam_record,
+	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, J.err); },
+	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
+		 hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
+};
+// the format a caller names (looked up once its file has been opened: the order in which the reference meets a bad file or literal)
+static int read_format_named(const char *name, const ReadFormat *&fmt) {
+	if (!name) return fail(LSQ_E_ARG, "null argument");
+	for (const ReadFormat &f : READ_FORMATS) if (strcmp(name, f.name) == 0) { fmt = &f; return LSQ_OK; }
+	return fail(LSQ_E_FORMAT, "Unknown file format error: %s", name);
+}
+
+// Parses staged text on the device into the arrays of lsq_mrf_parse (file order): lsq_mrf_parse_device.
+static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, unsigned long long first_line, DevParsed &out, float *h2d_ms, float *parse_ms) {
+	const unsigned has_header = fmt->has_header;
 	hipStream_t st = c->stream;
 	int rc;
-	c->ing_sam = sam;
+	if ((rc = ensure_lanes(c))) return rc;                 // (c->ev1 / c->ev2 are the lanes thread's)
+	const unsigned long long zero_off = 0;
+	out.n_reads = out.n_blocks = 0;
+	auto empty_result = [&]() -> int {
+		int r2;
+		if ((r2 = out.blk_off.upload(&zero_off, 1, st)) || (r2 = out.line_no.alloc(0)) || (r2 = out.bs.alloc(0)) || (r2 = out.be.alloc(0)) ||
+		    (r2 = out.bc.alloc(0)) || (r2 = out.bst.alloc(0))) return r2;
+		HIP_TRY(hipStreamSynchronize(st));
+		return LSQ_OK;
+	};
+	if (h2d_ms) *h2d_ms = T.h2d_ms;
+	if (parse_ms) *parse_ms = 0;
+	if (T.len == 0) return empty_result();
+	HIP_TRY(hipEventRecord(c->ev1, st));
+	if ((rc = scan_newlines(c, T))) return rc;
+	const unsigned long long n_nl = T.n_nl;
+	if (n_nl < 1 + has_header) return empty_result();   // header only (or no terminated line at all)
+	const unsigned long long n_lines = n_nl - has_header;
+	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
+	DevBuf<unsigned> d_line_nb;
+	DevBuf<unsigned long long> d_rd_idx, d_bk_off;
+	ScanScratch SS;
+	MrfDictDev DD;
+	if ((rc = d_line_nb.alloc(n_lines)) || (rc = d_rd_idx.alloc(n_lines + 1)) || (rc = d_bk_off.alloc(n_lines + 1)) || (rc = SS.reserve(n_lines)) || (rc = DD.build(c, st))) return rc;
+	TextJob J{};
+	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
+	J.n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
+	fmt->count(J, st, d_line_nb.p);
+	HIP_TRY(hipGetLastError());
+	if ((rc = device_scan<1, true>(SS, d_line_nb.p, n_lines, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, n_lines, d_bk_off.p, st))) return rc;
+	unsigned long long n_reads = 0, n_blocks = 0;
+	HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + n_lines, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + n_lines, 8, hipMemcpyDeviceToHost, st));
+	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;          // (waits for the stream) the first failing line ends the run here
+	if ((rc = out.blk_off.alloc(n_reads + 1)) || (rc = out.line_no.alloc(n_reads)) || (rc = out.bs.alloc(n_blocks)) || (rc = out.be.alloc(n_blocks)) ||
+	    (rc = out.bc.alloc(n_blocks)) || (rc = out.bst.alloc(n_blocks))) return rc;
+	const MrfOut O{out.blk_off.p, out.line_no.p, out.bs.p, out.be.p, out.bc.p, out.bst.p};
+	fmt->write(J, st, d_line_nb.p, d_rd_idx.p, d_bk_off.p, O);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipEventRecord(c->ev2, st));
+	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;
+	if (parse_ms) (void)hipEventElapsedTime(parse_ms, c->ev1, c->ev2);
+	out.n_reads = n_reads; out.n_blocks = n_blocks;
+	return LSQ_OK;
+}
+
+// A read file's text in HBM through the chain: newline counts, then the format's parse as the chain's routing pass
+static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &T, unsigned has_header, unsigned long long first_line) {
+	hipStream_t st = c->stream;
+	int rc;
+	if ((rc = ensure_lanes(c))) return rc;
+	c->ing_format = (int)(fmt - READ_FORMATS);
 	c->mrf_h2d_ms = T.h2d_ms; c->mrf_parse_ms = 0;
 	stages_reset(c, T.scanned);
 	if (T.len && (rc = scan_newlines(c, T))) return rc;
@@ -1063,123 +1262,45 @@ static int ingest_text(lsq_ctx *c, int method, const char *read_format, lsq_text
 	if ((rc = DD.build(c, st))) return rc;
 	Front F;
 	F.n = n_lines; F.line_no = nullptr; F.first_line = first_line; F.in_bytes = T.len;
-	const unsigned n_tiles = (unsigned)((T.len + MRF_TILE - 1) / MRF_TILE);
-	const MrfText X{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines};
-	// what the fast kernel hands on: tiles with more delimiters than its tables hold, lines of another shape than a read's
-	// (at most one a tile begins ahead of its window; the rest is whatever the file holds -- when the list runs over, the
-	// whole file goes through the kernel that walks bytes)
+	const unsigned n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
+	// what a format's tile kernel hands on: tiles it does not take (MRF: more delimiters than the fast kernel's tables hold), lines
+	// it does not settle (another shape than a read's; at most one a tile begins ahead of its window; the rest is whatever the
+	// file holds -- when the list runs over, the whole file goes through the format's byte-walking kernel)
 	unsigned long long list_cap = 1ull << 22;
-	if (const char *e = getenv(sam ? "LSQ_SAM_LINE_LIST" : "LSQ_MRF_LINE_LIST")) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }      // tests: the run-over path on a small file
+	if (const char *e = getenv(fmt->line_list_env)) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }
 	const unsigned line_cap = (unsigned)std::min<unsigned long long>(n_lines, list_cap) + n_tiles + 1u;
 	DevBuf<MrfLongLine> d_lines;
 	DevBuf<unsigned> d_tiles, d_counts;
-	DevBuf<unsigned long long> d_ckey;
-	DevBuf<unsigned short> d_cid;
 	if ((rc = d_lines.alloc(line_cap)) || (rc = d_tiles.alloc(n_tiles)) || (rc = d_counts.alloc(4))) return rc;
 	HIP_TRY(hipMemsetAsync(d_counts.p, 0, 16, st));          // (a file without lines launches nothing; the verdict below still reads these)
-	MrfHandOff H{d_counts.p, d_tiles.p, n_tiles, d_lines.p, line_cap};
-	// the chromosomes' names as 64-bit keys (names of at most seven bytes; a longer one has no slot and its lines go to the list)
-	MrfFastDict FD{};
-	{
-		const lsq_events &E = *c->E;
-		const size_t nc = E.covered.size();
-		std::vector<unsigned long long> ck(FP_DICT, 0);
-		std::vector<unsigned short> ci(FP_DICT, 0);
-		bool usable = nc <= ROUTE_CHROM_LDS && getenv("LSQ_MRF_SLOW") == nullptr;       // (LSQ_MRF_SLOW: the tests run the byte-walking kernel over whole files with it)
-		for (size_t id = 0; usable && id < nc; ++id) {
-			const std::string &nm = E.chroms.names[id];
-			if (nm.empty() || nm.size() > 7) continue;
-			const unsigned long long key = mrf_strand_key(nm.data(), nm.size());
-			unsigned sl = mrf_key_slot(key);
-			while (ck[sl] != 0) sl = (sl + 1u) & (FP_DICT - 1u);
-			ck[sl] = key; ci[sl] = (unsigned short)id;
-		}
-		if ((rc = d_ckey.upload(ck.data(), FP_DICT, st)) || (rc = d_cid.upload(ci.data(), FP_DICT, st))) return rc;
-		HIP_TRY(hipStreamSynchronize(st));
-		FD.ckey = d_ckey.p; FD.cid = d_cid.p; FD.usable = usable ? 1u : 0u;
-	}
-	bool all_slow = sam ? getenv("LSQ_SAM_SLOW") != nullptr : !FD.usable;       // (LSQ_SAM_SLOW: the tests run the byte-walking form over whole files with it)
-	const unsigned side_grid = std::min(std::max(n_tiles, 1u), 4u * (unsigned)c->n_cu);
-	// a workgroup a tile: the kernel can also run as a grid of resident workgroups that stay for many tiles (LSQ_FAST_GRID workgroups a
-	// compute unit; developer aid) -- measured slower on C3: 7.4 ms at 6, 7.0 at 12, 6.7 at 24 against 6.1 with a workgroup a tile
-	unsigned fast_grid = std::max(n_tiles, 1u);
-	if (const char *e = getenv("LSQ_FAST_GRID")) { const int v = atoi(e); if (v > 0) fast_grid = (unsigned)v * (unsigned)c->n_cu; }
+	TextJob J{};
+	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
+	J.H = MrfHandOff{d_counts.p, d_tiles.p, n_tiles, d_lines.p, line_cap}; J.n_tiles = n_tiles;
+	if ((rc = fmt->prepare(J))) return rc;
 	F.launch = [&](const RouteTables &RT, const RouteOut &O, hipStream_t s) -> int {
-		int r2 = DD.reset_errors(s);
+		const int r2 = DD.reset_errors(s);
 		if (r2) return r2;
 		HIP_TRY(hipMemsetAsync(d_counts.p, 0, 16, s));
-		if (sam) {
-			// a workgroup a tile, as the MRF kernel is launched; the listed lines behind it
-			if (n_tiles && all_slow) hipLaunchKernelGGL(lsq_sam_route_kernel<true>, dim3(n_tiles), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H, n_tiles);
-			else if (n_tiles) {
-				hipLaunchKernelGGL(lsq_sam_route_kernel<false>, dim3(n_tiles), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H, n_tiles);
-				hipLaunchKernelGGL(lsq_sam_route_lines_kernel, dim3(std::min(line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, X, Q, DD.D, RT, O, DD.d_err.p, H);
-			}
-			HIP_TRY(hipGetLastError());
-			return LSQ_OK;
-		}
-		if (!all_slow) {
-			hipLaunchKernelGGL(lsq_mrf_route_fast_kernel, dim3(std::min(n_tiles, fast_grid)), dim3(256), 0, s, X, DD.D, FD, RT, O, DD.d_err.p, H, n_tiles);
-			hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(std::min(side_grid, 256u)), dim3(256), 0, s, X, DD.D, RT, O, DD.d_err.p, H, n_tiles, 1u);
-		} else hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(n_tiles), dim3(256), 0, s, X, DD.D, RT, O, DD.d_err.p, H, n_tiles, 0u);
-		hipLaunchKernelGGL(lsq_mrf_route_lines_kernel, dim3(std::min(line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, X, DD.D, RT, O, DD.d_err.p, H);
+		fmt->launch(J, RT, O, s);
 		HIP_TRY(hipGetLastError());
 		return LSQ_OK;
 	};
 	F.settle = [&](hipStream_t s) -> int {
 		// the line list ran over (a file of lines of another shape than a read's): once more, every tile through the byte-walking kernel
-		unsigned counts[4] = {0, 0, 0, 0};
-		HIP_TRY(hipMemcpy(counts, d_counts.p, 16, hipMemcpyDeviceToHost));
-		if (counts[2] && !all_slow) { all_slow = true; return LSQ_RETRY; }
-		if (counts[2]) return fail(LSQ_E_INTERNAL, "the device parser's line list ran over");
-		if (sam) { c->sam_lines_listed = all_slow ? 0u : counts[1]; c->sam_all_slow = all_slow ? 1u : 0u; }
-		else { c->parse_tiles_handed = all_slow ? 0u : counts[0]; c->parse_lines_listed = counts[1]; c->parse_all_slow = all_slow ? 1u : 0u; }
+		HIP_TRY(hipMemcpy(J.counts, d_counts.p, 16, hipMemcpyDeviceToHost));
+		if (J.counts[2] && !J.all_slow) { J.all_slow = true; return LSQ_RETRY; }
+		if (J.counts[2]) return fail(LSQ_E_INTERNAL, "the device parser's line list ran over");
+		fmt->record(J);
 		return DD.settle(c, T, has_header, first_line, s);
 	};
 	c->reads[method].named = false;
-	rc = ingest_device(c, method, F);
-	if (rc) return rc;
+	if ((rc = ingest_device(c, method, F))) return rc;
 	// (device time of the parse = the newline count and the routing pass; the rest of the chain is the ingest)
 	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1];
 	return LSQ_OK;
 }
 
 } // namespace
-
-// What the GTF parser (lsq_gtf.hip) shares with the loader: the staging of a text and its newline tiles.
-namespace lsq {
-
-// lsq_text_stage for bytes that are already in host memory (standard input of an executable, a mapped file): the same copy
-// paths as stage_text_file -- the runtime's own staging below a gigabyte, the context's two pinned buffers filled by
-// memcpy() above -- and the same 16 bytes of slack behind the text.
-int text_stage_buffer(lsq_ctx *c, const void *bytes, unsigned long long len, const char *label, lsq_text &T) {
-	hipStream_t st = c->stream;
-	T.path = label; T.len = len; T.offset = 0; T.h2d_ms = 0; T.scanned = false; T.n_nl = 0;
-	if (len == 0) return LSQ_OK;
-	int rc;
-	if ((rc = T.d_text.alloc(len + 16))) return rc;
-	unsigned long long pinned_min = 1ull << 30;
-	if (const char *e = getenv("LSQ_PINNED_COPY_MIN")) { const long long v = atoll(e); if (v >= 0) pinned_min = (unsigned long long)v; }   // tests
-	bool pinned = len >= pinned_min && len >= 2 * PIN_SLICE;
-	HIP_TRY(hipEventRecord(c->evt0, st));
-	if (pinned && ensure_pinned_buffers(c) != LSQ_OK) pinned = false;
-	const unsigned char *src = (const unsigned char *)bytes;
-	if (pinned) {
-		if ((rc = pinned_pipeline(c, T.d_text.p, (size_t)len, [&](unsigned char *dst, size_t off, size_t n) { memcpy(dst, src + off, n); return true; }, label))) return rc;
-	} else {
-		for (unsigned long long off = 0; off < len; off += PIN_SLICE)
-			HIP_TRY(hipMemcpyAsync(T.d_text.p + off, src + off, (size_t)std::min<unsigned long long>(PIN_SLICE, len - off), hipMemcpyHostToDevice, st));
-		HIP_TRY(hipStreamSynchronize(st));
-	}
-	HIP_TRY(hipEventRecord(c->evt1, st));
-	HIP_TRY(hipEventSynchronize(c->evt1));
-	(void)hipEventElapsedTime(&T.h2d_ms, c->evt0, c->evt1);
-	return LSQ_OK;
-}
-int text_scan_newlines(lsq_ctx *c, lsq_text &T) { return scan_newlines(c, T); }
-unsigned text_tile_bytes() { return MRF_TILE; }
-
-} // namespace lsq
 
 extern "C" {
 
@@ -1222,7 +1343,7 @@ int lsq_reads_upload(lsq_ctx *c, int method, const lsq_reads *R) LSQ_API_TRY {
 	SW.mark("upload: allocations, copies queued");
 	if (SW.on) { HIP_TRY(hipStreamSynchronize(st)); SW.mark("upload: copies done"); }
 	stages_reset(c, false);
-	c->ing_sam = false;
+	c->ing_format = -1;
 	Front F;
 	front_of_raw(c, Rw, nblk, F);
 	if ((rc = ingest_device(c, method, F))) return rc;
@@ -1242,38 +1363,20 @@ int lsq_reads_upload_mrf(lsq_ctx *c, int method, const char *read_format, const 
 	if (method < 0 || method >= c->E->n_methods) return fail(LSQ_E_ARG, "method %d out of range", method);
 	HIP_TRY(hipSetDevice(c->device));
 	HostStopwatch SW;
-	int rc = check_mrf_file(read_format, path);
-	if (rc) return rc;
+	if (!read_format || !path) return fail(LSQ_E_ARG, "null argument");
+	const ReadFormat *fmt;
 	lsq_text T;
-	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
-	rc = ingest_text(c, method, read_format, T, text_has_header(read_format), 1ull);
+	int rc;
+	if ((rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
+	rc = ingest_text(c, method, fmt, T, fmt->has_header, 1ull);
 	SW.mark("upload_mrf: all");
 	return rc;
 } LSQ_API_CATCH
 
-int lsq_text_stage_range(lsq_ctx *c, const char *path, uint64_t byte_begin, uint64_t byte_end, lsq_text **out) LSQ_API_TRY {
-	if (!c || !path || !out) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	std::unique_ptr<lsq_text> T(new lsq_text);
-	int rc = stage_text_file(c, path, byte_begin, byte_end, *T);
-	if (rc) return rc;
-	*out = T.release();
-	return LSQ_OK;
-} LSQ_API_CATCH
-int lsq_text_stage(lsq_ctx *c, const char *path, lsq_text **out) { return lsq_text_stage_range(c, path, 0, ~0ull, out); }
-
-int lsq_text_lines(lsq_ctx *c, lsq_text *t, uint64_t *n_newlines) LSQ_API_TRY {
-	if (!c || !t || !n_newlines) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	int rc = t->len ? scan_newlines(c, *t) : LSQ_OK;
-	if (rc) return rc;
-	*n_newlines = t->len ? t->n_nl : 0;
-	return LSQ_OK;
-} LSQ_API_CATCH
-void lsq_text_free(lsq_text *t) { delete t; }
-
 int lsq_reads_upload_text(lsq_ctx *c, int method, const char *read_format, lsq_text *t) LSQ_API_TRY {
-	return lsq_reads_upload_text_at(c, method, read_format, t, read_format ? (int)text_has_header(read_format) : 1, 1);
+	const ReadFormat *fmt = nullptr;          // (a whole file of its format: the first line as the format has it; a bad literal is reported below)
+	(void)read_format_named(read_format, fmt);
+	return lsq_reads_upload_text_at(c, method, read_format, t, fmt ? (int)fmt->has_header : 1, 1);
 } LSQ_API_CATCH
 
 int lsq_reads_upload_text_at(lsq_ctx *c, int method, const char *read_format, lsq_text *t, int has_header, uint64_t first_line) LSQ_API_TRY {
@@ -1281,19 +1384,22 @@ int lsq_reads_upload_text_at(lsq_ctx *c, int method, const char *read_format, ls
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
 	if (method < 0 || method >= c->E->n_methods) return fail(LSQ_E_ARG, "method %d out of range", method);
 	HIP_TRY(hipSetDevice(c->device));
-	return ingest_text(c, method, read_format, *t, has_header ? 1u : 0u, first_line);
+	const ReadFormat *fmt;
+	const int rc = read_format_named(read_format, fmt);
+	return rc ? rc : ingest_text(c, method, fmt, *t, has_header ? 1u : 0u, first_line);
 } LSQ_API_CATCH
 
 int lsq_mrf_parse_device(lsq_ctx *c, const char *read_format, const char *path, lsq_reads **out) LSQ_API_TRY {
 	if (!c || !out) return fail(LSQ_E_ARG, "null argument");
 	HIP_TRY(hipSetDevice(c->device));
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	int rc = check_mrf_file(read_format, path);
-	if (rc) return rc;
+	if (!read_format || !path) return fail(LSQ_E_ARG, "null argument");
+	const ReadFormat *fmt;
 	lsq_text T;
-	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
+	int rc;
+	if ((rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
 	DevParsed P;
-	if ((rc = parse_staged_text(c, read_format, T, text_has_header(read_format), 1ull, P, &c->mrf_h2d_ms, &c->mrf_parse_ms))) return rc;
+	if ((rc = parse_staged_text(c, fmt, T, 1ull, P, &c->mrf_h2d_ms, &c->mrf_parse_ms))) return rc;
 	std::unique_ptr<lsq_reads> R(new lsq_reads);
 	R->o_blk_off.resize(P.n_reads + 1); R->o_line_no.resize(P.n_reads);
 	R->o_start.resize(P.n_blocks); R->o_end.resize(P.n_blocks); R->o_chrom.resize(P.n_blocks); R->o_strand.resize(P.n_blocks);
@@ -1330,7 +1436,7 @@ static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
 	"newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"};
 int lsq_ingest_stage_count(void) { return LSQ_INGEST_STAGES; }
 const char *lsq_ingest_stage_name(int stage) { return stage >= 0 && stage < LSQ_INGEST_STAGES ? INGEST_STAGE_NAMES[stage] : nullptr; }
-const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) { return c && c->ing_sam && stage == 1 ? "sam_route" : lsq_ingest_stage_name(stage); }
+const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) { return c && c->ing_format >= 0 && stage == 1 ? READ_FORMATS[c->ing_format].stage : lsq_ingest_stage_name(stage); }
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {
 	if (!c) return LSQ_E_ARG;
 	if (lines_listed) *lines_listed = c->sam_lines_listed;

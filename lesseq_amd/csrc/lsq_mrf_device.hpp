@@ -1,14 +1,13 @@
 // MRF_SINGLE parsed on the device (included by lsq_ingest.hip; not a public header).
 //
-// The text goes to HBM as it is and is read there twice: once to count the newlines of every 7 680-byte tile (16 bytes per
-// lane, the exact zero-byte test on word ^ 0x0A0A0A0A), once to parse.  A workgroup of the parse owns the lines that END
-// in its tile and sees the tile and the 512 bytes before it.  The newline ordinal of a line (tile base from a prefix sum
-// over the tile counts + its place in the tile) is its line number: the header and "read-<n>" fall out as in the
-// reference (count/count.cpp:283,286,293-295).
+// The text lies in HBM as lsq_text.hip staged it, its newlines counted per tile (lsq_text.hpp).  A workgroup of the parse owns
+// the lines that END in its tile and sees the tile and the 512 bytes before it.  The newline ordinal of a line (tile base from
+// the prefix sum over the tile counts + its place in the tile) is its line number: the header and "read-<n>" fall out as in
+// the reference (count/count.cpp:283,286,293-295).
 //
-// Round 4: the parse IS the routing pass of the loader chain (lsq_ingest.hip): per line, every block goes through the
-// containment filter and the merge as it is split off, and nothing but the routed read leaves the kernel -- no parsed
-// array exists in HBM either.  Three kernels:
+// The parse IS the routing pass of the loader chain (lsq_ingest.hip): per line, every block goes through the containment
+// filter and the merge as it is split off, and nothing but the routed read leaves the kernel -- no parsed array exists in HBM
+// either.  Three kernels, launched by the format's front end (mrf_launch, at the end of this file):
 //   lsq_mrf_route_fast_kernel   every tile: delimiter tables from byte-parallel zero-byte tests, lines walk table entries,
 //                               a lane a block does the coordinates (eight-digit sums), the chromosome and strand (64-bit
 //                               keys), the filter; settles every line of a read's usual shape and lists the others
@@ -26,16 +25,10 @@
 //     with byte-wise verification for the byte-walking kernels); strand strings against a 256-slot table seeded with the
 //     strands already known, grown with atomicCAS (strings of at most 7 bytes; longer ones give LSQ_E_UNSUPPORTED -- use
 //     lsq_mrf_parse)
+// The SAM parser (lsq_sam_device.hpp, included behind this file) resolves chromosomes and strands with the dictionary code here.
 #pragma once
 
-#ifndef LSQ_MRF_TILE
-#define LSQ_MRF_TILE 7680
-#endif
-constexpr unsigned MRF_TILE = LSQ_MRF_TILE;         // text bytes per workgroup: with the 512 bytes ahead, a window of 8 KiB (7 680) or 4 KiB (3 584)
-static_assert(MRF_TILE == 7680 || MRF_TILE == 3584, "the fast kernel's window is 256 lanes x 32 or x 16 bytes");
-constexpr unsigned MRF_TILE_Q = (MRF_TILE + 4095) / 4096;      // 16-byte words a lane of 256 takes
-constexpr unsigned MRF_LB = 512;                    // bytes ahead of the tile that are staged with it
-constexpr unsigned MRF_NLCAP = 1024;                // newline positions held at a time (a tile of shorter lines takes several rounds)
+constexpr unsigned MRF_LB = 512;                    // bytes ahead of the tile that are staged with it: a window of 8 KiB (tiles of 7 680 bytes) or 4 KiB (3 584)
 constexpr unsigned long long MRF_NO_ERR = ~0ull;
 constexpr unsigned long long STRAND_EMPTY = ~0ull;
 constexpr unsigned long long STRAND_UNMATCHABLE = ~0ull - 1;
@@ -46,20 +39,9 @@ constexpr unsigned MRF_DICT_LDS_NAMES = 1024;
 typedef const __attribute__((address_space(3))) char *mrf_lds_cptr;
 typedef lsq::MrfViewT<mrf_lds_cptr, unsigned> MrfLdsView;
 
-struct MrfDict {
-	const unsigned *chrom_hash;             // open addressing, 0 = empty; 32-bit FNV-1a of the name
-	const unsigned *chrom_id;
-	const unsigned *name_off;               // per chromosome id, into names
-	const char *names;
-	unsigned mask, n_chrom, names_bytes;
-	unsigned long long *strand_tab;         // 256 slots
-};
-
 struct MrfTileLds {
-	__align__(16) unsigned char text[MRF_LB + MRF_TILE + 16];
-	unsigned short nlpos[MRF_NLCAP];
-	unsigned scan4[4];
-	unsigned carry;                         // last newline of the previous round
+	__align__(16) unsigned char text[MRF_LB + TEXT_TILE + 16];
+	TextNlLds nl;
 	long long first_start;                  // first byte of the first line that ends in the tile
 	// the dictionaries, when they are small
 	unsigned long long strand[256];
@@ -68,89 +50,20 @@ struct MrfTileLds {
 	__align__(16) RouteChrom chrom[ROUTE_CHROM_LDS];      // the routing pass's chromosome records (lsq_mrf_route_kernel)
 };
 
-__device__ inline unsigned mrf_wave_incl_scan(unsigned v) {
-	const unsigned lane = threadIdx.x & 63u;
-	for (unsigned d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane >= d) v += t; }
-	return v;
-}
-// exclusive prefix over the 256 lanes of the workgroup; `total` = sum over the workgroup
-__device__ inline unsigned mrf_block_excl_scan(unsigned v, unsigned *lds4, unsigned &total) {
-	const unsigned inc = mrf_wave_incl_scan(v);
-	const unsigned w = threadIdx.x >> 6;
-	if ((threadIdx.x & 63u) == 63u) lds4[w] = inc;
-	__syncthreads();
-	unsigned base = 0; total = 0;
-	for (unsigned q = 0; q < 4; ++q) { const unsigned t = lds4[q]; base += q < w ? t : 0u; total += t; }
-	__syncthreads();
-	return base + inc - v;
-}
-
-// bit j set iff byte j of the 16 bytes is '\n'; only the first `valid` bytes count
-__device__ inline unsigned mrf_newline_bits16(const uint4 v, unsigned valid) {
-	const unsigned w[4] = {v.x, v.y, v.z, v.w};
-	unsigned bits = 0;
-#pragma unroll
-	for (int q = 0; q < 4; ++q) {
-		const unsigned x = w[q] ^ 0x0A0A0A0Au;
-		const unsigned z = ~(((x & 0x7F7F7F7Fu) + 0x7F7F7F7Fu) | x) & 0x80808080u;   // 0x80 in every zero byte
-		bits |= (((z >> 7) & 1u) | ((z >> 14) & 2u) | ((z >> 21) & 4u) | ((z >> 28) & 8u)) << (4 * q);
-	}
-	return valid >= 16u ? bits : (bits & ((1u << valid) - 1u));
-}
-// the 16 bytes at `at` of a text of `len` bytes (the buffer holds 16 bytes of slack behind the text) and how many of them are text
-__device__ inline uint4 mrf_load16(const unsigned char *text, unsigned long long len, unsigned long long at, unsigned &valid) {
-	if (at >= len) { valid = 0; return make_uint4(0, 0, 0, 0); }
-	valid = (unsigned)min(16ull, len - at);
-	return *reinterpret_cast<const uint4 *>(text + at);
-}
-
-// newlines per tile
-__global__ void __launch_bounds__(256) lsq_mrf_newline_count_kernel(const unsigned char *text, unsigned long long len, unsigned *tile_cnt) {
-	__shared__ unsigned lds4[4];
-	const unsigned long long t0 = (unsigned long long)blockIdx.x * MRF_TILE;
-	unsigned n = 0;
-#pragma unroll
-	for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-		unsigned valid = 0;
-		const unsigned off = q * 4096u + threadIdx.x * 16u;
-		const uint4 v = off < MRF_TILE ? mrf_load16(text, len, t0 + off, valid) : make_uint4(0, 0, 0, 0);
-		n += (unsigned)__popc(mrf_newline_bits16(v, valid));
-	}
-	unsigned total;
-	(void)mrf_block_excl_scan(n, lds4, total);
-	if (threadIdx.x == 0) tile_cnt[blockIdx.x] = total;
-}
-
 // The lines that end in this workgroup's tile: fn(i, view) is called once per data line -- i its 0-based index among the
 // data lines (with a header: the lines after the first), view the line's bytes without the newline -- by the lane that
 // owns it.  view is an LDS view, or a plain one for a line that began more than MRF_LB bytes ahead of the tile.
-// A line that began more than MRF_LB bytes ahead of its tile: its data line index, first byte and length.  At most one per tile.
-struct MrfLongLine { unsigned long long i, start, n; };
-
 template <bool DEFER, class Fn>
 __device__ inline void mrf_tile_lines(MrfTileLds &S, const unsigned tile, const unsigned char *text, const unsigned long long len, const unsigned long long *tile_base,
                                       const unsigned has_header, MrfLongLine *long_lines, unsigned *n_long, const unsigned long_cap, unsigned *long_over, Fn &&fn) {
 	const unsigned tid = threadIdx.x;
-	const unsigned long long t0 = (unsigned long long)tile * MRF_TILE;
-	unsigned bits[MRF_TILE_Q];
-#pragma unroll
-	for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-		unsigned valid = 0;
-		const unsigned off = q * 4096u + tid * 16u;
-		const uint4 v = off < MRF_TILE ? mrf_load16(text, len, t0 + off, valid) : make_uint4(0, 0, 0, 0);
-		if (off < MRF_TILE) *reinterpret_cast<uint4 *>(&S.text[MRF_LB + off]) = v;
-		bits[q] = mrf_newline_bits16(v, valid);
-	}
+	const unsigned long long t0 = (unsigned long long)tile * TEXT_TILE;
+	TextTileNl N;
+	N.load(&S.text[MRF_LB], text, len, t0);
 	if (tid < MRF_LB / 16u && t0 >= MRF_LB)
 		*reinterpret_cast<uint4 *>(&S.text[tid * 16u]) = *reinterpret_cast<const uint4 *>(text + (t0 - MRF_LB) + tid * 16ull);
-	// ordinals of the newlines: the lanes' first words cover bytes 0..4095 of the tile, their second words the rest
-	unsigned ord[MRF_TILE_Q], nt = 0;
-#pragma unroll
-	for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-		unsigned total;
-		ord[q] = nt + mrf_block_excl_scan((unsigned)__popc(bits[q]), S.scan4, total);
-		nt += total;
-	}
+	N.number(S.nl);
+	const unsigned nt = N.nt;
 	if (nt == 0) return;                      // (uniform: every lane holds the same total)
 	// the first line that ends here began after the last newline ahead of the tile
 	if (tid < 64u) {
@@ -168,26 +81,17 @@ __device__ inline void mrf_tile_lines(MrfTileLds &S, const unsigned tile, const 
 	}
 	const unsigned long long g0 = tile_base[tile];
 	const mrf_lds_cptr lds_text = (mrf_lds_cptr)(const char *)S.text;
-	for (unsigned rb = 0; rb < nt; rb += MRF_NLCAP) {
-#pragma unroll
-		for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-			unsigned b = bits[q], o = ord[q];
-			while (b) {
-				const unsigned j = (unsigned)__ffs((int)b) - 1u; b &= b - 1u;
-				if (o >= rb && o < rb + MRF_NLCAP) S.nlpos[o - rb] = (unsigned short)(q * 4096u + tid * 16u + j);
-				++o;
-			}
-		}
-		__syncthreads();
-		const unsigned r_end = min(nt, rb + MRF_NLCAP);
+	for (unsigned rb = 0; rb < nt; rb += TEXT_NLCAP) {
+		N.round(S.nl, rb);                     // (its barrier also publishes S.first_start)
+		const unsigned r_end = min(nt, rb + TEXT_NLCAP);
 		for (unsigned j = rb + tid; j < r_end; j += 256u) {
 			const unsigned long long g = g0 + j;                 // the newline's ordinal in the text = the 0-based number of the line it ends
 			if (has_header && g == 0) continue;
-			const int end_rel = (int)S.nlpos[j - rb];
+			const int end_rel = (int)S.nl.nlpos[j - rb];
 			long long start_rel;
 			if (j == 0) start_rel = S.first_start - (long long)t0;
-			else if (j > rb) start_rel = (long long)S.nlpos[j - 1 - rb] + 1;
-			else start_rel = (long long)S.carry + 1;
+			else if (j > rb) start_rel = (long long)S.nl.nlpos[j - 1 - rb] + 1;
+			else start_rel = (long long)S.nl.carry + 1;
 			const unsigned long long i = g - has_header;
 			if (start_rel >= -(long long)MRF_LB) fn(i, MrfLdsView{lds_text + (MRF_LB + (int)start_rel), (unsigned)(end_rel - (int)start_rel)});
 			else if constexpr (DEFER) {
@@ -196,9 +100,6 @@ __device__ inline void mrf_tile_lines(MrfTileLds &S, const unsigned tile, const 
 			}
 			else fn(i, lsq::MrfView{reinterpret_cast<const char *>(text) + (t0 + start_rel), (size_t)((long long)end_rel - start_rel)});
 		}
-		__syncthreads();
-		if (tid == 0) S.carry = S.nlpos[MRF_NLCAP - 1];
-		__syncthreads();
 	}
 }
 
@@ -272,21 +173,8 @@ __device__ inline unsigned mrf_strand_slot(const unsigned long long *lds_tab, un
 	return 0;
 }
 
-struct MrfText {
-	const unsigned char *text;
-	unsigned long long len;
-	const unsigned long long *tile_base;
-	unsigned has_header;
-	unsigned long long first_line;            // the number of data line 0 in the whole file (read name "read-<L>")
-	unsigned long long n_lines;
-};
-
 // ---- the parse that feeds the load-time filter (the product path): per line, every block through the covered regions and
-// the merge as it is split off; the routed read to key[i] / rec[i], i the data line's index.  Three kernels:
-//   lsq_mrf_route_fast_kernel   every tile; settles the lines of the usual shape (below) and lists the others
-//   lsq_mrf_route_kernel        the tiles the fast kernel could not table (more delimiters than its LDS tables hold), or every
-//                               tile when the fast kernel does not apply: the shared splitter over LDS bytes, a lane a line
-//   lsq_mrf_route_lines_kernel  the listed lines, a lane a line, the shared splitter over the bytes in HBM
+// the merge as it is split off; the routed read to key[i] / rec[i], i the data line's index
 template <class V>
 __device__ inline void mrf_route_line(const MrfText &X, const MrfDict &D, const unsigned long long *lds_strand, const RouteTables &T, const RouteChrom *chroms, const RouteOut &O,
                                       unsigned long long *err, const unsigned long long i, const V line) {
@@ -307,13 +195,6 @@ __device__ inline void mrf_route_line(const MrfText &X, const MrfDict &D, const 
 	if (!ok) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; return; }
 	A.finish(B, T, chroms, P, O, (unsigned)i);
 }
-
-// lists of work the fast kernel hands on: counts[0] tiles, counts[1] lines, counts[2] set when the line list ran over
-struct MrfHandOff {
-	unsigned *counts;
-	unsigned *tiles; unsigned tile_cap;
-	MrfLongLine *lines; unsigned line_cap;
-};
 
 __global__ void __launch_bounds__(256) lsq_mrf_route_kernel(MrfText X, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles, unsigned listed) {
 	__shared__ MrfTileLds S;
@@ -370,7 +251,7 @@ __global__ void __launch_bounds__(256) lsq_mrf_route_lines_kernel(MrfText X, Mrf
 #else
 #define LSQ_FAST_WAVES_ATTR
 #endif
-constexpr unsigned FP_WIN = MRF_LB + MRF_TILE;          // 8 192
+constexpr unsigned FP_WIN = MRF_LB + TEXT_TILE;          // 8 192
 constexpr unsigned FP_PAD = 16;                          // bytes of LDS ahead of the window (a coordinate's eight bytes may begin there)
 constexpr unsigned FP_LANE = FP_WIN / 256;               // window bytes a lane takes: 32 or 16
 constexpr unsigned FP_DCAP = FP_WIN * 5 / 16, FP_NCAP = FP_WIN / 8;       // delimiters / newlines a window may hold (8 KiB of reads: ~1 500 / ~220)
@@ -446,7 +327,7 @@ __global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_ke
 	};
 	// a workgroup stays for many tiles (the dictionaries above are staged once: 4 KB per workgroup beside 8 KB of text per tile otherwise)
 	for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-	const unsigned long long t0 = (unsigned long long)tile * MRF_TILE;
+	const unsigned long long t0 = (unsigned long long)tile * TEXT_TILE;
 	__syncthreads();                          // (the tile before is done with the tables below)
 	// ---- the window: FP_LANE bytes a lane, in text order (window byte FP_LANE x lane); bytes ahead of the text or behind it count as none
 	unsigned w[FP_LANE / 4];
@@ -477,7 +358,7 @@ __global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_ke
 	m_nl &= live; m_colon &= live; m_comma &= live;
 	const unsigned m_any = m_nl | m_colon | m_comma;
 	unsigned total;
-	const unsigned ex = mrf_block_excl_scan(((unsigned)__popc(m_any) << 16) | (unsigned)__popc(m_nl), S.scan4, total);
+	const unsigned ex = scan_block_excl32(((unsigned)__popc(m_any) << 16) | (unsigned)__popc(m_nl), S.scan4, total);
 	const unsigned n_delim = total >> 16, n_nl = total & 0xFFFFu;
 	if (tid == MRF_LB / FP_LANE) S.nl_ahead = ex & 0xFFFFu;          // (the first lane of the tile proper: what lies ahead of it is the 512 bytes)
 	if (n_delim > FP_DCAP || n_nl > FP_NCAP) {
@@ -669,14 +550,6 @@ __global__ void __launch_bounds__(256) lsq_mrf_count_kernel(MrfText X, unsigned 
 	});
 }
 
-struct MrfOut {
-	unsigned long long *blk_off;
-	unsigned *line_no;
-	int *blk_start, *blk_end;
-	unsigned short *blk_chrom;
-	unsigned char *blk_strand;
-};
-
 // pass 2: every read's blocks to their place (rd_idx / bk_off: exclusive prefix sums of "has blocks" / of the block counts over the data lines)
 __global__ void __launch_bounds__(256) lsq_mrf_write_kernel(MrfText X, const unsigned *line_nb, const unsigned long long *rd_idx, const unsigned long long *bk_off,
                                                             MrfDict G, MrfOut O, unsigned long long *err) {
@@ -703,330 +576,44 @@ __global__ void __launch_bounds__(256) lsq_mrf_write_kernel(MrfText X, const uns
 	});
 }
 
+// ---- the front end (READ_FORMATS, lsq_ingest.hip): the fast kernel's dictionary, the routing launches, what they handed on
+static int mrf_prepare(TextJob &J) {
+	hipStream_t st = J.c->stream;
+	int rc;
+	// the chromosomes' names as 64-bit keys (names of at most seven bytes; a longer one has no slot and its lines go to the list)
+	const lsq_events &E = *J.c->E;
+	const size_t nc = E.covered.size();
+	std::vector<unsigned long long> ck(FP_DICT, 0);
+	std::vector<unsigned short> ci(FP_DICT, 0);
+	const bool usable = nc <= ROUTE_CHROM_LDS && getenv("LSQ_MRF_SLOW") == nullptr;       // (LSQ_MRF_SLOW: the tests run the byte-walking kernel over whole files with it)
+	for (size_t id = 0; usable && id < nc; ++id) {
+		const std::string &nm = E.chroms.names[id];
+		if (nm.empty() || nm.size() > 7) continue;
+		const unsigned long long key = mrf_strand_key(nm.data(), nm.size());
+		unsigned sl = mrf_key_slot(key);
+		while (ck[sl] != 0) sl = (sl + 1u) & (FP_DICT - 1u);
+		ck[sl] = key; ci[sl] = (unsigned short)id;
+	}
+	if ((rc = J.tab64.upload(ck.data(), FP_DICT, st)) || (rc = J.tab16.upload(ci.data(), FP_DICT, st))) return rc;
+	HIP_TRY(hipStreamSynchronize(st));
+	J.all_slow = !usable;
+	return LSQ_OK;
+}
+static void mrf_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
+	const unsigned n_cu = (unsigned)J.c->n_cu, side_grid = std::min(std::max(J.n_tiles, 1u), 4u * n_cu);
+	// a workgroup a tile: the kernel can also run as a grid of resident workgroups that stay for many tiles (LSQ_FAST_GRID workgroups a
+	// compute unit; developer aid) -- measured slower on C3: 7.4 ms at 6, 7.0 at 12, 6.7 at 24 against 6.1 with a workgroup a tile
+	unsigned fast_grid = std::max(J.n_tiles, 1u);
+	if (const char *e = getenv("LSQ_FAST_GRID")) { const int v = atoi(e); if (v > 0) fast_grid = (unsigned)v * n_cu; }
+	const MrfFastDict FD{J.tab64.p, J.tab16.p, 1u};        // (usable, or J.all_slow is set)
+	if (!J.all_slow) {
+		hipLaunchKernelGGL(lsq_mrf_route_fast_kernel, dim3(std::min(J.n_tiles, fast_grid)), dim3(256), 0, s, J.X, J.D, FD, RT, O, J.err, J.H, J.n_tiles);
+		hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(std::min(side_grid, 256u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 1u);
+	} else hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(J.n_tiles), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 0u);
+	hipLaunchKernelGGL(lsq_mrf_route_lines_kernel, dim3(std::min(J.H.line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H);
+}
+static void mrf_record(const TextJob &J) {
+	J.c->parse_tiles_handed = J.all_slow ? 0u : J.counts[0]; J.c->parse_lines_listed = J.counts[1]; J.c->parse_all_slow = J.all_slow ? 1u : 0u;
+}
+
 #include "lsq_sam_device.hpp"
-
-struct DevParsed {
-	uint64_t n_reads = 0, n_blocks = 0;
-	DevBuf<unsigned long long> blk_off;
-	DevBuf<unsigned> line_no;
-	DevBuf<int> bs, be;
-	DevBuf<unsigned short> bc;
-	DevBuf<unsigned char> bst;
-};
-
-struct MappedFile {
-	const char *data = nullptr;
-	size_t len = 0;
-	~MappedFile() { if (data) munmap((void *)data, len); }
-};
-
-// Host memory (or a file) to HBM through two pinned 32 MiB buffers of the context: a few worker threads fill one -- fill(dst, offset,
-// bytes) of their share of the slice: pread() of a file, memcpy() of an array -- while the DMA engine drains the other.  38-53 GB/s,
-// against 18-20 GB/s of the runtime's own staging of pageable memory on its first pass over it (it pins the pages it is given, which
-// is what a first copy of fresh arrays or of a fresh mapping pays for).  The buffers are made once per context.
-constexpr size_t PIN_SLICE = 32ull << 20;
-static int ensure_pinned_buffers(lsq_ctx *c) {
-	if (c->pin_buf[0] && c->pin_buf[1] && c->pin_ev[0] && c->pin_ev[1]) return LSQ_OK;
-	const bool ok = hipHostMalloc((void **)&c->pin_buf[0], PIN_SLICE, hipHostMallocDefault) == hipSuccess &&
-	                hipHostMalloc((void **)&c->pin_buf[1], PIN_SLICE, hipHostMallocDefault) == hipSuccess &&
-	                hipEventCreateWithFlags(&c->pin_ev[0], hipEventDisableTiming) == hipSuccess &&
-	                hipEventCreateWithFlags(&c->pin_ev[1], hipEventDisableTiming) == hipSuccess;
-	if (!ok) {
-		(void)hipGetLastError();
-		for (int q = 0; q < 2; ++q) { if (c->pin_buf[q]) (void)hipHostFree(c->pin_buf[q]); if (c->pin_ev[q]) (void)hipEventDestroy(c->pin_ev[q]); c->pin_buf[q] = nullptr; c->pin_ev[q] = nullptr; }
-		return fail(LSQ_E_INTERNAL, "no pinned host buffers");
-	}
-	return LSQ_OK;
-}
-template <class Fill>
-static int pinned_pipeline(lsq_ctx *c, unsigned char *d_dst, const size_t len, Fill &&fill, const char *what) {
-	if (len == 0) return LSQ_OK;
-	int rc = ensure_pinned_buffers(c);
-	if (rc) return rc;
-	hipStream_t st = c->stream;
-	unsigned char *const *pin = c->pin_buf;
-	int rc_copy = LSQ_OK;
-	int T = std::max(1, std::min(16, host_threads(0)));
-	if (const char *e = getenv("LSQ_COPY_THREADS")) { const int v = atoi(e); if (v > 0 && v <= 64) T = v; }      // developer aid
-	const long n_slices = (long)((len + PIN_SLICE - 1) / PIN_SLICE);
-	std::atomic<long> go{-1}, filled{0};
-	std::atomic<int> io_error{0};
-	std::atomic<bool> give_up{false};         // set on every way out of this function: a worker that still waits for its slice leaves
-	ThreadGroup workers;                      // (joined on every way out, after give_up is set: declared first, destroyed last)
-	struct GiveUp { std::atomic<bool> &f; ~GiveUp() { f.store(true, std::memory_order_release); } } give_up_on_exit{give_up};
-	for (int t = 0; t < T; ++t) workers.spawn([&, t] {
-		for (long sl = 0; sl < n_slices; ++sl) {
-			while (go.load(std::memory_order_acquire) < sl) { if (give_up.load(std::memory_order_acquire)) return; std::this_thread::yield(); }
-			const size_t off = (size_t)sl * PIN_SLICE, nby = std::min<size_t>(PIN_SLICE, len - off);
-			const size_t a = nby * (size_t)t / (size_t)T, b = nby * (size_t)(t + 1) / (size_t)T;
-			if (b > a && !fill(pin[sl & 1] + a, off + a, b - a)) io_error.store(1);
-			filled.fetch_add(1, std::memory_order_release);
-		}
-	});
-	for (long sl = 0; sl < n_slices; ++sl) {
-		const int k = (int)(sl & 1);
-		if (sl >= 2 && rc_copy == LSQ_OK && hipEventSynchronize(c->pin_ev[k]) != hipSuccess) rc_copy = fail(LSQ_E_DEVICE, "hipEventSynchronize failed in the copy of %s", what);
-		go.store(sl, std::memory_order_release);
-		while (filled.load(std::memory_order_acquire) < (long)T * (sl + 1)) std::this_thread::yield();
-		const size_t off = (size_t)sl * PIN_SLICE, nby = std::min<size_t>(PIN_SLICE, len - off);
-		if (rc_copy == LSQ_OK && (hipMemcpyAsync(d_dst + off, pin[k], nby, hipMemcpyHostToDevice, st) != hipSuccess || hipEventRecord(c->pin_ev[k], st) != hipSuccess))
-			rc_copy = fail(LSQ_E_DEVICE, "hipMemcpyAsync failed in the copy of %s", what);
-	}
-	workers.join();
-	if (hipStreamSynchronize(st) != hipSuccess && rc_copy == LSQ_OK) rc_copy = fail(LSQ_E_DEVICE, "the copy of %s failed", what);
-	if (workers.failed() && rc_copy == LSQ_OK) rc_copy = fail(LSQ_E_INTERNAL, "a helper thread failed: %s", workers.error().c_str());
-	if (io_error.load() && rc_copy == LSQ_OK) rc_copy = fail(LSQ_E_IO, "cannot read %s", what);
-	return rc_copy;
-}
-
-static int stage_text_file(lsq_ctx *c, const char *path, unsigned long long byte_begin, unsigned long long byte_end, lsq_text &T) {
-	HostStopwatch SW;
-	int fd = open(path, O_RDONLY);
-	if (fd < 0) return fail(LSQ_E_IO, "cannot open reads file %s", path);
-	struct stat sb;
-	if (fstat(fd, &sb) != 0) { close(fd); return fail(LSQ_E_IO, "cannot stat %s", path); }
-	// Small files are mapped and copied as they are (the runtime stages pageable memory through its own
-	// pinned buffers on one thread: 18 GB/s measured).  Files of a gigabyte and more are never mapped:
-	// a few worker threads pread() them, a slice at a time, into the context's two pinned buffers while
-	// the DMA engine drains the other buffer (38 GB/s, and no page-table build-up and tear-down for
-	// gigabytes of mapping).
-	const unsigned long long file_len = (unsigned long long)sb.st_size;
-	byte_end = std::min(byte_end, file_len);
-	byte_begin = std::min(byte_begin, byte_end);
-	const unsigned long long len = byte_end - byte_begin;          // the bytes [byte_begin, byte_end) of the file
-	unsigned long long pinned_min = 1ull << 30;           // below a gigabyte making the pinned buffers (once per context) costs more than they save
-	if (const char *e = getenv("LSQ_PINNED_COPY_MIN")) { const long long v = atoll(e); if (v >= 0) pinned_min = (unsigned long long)v; }   // tests
-	bool pinned = len >= pinned_min && len >= 2 * PIN_SLICE;
-	struct FdCloser { int fd; ~FdCloser() { if (fd >= 0) close(fd); } } fdc{fd};
-	MappedFile mf;
-	hipStream_t st = c->stream;
-	int rc;
-	T.path = path; T.len = len; T.offset = byte_begin; T.h2d_ms = 0;
-	if (len == 0) return LSQ_OK;
-	DevBuf<unsigned char> &d_text = T.d_text;
-	if ((rc = d_text.alloc(len + 16))) return rc;
-	HIP_TRY(hipEventRecord(c->evt0, st));
-	if (pinned && ensure_pinned_buffers(c) != LSQ_OK) pinned = false;
-	if (pinned) {
-		// (tried: the workers copying out of a mapping of the file instead -- 55 GB/s against 40-46, but the mapping's tear-down
-		// costs 70 ms on one thread and more when the workers share it; and 24 / 32 workers on a box's 16 cores: slower)
-		rc = pinned_pipeline(c, d_text.p, (size_t)len, [&](unsigned char *dst, size_t off, size_t n) {
-			size_t a = 0;
-			while (a < n) {
-				const ssize_t got = pread(fd, dst + a, n - a, (off_t)(byte_begin + off + a));
-				if (got <= 0) return false;
-				a += (size_t)got;
-			}
-			return true;
-		}, path);
-		if (rc) return rc;
-	} else {
-		int rc_copy = LSQ_OK;
-		void *m = mmap(nullptr, (size_t)file_len, PROT_READ, MAP_PRIVATE, fd, 0);
-		if (m == MAP_FAILED) rc_copy = fail(LSQ_E_IO, "cannot map %s", path);
-		else {
-			mf.data = (const char *)m; mf.len = (size_t)file_len;
-			madvise(m, mf.len, MADV_SEQUENTIAL);
-			for (size_t off = 0; off < len && rc_copy == LSQ_OK; off += PIN_SLICE) {
-				const size_t nby = std::min<size_t>(PIN_SLICE, len - off);
-				if (hipMemcpyAsync(d_text.p + off, mf.data + byte_begin + off, nby, hipMemcpyHostToDevice, st) != hipSuccess) rc_copy = fail(LSQ_E_DEVICE, "hipMemcpyAsync failed in the text copy");
-			}
-			if (hipStreamSynchronize(st) != hipSuccess && rc_copy == LSQ_OK) rc_copy = fail(LSQ_E_DEVICE, "text copy failed");
-		}
-		if (rc_copy) return rc_copy;
-	}
-	HIP_TRY(hipEventRecord(c->evt1, st));
-	HIP_TRY(hipEventSynchronize(c->evt1));
-	(void)hipEventElapsedTime(&T.h2d_ms, c->evt0, c->evt1);
-	SW.mark("text: open and copy to HBM");
-	return LSQ_OK;
-}
-
-
-// newline counts of a staged text, per tile, and their prefix sums (kept with the text): lsq_text_lines runs this ahead of the parse
-static int scan_newlines(lsq_ctx *c, lsq_text &T) {
-	if (T.scanned) return LSQ_OK;
-	hipStream_t st = c->stream;
-	int rc;
-	const unsigned long long len = T.len;
-	T.n_nl = 0;
-	if (len) {
-		const unsigned long long n_tiles = (len + MRF_TILE - 1) / MRF_TILE;
-		if (n_tiles > 0x7FFFFFFFull) return fail(LSQ_E_RANGE, "reads file larger than 16 TiB");
-		DevBuf<unsigned> d_tile_cnt;
-		ScanScratch SS;
-		if ((rc = d_tile_cnt.alloc(n_tiles)) || (rc = T.d_tile_base.alloc(n_tiles + 1)) || (rc = SS.reserve(n_tiles))) return rc;
-		StageClock k(c, st, 0);
-		hipLaunchKernelGGL(lsq_mrf_newline_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, T.d_text.p, len, d_tile_cnt.p);
-		HIP_TRY(hipGetLastError());
-		if ((rc = device_scan<1>(SS, d_tile_cnt.p, n_tiles, T.d_tile_base.p, st))) return rc;
-		k.end(len + 12ull * n_tiles);
-		HIP_TRY(hipMemcpyAsync(&T.n_nl, T.d_tile_base.p + n_tiles, 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-	}
-	T.scanned = true;
-	return LSQ_OK;
-}
-
-// The dictionaries of a parse: the events' chromosome names behind a hash table, the strand table seeded with the strands
-// already known.  The events' strand dictionary grows by the strings the file introduces (as it does under lsq_mrf_parse).
-struct MrfDictDev {
-	DevBuf<unsigned> d_hash, d_id, d_off;
-	DevBuf<unsigned long long> d_strand, d_err;
-	DevBuf<char> d_names;
-	size_t n_seed = 0;
-	MrfDict D{};
-	int build(lsq_ctx *c, hipStream_t st) {
-		lsq_events &E = *c->E;
-		int rc;
-		const size_t nc = E.covered.size();
-		size_t tab = 2;
-		while (tab < 4 * nc) tab <<= 1;
-		std::vector<unsigned> h_hash(tab, 0), h_id(tab, 0), h_off(nc + 1, 0);
-		std::string h_names;
-		for (size_t id = 0; id < nc; ++id) {
-			const std::string &nm = E.chroms.names[id];
-			const unsigned h = mrf_fnv32(nm.data(), nm.size());
-			size_t i = (size_t)(h & (unsigned)(tab - 1));
-			while (h_hash[i] != 0) i = (i + 1) & (tab - 1);
-			h_hash[i] = h; h_id[i] = (unsigned)id;
-			h_names += nm;
-			h_off[id + 1] = (unsigned)h_names.size();
-		}
-		if (E.strands.names.size() > 256) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
-		n_seed = E.strands.names.size();
-		std::vector<unsigned long long> h_strand(256, STRAND_EMPTY);
-		for (size_t i = 0; i < n_seed; ++i) {
-			const std::string &s = E.strands.names[i];
-			h_strand[i] = s.size() <= 7 ? mrf_strand_key(s.data(), s.size()) : STRAND_UNMATCHABLE;
-		}
-		const unsigned long long err[4] = {MRF_NO_ERR, 0, 0, 0};
-		if ((rc = d_hash.upload(h_hash.data(), tab, st)) || (rc = d_id.upload(h_id.data(), tab, st)) || (rc = d_off.upload(h_off.data(), nc + 1, st)) ||
-		    (rc = d_names.upload(h_names.data(), h_names.size(), st)) || (rc = d_strand.upload(h_strand.data(), 256, st)) || (rc = d_err.upload(err, 4, st))) return rc;
-		HIP_TRY(hipStreamSynchronize(st));            // the host vectors go out of scope
-		D.chrom_hash = d_hash.p; D.chrom_id = d_id.p; D.name_off = d_off.p; D.names = d_names.p; D.mask = (unsigned)(tab - 1);
-		D.n_chrom = (unsigned)nc; D.names_bytes = (unsigned)h_names.size(); D.strand_tab = d_strand.p;
-		return LSQ_OK;
-	}
-	int reset_errors(hipStream_t st) {
-		static const unsigned long long err0[4] = {MRF_NO_ERR, 0, 0, 0};
-		HIP_TRY(hipMemcpyAsync(d_err.p, err0, sizeof(err0), hipMemcpyHostToDevice, st));
-		return LSQ_OK;
-	}
-	// after the parse kernels have run and the stream has been waited for: the first failing line, strand strings out of range, new strands
-	int settle(lsq_ctx *c, const lsq_text &T, unsigned has_header, unsigned long long first_line, hipStream_t st) {
-		lsq_events &E = *c->E;
-		unsigned long long err[4];
-		std::vector<unsigned long long> h_strand(256);
-		HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(h_strand.data(), d_strand.p, 256 * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (err[0] != MRF_NO_ERR) {
-			// the text of the failing line, from the file: between the newline that ends the line before it and its own
-			const unsigned long long want = err[0] - first_line + has_header;      // ordinal of the newline that ends the failing line
-			std::string text;
-			const int fd = open(T.path.c_str(), O_RDONLY);
-			if (fd >= 0) {
-				// walk the file's range for the want-th newline (an error path: speed does not matter, bounded memory does)
-				std::vector<char> buf(1 << 20);
-				unsigned long long seen = 0, pos = 0;
-				bool in_line = want == 0, done = false;
-				while (!done && pos < T.len) {
-					const size_t ask = (size_t)std::min<unsigned long long>(buf.size(), T.len - pos);
-					const ssize_t got = pread(fd, buf.data(), ask, (off_t)(T.offset + pos));
-					if (got <= 0) break;
-					for (ssize_t q = 0; q < got && !done; ++q) {
-						if (buf[(size_t)q] == '\n') {
-							if (in_line) done = true;
-							else if (++seen == want) in_line = true;
-						} else if (in_line) text.push_back(buf[(size_t)q]);
-					}
-					pos += (unsigned long long)got;
-				}
-				close(fd);
-			}
-			return fail(LSQ_E_PARSE, "#%llu:%s", err[0], text.c_str());
-		}
-		if (err[1]) return fail(LSQ_E_UNSUPPORTED, "a strand string longer than 7 bytes: outside the device parser's range (lsq_mrf_parse handles it)");
-		if (err[2]) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
-		for (size_t i = n_seed; i < 256 && h_strand[i] != STRAND_EMPTY; ++i) {
-			const unsigned long long k = h_strand[i];
-			std::string s;
-			for (unsigned j = 0; j < (unsigned)(k & 0xFF); ++j) s.push_back((char)(k >> (56 - 8 * j)));
-			const int id = E.strands.intern(s);
-			if (id != (int)i) return fail(LSQ_E_STATE, "strand dictionary changed while a reads file was being parsed");
-		}
-		n_seed = E.strands.names.size();
-		return LSQ_OK;
-	}
-};
-
-// Parses staged text on the device into the arrays of lsq_mrf_parse (file order): lsq_mrf_parse_device.
-static int parse_staged_text(lsq_ctx *c, const char *read_format, lsq_text &T, unsigned has_header, unsigned long long first_line, DevParsed &out, float *h2d_ms, float *parse_ms) {
-	if (!read_format) return fail(LSQ_E_ARG, "null argument");
-	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	const bool sam = strcmp(read_format, "SAM_SINGLE") == 0;
-	if (!sam && strcmp(read_format, "MRF_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
-	const SamOpts Q{c->opt_sam_skip_flags, c->opt_sam_min_mapq};
-	hipStream_t st = c->stream;
-	int rc;
-	const unsigned long long zero_off = 0;
-	out.n_reads = out.n_blocks = 0;
-	auto empty_result = [&]() -> int {
-		int r2;
-		if ((r2 = out.blk_off.upload(&zero_off, 1, st)) || (r2 = out.line_no.alloc(0)) || (r2 = out.bs.alloc(0)) || (r2 = out.be.alloc(0)) ||
-		    (r2 = out.bc.alloc(0)) || (r2 = out.bst.alloc(0))) return r2;
-		HIP_TRY(hipStreamSynchronize(st));
-		return LSQ_OK;
-	};
-	if (h2d_ms) *h2d_ms = T.h2d_ms;
-	if (parse_ms) *parse_ms = 0;
-	if (T.len == 0) return empty_result();
-	HIP_TRY(hipEventRecord(c->ev1, st));
-	if ((rc = scan_newlines(c, T))) return rc;
-	const unsigned long long n_nl = T.n_nl;
-	if (n_nl < 1 + has_header) return empty_result();   // header only (or no terminated line at all)
-	const unsigned long long n_lines = n_nl - has_header;
-	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
-	const unsigned n_tiles = (unsigned)((T.len + MRF_TILE - 1) / MRF_TILE);
-	DevBuf<unsigned> d_line_nb;
-	DevBuf<unsigned long long> d_rd_idx, d_bk_off;
-	ScanScratch SS;
-	MrfDictDev DD;
-	if ((rc = d_line_nb.alloc(n_lines)) || (rc = d_rd_idx.alloc(n_lines + 1)) || (rc = d_bk_off.alloc(n_lines + 1)) || (rc = SS.reserve(n_lines)) || (rc = DD.build(c, st))) return rc;
-	MrfText X{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines};
-	if (sam) hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(n_tiles), dim3(256), 0, st, X, Q, d_line_nb.p, DD.d_err.p);
-	else hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(n_tiles), dim3(256), 0, st, X, d_line_nb.p, DD.d_err.p);
-	HIP_TRY(hipGetLastError());
-	if ((rc = device_scan<1, true>(SS, d_line_nb.p, n_lines, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, n_lines, d_bk_off.p, st))) return rc;
-	unsigned long long n_reads = 0, n_blocks = 0;
-	HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + n_lines, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + n_lines, 8, hipMemcpyDeviceToHost, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;          // (waits for the stream) the first failing line ends the run here
-	if ((rc = out.blk_off.alloc(n_reads + 1)) || (rc = out.line_no.alloc(n_reads)) || (rc = out.bs.alloc(n_blocks)) || (rc = out.be.alloc(n_blocks)) ||
-	    (rc = out.bc.alloc(n_blocks)) || (rc = out.bst.alloc(n_blocks))) return rc;
-	MrfOut O{};
-	O.blk_off = out.blk_off.p; O.line_no = out.line_no.p; O.blk_start = out.bs.p; O.blk_end = out.be.p; O.blk_chrom = out.bc.p; O.blk_strand = out.bst.p;
-	if (sam) hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(n_tiles), dim3(256), 0, st, X, Q, (const unsigned *)d_line_nb.p, (const unsigned long long *)d_rd_idx.p,
-	                            (const unsigned long long *)d_bk_off.p, DD.D, O, DD.d_err.p);
-	else hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(n_tiles), dim3(256), 0, st, X, (const unsigned *)d_line_nb.p, (const unsigned long long *)d_rd_idx.p,
-	                   (const unsigned long long *)d_bk_off.p, DD.D, O, DD.d_err.p);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c->ev2, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;
-	if (parse_ms) (void)hipEventElapsedTime(parse_ms, c->ev1, c->ev2);
-	out.n_reads = n_reads; out.n_blocks = n_blocks;
-	return LSQ_OK;
-}
-
-// open -> format literal: the order in which the reference meets a bad file or literal
-static int check_mrf_file(const char *read_format, const char *path) {
-	if (!read_format || !path) return fail(LSQ_E_ARG, "null argument");
-	FILE *f = fopen(path, "rb");
-	if (!f) return fail(LSQ_E_IO, "cannot open reads file %s", path);
-	fclose(f);
-	if (strcmp(read_format, "MRF_SINGLE") != 0 && strcmp(read_format, "SAM_SINGLE") != 0) return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format);
-	return LSQ_OK;
-}
-// a whole file: MRF's first line is its header; every line of a SAM file counts ("read-<k>", k from 1)
-static unsigned text_has_header(const char *read_format) { return strcmp(read_format, "SAM_SINGLE") == 0 ? 0u : 1u; }

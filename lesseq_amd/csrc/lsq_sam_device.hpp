@@ -1,7 +1,6 @@
 // SAM_SINGLE parsed on the device (included by lsq_ingest.hip behind lsq_mrf_device.hpp; not a public header).
 //
-// The text lies in HBM as lsq_text_stage left it and the newline-count pass (lsq_mrf_newline_count_kernel) has numbered its
-// tiles, as for MRF.  What differs is the shape of a line: a record with SEQ and QUAL is 200-400 bytes of which only the
+// The text lies in HBM as lsq_text.hip staged it and its newline-count pass has numbered its tiles (lsq_text.hpp), as for MRF.  What differs is the shape of a line: a record with SEQ and QUAL is 200-400 bytes of which only the
 // first six fields, 40-90 bytes, are ever read, so a 7 680-byte tile holds about 25 lines.  Hence another form than MRF's:
 //   - a line belongs to the tile in which it STARTS (MRF: ends), so that its head is in the tile or the 512 bytes staged
 //     behind it and never in the tile before;
@@ -19,6 +18,7 @@
 //   lsq_sam_route_lines_kernel    the listed lines
 //   lsq_sam_count_kernel / lsq_sam_write_kernel   the same walk for lsq_mrf_parse_device("SAM_SINGLE"): blocks per line,
 //                                 then the parsed arrays, around two prefix sums
+// The format's front end (sam_launch, at the end of this file) launches the route kernels; READ_FORMATS (lsq_ingest.hip) the other two.
 // Line numbers: the ordinal of the newline ahead of a line (tile base + place in the tile) is the line's 0-based number;
 // "read-<k>" counts every line from 1, so has_header = 0 and first_line = 1 for a whole file.
 #pragma once
@@ -36,72 +36,48 @@ struct SamOpts { unsigned skip_flags, min_mapq; };
 template <class Fn>
 __device__ inline void sam_tile_lines(MrfTileLds &S, const unsigned tile, const MrfText &X, Fn &&fn) {
 	const unsigned tid = threadIdx.x;
-	const unsigned long long t0 = (unsigned long long)tile * MRF_TILE;
-	unsigned bits[MRF_TILE_Q];
-#pragma unroll
-	for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-		unsigned valid = 0;
-		const unsigned off = q * 4096u + tid * 16u;
-		const uint4 v = off < MRF_TILE ? mrf_load16(X.text, X.len, t0 + off, valid) : make_uint4(0, 0, 0, 0);
-		if (off < MRF_TILE) *reinterpret_cast<uint4 *>(&S.text[off]) = v;
-		bits[q] = mrf_newline_bits16(v, valid);
-	}
+	const unsigned long long t0 = (unsigned long long)tile * TEXT_TILE;
+	TextTileNl N;
+	N.load(S.text, X.text, X.len, t0);
 	// the bytes behind the tile and the first newline among them (wave 0)
 	if (tid < 64u) {
 		unsigned first = 0xFFFFu;
 		if (tid < SAM_TAIL / 16u) {
 			unsigned valid = 0;
-			const uint4 v = mrf_load16(X.text, X.len, t0 + MRF_TILE + tid * 16ull, valid);
-			*reinterpret_cast<uint4 *>(&S.text[MRF_TILE + tid * 16u]) = v;
-			const unsigned b = mrf_newline_bits16(v, valid);
-			if (b) first = MRF_TILE + tid * 16u + ((unsigned)__ffs((int)b) - 1u);
+			const uint4 v = text_load16(X.text, X.len, t0 + TEXT_TILE + tid * 16ull, valid);
+			*reinterpret_cast<uint4 *>(&S.text[TEXT_TILE + tid * 16u]) = v;
+			const unsigned b = text_newline_bits16(v, valid);
+			if (b) first = TEXT_TILE + tid * 16u + ((unsigned)__ffs((int)b) - 1u);
 		}
 		for (unsigned d = 1; d < 64u; d <<= 1) first = min(first, (unsigned)__shfl_xor((int)first, (int)d));
 		if (tid == 0) S.first_start = first == 0xFFFFu ? -1ll : (long long)first;
 	}
 	// a line starts at the tile's first byte when the byte ahead of it is a newline (or there is none)
 	const bool lead = t0 == 0 || X.text[t0 - 1] == '\n';
-	unsigned ord[MRF_TILE_Q], nt = 0;
-#pragma unroll
-	for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-		unsigned total;
-		ord[q] = nt + mrf_block_excl_scan((unsigned)__popc(bits[q]), S.scan4, total);       // (its barriers also publish S.text and S.first_start)
-		nt += total;
-	}
+	N.number(S.nl);                                                 // (its barriers also publish S.text and S.first_start)
+	const unsigned nt = N.nt;
 	const unsigned long long g0 = X.tile_base[tile];                // newlines ahead of the tile = the number of a line that starts at its first byte
-	const unsigned win = (unsigned)min((unsigned long long)(MRF_TILE + SAM_TAIL), X.len - t0);       // bytes of the window that are text
+	const unsigned win = (unsigned)min((unsigned long long)(TEXT_TILE + SAM_TAIL), X.len - t0);       // bytes of the window that are text
 	// line v of the tile: v = 0 starts at the tile's first byte (if `lead`), v = j + 1 behind the tile's newline j
-	for (unsigned rb = 0; rb <= nt; rb += MRF_NLCAP) {
-#pragma unroll
-		for (unsigned q = 0; q < MRF_TILE_Q; ++q) {
-			unsigned b = bits[q], o = ord[q];
-			while (b) {
-				const unsigned j = (unsigned)__ffs((int)b) - 1u; b &= b - 1u;
-				if (o >= rb && o < rb + MRF_NLCAP) S.nlpos[o - rb] = (unsigned short)(q * 4096u + tid * 16u + j);
-				++o;
-			}
-		}
-		__syncthreads();
-		const unsigned v_end = min(nt + 1u, rb + MRF_NLCAP);
+	for (unsigned rb = 0; rb <= nt; rb += TEXT_NLCAP) {
+		N.round(S.nl, rb);
+		const unsigned v_end = min(nt + 1u, rb + TEXT_NLCAP);
 		// (neighbouring lines go to different waves: a tile of records holds ~25 lines, and one wave walking them all while three
 		// wait is what a lane a line in thread order comes to)
 		for (unsigned v = rb + (tid & 63u) * 4u + (tid >> 6); v < v_end; v += 256u) {
 			unsigned start;
 			if (v == 0) { if (!lead) continue; start = 0; }
-			else start = (v - 1u >= rb ? (unsigned)S.nlpos[v - 1u - rb] : S.carry) + 1u;
-			if (start >= MRF_TILE) continue;                       // (the tile's last byte is a newline: the line behind it is the next tile's)
+			else start = (v - 1u >= rb ? (unsigned)S.nl.nlpos[v - 1u - rb] : S.nl.carry) + 1u;
+			if (start >= TEXT_TILE) continue;                      // (the tile's last byte is a newline: the line behind it is the next tile's)
 			const unsigned long long g = g0 + v;
 			if ((X.has_header && g == 0) || g - X.has_header >= X.n_lines) continue;        // the header; a last line without '\n'
 			bool whole = true;
 			unsigned end;
-			if (v < nt) end = S.nlpos[v - rb];
+			if (v < nt) end = S.nl.nlpos[v - rb];
 			else if (S.first_start >= 0) end = (unsigned)S.first_start;
 			else { end = win; whole = false; }
 			fn(g - X.has_header, start, end - start, whole);
 		}
-		__syncthreads();
-		if (tid == 0) S.carry = S.nlpos[MRF_NLCAP - 1];
-		__syncthreads();
 	}
 }
 
@@ -193,7 +169,7 @@ __global__ void __launch_bounds__(256) LSQ_SAM_WAVES_ATTR lsq_sam_route_kernel(M
 	const RouteChrom *chroms = route_stage_chroms(T, S.chrom);
 	const mrf_lds_cptr lds_text = (mrf_lds_cptr)(const char *)S.text;
 	for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-		const unsigned long long t0 = (unsigned long long)tile * MRF_TILE;
+		const unsigned long long t0 = (unsigned long long)tile * TEXT_TILE;
 		sam_tile_lines(S, tile, X, [&](const unsigned long long i, const unsigned start, const unsigned n, const bool whole) {
 			if constexpr (ALL_HBM) sam_route_whole_line(X, Q, D, S.strand, T, chroms, O, err, i, sam_hbm_line(X, t0 + start));
 			else {
@@ -226,7 +202,7 @@ __global__ void __launch_bounds__(256) lsq_sam_route_lines_kernel(MrfText X, Sam
 // ---- lsq_mrf_parse_device("SAM_SINGLE"): pass 1, blocks per data line (0 for lines that make no read), first malformed line
 __global__ void __launch_bounds__(256) lsq_sam_count_kernel(MrfText X, SamOpts Q, unsigned *line_nb, unsigned long long *err) {
 	__shared__ MrfTileLds S;
-	const unsigned long long t0 = (unsigned long long)blockIdx.x * MRF_TILE;
+	const unsigned long long t0 = (unsigned long long)blockIdx.x * TEXT_TILE;
 	sam_tile_lines(S, blockIdx.x, X, [&](const unsigned long long i, const unsigned start, unsigned, bool) {
 		unsigned nb = 0;
 		const int verdict = lsq::sam_split_line(sam_hbm_line(X, t0 + start), Q.skip_flags, Q.min_mapq, [&](lsq::MrfView, bool, int64_t, int64_t, int64_t, int64_t) { ++nb; });
@@ -241,7 +217,7 @@ __global__ void __launch_bounds__(256) lsq_sam_write_kernel(MrfText X, SamOpts Q
 	__shared__ MrfTileLds S;
 	const MrfDict D = mrf_stage_dict(S, G);
 	const long long LIM = 1ll << 30;
-	const unsigned long long t0 = (unsigned long long)blockIdx.x * MRF_TILE;
+	const unsigned long long t0 = (unsigned long long)blockIdx.x * TEXT_TILE;
 	sam_tile_lines(S, blockIdx.x, X, [&](const unsigned long long i, const unsigned start, unsigned, bool) {
 		const unsigned nb = line_nb[i];
 		const unsigned long long r = rd_idx[i], o = bk_off[i];
@@ -262,3 +238,20 @@ __global__ void __launch_bounds__(256) lsq_sam_write_kernel(MrfText X, SamOpts Q
 		});
 	});
 }
+
+// ---- the front end (READ_FORMATS, lsq_ingest.hip)
+static SamOpts sam_opts(const lsq_ctx *c) { return SamOpts{c->opt_sam_skip_flags, c->opt_sam_min_mapq}; }
+static int sam_prepare(TextJob &J) {
+	J.all_slow = getenv("LSQ_SAM_SLOW") != nullptr;       // (LSQ_SAM_SLOW: the tests run the byte-walking form over whole files with it)
+	return LSQ_OK;
+}
+static void sam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
+	const SamOpts Q = sam_opts(J.c);
+	// a workgroup a tile, as the MRF kernel is launched; the listed lines behind it
+	if (J.n_tiles && J.all_slow) hipLaunchKernelGGL(lsq_sam_route_kernel<true>, dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
+	else if (J.n_tiles) {
+		hipLaunchKernelGGL(lsq_sam_route_kernel<false>, dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
+		hipLaunchKernelGGL(lsq_sam_route_lines_kernel, dim3(std::min(J.H.line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H);
+	}
+}
+static void sam_record(const TextJob &J) { J.c->sam_lines_listed = J.all_slow ? 0u : J.counts[1]; J.c->sam_all_slow = J.all_slow ? 1u : 0u; }

@@ -1,4 +1,4 @@
-// Exclusive prefix sums on the device, for the loader (included by lsq_ingest.hip; not a public header).
+// Exclusive prefix sums on the device (included by the translation units that scan; not a public header).
 //
 //   out[i] = sum of f(in[0..i)),  out[n] = the total          (u32 in, u64 out)
 //
@@ -35,6 +35,23 @@ __device__ inline unsigned long long scan_block_excl(unsigned long long v, unsig
 	__syncthreads();
 	unsigned long long base = 0; total = 0;
 	for (unsigned q = 0; q < nw; ++q) { const unsigned long long t = lds16[q]; base += q < w ? t : 0ull; total += t; }
+	__syncthreads();
+	return base + inc - v;
+}
+
+// the same over 32-bit values and the 256 lanes of a workgroup (the text parsers' tile walks: counts of a few thousand)
+__device__ inline unsigned scan_wave_incl32(unsigned v) {
+	const unsigned lane = threadIdx.x & 63u;
+	for (unsigned d = 1; d < 64; d <<= 1) { const unsigned t = __shfl_up(v, d); if (lane >= d) v += t; }
+	return v;
+}
+__device__ inline unsigned scan_block_excl32(unsigned v, unsigned *lds4, unsigned &total) {
+	const unsigned inc = scan_wave_incl32(v);
+	const unsigned w = threadIdx.x >> 6;
+	if ((threadIdx.x & 63u) == 63u) lds4[w] = inc;
+	__syncthreads();
+	unsigned base = 0; total = 0;
+	for (unsigned q = 0; q < 4; ++q) { const unsigned t = lds4[q]; base += q < w ? t : 0u; total += t; }
 	__syncthreads();
 	return base + inc - v;
 }

@@ -198,6 +198,20 @@ def test_tile_edge_sweep(gpu_ctx):
         check_against_restatement(gpu_ctx, text_with_line_ending_at(rng, TILE - 1 + delta, tail_lines=8))
 
 
+def test_more_lines_in_a_tile_than_one_round_lists(gpu_ctx):
+    """runs of empty and '#' lines, one and two bytes each: thousands of newlines in a 7 680-byte tile, which the kernel lists
+    1 024 at a time; the exon lines between and behind them keep their places, and a short line behind them its number"""
+    rng = random.Random(9)
+    ex = [exon_line(rng, "G%d" % (k % 3), "t%d" % (k % 5)) for k in range(41)]
+    data = b"".join(ex[:10]) + b"\n" * 5000 + ex[10] + b"#\n" * 3000 + b"".join(ex[11:40]) + b"\n" * 1024 + ex[40]
+    g = check_against_restatement(gpu_ctx, data)
+    assert g.num_exon_lines == 41
+    bad = data + b"short\n"
+    with pytest.raises(L.LsqError) as e:
+        gencode.parse_gtf(gpu_ctx, bad)
+    assert "PROBLEM: line %d has fewer than nine TAB-separated fields" % bad.count(b"\n") in str(e.value)
+
+
 def test_long_lines_and_many_exons(gpu_ctx):
     rng = random.Random(77)
     lines = [exon_line(rng, "G%d" % (k % 9), "t%d" % (k % 31)) for k in range(300)]

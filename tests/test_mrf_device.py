@@ -313,6 +313,47 @@ def test_windows_with_more_delimiters_than_the_tables_hold(tmp_path):
     ctx.close()
 
 
+def test_mrf_lines_on_every_tile_boundary(tmp_path, monkeypatch):
+    """reads whose newline falls on, just ahead of and just behind a tile boundary; a run of two-byte lines (more newlines in a
+    tile than one round of the tile walk holds, and more than the fast kernel's tables hold: those tiles are handed to the
+    byte-walking kernel); a last line without a newline; files that end with the tile"""
+    tile = 7680
+    iv, mp = write_annot(tmp_path)
+    read, bare = "c1:+:101:150:1:50", "c1:+:101:150"
+    for shift in list(range(0, 16)) + [tile - 16 - 17 - 2 + k for k in range(-3, 4)]:
+        body = ["AlignmentBlocks", "#" + "x" * shift] + [read] * 60 + ["#"] * 3000 + [bare] * 500 + [read] * 30
+        text = "\n".join(body) + "\n"
+        if shift == 7:
+            text += read                     # ... and a last line without a newline
+        path = str(tmp_path / "b.mrf")
+        with open(path, "w") as f:
+            f.write(text)
+        ev, ctx = setup(iv, mp)
+        host = L.Reads.from_mrf(path, ev)
+        parsed_equal(ev, host, ctx.parse_mrf_device(path))
+        want = pools_and_counts(ctx, reads=host)
+        assert want[0] == 590
+        assert same(want, pools_and_counts(ctx, path=path))
+        assert parse_paths(ctx)[0] > 0       # the tiles of two-byte lines went to the byte-walking kernel
+        monkeypatch.setenv("LSQ_MRF_SLOW", "1")
+        assert same(want, pools_and_counts(ctx, path=path))
+        monkeypatch.delenv("LSQ_MRF_SLOW")
+        ctx.close()
+    # exactly one tile, exactly two tiles
+    for n_tiles in (1, 2):
+        body = "AlignmentBlocks\n" + (read + "\n") * 20
+        text = body + "#" + "y" * (n_tiles * tile - len(body) - 2) + "\n"
+        assert len(text) == n_tiles * tile
+        path = str(tmp_path / "t.mrf")
+        with open(path, "w") as f:
+            f.write(text)
+        ev, ctx = setup(iv, mp)
+        parsed_equal(ev, L.Reads.from_mrf(path, ev), ctx.parse_mrf_device(path))
+        ctx.upload_reads_mrf(0, path)
+        assert ctx.retained(0) == 20
+        ctx.close()
+
+
 @pytest.mark.parametrize("bad", ["c1:+:10x:20:1:10", "c1:+:99999999999999999999:5:1:1", "c1:+:1:5,c1:+:7:9", "", "c1:+"])
 def test_first_failing_line_through_the_ingest_path(bad, tmp_path):
     """the same verdict and the same line number whether the fast kernel meets the line or the list does"""

@@ -12,7 +12,7 @@ for f in lsq_annot lsq_mrf lsq_cli lsq_synth lsq_as lsq_localev lsq_gtf; do
 done
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fsanitize=address -o $O/liblesseq_hip.so $O/lsq_annot.o $O/lsq_mrf.o $O/lsq_cli.o $O/lsq_synth.o $O/lsq_as.o $O/lsq_localev.o $O/lsq_gtf.o \
-	../_build/lsq_device.hip.o ../_build/lsq_count.hip.o ../_build/lsq_em.hip.o ../_build/lsq_ingest.hip.o ../_build/lsq_replay.hip.o ../_build/lsq_as.hip.o ../_build/lsq_localev.hip.o ../_build/lsq_gtf.hip.o -pthread
+	../_build/lsq_device.hip.o ../_build/lsq_count.hip.o ../_build/lsq_em.hip.o ../_build/lsq_text.hip.o ../_build/lsq_ingest.hip.o ../_build/lsq_replay.hip.o ../_build/lsq_as.hip.o ../_build/lsq_localev.hip.o ../_build/lsq_gtf.hip.o -pthread
 cp ../_build/liblesseq_rccl.so $O/
 cd $R
 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 LD_PRELOAD=$(gcc -print-file-name=libasan.so) LSQ_LIB=$O/liblesseq_hip.so \
