@@ -381,11 +381,9 @@ int run_test_as(int argc, const char *const *argv, std::string &out) {
 		return 1;
 	}
 	std::unique_ptr<FILE, int (*)(FILE *)> close_of(of, [](FILE *f) { return f ? fclose(f) : 0; });
-	int dev = 0;
-	if (const char *e = getenv("LSQ_DEVICE")) dev = atoi(e);
 	lsq_ctx *c = nullptr;
 	std::vector<double> stat(n, 0.0), p(n), bon(n), bh(n);
-	st = lsq_ctx_create(dev, &c);
+	st = lsq_ctx_create(cli_device(), &c);
 	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(c, lsq_ctx_destroy);
 	if (!st) {
 		if (t == T_FISHER) st = lsq_as_fisher(c, n, in->values.data(), p.data());

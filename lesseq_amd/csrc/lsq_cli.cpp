@@ -14,14 +14,13 @@
 #include <cstring>
 #include <ctime>
 #include <stdexcept>
-#include <condition_variable>
-#include <mutex>
 #include <string>
 #include <vector>
 
 #include "lsq_internal.hpp"
 #include "lsq_localev.hpp"
 #include "lsq_gtf.hpp"
+#include "lsq_team.hpp"
 
 using namespace lsq;
 
@@ -126,8 +125,7 @@ int precheck_reads_file(const char *fmt, const char *path, bool solve) {
 
 struct Freer {
 	lsq_annotation *a = nullptr; lsq_events *e = nullptr; lsq_ctx *c = nullptr;
-	std::vector<lsq_reads *> r;
-	~Freer() { for (auto *x : r) lsq_reads_free(x); if (c) lsq_ctx_destroy(c); lsq_events_free(e); lsq_annotation_free(a); }
+	~Freer() { if (c) lsq_ctx_destroy(c); lsq_events_free(e); lsq_annotation_free(a); }
 };
 
 int run_classify(int argc, const char *const *argv) {
@@ -227,8 +225,7 @@ struct ShardedJob {
 struct RcclApi {
 	void *handle = nullptr;
 	int (*init_all)(int, const int *, double, void **) = nullptr;     // lsq_comm_init_all_for
-	void (*destroy)(void *) = nullptr;
-	void (*abort_comm)(void *) = nullptr;
+	void (*destroy)(void *) = nullptr, (*abort_comm)(void *) = nullptr;
 	int (*gather)(lsq_ctx *, void *, const void *, void *, uint64_t) = nullptr;
 	int (*allreduce_counts)(lsq_ctx *, void *, void *) = nullptr;
 	const char *(*last_error)(void) = nullptr;
@@ -250,20 +247,84 @@ struct RcclApi {
 	}
 };
 
-// Where the host threads of a job's GPUs meet: everybody arrives, and learns whether everybody is well.  A thread that
-// failed on the way must keep the others out of the collective that follows (they would spin in it for a peer that never comes).
-struct Agreement {
-	std::mutex mu; std::condition_variable cv; int arrived = 0, failed = 0; const int G;
-	explicit Agreement(int g) : G(g) {}
-	bool arrive(bool ok) {
-		std::unique_lock<std::mutex> lk(mu);
-		++arrived; if (!ok) ++failed;
-		cv.notify_all();
-		cv.wait(lk, [&] { return arrived == G; });
-		return failed == 0;
+// What both jobs need around their collective: how the blocks travel, the communicators, and the time limit (default 120 s).
+// Nothing on this path waits without one: the communicator set-up, and the collective, whose kernel spins until every peer has joined it.
+struct Collective {
+	bool via_host = false; double time_limit = 120.0;
+	RcclApi rccl; std::vector<void *> comms;
+	Collective() {
+		if (const char *e = getenv("LSQ_GATHER")) via_host = strcmp(e, "host") == 0;
+		if (const char *e = getenv("LSQ_COLLECTIVE_TIMEOUT")) { const double v = atof(e); if (v > 0) time_limit = v; }
 	}
-	void absent() { std::lock_guard<std::mutex> g(mu); ++arrived; ++failed; cv.notify_all(); }      // a slice that never started
+	~Collective() { for (void *cm : comms) if (cm) rccl.destroy(cm); }
+	// a communicator per slice; 0, or the exit status with the reason logged
+	int init(const ShardedJob &J) {
+		comms.assign((size_t)J.G, nullptr);
+		if (via_host) return 0;
+		if (!rccl.load()) { logf(0, "LSQ_GPUS=%d needs liblesseq_rccl.so beside the library (%s)", J.G, rccl.why.empty() ? "symbols missing" : rccl.why.c_str()); return 3; }
+		if (rccl.init_all(J.G, J.devices.data(), time_limit, comms.data())) { logf(0, "%s", rccl.last_error()); return 3; }
+		return 0;
+	}
+	// slice r waits for its collective, with the limit; on expiry it aborts its communicator, which ends the spinning kernel
+	int wait(lsq_ctx *c, int r) {
+		const int q = lsq_ctx_synchronize_for(c, time_limit);
+		if (q == LSQ_E_TIMEOUT) { rccl.abort_comm(comms[(size_t)r]); comms[(size_t)r] = nullptr; }
+		return q;
+	}
 };
+
+// What a slice works on.  Slice 0 borrows the caller's context and events; every other slice makes its own -- a context on
+// its device under the job's options, the whole selected range compiled -- and releases them with its scope.
+struct SliceContext {
+	lsq_ctx *c = nullptr; lsq_events *e = nullptr; bool own = true;
+	SliceContext() = default; SliceContext(const SliceContext &) = delete;
+	~SliceContext() { if (own) { if (c) lsq_ctx_destroy(c); lsq_events_free(e); } }
+	void borrow(lsq_ctx *c0, lsq_events *e0) { c = c0; e = e0; own = false; }
+	int create(const ShardedJob &J, int r) {
+		int q = lsq_ctx_create(J.devices[(size_t)r], &c);
+		if (!q) q = apply_env_options(c);
+		return q ? q : lsq_events_compile(J.ann, J.M, J.types.data(), J.lens.data(), &e);
+	}
+};
+// the developer's way to see the meeting at work: a slice whose number this variable holds fails where its job asks this
+int failure_requested(SliceTeam &team, int r) {
+	const char *fr = getenv("LSQ_FAIL_RANK");
+	return fr && atoi(fr) == r ? team.fail(r, LSQ_E_STATE, "failure of this slice requested (LSQ_FAIL_RANK)") : LSQ_OK;
+}
+// the first failing slice in slice order speaks (read-sharded: file order -- a field that fails the cast: the reference reports the first such line)
+int report_failure(const SliceTeam &team, const std::vector<int> &devices) {
+	const int r = team.first_failure();
+	if (r < 0) return 0;
+	if (team.status(r) == LSQ_E_PARSE) { logf(0, "%s", team.error(r).c_str()); logf(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
+	logf(0, "GPU %d: %s", devices[(size_t)r], team.error(r).c_str());
+	return 3;
+}
+// One read file into method m of a context: the staged text where there is one, else the file's text through the device
+// parser, else -- name-keyed formats, strand strings beyond the device parser's 7 bytes -- the host parser.
+int load_read_file(lsq_ctx *c, lsq_events *e, int m, const char *fmt, const char *path, lsq_text *staged_text) {
+	int st = staged_text ? lsq_reads_upload_text(c, m, fmt, staged_text) : line_text_format(fmt) ? lsq_reads_upload_mrf(c, m, fmt, path) : LSQ_E_UNSUPPORTED;
+	if (st != LSQ_E_UNSUPPORTED) return st;
+	lsq_reads *rd = nullptr;
+	st = lsq_reads_parse(fmt, path, e, 0, &rd);
+	if (!st) { st = lsq_reads_upload(c, m, rd); lsq_reads_free(rd); }
+	return st;
+}
+// G + 1 byte cuts of a file, moved to line starts (the first slice keeps the header line); false: the file does not open
+bool line_cuts(const char *path, int G, std::vector<uint64_t> &cuts) {
+	FILE *f = fopen(path, "rb");
+	if (!f) return false;
+	fseeko(f, 0, SEEK_END);
+	const uint64_t size = (uint64_t)ftello(f);
+	cuts.assign((size_t)G + 1, size); cuts[0] = 0;
+	for (int r = 1; r < G; ++r) {
+		uint64_t at = std::max(size / (uint64_t)G * (uint64_t)r, cuts[(size_t)r - 1]);
+		fseeko(f, (off_t)at, SEEK_SET);
+		for (int ch; at < size && (ch = fgetc(f)) != EOF;) { ++at; if (ch == '\n') break; }      // to the first byte after the next newline
+		cuts[(size_t)r] = std::min(at, size);
+	}
+	fclose(f);
+	return true;
+}
 
 // The other way to cut one job (LSQ_SHARD=reads; SURVEY 8(e)'s alternative): every GPU takes a slice of the READS -- a byte
 // range of each MRF file, cut at line starts, copied and parsed on that GPU only -- against ALL events; the slices' newline
@@ -277,137 +338,73 @@ struct Agreement {
 // On return ctx0 holds the whole job's counts (lsq_counts_import_device).
 int run_read_sharded_job(const ShardedJob &J, lsq_ctx *ctx0, lsq_events *ev0) {
 	const int G = J.G, M = J.M;
-	const char *gmode = getenv("LSQ_GATHER");
-	const bool via_host = gmode && strcmp(gmode, "host") == 0;
-	double time_limit = 120.0;
-	if (const char *e = getenv("LSQ_COLLECTIVE_TIMEOUT")) { const double v = atof(e); if (v > 0) time_limit = v; }
-	RcclApi rccl;
-	std::vector<void *> comms((size_t)G, nullptr);
-	if (!via_host) {
-		if (!rccl.load()) { logf(0, "LSQ_GPUS=%d needs liblesseq_rccl.so beside the library (%s)", G, rccl.why.empty() ? "symbols missing" : rccl.why.c_str()); return 3; }
-		const int st = rccl.init_all(G, J.devices.data(), time_limit, comms.data());
-		if (st) { logf(0, "%s", rccl.last_error()); return 3; }
-	}
-	// the slices: byte cuts moved to line starts (the first slice keeps the header line)
+	Collective coll;
+	if (const int rc = coll.init(J)) return rc;
 	std::vector<std::vector<uint64_t>> cuts((size_t)M);
-	for (int m = 0; m < M; ++m) {
-		FILE *f = fopen(J.paths[(size_t)m], "rb");
-		if (!f) { logf(0, "cannot open reads file %s", J.paths[(size_t)m]); return EXIT_ABORT; }
-		fseeko(f, 0, SEEK_END);
-		const uint64_t size = (uint64_t)ftello(f);
-		cuts[(size_t)m].assign((size_t)G + 1, size);
-		cuts[(size_t)m][0] = 0;
-		for (int r = 1; r < G; ++r) {
-			uint64_t at = std::max(size / (uint64_t)G * (uint64_t)r, cuts[(size_t)m][(size_t)r - 1]);
-			fseeko(f, (off_t)at, SEEK_SET);
-			int ch;
-			while (at < size && (ch = fgetc(f)) != EOF) { ++at; if (ch == '\n') break; }      // to the first byte after the next newline
-			cuts[(size_t)m][(size_t)r] = std::min(at, size);
-		}
-		fclose(f);
-	}
+	for (int m = 0; m < M; ++m)
+		if (!line_cuts(J.paths[(size_t)m], G, cuts[(size_t)m])) { logf(0, "cannot open reads file %s", J.paths[(size_t)m]); return EXIT_ABORT; }
 	const uint64_t words = lsq_counts_device_words(ctx0);
 	std::vector<std::vector<uint64_t>> lines((size_t)G, std::vector<uint64_t>((size_t)M, 0));     // newlines per slice and file
-	std::vector<std::vector<uint64_t>> host_words(via_host ? (size_t)G : 0, std::vector<uint64_t>(std::max<uint64_t>(words, 1), 0));
-	std::vector<int> status((size_t)G, LSQ_OK);
-	std::vector<std::string> errors((size_t)G);
-	std::vector<lsq_ctx *> ctxs((size_t)G, nullptr);
-	std::vector<lsq_events *> evs((size_t)G, nullptr);
-	std::vector<std::vector<lsq_text *>> texts((size_t)G, std::vector<lsq_text *>((size_t)M, nullptr));
-	std::vector<void *> d_words((size_t)G, nullptr);
-	ctxs[0] = ctx0; evs[0] = ev0;
-	Agreement staged(G), counted(G);
-	auto work = [&](int r) {
-		auto bad = [&](int s2, const char *msg) { status[(size_t)r] = s2 ? s2 : LSQ_E_STATE; errors[(size_t)r] = msg; return status[(size_t)r]; };
-		auto guarded = [&](auto &&body) -> int {
-			try { return body(); }
-			catch (const std::exception &ex) { return bad(LSQ_E_INTERNAL, ex.what()); }
-			catch (...) { return bad(LSQ_E_INTERNAL, "unknown exception"); }
-		};
+	std::vector<std::vector<uint64_t>> host_words(coll.via_host ? (size_t)G : 0, std::vector<uint64_t>(std::max<uint64_t>(words, 1), 0));
+	std::vector<SliceContext> slices((size_t)G);
+	slices[0].borrow(ctx0, ev0);
+	SliceTeam team(G);
+	team.run([&](int r) {
+		SliceContext &S = slices[(size_t)r];
+		std::vector<lsq_text *> text((size_t)M, nullptr);
+		void *d_words = nullptr;
 		// 1. context, event tables, this GPU's byte range of every file, its newline counts
-		int s = guarded([&]() -> int {
+		team.guard(r, lsq_last_error, [&]() -> int {
 			int q;
-			if (r > 0) {
-				if ((q = lsq_ctx_create(J.devices[(size_t)r], &ctxs[(size_t)r])) || (q = apply_env_options(ctxs[(size_t)r]))) return bad(q, lsq_last_error());
-				if ((q = lsq_events_compile(J.ann, M, J.types.data(), J.lens.data(), &evs[(size_t)r]))) return bad(q, lsq_last_error());
-				if ((q = lsq_events_upload(ctxs[(size_t)r], evs[(size_t)r]))) return bad(q, lsq_last_error());
-			}
-			for (int m = 0; m < M; ++m) {
-				if ((q = lsq_text_stage_range(ctxs[(size_t)r], J.paths[(size_t)m], cuts[(size_t)m][(size_t)r], cuts[(size_t)m][(size_t)r + 1], &texts[(size_t)r][(size_t)m]))) return bad(q, lsq_last_error());
-				if ((q = lsq_text_lines(ctxs[(size_t)r], texts[(size_t)r][(size_t)m], &lines[(size_t)r][(size_t)m]))) return bad(q, lsq_last_error());
-			}
+			if (r > 0 && ((q = S.create(J, r)) || (q = lsq_events_upload(S.c, S.e)))) return q;
+			for (int m = 0; m < M; ++m)
+				if ((q = lsq_text_stage_range(S.c, J.paths[(size_t)m], cuts[(size_t)m][(size_t)r], cuts[(size_t)m][(size_t)r + 1], &text[(size_t)m])) ||
+				    (q = lsq_text_lines(S.c, text[(size_t)m], &lines[(size_t)r][(size_t)m]))) return q;
 			return LSQ_OK;
 		});
-		bool everyone = staged.arrive(s == LSQ_OK);
-		lsq_ctx *c = ctxs[(size_t)r];
+		bool everyone = team.meet(r);
 		// 2. parse and ingest the slice under its file-wide line numbers, count, hand the counters over
-		s = LSQ_E_STATE;
-		if (everyone) s = guarded([&]() -> int {
+		if (everyone) team.guard(r, lsq_last_error, [&]() -> int {
 			int q;
 			for (int m = 0; m < M; ++m) {
 				uint64_t before = 0;
 				for (int p = 0; p < r; ++p) before += lines[(size_t)p][(size_t)m];
-				if ((q = lsq_reads_upload_text_at(c, m, J.fmts[(size_t)m], texts[(size_t)r][(size_t)m], r == 0 ? 1 : 0, r == 0 ? 1 : before))) return bad(q, lsq_last_error());
-				lsq_text_free(texts[(size_t)r][(size_t)m]); texts[(size_t)r][(size_t)m] = nullptr;
+				if ((q = lsq_reads_upload_text_at(S.c, m, J.fmts[(size_t)m], text[(size_t)m], r == 0 ? 1 : 0, r == 0 ? 1 : before))) return q;
+				lsq_text_free(text[(size_t)m]); text[(size_t)m] = nullptr;
 			}
-			if ((q = lsq_count(c))) return bad(q, lsq_last_error());
-			if ((q = lsq_device_alloc(c, std::max<uint64_t>(words, 1) * 8, &d_words[(size_t)r]))) return bad(q, lsq_last_error());
-			if (via_host) {
-				if ((q = lsq_counts_export_device(c, d_words[(size_t)r])) || (q = lsq_device_read(c, host_words[(size_t)r].data(), d_words[(size_t)r], words * 8))) return bad(q, lsq_last_error());
-			}
-			if (const char *fr = getenv("LSQ_FAIL_RANK")) if (atoi(fr) == r) return bad(LSQ_E_STATE, "failure of this slice requested (LSQ_FAIL_RANK)");
-			return LSQ_OK;
+			if ((q = lsq_count(S.c)) || (q = lsq_device_alloc(S.c, std::max<uint64_t>(words, 1) * 8, &d_words))) return q;
+			if (coll.via_host && ((q = lsq_counts_export_device(S.c, d_words)) || (q = lsq_device_read(S.c, host_words[(size_t)r].data(), d_words, words * 8)))) return q;
+			return failure_requested(team, r);
 		});
-		everyone = everyone && counted.arrive(s == LSQ_OK);
+		everyone = team.meet(r);
 		// 3. the sum over the GPUs; GPU 0 takes it as its counts
-		if (everyone) (void)guarded([&]() -> int {
+		if (everyone) team.guard(r, lsq_last_error, [&]() -> int {
 			int q;
-			if (via_host) {
-				if (r == 0) {
-					for (int p = 1; p < G; ++p) for (uint64_t w = 0; w < words; ++w) host_words[0][(size_t)w] += host_words[(size_t)p][(size_t)w];
-					if ((q = lsq_device_write(c, d_words[0], host_words[0].data(), words * 8)) || (q = lsq_counts_import_device(c, d_words[0])) || (q = lsq_ctx_synchronize(c))) return bad(q, lsq_last_error());
-				}
-				return LSQ_OK;
+			if (!coll.via_host) {
+				if ((q = coll.rccl.allreduce_counts(S.c, coll.comms[(size_t)r], d_words))) return team.fail(r, q, coll.rccl.last_error());
+				if ((q = coll.wait(S.c, r))) return q;
 			}
-			if ((q = rccl.allreduce_counts(c, comms[(size_t)r], d_words[(size_t)r]))) return bad(q, rccl.last_error());
-			if ((q = lsq_ctx_synchronize_for(c, time_limit))) {
-				bad(q, lsq_last_error());
-				if (q == LSQ_E_TIMEOUT) { rccl.abort_comm(comms[(size_t)r]); comms[(size_t)r] = nullptr; }       // ends the spinning kernel
-				return q;
+			if (r > 0) return LSQ_OK;
+			if (coll.via_host) {
+				for (int p = 1; p < G; ++p) for (uint64_t w = 0; w < words; ++w) host_words[0][(size_t)w] += host_words[(size_t)p][(size_t)w];
+				if ((q = lsq_device_write(S.c, d_words, host_words[0].data(), words * 8))) return q;
 			}
-			if (r == 0 && ((q = lsq_counts_import_device(c, d_words[0])) || (q = lsq_ctx_synchronize(c)))) return bad(q, lsq_last_error());
-			return LSQ_OK;
+			return (q = lsq_counts_import_device(S.c, d_words)) ? q : lsq_ctx_synchronize(S.c);
 		});
-		for (auto *&t : texts[(size_t)r]) { lsq_text_free(t); t = nullptr; }
-		if (c) lsq_device_free(c, d_words[(size_t)r]);
-		if (everyone && !status[(size_t)r])
+		for (auto *&t : text) { lsq_text_free(t); t = nullptr; }
+		if (S.c) lsq_device_free(S.c, d_words);
+		if (everyone && !team.status(r))
 			logf(2, "GPU %d: bytes %llu..%llu of %s%s, %llu reads retained of them", J.devices[(size_t)r], (unsigned long long)cuts[0][(size_t)r], (unsigned long long)cuts[0][(size_t)r + 1],
-			     J.paths[0], M > 1 ? " (and the like of the other files)" : "", (unsigned long long)lsq_reads_retained(c, 0));
-	};
-	{
-		ThreadGroup th;
-		for (int r = 1; r < G; ++r) {
-			try { th.spawn([&work, r] { work(r); }); }
-			catch (...) { status[(size_t)r] = LSQ_E_INTERNAL; errors[(size_t)r] = "the slice's host thread could not be started"; staged.absent(); }
-		}
-		work(0);
-		th.join();
-	}
+			     J.paths[0], M > 1 ? " (and the like of the other files)" : "", (unsigned long long)lsq_reads_retained(S.c, 0));
+	});
+	if (const int rc = report_failure(team, J.devices)) return rc;
 	uint64_t retained_all = 0;
-	for (int r = 0; r < G; ++r) if (ctxs[(size_t)r]) retained_all += lsq_reads_retained(ctxs[(size_t)r], 0);
-	for (int r = 1; r < G; ++r) { if (ctxs[(size_t)r]) lsq_ctx_destroy(ctxs[(size_t)r]); lsq_events_free(evs[(size_t)r]); }
-	if (!via_host) for (void *cm : comms) if (cm) rccl.destroy(cm);
-	// the first failing slice in file order speaks (a field that fails the cast: the reference reports the first such line)
-	for (int r = 0; r < G; ++r) if (status[(size_t)r]) {
-		if (status[(size_t)r] == LSQ_E_PARSE) { logf(0, "%s", errors[(size_t)r].c_str()); logf(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
-		logf(0, "GPU %d: %s", J.devices[(size_t)r], errors[(size_t)r].c_str());
-		return 3;
-	}
+	for (const SliceContext &S : slices) retained_all += lsq_reads_retained(S.c, 0);
 	logf(2, "Sampling method #0: loaded %llu reads associated with the selected gene regions (over %d GPUs)", (unsigned long long)retained_all, G);
 	return 0;
 }
 
-// F.c / F.e: GPU 0's context with the whole job counted on it (the pre-pass); texts0: its staged MRF texts (kept)
+// the job sharded by events; ctx0 / ev0: GPU 0's context with the whole job counted on it (the pre-pass); texts0: its staged texts (kept)
 int run_sharded_job(const ShardedJob &J, lsq_ctx *ctx0, lsq_events *ev0, std::vector<lsq_text *> &texts0, const std::vector<double> &trb, std::string &out) {
 	const int G = J.G, M = J.M;
 	const int64_t n_ev = lsq_events_count(ev0);
@@ -427,103 +424,44 @@ int run_sharded_job(const ShardedJob &J, lsq_ctx *ctx0, lsq_events *ev0, std::ve
 	if (st) { logf(0, "%s", lsq_last_error()); return 2; }
 	uint64_t stride = 1;
 	for (int r = 0; r < G; ++r) stride = std::max(stride, lsq_record_words(ev0, first[(size_t)r], count[(size_t)r]));
-	const char *gmode = getenv("LSQ_GATHER");
-	const bool via_host = gmode && strcmp(gmode, "host") == 0;
-	RcclApi rccl;
-	std::vector<void *> comms((size_t)G, nullptr);
-	// nothing on this path waits without a limit (LSQ_COLLECTIVE_TIMEOUT seconds, default 120): the communicator set-up, and
-	// the gather itself -- whose kernel spins until every peer has joined it
-	double time_limit = 120.0;
-	if (const char *e = getenv("LSQ_COLLECTIVE_TIMEOUT")) { const double v = atof(e); if (v > 0) time_limit = v; }
-	if (!via_host) {
-		if (!rccl.load()) { logf(0, "LSQ_GPUS=%d needs liblesseq_rccl.so beside the library (%s)", G, rccl.why.empty() ? "symbols missing" : rccl.why.c_str()); return 3; }
-		st = rccl.init_all(G, J.devices.data(), time_limit, comms.data());
-		if (st) { logf(0, "%s", rccl.last_error()); return 3; }
-	}
 	std::vector<uint64_t> host_blocks((size_t)G * stride, 0);
-	std::vector<int> status((size_t)G, LSQ_OK);
-	std::vector<std::string> errors((size_t)G);
-	std::vector<lsq_ctx *> ctxs((size_t)G, nullptr);
-	std::vector<lsq_events *> evs((size_t)G, nullptr);
-	std::vector<void *> d_blocks((size_t)G, nullptr), d_alls((size_t)G, nullptr);
-	std::vector<uint32_t> replayed((size_t)G, 0);
-	ctxs[0] = ctx0; evs[0] = ev0;
-	// Every GPU's thread does its slice up to the packed block, then all of them AGREE before any enters the collective: a
-	// thread that failed on the way (no context, a file it cannot parse, out of memory) would otherwise leave the others
-	// spinning in ncclAllGather for a peer that never comes.  One failure: nobody gathers, the job exits 3 with the message.
-	Agreement agreement(G);
-	auto prepare = [&](int r) -> int {
-		auto bad = [&](int s2, const char *msg) { status[(size_t)r] = s2 ? s2 : LSQ_E_STATE; errors[(size_t)r] = msg; return status[(size_t)r]; };
-		int s;
-		if (r > 0) {
-			if ((s = lsq_ctx_create(J.devices[(size_t)r], &ctxs[(size_t)r])) || (s = apply_env_options(ctxs[(size_t)r]))) return bad(s, lsq_last_error());
-			if ((s = lsq_events_compile(J.ann, M, J.types.data(), J.lens.data(), &evs[(size_t)r]))) return bad(s, lsq_last_error());
-		}
-		lsq_ctx *c = ctxs[(size_t)r];
-		lsq_events *e = evs[(size_t)r];
-		if ((s = lsq_events_set_shard(e, first[(size_t)r], count[(size_t)r])) || (s = lsq_events_upload(c, e))) return bad(s, lsq_last_error());
-		for (int m = 0; m < M; ++m) {
-			if (r == 0 && texts0[(size_t)m]) s = lsq_reads_upload_text(c, m, J.fmts[(size_t)m], texts0[(size_t)m]);
-			else if (line_text_format(J.fmts[(size_t)m]) && (r > 0 || !texts0[(size_t)m])) s = lsq_reads_upload_mrf(c, m, J.fmts[(size_t)m], J.paths[(size_t)m]);
-			else s = LSQ_E_UNSUPPORTED;
-			if (s == LSQ_E_UNSUPPORTED) {         // name-keyed formats, long strand strings: the host parser
-				lsq_reads *rd = nullptr;
-				s = lsq_reads_parse(J.fmts[(size_t)m], J.paths[(size_t)m], e, 0, &rd);
-				if (!s) { s = lsq_reads_upload(c, m, rd); lsq_reads_free(rd); }
-			}
-			if (s) return bad(s, lsq_last_error());
-		}
-		if ((s = lsq_count(c)) || (s = lsq_solve(c)) || (s = lsq_solve_finalize(c, &replayed[(size_t)r]))) return bad(s, lsq_last_error());
-		if ((s = lsq_device_alloc(c, stride * 8, &d_blocks[(size_t)r]))) return bad(s, lsq_last_error());
-		if (!via_host && (s = lsq_device_alloc(c, (uint64_t)G * stride * 8, &d_alls[(size_t)r]))) return bad(s, lsq_last_error());
-		if ((s = lsq_results_pack_device(c, d_blocks[(size_t)r]))) return bad(s, lsq_last_error());
-		// (the developer's way to see the agreement at work: LSQ_FAIL_RANK=r makes slice r fail here)
-		if (const char *fr = getenv("LSQ_FAIL_RANK")) if (atoi(fr) == r) return bad(LSQ_E_STATE, "failure of this slice requested (LSQ_FAIL_RANK)");
-		return LSQ_OK;
-	};
-	auto work = [&](int r) {
-		int s = LSQ_E_INTERNAL;
-		try { s = prepare(r); }
-		catch (const std::exception &ex) { status[(size_t)r] = LSQ_E_INTERNAL; errors[(size_t)r] = ex.what(); }
-		catch (...) { status[(size_t)r] = LSQ_E_INTERNAL; errors[(size_t)r] = "unknown exception"; }
-		const bool everyone = agreement.arrive(s == LSQ_OK);
-		lsq_ctx *c = ctxs[(size_t)r];
-		if (everyone) {
-			auto bad = [&](int s2, const char *msg) { status[(size_t)r] = s2 ? s2 : LSQ_E_STATE; errors[(size_t)r] = msg; };
-			if (via_host) {
-				s = lsq_device_read(c, host_blocks.data() + (size_t)r * stride, d_blocks[(size_t)r], stride * 8);
-				if (s) bad(s, lsq_last_error());
-			} else {
-				s = rccl.gather(c, comms[(size_t)r], d_blocks[(size_t)r], d_alls[(size_t)r], stride);
-				if (s) bad(s, rccl.last_error());
-				else if ((s = lsq_ctx_synchronize_for(c, time_limit))) {
-					bad(s, lsq_last_error());
-					if (s == LSQ_E_TIMEOUT) { rccl.abort_comm(comms[(size_t)r]); comms[(size_t)r] = nullptr; }       // ends the spinning kernel
-				}
-				else if (r == 0) { s = lsq_device_read(c, host_blocks.data(), d_alls[0], (uint64_t)G * stride * 8); if (s) bad(s, lsq_last_error()); }
-			}
-		}
-		if (c) { lsq_device_free(c, d_alls[(size_t)r]); lsq_device_free(c, d_blocks[(size_t)r]); }
-		if (everyone && !status[(size_t)r]) {
+	Collective coll;
+	if (const int rc = coll.init(J)) return rc;
+	std::vector<SliceContext> slices((size_t)G);
+	slices[0].borrow(ctx0, ev0);
+	// Every GPU's thread does its slice up to the packed block, then all of them MEET before any enters the collective
+	// (lsq_team.hpp).  One failure -- no context, a file it cannot parse, out of memory: nobody gathers, the job exits 3 with the message.
+	SliceTeam team(G);
+	team.run([&](int r) {
+		SliceContext &S = slices[(size_t)r];
+		void *d_block = nullptr, *d_all = nullptr;
+		uint32_t replayed = 0;
+		team.guard(r, lsq_last_error, [&]() -> int {
+			int s;
+			if ((r > 0 && (s = S.create(J, r))) || (s = lsq_events_set_shard(S.e, first[(size_t)r], count[(size_t)r])) || (s = lsq_events_upload(S.c, S.e))) return s;
+			for (int m = 0; m < M; ++m)
+				if ((s = load_read_file(S.c, S.e, m, J.fmts[(size_t)m], J.paths[(size_t)m], r == 0 ? texts0[(size_t)m] : nullptr))) return s;
+			if ((s = lsq_count(S.c)) || (s = lsq_solve(S.c)) || (s = lsq_solve_finalize(S.c, &replayed)) || (s = lsq_device_alloc(S.c, stride * 8, &d_block)) ||
+			    (!coll.via_host && (s = lsq_device_alloc(S.c, (uint64_t)G * stride * 8, &d_all))) || (s = lsq_results_pack_device(S.c, d_block))) return s;
+			return failure_requested(team, r);
+		});
+		const bool everyone = team.meet(r);
+		if (everyone) team.guard(r, lsq_last_error, [&]() -> int {
+			int s;
+			if (coll.via_host) return lsq_device_read(S.c, host_blocks.data() + (size_t)r * stride, d_block, stride * 8);
+			if ((s = coll.rccl.gather(S.c, coll.comms[(size_t)r], d_block, d_all, stride))) return team.fail(r, s, coll.rccl.last_error());
+			if ((s = coll.wait(S.c, r)) || r > 0) return s;
+			return lsq_device_read(S.c, host_blocks.data(), d_all, (uint64_t)G * stride * 8);
+		});
+		if (S.c) { lsq_device_free(S.c, d_all); lsq_device_free(S.c, d_block); }
+		if (everyone && !team.status(r)) {
 			unsigned long long pooled = 0;
-			for (int m = 0; m < M; ++m) pooled += lsq_reads_pooled(c, m);
+			for (int m = 0; m < M; ++m) pooled += lsq_reads_pooled(S.c, m);
 			logf(2, "GPU %d: events %llu..%llu of the sorted list, %llu reads pooled for them%s", J.devices[(size_t)r], (unsigned long long)first[(size_t)r],
-			     (unsigned long long)(first[(size_t)r] + count[(size_t)r]), pooled, replayed[(size_t)r] ? " (guard-band events solved again in per-read order)" : "");
+			     (unsigned long long)(first[(size_t)r] + count[(size_t)r]), pooled, replayed ? " (guard-band events solved again in per-read order)" : "");
 		}
-	};
-	{
-		ThreadGroup th;          // joined on every way out
-		// (a thread that cannot even be started counts as a slice that failed: the others must not wait for it)
-		for (int r = 1; r < G; ++r) {
-			try { th.spawn([&work, r] { work(r); }); }
-			catch (...) { status[(size_t)r] = LSQ_E_INTERNAL; errors[(size_t)r] = "the slice's host thread could not be started"; agreement.absent(); }
-		}
-		work(0);
-		th.join();
-	}
-	for (int r = 1; r < G; ++r) { if (ctxs[(size_t)r]) lsq_ctx_destroy(ctxs[(size_t)r]); lsq_events_free(evs[(size_t)r]); }
-	if (!via_host) for (void *cm : comms) if (cm) rccl.destroy(cm);
-	for (int r = 0; r < G; ++r) if (status[(size_t)r]) { logf(0, "GPU %d: %s", J.devices[(size_t)r], errors[(size_t)r].c_str()); return 3; }
+	});
+	if (const int rc = report_failure(team, J.devices)) return rc;
 	// the whole job's tables, in output order
 	const size_t n_iso = (size_t)lsq_events_total_isoforms(ev0);
 	std::vector<uint64_t> cnt(std::max<size_t>((size_t)M * n_cls, 1)), bases(cnt.size());
@@ -574,16 +512,17 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	}
 	const int M = (int)paths.size();
 	if (M > LSQ_MAX_METHODS) { logf(0, "more than %d read files", LSQ_MAX_METHODS); return 2; }
-	// LSQ_DEVICE picks the GPU; LSQ_GPUS=N runs the job over N of them (LSQ_DEVICES="a,b,..." names them, default 0..N-1)
+	// LSQ_DEVICE picks the GPU (cli_device); LSQ_GPUS=N runs the job over N of them (LSQ_DEVICES="a,b,..." names them, default 0..N-1)
 	int G = 1;
 	if (const char *e = getenv("LSQ_GPUS")) G = std::max(1, atoi(e));
 	if (want_fim) G = 1;
 	std::vector<int> devices;
 	if (const char *e = getenv("LSQ_DEVICES")) { const char *q = e; while (*q) { devices.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; } }
 	if (G > 1 && devices.size() < (size_t)G) { devices.clear(); for (int r = 0; r < G; ++r) devices.push_back(r); }
-	if (G == 1) { int dev = 0; if (const char *e = getenv("LSQ_DEVICE")) dev = atoi(e); devices.assign(1, dev); }
+	if (G == 1) devices.assign(1, cli_device());
 	devices.resize((size_t)G);
 	// LSQ_SHARD=reads: the job's GPUs share the READS instead of the events (run_read_sharded_job): MRF_SINGLE files only
+	const char *const gather_mode = getenv("LSQ_GATHER");          // (set at all: the staged texts are kept for the event-sharded job below, its one-slice self-check included)
 	bool shard_reads = false;
 	if (const char *e = getenv("LSQ_SHARD")) shard_reads = strcmp(e, "reads") == 0 && G > 1 && !want_fim;
 	for (const char *f : fmts) if (strcmp(f, "MRF_SINGLE") != 0) shard_reads = false;
@@ -682,16 +621,8 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 		}
 		if (shard_reads) continue;          // (the files open and are MRF_SINGLE: the GPUs read their slices below)
 		// MRF text -> HBM -> parsed and ingested there; the name-keyed formats are grouped by name on the host first
-		if (texts[(size_t)m]) {
-			st = lsq_reads_upload_text(F.c, m, fmts[m], texts[(size_t)m]);
-			if ((G == 1 && !getenv("LSQ_GATHER")) || st) { lsq_text_free(texts[(size_t)m]); texts[(size_t)m] = nullptr; }      // several GPUs: GPU 0 ingests it again, for its slice
-		} else st = named_read_format(fmts[m]) ? LSQ_E_UNSUPPORTED : lsq_reads_upload_mrf(F.c, m, fmts[m], paths[m]);
-		if (st == LSQ_E_UNSUPPORTED) {
-			// a strand string beyond the device parser's 7 bytes: the host parser reads such files
-			lsq_reads *r = nullptr;
-			st = lsq_reads_parse(fmts[m], paths[m], F.e, 0, &r);
-			if (!st) { F.r.push_back(r); st = lsq_reads_upload(F.c, m, r); lsq_reads_free(r); F.r.back() = nullptr; }
-		}
+		st = load_read_file(F.c, F.e, m, fmts[m], paths[m], texts[(size_t)m]);
+		if ((G == 1 && !gather_mode) || st) { lsq_text_free(texts[(size_t)m]); texts[(size_t)m] = nullptr; }      // several GPUs: GPU 0 ingests it again, for its slice
 		if (st == LSQ_E_PARSE) { logf(0, "%s", lsq_last_error()); logf(0, "Lexical_cast error when converting arguments to numeric values"); return status_to_exit(st); }
 		if (st) { logf(0, "%s", lsq_last_error()); return st == LSQ_E_DEVICE ? 3 : (st == LSQ_E_IO || st == LSQ_E_FORMAT ? status_to_exit(st) : 2); }
 		logf(2, "Sampling method #%d: loaded %llu reads associated with the selected gene regions", m, (unsigned long long)lsq_reads_retained(F.c, m));
@@ -701,13 +632,13 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	// (read-sharded: the reads are loaded below, and a line that fails the cast there comes first, as in the reference)
 	if (bad_type && n_ev > 0 && !shard_reads) { logf(0, "Unknown read type error: %s", bad_type_name.c_str()); return 1; }
 	logf(2, "Processing reads info for genes");
+	ShardedJob J{solve, G, M, F.a, fmts, use_types, paths, lens, devices};
 	if (shard_reads && n_ev > 0) {
-		ShardedJob J{solve, G, M, F.a, fmts, use_types, paths, lens, devices};
 		const int rc = run_read_sharded_job(J, F.c, F.e);
 		T.mark("read-sharded ingest + count + sum");
 		if (rc) return rc;
 		if (bad_type) { logf(0, "Unknown read type error: %s", bad_type_name.c_str()); return 1; }
-		G = 1;                  // the sums are GPU 0's counts now: the rest is a single-GPU run
+		J.G = G = 1;            // the sums are GPU 0's counts now: the rest is a single-GPU run
 	} else {
 		shard_reads = false;
 		st = lsq_count(F.c);
@@ -720,9 +651,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 			     (unsigned long long)hg, LSQ_MAX_ISOFORMS, LSQ_MAX_SEGMENTS, (unsigned long long)hr);
 	}
 	// (LSQ_GPUS=1 with LSQ_GATHER=rccl spelled out takes the same path with one slice: a self-check of the gather on one GPU)
-	const char *gm = getenv("LSQ_GATHER");
-	if ((G > 1 || (getenv("LSQ_GPUS") && gm && strcmp(gm, "rccl") == 0 && !want_fim)) && n_ev > 0) {
-		ShardedJob J{solve, G, M, F.a, fmts, use_types, paths, lens, devices};
+	if ((G > 1 || (getenv("LSQ_GPUS") && gather_mode && strcmp(gather_mode, "rccl") == 0 && !want_fim)) && n_ev > 0) {
 		const int rc = run_sharded_job(J, F.c, F.e, texts, trb, out);
 		T.mark("sharded job");
 		return rc;
@@ -809,6 +738,7 @@ std::string format_events_parallel(size_t n, F &&one) {
 } // namespace
 
 void lsq::cli_log(int level, const char *text) { logf(level, "%s", text); }
+int lsq::cli_device() { const char *e = getenv("LSQ_DEVICE"); return e ? atoi(e) : 0; }
 
 extern "C" {
 

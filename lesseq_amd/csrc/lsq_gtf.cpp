@@ -147,11 +147,6 @@ int isoform_map(const char *s, size_t len, std::string &o) {
 	return LSQ_OK;
 }
 
-int device_from_env() {
-	const char *e = getenv("LSQ_DEVICE");
-	return e ? atoi(e) : 0;
-}
-
 } // namespace
 
 // parseGencode [gtf_path]: the GTF from standard input (or the file) to the LH_GENE_TXT text.  Exit status 0; 1 for an
@@ -161,7 +156,7 @@ int run_parse_gencode(int argc, const char *const *argv, std::string &out) {
 	std::string bytes;
 	if (argc < 2 && read_all(nullptr, bytes)) { cli_log(0, lsq_last_error()); return 1; }
 	lsq_ctx *c = nullptr;
-	int st = lsq_ctx_create(device_from_env(), &c);
+	int st = lsq_ctx_create(cli_device(), &c);
 	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(c, lsq_ctx_destroy);
 	if (st) { cli_log(0, lsq_last_error()); return 2; }
 	lsq_gtf *raw = nullptr;

@@ -295,6 +295,7 @@ namespace lsq {
 int plan_device(lsq_events &E);
 int host_threads(int requested);
 void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
+int cli_device();                                                            // lsq_cli.cpp: the GPU the environment picks for an executable (default 0)
 int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
 int run_sam2mrf(int argc, const char *const *argv, std::string &out);        // lsq_sam.cpp: the sam2mrf executable
 

@@ -468,8 +468,6 @@ int le_graphs_from_texts(const std::string &interval_text, const std::string &ma
 int run_events(int argc, const char *const *argv, std::string &out) {
 	const bool annot = argc >= 2 && strcmp(argv[1], "--annotation") == 0, gtf = argc >= 2 && strcmp(argv[1], "--gtf") == 0;
 	if (annot ? argc != 7 : argc != 4) { cli_log(0, USAGE); return 1; }
-	int dev = 0;
-	if (const char *e = getenv("LSQ_DEVICE")) dev = atoi(e);
 	lsq_ctx *c = nullptr;
 	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(nullptr, lsq_ctx_destroy);
 	lsq_le_graphs *raw = nullptr;
@@ -477,7 +475,7 @@ int run_events(int argc, const char *const *argv, std::string &out) {
 	if (gtf) {
 		// the GTF is parsed on the device (lsq_gtf.hip), so the context comes first; the output directory is still checked before anything is written
 		if ((st = check_out_prefix(argv[3]))) { cli_log(0, lsq_last_error()); return 1; }
-		st = lsq_ctx_create(dev, &c);
+		st = lsq_ctx_create(cli_device(), &c);
 		ctx.reset(c);
 		if (st) { cli_log(0, lsq_last_error()); return 2; }
 		st = lsq_le_load_gtf(c, argv[2], &raw);
@@ -492,7 +490,7 @@ int run_events(int argc, const char *const *argv, std::string &out) {
 	if ((st = check_out_prefix(prefix))) { cli_log(0, lsq_last_error()); return 1; }
 	lsq_le_result *res = nullptr;
 	if (!c) {
-		st = lsq_ctx_create(dev, &c);
+		st = lsq_ctx_create(cli_device(), &c);
 		ctx.reset(c);
 	}
 	if (!st) st = lsq_le_detect(c, g.get(), &res);

@@ -424,6 +424,27 @@ def test_in_process_cli_leaves_no_thread_behind(tmp_path, monkeypatch):
     assert threading.active_count() >= 1
 
 
+def test_slice_team_alone_under_sanitizers(tmp_path):
+    """lesseq_amd/csrc/lsq_team.hpp -- the host threads of a job over several GPUs: statuses, the stage guard, the meetings --
+    driven by tests/host/slice_team_check.cpp with fake stages (no device, nothing loaded into this process): one slice;
+    four slices well over two meetings; a slice that fails before the first meeting (nobody goes on, nobody blocks, it is the
+    one reported with its text); a slice that throws in its second stage (LSQ_E_INTERNAL with what(), the others complete the
+    stage, the second meeting says no); two failing slices (the first in slice order speaks); two failures of one slice (the
+    first is kept).  Each case 300 times, under ThreadSanitizer and under AddressSanitizer + UBSan.  The sanitizers' runtimes
+    are linked statically and ThreadSanitizer's program runs without address-space randomisation where setarch offers that:
+    neither runtime then depends on what else a process loads or on where the kernel maps it."""
+    import platform, shutil, subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    fixed_layout = ["setarch", platform.machine(), "-R"] if shutil.which("setarch") else []
+    for sanitizers, runtimes in (("thread", ["-static-libtsan"]), ("address,undefined", ["-static-libasan", "-static-libubsan"])):
+        exe = str(tmp_path / ("slice_team_check_" + sanitizers.split(",")[0]))
+        subprocess.run(["g++", "-std=c++17", "-pthread", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=" + sanitizers, "-fno-sanitize-recover=all"] + runtimes + [
+                        "-I", os.path.join(root, "lesseq_amd", "csrc"), "-o", exe, os.path.join(root, "tests", "host", "slice_team_check.cpp")],
+                       check=True, capture_output=True, text=True, timeout=120)
+        p = subprocess.run((fixed_layout if sanitizers == "thread" else []) + [exe], capture_output=True, text=True, timeout=120)
+        assert p.returncode == 0 and p.stdout == "slice team ok\n" and p.stderr == "", (sanitizers, p.returncode, p.stdout, p.stderr[-2000:])
+
+
 def test_share_plan_of_a_count_launch():
     """run_count's share plan on made-up buckets (host only, lsq_debug_plan_shares): the bounds rise from 0 to the last slot,
     no share is longer than 2^21 slots, weighted shares are equal in cost where no cut snaps (a two-block record, a walk

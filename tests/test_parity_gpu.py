@@ -1288,6 +1288,7 @@ def test_executables_run_one_job_over_several_gpus_by_reads(name, env, tmp_path)
     {"LSQ_GPUS": "3", "LSQ_DEVICES": "0,0,0", "LSQ_GATHER": "host", "LSQ_FAIL_RANK": "2", "LSQ_SHARD": "reads"},      # ... of a read-sharded job
     {"LSQ_GPUS": "2", "LSQ_DEVICES": "0,99", "LSQ_GATHER": "host"},                               # a slice whose device does not exist
     {"LSQ_GPUS": "1", "LSQ_GATHER": "rccl", "LSQ_FAIL_RANK": "0"},                                # ... with the RCCL communicator made
+    {"LSQ_GPUS": "3", "LSQ_DEVICES": "0,0,99", "LSQ_GATHER": "host", "LSQ_SHARD": "reads"},       # ... of a read-sharded job
 ])
 def test_a_failing_slice_ends_the_job_with_its_message(env, tmp_path):
     """The slices' host threads agree before anyone enters the collective: one slice that failed on the way (no context,
