@@ -154,6 +154,21 @@ int lsq_sam_parse(const char *path, lsq_events *e, unsigned skip_flags, unsigned
  * and NUL-terminated (lsq_free); *mrf_len (may be null) its length.  Status as lsq_sam_parse.  The sam2mrf executable
  * wraps this call. */
 int lsq_sam_to_mrf(const void *sam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len);
+/* "BAM_SINGLE": the same alignments as aligners and `samtools sort` hand them over, taken wherever "SAM_SINGLE" is.  The
+ * format is DEFINED by its SAM equivalent (lesseq_amd/csrc/lsq_bam_record.hpp): the text `samtools view -h`
+ * prints -- the lines of the header text, then a line per record in file order, RNAME the name of refID ("*" for -1), POS
+ * pos + 1, CIGAR from the operations ("*" for none) -- under the rules and the two filters of SAM_SINGLE.  Record i (from 0) is
+ * the read "read-<h + i + 1>", h the lines of the header text.  The BGZF blocks are inflated by the library's own decoder (no
+ * zlib; the CRC32 is not verified).  LSQ_E_FORMAT, naming the block's file offset, for a file that is not BGZF or BAM (bad
+ * magic, no BC subfield, BSIZE past the end, an invalid deflate stream, other than ISIZE bytes); LSQ_E_PARSE with
+ * "#<k>:<BAM record at byte N of the inflated stream>" for the first malformed record (block_size < 32, l_read_name 0, name and
+ * CIGAR beyond block_size, refID outside -1 .. n_ref-1, an operation code above 8, a record past the end of the stream, POS or
+ * a reference end beyond 2^31-1).  A CIGAR kept in the CG tag (more than 65 535 operations) is read as stored and makes no
+ * read; CRAM and mate pairing are out of scope.  lsq_reads_parse("BAM_SINGLE") calls lsq_bam_parse with the SAM defaults. */
+int lsq_bam_parse(const char *path, lsq_events *e, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out);
+/* The MRF_SINGLE text of a BAM file's bytes, as lsq_sam_to_mrf gives it for the equivalent SAM text ("#" for every header line).
+ * The bam2mrf executable wraps this call. */
+int lsq_bam_to_mrf(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len);
 /* Wraps caller-made arrays as a read set without copying (the arrays must outlive it).
  * blk_off has n_reads+1 entries; blocks are 0-based half-open; chrom_id / strand_id index
  * lsq_events_chrom_id() / lsq_events_strand_id() dictionaries; line_no is the 1-based line
@@ -255,10 +270,18 @@ int lsq_last_ingest_stages(const lsq_ctx *c, float *ms, uint64_t *bytes, int cap
 /* The name of pass `stage` as the latest lsq_reads_upload* of the context ran it: lsq_ingest_stage_name's, except that the
  * routing pass over SAM_SINGLE text is "sam_route" (other kernels than "route": lsq_sam_device.hpp). */
 const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage);
+/* The passes of the latest lsq_reads_upload* of the context: lsq_ingest_stage_count(), except after a BAM_SINGLE file, whose
+ * chain begins with three passes of its own in place of the newline count and the route -- "bgzf_inflate", "bam_record_starts",
+ * "bam_route" (lsq_bam_device.hpp) -- and so has one more.  lsq_last_ingest_stages and lsq_last_ingest_stage_name index the
+ * passes of that ingest, in order. */
+int lsq_last_ingest_stage_count(const lsq_ctx *c);
 /* Which of the SAM parse's kernels the latest SAM_SINGLE text of the context went through: lines the tile kernel handed to
  * the fall-back kernel (a head longer than the tile kernel's window), and whether the whole file went through the
  * byte-walking form (the line list ran over, or LSQ_SAM_SLOW is set).  Either pointer may be null. */
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow);
+/* How the record starts of the latest BAM_SINGLE file of the context were found: its BGZF blocks, and how many of them the
+ * repair pass walked again because a record did not begin with the block (0 for a file as htslib writes it).  Either may be null. */
+int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_repaired);
 uint64_t lsq_reads_retained(const lsq_ctx *c, int method);      /* "loaded N reads" log line */
 uint64_t lsq_reads_retained_blocks(const lsq_ctx *c, int method);
 /* Of the retained reads, those kept in the pools: reads whose first base lies in the span of an event planned on this

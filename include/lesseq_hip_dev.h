@@ -58,6 +58,11 @@ int lsq_debug_throw(int kind);
  * list that ran over).  A file of reads: 0, 0, 0 -- a test holds that, so that a silent fall-back cannot pass as the fast path. */
 int lsq_debug_last_parse_paths(const lsq_ctx *c, unsigned *tiles_handed, unsigned *lines_listed, unsigned *all_slow);
 
+/* The staging and the inflate kernel of the BAM_SINGLE chain alone (lsq_bam_device.hpp): the bytes of a BGZF file to HBM, every
+ * block through the inflate kernel, the inflated stream back into out (cap bytes; *n = its length, also when cap is too small:
+ * LSQ_E_RANGE then).  Status as lsq_bam_parse for the block chain and the deflate streams. */
+int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *out, uint64_t cap, uint64_t *n);
+
 /* HIP_VERSION the library was compiled against and hipRuntimeGetVersion() of the runtime it found in the process (0
  * when that call fails, e.g. without a driver): a binding that loads another runtime first (PyTorch's) can compare. */
 int lsq_debug_hip_versions(int *compiled, int *runtime);

@@ -80,6 +80,8 @@ _sig("lsq_mrf_parse", C.c_int, cs, cs, vp, C.c_int, P(vp))
 _sig("lsq_reads_parse", C.c_int, cs, cs, vp, C.c_int, P(vp))
 _sig("lsq_sam_parse", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
 _sig("lsq_sam_to_mrf", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
+_sig("lsq_bam_parse", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
+_sig("lsq_bam_to_mrf", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
 _sig("lsq_reads_wrap", C.c_int, u64, P(u64), P(u32), P(i32), P(i32), P(u16), P(u8), P(vp))
 _sig("lsq_reads_free", None, vp)
 _sig("lsq_reads_count", u64, vp)
@@ -113,6 +115,9 @@ _sig("lsq_ingest_stage_name", cs, C.c_int)
 _sig("lsq_last_ingest_stages", C.c_int, vp, P(C.c_float), P(u64), C.c_int)
 _sig("lsq_last_ingest_stage_name", cs, vp, C.c_int)
 _sig("lsq_last_sam_paths", C.c_int, vp, P(u32), P(u32))
+_sig("lsq_last_ingest_stage_count", C.c_int, vp)
+_sig("lsq_last_bam_paths", C.c_int, vp, P(u64), P(u64))
+_sig("lsq_debug_bgzf_inflate", C.c_int, vp, cs, u64, vp, u64, P(u64))
 _sig("lsq_reads_retained", u64, vp, C.c_int)
 _sig("lsq_reads_retained_blocks", u64, vp, C.c_int)
 _sig("lsq_reads_pooled", u64, vp, C.c_int)

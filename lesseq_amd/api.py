@@ -179,6 +179,17 @@ def sam_to_mrf(sam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0):
         lib.lsq_free(out)
 
 
+def bam_to_mrf(bam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0):
+    """the MRF_SINGLE text (bytes) that defines what a BAM_SINGLE file means (lsq_bam_to_mrf): that of its SAM equivalent"""
+    data = bytes(bam_bytes)
+    out, n = vp(), u64()
+    check(lib.lsq_bam_to_mrf(data, len(data), skip_flags, min_mapq, C.byref(out), C.byref(n)))
+    try:
+        return C.string_at(out.value, n.value)
+    finally:
+        lib.lsq_free(out)
+
+
 class Reads:
     """A parsed read set in file order: from an MRF file, caller arrays, or the synthetic generator"""
 
@@ -197,6 +208,13 @@ class Reads:
         """a SAM_SINGLE file through the host parser (lsq_sam_parse): the arrays from_mrf gives for its MRF equivalent"""
         h = vp()
         check(lib.lsq_sam_parse(_b(path), events.h, skip_flags, min_mapq, n_threads, C.byref(h)))
+        return cls(h)
+
+    @classmethod
+    def from_bam(cls, path, events, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0, n_threads=0):
+        """a BAM_SINGLE file through the host parser (lsq_bam_parse): the arrays from_sam gives for its SAM equivalent"""
+        h = vp()
+        check(lib.lsq_bam_parse(_b(path), events.h, skip_flags, min_mapq, n_threads, C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -298,6 +316,35 @@ class Context:
         check(lib.lsq_last_sam_paths(self.h, C.byref(a), C.byref(b)))
         return {"lines_to_fall_back_kernel": a.value, "whole_file_byte_walking": bool(b.value)}
 
+    def upload_reads_bam(self, method, path):
+        """BAM file -> HBM -> inflated, parsed and ingested on the device (lsq_reads_upload_mrf with "BAM_SINGLE"; the filters are
+        SAM's options sam_skip_flags / sam_min_mapq)"""
+        check(lib.lsq_reads_upload_mrf(self.h, method, b"BAM_SINGLE", _b(path)))
+
+    def parse_bam_device(self, path):
+        """the device BAM chain's blocks, copied back as a Reads (tests, tools)"""
+        return self.parse_mrf_device(path, read_format="BAM_SINGLE")
+
+    def bam_paths(self):
+        """(BGZF blocks, blocks the repair pass walked again) of the latest BAM file: 0 repaired for a file as htslib writes it"""
+        a, b = u64(), u64()
+        check(lib.lsq_last_bam_paths(self.h, C.byref(a), C.byref(b)))
+        return {"blocks": a.value, "blocks_repaired": b.value}
+
+    def bgzf_inflate(self, data):
+        """the inflated stream of a BGZF file's bytes through the staging and the inflate kernel alone (lsq_debug_bgzf_inflate)"""
+        data = bytes(data)
+        n = u64()
+        cap = 1 << 16
+        while True:
+            out = C.create_string_buffer(cap)
+            st = lib.lsq_debug_bgzf_inflate(self.h, data, len(data), out, cap, C.byref(n))
+            if st == -5 and n.value > cap:
+                cap = n.value
+                continue
+            check(st)
+            return out.raw[:n.value]
+
     def mrf_timing(self):
         a, b = C.c_float(), C.c_float()
         check(lib.lsq_last_mrf_timing(self.h, C.byref(a), C.byref(b)))
@@ -314,7 +361,7 @@ class Context:
 
     def ingest_stages(self):
         """device milliseconds and minimum bytes of every pass of the latest ingest (lsq_last_ingest_stages), in order"""
-        n = lib.lsq_ingest_stage_count()
+        n = lib.lsq_last_ingest_stage_count(self.h)
         ms, by = (C.c_float * n)(), (C.c_uint64 * n)()
         check(lib.lsq_last_ingest_stages(self.h, ms, by, n))
         return [{"stage": lib.lsq_last_ingest_stage_name(self.h, i).decode(), "ms": float(ms[i]), "bytes": int(by[i])} for i in range(n)]

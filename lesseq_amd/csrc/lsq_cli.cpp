@@ -112,8 +112,8 @@ bool named_read_format(const char *fmt) {       // the read formats only `solve`
 	return strcmp(fmt, "UCSC_GFF") == 0 || strcmp(fmt, "UCSC_BED") == 0 || strcmp(fmt, "WORMBASE_GFF3") == 0;
 }
 
-// the read formats of one read per line that the device parses from the text itself (lsq_reads_upload_text)
-bool line_text_format(const char *fmt) { return strcmp(fmt, "MRF_SINGLE") == 0 || strcmp(fmt, "SAM_SINGLE") == 0; }
+// the read formats that the device parses from the file's own bytes (lsq_reads_upload_text): a read per line, or per BAM record
+bool line_text_format(const char *fmt) { return strcmp(fmt, "MRF_SINGLE") == 0 || strcmp(fmt, "SAM_SINGLE") == 0 || strcmp(fmt, "BAM_SINGLE") == 0; }
 
 int precheck_reads_file(const char *fmt, const char *path, bool solve) {
 	FILE *f = fopen(path, "rb");
@@ -827,7 +827,8 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "events") == 0) rc = run_events(argc, argv, out);
 	else if (tool && strcmp(tool, "parseGencode") == 0) rc = run_parse_gencode(argc, argv, out);
 	else if (tool && strcmp(tool, "gencodeIsoformMap") == 0) rc = run_isoform_map(argc, argv, out);
-	else if (tool && strcmp(tool, "sam2mrf") == 0) rc = run_sam2mrf(argc, argv, out);
+	else if (tool && strcmp(tool, "sam2mrf") == 0) rc = run_sam2mrf(false, argc, argv, out);
+	else if (tool && strcmp(tool, "bam2mrf") == 0) rc = run_sam2mrf(true, argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -36,6 +36,7 @@ using namespace lsq;
 constexpr unsigned P2_GROUP_PAD = LSQ_P2_PAD;      // ... and a junction group of the two-block pool (eight, with eight two-block reads per look, measured 2 % slower on C3: more padding, longer steps)
 constexpr unsigned P1_GROUP_PAD = LSQ_P1_PAD;      // records a cell's group of the one-block pool is padded to: what a lane of the count kernel takes per look
 constexpr int LSQ_INGEST_STAGES = 7;     // newline count, route, partition count, partition scatter, group classify, group offsets, group place
+constexpr int LSQ_INGEST_SLOTS = LSQ_INGEST_STAGES + 2;      // ... and the two passes ahead of a BAM file's route: inflate, record starts (lsq_bam_device.hpp)
 constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
 
 namespace lsq {
@@ -287,14 +288,15 @@ struct lsq_ctx {
 	unsigned opt_sam_skip_flags = 0x904u, opt_sam_min_mapq = 0u;
 	int ing_format = -1;                    // the read format of the latest ingest (lsq_ingest.hip: READ_FORMATS), -1: parsed blocks from the host
 	unsigned sam_lines_listed = 0, sam_all_slow = 0;
+	unsigned long long bam_blocks = 0, bam_blocks_repaired = 0;      // the latest BAM_SINGLE file (lsq_last_bam_paths)
 	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_text.hip: pinned_pipeline)
 	unsigned char *pin_buf[2] = {nullptr, nullptr};
 	hipEvent_t pin_ev[2] = {nullptr, nullptr};
 	// device time and bytes of the stages of the latest ingest (lsq_ingest.hip: lsq_last_ingest_stages)
-	hipEvent_t ing_ev[2 * LSQ_INGEST_STAGES] = {};
-	float ing_ms[LSQ_INGEST_STAGES] = {};
-	unsigned long long ing_bytes[LSQ_INGEST_STAGES] = {};
-	bool ing_seen[LSQ_INGEST_STAGES] = {};
+	hipEvent_t ing_ev[2 * LSQ_INGEST_SLOTS] = {};
+	float ing_ms[LSQ_INGEST_SLOTS] = {};
+	unsigned long long ing_bytes[LSQ_INGEST_SLOTS] = {};
+	bool ing_seen[LSQ_INGEST_SLOTS] = {};
 };
 
 // The text of one file in HBM (lsq_text_stage).  Staging needs no event tables: the executables start it

@@ -20,11 +20,14 @@
 // 10 ms + 6 ms of one-workgroup scans per C3 file, >= 56 GB of HBM traffic for 3.7 GB of text.
 // This replaces the reference's load-time filter and its read index (count/count.cpp:348-364).
 #include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
 #include <unistd.h>
 
 #include "lsq_text.hpp"
 #include "lsq_mrf_line.hpp"
 #include "lsq_sam_line.hpp"
+#include "lsq_bam.hpp"
 
 namespace {
 
@@ -269,10 +272,10 @@ struct ReadAcc {
 
 // ---- device time of the chain's stages (lsq_last_ingest_stages; StageClock, lsq_text.hpp, records them)
 static void stages_reset(lsq_ctx *c, bool keep_text_stage) {
-	for (int s = keep_text_stage ? 1 : 0; s < LSQ_INGEST_STAGES; ++s) { c->ing_seen[s] = false; c->ing_ms[s] = 0; c->ing_bytes[s] = 0; }
+	for (int s = keep_text_stage ? 1 : 0; s < LSQ_INGEST_SLOTS; ++s) { c->ing_seen[s] = false; c->ing_ms[s] = 0; c->ing_bytes[s] = 0; }
 }
 static void stages_collect(lsq_ctx *c) {          // (the stream has been waited for)
-	for (int s = 0; s < LSQ_INGEST_STAGES; ++s) {
+	for (int s = 0; s < LSQ_INGEST_SLOTS; ++s) {
 		if (!c->ing_seen[s] || !c->ing_ev[2 * s] || !c->ing_ev[2 * s + 1]) continue;
 		float ms = 0;
 		if (hipEventElapsedTime(&ms, c->ing_ev[2 * s], c->ing_ev[2 * s + 1]) == hipSuccess) c->ing_ms[s] = ms;
@@ -328,11 +331,21 @@ struct MrfOut {
 	unsigned char *blk_strand;
 };
 
+// what the record kernels of a BAM file see (lsq_bam_device.hpp): the inflated stream, the records' offsets, the reference table
+struct BamView {
+	const unsigned char *s;
+	unsigned long long len;
+	const unsigned long long *rec_off;
+	const unsigned *ref_cid;                 // per refID: chromosome id, MRF_NOCHROM, or "its records make no read"
+	long long n_ref;
+};
+
 // What ingest_text hands a read format's front end, and parse_staged_text the format's count / write launches: the
 // text, the dictionaries and the error words, the hand-off lists.
 struct TextJob {
 	lsq_ctx *c;
-	MrfText X;
+	MrfText X;                              // (a BAM file: no text; n_lines records, first_line the number of record 0)
+	BamView R;
 	MrfDict D;
 	unsigned long long *err;
 	MrfHandOff H;
@@ -1108,13 +1121,15 @@ struct MrfDictDev {
 		return LSQ_OK;
 	}
 	// after the parse kernels have run and the stream has been waited for: the first failing line, strand strings out of range, new strands
-	int settle(lsq_ctx *c, const lsq_text &T, unsigned has_header, unsigned long long first_line, hipStream_t st) {
+	// (bad_record: a format of binary records names its failing record itself)
+	int settle(lsq_ctx *c, const lsq_text &T, unsigned has_header, unsigned long long first_line, hipStream_t st, const std::function<int(unsigned long long)> &bad_record = nullptr) {
 		lsq_events &E = *c->E;
 		unsigned long long err[4];
 		std::vector<unsigned long long> h_strand(256);
 		HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(h_strand.data(), d_strand.p, 256 * 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipStreamSynchronize(st));
+		if (err[0] != MRF_NO_ERR && bad_record) return bad_record(err[0]);
 		if (err[0] != MRF_NO_ERR) {
 			// the text of the failing line, from the file: between the newline that ends the line before it and its own
 			const unsigned long long want = err[0] - first_line + has_header;      // ordinal of the newline that ends the failing line
@@ -1164,6 +1179,8 @@ struct DevParsed {
 	DevBuf<unsigned char> bst;
 };
 
+#include "lsq_bam_device.hpp"
+
 // ---- the read formats: the one place that names them.  Per format: whether a whole file's first line is a header (MRF; every
 // line of a SAM file counts: "read-<k>", k from 1), the switch that shortens its line list (tests: the run-over path on a small
 // file), the routing stage's name, its front end for the chain (prepare once; launch the routing kernels, once more with
@@ -1172,21 +1189,27 @@ struct ReadFormat {
 	const char *name;
 	unsigned has_header;
 	const char *line_list_env, *stage;
-	int (*prepare)(TextJob &);
+	int (*open)(lsq_ctx *, lsq_text &, BamRecords &);       // a file of binary records: inflates the staged bytes and finds the records (null: text, its newlines counted)
+	int (*prepare)(TextJob &);                               // (prepare and record may be null)
 	void (*launch)(const TextJob &, const RouteTables &, const RouteOut &, hipStream_t);
 	void (*record)(const TextJob &);
 	void (*count)(const TextJob &, hipStream_t, unsigned *);
 	void (*write)(const TextJob &, hipStream_t, const unsigned *, const unsigned long long *, const unsigned long long *, const MrfOut &);
 };
 static const ReadFormat READ_FORMATS[] = {
-	{"MRF_SINGLE", 1u, "LSQ_MRF_LINE_LIST", "route", mrf_prepare, mrf_launch, mrf_record,
+	{"MRF_SINGLE", 1u, "LSQ_MRF_LINE_LIST", "route", nullptr, mrf_prepare, mrf_launch, mrf_record,
 	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, J.err); },
 	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
 		 hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, rd, bk, J.D, O, J.err); }},
-	{"SAM_SINGLE", 0u, "LSQ_SAM_LINE_LIST", "sam_route", sam_prepare, sam_launch, sam_record,
+	{"SAM_SINGLE", 0u, "LSQ_SAM_LINE_LIST", "sam_route", nullptr, sam_prepare, sam_launch, sam_record,
 	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, J.err); },
 	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
 		 hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
+	{"BAM_SINGLE", 0u, nullptr, "bam_route", bam_open_staged, nullptr, bam_launch, nullptr,
+	 [](const TextJob &J, hipStream_t st, unsigned *nb) {
+		 hipLaunchKernelGGL(lsq_bam_count_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, J.err); },
+	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
+		 hipLaunchKernelGGL(lsq_bam_write_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
 };
 // the format a caller names (looked up once its file has been opened: the order in which the reference meets a bad file or literal)
 static int read_format_named(const char *name, const ReadFormat *&fmt) {
@@ -1198,6 +1221,7 @@ static int read_format_named(const char *name, const ReadFormat *&fmt) {
 // Parses staged text on the device into the arrays of lsq_mrf_parse (file order): lsq_mrf_parse_device.
 static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, unsigned long long first_line, DevParsed &out, float *h2d_ms, float *parse_ms) {
 	const unsigned has_header = fmt->has_header;
+	BamRecords BR;                                         // (a file of records: what takes the place of the text's newline tiles)
 	hipStream_t st = c->stream;
 	int rc;
 	if ((rc = ensure_lanes(c))) return rc;                 // (c->ev1 / c->ev2 are the lanes thread's)
@@ -1212,12 +1236,14 @@ static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, uns
 	};
 	if (h2d_ms) *h2d_ms = T.h2d_ms;
 	if (parse_ms) *parse_ms = 0;
-	if (T.len == 0) return empty_result();
+	if (T.len == 0 && !fmt->open) return empty_result();
 	HIP_TRY(hipEventRecord(c->ev1, st));
-	if ((rc = scan_newlines(c, T))) return rc;
-	const unsigned long long n_nl = T.n_nl;
+	if (fmt->open) { if ((rc = fmt->open(c, T, BR))) return rc; first_line = BR.H.h_lines + 1; }
+	else if ((rc = scan_newlines(c, T))) return rc;
+	const unsigned long long n_nl = fmt->open ? BR.n_rec : T.n_nl;
 	if (n_nl < 1 + has_header) return empty_result();   // header only (or no terminated line at all)
 	const unsigned long long n_lines = n_nl - has_header;
+	const std::function<int(unsigned long long)> bad_record = fmt->open ? std::function<int(unsigned long long)>([&](unsigned long long k) { return BR.fail_record(k, st); }) : nullptr;
 	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
 	DevBuf<unsigned> d_line_nb;
 	DevBuf<unsigned long long> d_rd_idx, d_bk_off;
@@ -1226,6 +1252,7 @@ static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, uns
 	if ((rc = d_line_nb.alloc(n_lines)) || (rc = d_rd_idx.alloc(n_lines + 1)) || (rc = d_bk_off.alloc(n_lines + 1)) || (rc = SS.reserve(n_lines)) || (rc = DD.build(c, st))) return rc;
 	TextJob J{};
 	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
+	J.R = BR.view();
 	J.n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
 	fmt->count(J, st, d_line_nb.p);
 	HIP_TRY(hipGetLastError());
@@ -1233,14 +1260,14 @@ static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, uns
 	unsigned long long n_reads = 0, n_blocks = 0;
 	HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + n_lines, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + n_lines, 8, hipMemcpyDeviceToHost, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;          // (waits for the stream) the first failing line ends the run here
+	if ((rc = DD.settle(c, T, has_header, first_line, st, bad_record))) return rc;          // (waits for the stream) the first failing line ends the run here
 	if ((rc = out.blk_off.alloc(n_reads + 1)) || (rc = out.line_no.alloc(n_reads)) || (rc = out.bs.alloc(n_blocks)) || (rc = out.be.alloc(n_blocks)) ||
 	    (rc = out.bc.alloc(n_blocks)) || (rc = out.bst.alloc(n_blocks))) return rc;
 	const MrfOut O{out.blk_off.p, out.line_no.p, out.bs.p, out.be.p, out.bc.p, out.bst.p};
 	fmt->write(J, st, d_line_nb.p, d_rd_idx.p, d_bk_off.p, O);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipEventRecord(c->ev2, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st))) return rc;
+	if ((rc = DD.settle(c, T, has_header, first_line, st, bad_record))) return rc;
 	if (parse_ms) (void)hipEventElapsedTime(parse_ms, c->ev1, c->ev2);
 	out.n_reads = n_reads; out.n_blocks = n_blocks;
 	return LSQ_OK;
@@ -1253,21 +1280,27 @@ static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &
 	if ((rc = ensure_lanes(c))) return rc;
 	c->ing_format = (int)(fmt - READ_FORMATS);
 	c->mrf_h2d_ms = T.h2d_ms; c->mrf_parse_ms = 0;
-	stages_reset(c, T.scanned);
-	if (T.len && (rc = scan_newlines(c, T))) return rc;
-	const unsigned long long n_nl = T.len ? T.n_nl : 0;
+	stages_reset(c, T.scanned && !fmt->open);
+	BamRecords BR;                                         // (a file of records: what takes the place of the text's newline tiles)
+	if (fmt->open) {
+		if (has_header || first_line != 1ull) return fail(LSQ_E_ARG, "a %s file is taken whole, not in byte ranges", fmt->name);
+		if ((rc = fmt->open(c, T, BR))) return rc;
+		first_line = BR.H.h_lines + 1;
+	} else if (T.len && (rc = scan_newlines(c, T))) return rc;
+	const unsigned long long n_nl = fmt->open ? BR.n_rec : T.len ? T.n_nl : 0;
 	const unsigned long long n_lines = n_nl >= 1 + has_header ? n_nl - has_header : 0;       // (header only, or no terminated line at all: no reads)
 	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
 	MrfDictDev DD;
 	if ((rc = DD.build(c, st))) return rc;
 	Front F;
-	F.n = n_lines; F.line_no = nullptr; F.first_line = first_line; F.in_bytes = T.len;
+	F.n = n_lines; F.line_no = nullptr; F.first_line = first_line; F.in_bytes = fmt->open ? BR.total : T.len;
 	const unsigned n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
 	// what a format's tile kernel hands on: tiles it does not take (MRF: more delimiters than the fast kernel's tables hold), lines
 	// it does not settle (another shape than a read's; at most one a tile begins ahead of its window; the rest is whatever the
 	// file holds -- when the list runs over, the whole file goes through the format's byte-walking kernel)
 	unsigned long long list_cap = 1ull << 22;
-	if (const char *e = getenv(fmt->line_list_env)) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }
+	if (!fmt->line_list_env) list_cap = 0;                // (records, not lines: nothing is handed on)
+	else if (const char *e = getenv(fmt->line_list_env)) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }
 	const unsigned line_cap = (unsigned)std::min<unsigned long long>(n_lines, list_cap) + n_tiles + 1u;
 	DevBuf<MrfLongLine> d_lines;
 	DevBuf<unsigned> d_tiles, d_counts;
@@ -1276,7 +1309,8 @@ static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &
 	TextJob J{};
 	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
 	J.H = MrfHandOff{d_counts.p, d_tiles.p, n_tiles, d_lines.p, line_cap}; J.n_tiles = n_tiles;
-	if ((rc = fmt->prepare(J))) return rc;
+	J.R = BR.view();
+	if (fmt->prepare && (rc = fmt->prepare(J))) return rc;
 	F.launch = [&](const RouteTables &RT, const RouteOut &O, hipStream_t s) -> int {
 		const int r2 = DD.reset_errors(s);
 		if (r2) return r2;
@@ -1290,13 +1324,13 @@ static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &
 		HIP_TRY(hipMemcpy(J.counts, d_counts.p, 16, hipMemcpyDeviceToHost));
 		if (J.counts[2] && !J.all_slow) { J.all_slow = true; return LSQ_RETRY; }
 		if (J.counts[2]) return fail(LSQ_E_INTERNAL, "the device parser's line list ran over");
-		fmt->record(J);
-		return DD.settle(c, T, has_header, first_line, s);
+		if (fmt->record) fmt->record(J);
+		return DD.settle(c, T, has_header, first_line, s, fmt->open ? std::function<int(unsigned long long)>([&](unsigned long long k) { return BR.fail_record(k, s); }) : nullptr);
 	};
 	c->reads[method].named = false;
 	if ((rc = ingest_device(c, method, F))) return rc;
 	// (device time of the parse = the newline count and the routing pass; the rest of the chain is the ingest)
-	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1];
+	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1] + c->ing_ms[LSQ_INGEST_STAGES] + c->ing_ms[LSQ_INGEST_STAGES + 1];
 	return LSQ_OK;
 }
 
@@ -1436,7 +1470,37 @@ static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
 	"newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"};
 int lsq_ingest_stage_count(void) { return LSQ_INGEST_STAGES; }
 const char *lsq_ingest_stage_name(int stage) { return stage >= 0 && stage < LSQ_INGEST_STAGES ? INGEST_STAGE_NAMES[stage] : nullptr; }
-const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) { return c && c->ing_format >= 0 && stage == 1 ? READ_FORMATS[c->ing_format].stage : lsq_ingest_stage_name(stage); }
+// Pass k of the latest ingest -> its slot of the context's clocks.  A file of records (BAM) runs two passes of its own, kept in the
+// two slots behind the chain's seven, where a text runs the newline count.
+static bool last_ingest_of_records(const lsq_ctx *c) { return c && c->ing_format >= 0 && READ_FORMATS[c->ing_format].open != nullptr; }
+static int last_stage_slot(const lsq_ctx *c, int k) { return !last_ingest_of_records(c) ? k : k < 2 ? LSQ_INGEST_STAGES + k : k - 1; }
+int lsq_last_ingest_stage_count(const lsq_ctx *c) { return last_ingest_of_records(c) ? LSQ_INGEST_STAGES + 1 : LSQ_INGEST_STAGES; }
+const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) {
+	if (stage < 0 || stage >= lsq_last_ingest_stage_count(c)) return nullptr;
+	const int slot = last_stage_slot(c, stage);
+	if (slot >= LSQ_INGEST_STAGES) return slot == LSQ_INGEST_STAGES ? "bgzf_inflate" : "bam_record_starts";
+	return c && c->ing_format >= 0 && slot == 1 ? READ_FORMATS[c->ing_format].stage : lsq_ingest_stage_name(slot);
+}
+int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_repaired) {
+	if (!c) return LSQ_E_ARG;
+	if (n_blocks) *n_blocks = c->bam_blocks;
+	if (blocks_repaired) *blocks_repaired = c->bam_blocks_repaired;
+	return LSQ_OK;
+}
+// developer entry (include/lesseq_hip_dev.h): the staging and the inflate kernel of the BAM chain alone
+int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *out, uint64_t cap, uint64_t *n) LSQ_API_TRY {
+	if (!c || (!bytes && len) || (!out && cap) || !n) return fail(LSQ_E_ARG, "null argument");
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure_lanes(c))) return rc;
+	lsq_text T;
+	BamRecords B;
+	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B))) return rc;
+	*n = B.total;
+	if (B.total > cap) return fail(LSQ_E_RANGE, "the inflated stream holds %llu bytes, the buffer %llu", B.total, (unsigned long long)cap);
+	if (B.total) HIP_TRY(hipMemcpy(out, B.d_stream.p, (size_t)B.total, hipMemcpyDeviceToHost));
+	return LSQ_OK;
+} LSQ_API_CATCH
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {
 	if (!c) return LSQ_E_ARG;
 	if (lines_listed) *lines_listed = c->sam_lines_listed;
@@ -1445,9 +1509,10 @@ int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_s
 }
 int lsq_last_ingest_stages(const lsq_ctx *c, float *ms, uint64_t *bytes, int capacity) LSQ_API_TRY {
 	if (!c) return fail(LSQ_E_ARG, "null context");
-	for (int s = 0; s < LSQ_INGEST_STAGES && s < capacity; ++s) {
-		if (ms) ms[s] = c->ing_seen[s] ? c->ing_ms[s] : 0.0f;
-		if (bytes) bytes[s] = c->ing_seen[s] ? c->ing_bytes[s] : 0;
+	for (int k = 0; k < lsq_last_ingest_stage_count(c) && k < capacity; ++k) {
+		const int s = last_stage_slot(c, k);
+		if (ms) ms[k] = c->ing_seen[s] ? c->ing_ms[s] : 0.0f;
+		if (bytes) bytes[k] = c->ing_seen[s] ? c->ing_bytes[s] : 0;
 	}
 	return LSQ_OK;
 } LSQ_API_CATCH

@@ -297,6 +297,9 @@ int host_threads(int requested);
 void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
 int cli_device();                                                            // lsq_cli.cpp: the GPU the environment picks for an executable (default 0)
 int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
-int run_sam2mrf(int argc, const char *const *argv, std::string &out);        // lsq_sam.cpp: the sam2mrf executable
+int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out);      // lsq_sam.cpp: the sam2mrf and bam2mrf executables
+struct BamError;
+int bam_fail(const BamError &e);                                             // lsq_bam.cpp: a BAM error (lsq_bam.hpp) as the calling thread's status and text
+int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o);      // lsq_bam.cpp
 
 } // namespace lsq

@@ -234,6 +234,7 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 	const std::string fmt = read_format;
 	if (fmt == "MRF_SINGLE") return lsq_mrf_parse(read_format, path, E, n_threads, out);
 	if (fmt == "SAM_SINGLE") return lsq_sam_parse(path, E, SAM_DEFAULT_SKIP_FLAGS, SAM_DEFAULT_MIN_MAPQ, n_threads, out);
+	if (fmt == "BAM_SINGLE") return lsq_bam_parse(path, E, SAM_DEFAULT_SKIP_FLAGS, SAM_DEFAULT_MIN_MAPQ, n_threads, out);
 	FILE *fp = fopen(path, "rb");
 	if (!fp) return fail(LSQ_E_IO, "cannot open reads file %s", path);
 	if (fmt != "UCSC_GFF" && fmt != "UCSC_BED" && fmt != "WORMBASE_GFF3") { fclose(fp); return fail(LSQ_E_FORMAT, "Unknown file format error: %s", read_format); }

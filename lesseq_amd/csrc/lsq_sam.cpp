@@ -57,8 +57,9 @@ namespace lsq {
 
 // sam2mrf [--skip-flags N] [--min-mapq N] [file]: SAM from standard input (or the file) to the equivalent MRF on standard
 // output.  Exit status 0; 1 for a malformed line ("#<k>:<line>" and the lexical-cast line on standard error) or a file
-// that does not open; nothing on standard output then.
-int run_sam2mrf(int argc, const char *const *argv, std::string &out) {
+// that does not open; nothing on standard output then.  bam2mrf: the same for a BAM file (lsq_bam.cpp); a file that is no
+// BAM file is exit status 1 with its message alone.
+int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out) {
 	unsigned skip_flags = SAM_DEFAULT_SKIP_FLAGS, min_mapq = SAM_DEFAULT_MIN_MAPQ;
 	const char *path = nullptr;
 	bool bad = false;
@@ -69,11 +70,11 @@ int run_sam2mrf(int argc, const char *const *argv, std::string &out) {
 		else if (!path) path = argv[i];
 		else bad = true;
 	}
-	if (bad) { cli_log(0, "Usage:\nsam2mrf [--skip-flags N] [--min-mapq N] [sam_path]      (standard input without a path)"); return 1; }
+	if (bad) { cli_log(0, bam ? "Usage:\nbam2mrf [--skip-flags N] [--min-mapq N] [bam_path]      (standard input without a path)" : "Usage:\nsam2mrf [--skip-flags N] [--min-mapq N] [sam_path]      (standard input without a path)"); return 1; }
 	std::string bytes;
 	if (read_all(path, bytes)) { cli_log(0, lsq_last_error()); return 1; }
-	const int st = sam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out);
-	if (st) { out.clear(); cli_log(0, lsq_last_error()); cli_log(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
+	const int st = bam ? bam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out) : sam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out);
+	if (st) { out.clear(); cli_log(0, lsq_last_error()); if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
 	return 0;
 }
 

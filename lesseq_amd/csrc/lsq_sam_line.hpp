@@ -77,6 +77,32 @@ LSQ_HD inline int sam_field_bounds(V l, bool whole, typename V::index_type *b) {
 	return SAM_BOUNDS_OK;
 }
 
+// The walk's block-emitting half, one CIGAR operation at a time: the text splitter below and the binary-record walk
+// (lsq_bam_record.hpp) both feed it, so the rules above are written once.  emit(start, end, qstart, qend), 1-based inclusive.
+struct SamBlockWalk {
+	int64_t ref, bs, q, qs, qe;
+	unsigned n_blocks;
+	LSQ_HD inline void begin(int64_t pos) { ref = pos; bs = pos; q = 1; qs = 1; qe = 0; n_blocks = 0; }
+	// op: one of MIDNSHP=X, len <= 2^31-1.  false: the reference end lies beyond 2^31-1
+	template <class Emit>
+	LSQ_HD inline bool step(const char op, const int64_t len, Emit &&emit) {
+		if (op == 'M' || op == '=' || op == 'X' || op == 'D') {
+			if (len > 0) {
+				if (ref == bs) { qs = q; qe = q - 1; }
+				ref += len;
+				if (op != 'D') { q += len; qe = q - 1; }
+			}
+		} else if (op == 'N') {
+			if (ref > bs) { emit(bs, ref - 1, qs, qe); ++n_blocks; }
+			ref += len;
+			bs = ref;
+		} else if (op == 'I' || op == 'S') q += len;
+		return ref - 1 <= SAM_POS_MAX;
+	}
+	template <class Emit>
+	LSQ_HD inline void end(Emit &&emit) { if (ref > bs) { emit(bs, ref - 1, qs, qe); ++n_blocks; } }
+};
+
 // Calls on_block(rname, minus, start, end, qstart, qend) for every block of the record, in order (1-based inclusive).
 // SAM_MALFORMED may come after blocks have been delivered; SAM_READ only when at least one was.  `b`: sam_field_bounds
 // of a line that does not begin with '@'.
@@ -98,8 +124,9 @@ LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsi
 	if (no_cigar) return SAM_NO_READ;
 	if (cigar.n == 0) return SAM_MALFORMED;
 	const bool minus = ((unsigned)flag & 0x10u) != 0u;
-	int64_t ref = pos, bs = pos, q = 1, qs = 1, qe = 0;
-	unsigned n_blocks = 0;
+	auto emit = [&](int64_t s, int64_t e, int64_t qs, int64_t qe) { on_block(rname, minus, s, e, qs, qe); };
+	SamBlockWalk W;
+	W.begin(pos);
 	Idx j = 0;
 	while (j < cigar.n) {
 		Idx k = j;
@@ -111,21 +138,10 @@ LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsi
 		const bool on_ref = op == 'M' || op == '=' || op == 'X' || op == 'D';
 		if (!on_ref && op != 'N' && op != 'I' && op != 'S' && op != 'H' && op != 'P') return SAM_MALFORMED;
 		if (!walk) continue;
-		if (on_ref) {
-			if (len > 0) {
-				if (ref == bs) { qs = q; qe = q - 1; }
-				ref += len;
-				if (op != 'D') { q += len; qe = q - 1; }
-			}
-		} else if (op == 'N') {
-			if (ref > bs) { on_block(rname, minus, bs, ref - 1, qs, qe); ++n_blocks; }
-			ref += len;
-			bs = ref;
-		} else if (op == 'I' || op == 'S') q += len;
-		if (ref - 1 > SAM_POS_MAX) return SAM_MALFORMED;
+		if (!W.step(op, len, emit)) return SAM_MALFORMED;
 	}
-	if (walk && ref > bs) { on_block(rname, minus, bs, ref - 1, qs, qe); ++n_blocks; }
-	return n_blocks ? SAM_READ : SAM_NO_READ;
+	if (walk) W.end(emit);
+	return W.n_blocks ? SAM_READ : SAM_NO_READ;
 }
 
 // a whole line
