@@ -159,7 +159,8 @@ int lsq_sam_to_mrf(const void *sam_bytes, uint64_t len, unsigned skip_flags, uns
  * prints -- the lines of the header text, then a line per record in file order, RNAME the name of refID ("*" for -1), POS
  * pos + 1, CIGAR from the operations ("*" for none) -- under the rules and the two filters of SAM_SINGLE.  Record i (from 0) is
  * the read "read-<h + i + 1>", h the lines of the header text.  The BGZF blocks are inflated by the library's own decoder (no
- * zlib; the CRC32 is not verified).  LSQ_E_FORMAT, naming the block's file offset, for a file that is not BGZF or BAM (bad
+ * zlib).  The CRC32 of a block and the end-of-file marker are checked where a caller asks for it -- the _checked entries below,
+ * the context option "bam_verify", lsq_bam_check -- and nowhere else.  LSQ_E_FORMAT, naming the block's file offset, for a file that is not BGZF or BAM (bad
  * magic, no BC subfield, BSIZE past the end, an invalid deflate stream, other than ISIZE bytes); LSQ_E_PARSE with
  * "#<k>:<BAM record at byte N of the inflated stream>" for the first malformed record (block_size < 32, l_read_name 0, name and
  * CIGAR beyond block_size, refID outside -1 .. n_ref-1, an operation code above 8, a record past the end of the stream, POS or
@@ -169,6 +170,23 @@ int lsq_bam_parse(const char *path, lsq_events *e, unsigned skip_flags, unsigned
 /* The MRF_SINGLE text of a BAM file's bytes, as lsq_sam_to_mrf gives it for the equivalent SAM text ("#" for every header line).
  * The bam2mrf executable wraps this call. */
 int lsq_bam_to_mrf(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len);
+/* The same two calls with the file verified on the way, as samtools and htslib do: behind the block chain and the deflate
+ * streams, and ahead of the header and the records, LSQ_E_FORMAT with "CRC32 mismatch (stored 0x%08x, computed 0x%08x) in the
+ * BGZF block at file offset N: ..." for the first block in file order whose bytes do not give the CRC-32 it stores, then with
+ * "no end-of-file marker in the BGZF block at file offset <file length>: ..." for a file whose last 28 bytes are not the empty
+ * BGZF block (a file cut at a block boundary).  On the device chain (lsq_reads_upload_mrf, lsq_reads_upload_text,
+ * lsq_mrf_parse_device with "BAM_SINGLE") lsq_ctx_set_option("bam_verify", 1) asks for the same checks, same order, same
+ * messages: a pass of its own behind the inflate ("bgzf_crc32" in lsq_last_ingest_stages), a wave a BGZF block.  Default 0:
+ * nothing is checked and the stage list is the unverified one. */
+int lsq_bam_parse_checked(const char *path, lsq_events *e, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out);
+int lsq_bam_to_mrf_checked(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len);
+/* A whole BAM file checked without an annotation (the bamcheck executable): block chain, deflate streams, CRC32s, end-of-file
+ * marker, header, every record -- the statuses and messages above, always verifying.  records / reads / read_blocks: the lines
+ * lsq_bam_to_mrf prints behind the header's, those of them that are not "#", and their blocks, under the context's
+ * sam_skip_flags / sam_min_mapq (lsq_bam_check_host: the defaults).  lsq_bam_check runs the device chain on a context that
+ * needs no events; blocks_repaired as lsq_last_bam_paths (0 from lsq_bam_check_host). */
+typedef struct { uint64_t file_bytes, blocks, inflated_bytes, header_lines, references, records, reads, read_blocks, blocks_repaired; } lsq_bam_report;
+int lsq_bam_check_host(const char *path, int n_threads, lsq_bam_report *r);
 /* Wraps caller-made arrays as a read set without copying (the arrays must outlive it).
  * blk_off has n_reads+1 entries; blocks are 0-based half-open; chrom_id / strand_id index
  * lsq_events_chrom_id() / lsq_events_strand_id() dictionaries; line_no is the 1-based line
@@ -282,6 +300,9 @@ int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_s
 /* How the record starts of the latest BAM_SINGLE file of the context were found: its BGZF blocks, and how many of them the
  * repair pass walked again because a record did not begin with the block (0 for a file as htslib writes it).  Either may be null. */
 int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_repaired);
+/* The whole-file check of a BAM file on the device chain, always verifying (lsq_bam_report and lsq_bam_check_host, above); the
+ * context needs no events. */
+int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r);
 uint64_t lsq_reads_retained(const lsq_ctx *c, int method);      /* "loaded N reads" log line */
 uint64_t lsq_reads_retained_blocks(const lsq_ctx *c, int method);
 /* Of the retained reads, those kept in the pools: reads whose first base lies in the span of an event planned on this
@@ -341,7 +362,8 @@ int lsq_host_evaluated(const lsq_ctx *c, uint64_t *n_genes, uint64_t *n_reads);
  * when the EM runs its one-lane-per-event kernel beside it and the read set is evenly deep, else as many as fit), "em_flat_min_events" (default 16 384: with at
  * least that many two-isoform events the ones that converged within 32 iterations last time are solved one lane per
  * event instead of four -- fewer instructions, longer passes), "sam_skip_flags" (default 0x904) and "sam_min_mapq" (default 0): which records of SAM_SINGLE
- * read files uploaded afterwards make no read -- these two do decide results; the executables also take them from LSQ_SAM_SKIP_FLAGS and LSQ_SAM_MIN_MAPQ), "em_closed_form" (default 0; 1: two-isoform events with one read
+ * read files uploaded afterwards make no read -- these two do decide results; the executables also take them from LSQ_SAM_SKIP_FLAGS and LSQ_SAM_MIN_MAPQ), "bam_verify" (0 or 1, default 0; 1: BAM_SINGLE read files uploaded or parsed on the
+ * device afterwards have every block's CRC32 and the end-of-file marker checked -- it decides which files are accepted, never a result; LSQ_BAM_VERIFY in the executables), "em_closed_form" (default 0; 1: two-isoform events with one read
  * file run six ordinary EM iterations and finish in the closed form of their EM map -- the step of read.h:592-618 is then a
  * Moebius map of theta_0, theta after m more iterations one exponential away, and the iteration at which read.h:659 stops
  * is found by search: the same iteration counts, theta within 1e-13; pays where the slowest events take hundreds of

@@ -63,6 +63,11 @@ int lsq_debug_last_parse_paths(const lsq_ctx *c, unsigned *tiles_handed, unsigne
  * LSQ_E_RANGE then).  Status as lsq_bam_parse for the block chain and the deflate streams. */
 int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *out, uint64_t cap, uint64_t *n);
 
+/* The same staging and inflate, then the CRC32 pass of the chain (lsq_bgzf_crc_kernel) without its comparison: the checksum the
+ * device COMPUTED for every block's inflated bytes, in file order, into crc (cap entries; *n = the number of blocks, also when
+ * cap is too small: LSQ_E_RANGE then).  The stored values are not looked at; a test holds the result against zlib. */
+int lsq_debug_bgzf_crc32(lsq_ctx *c, const void *bytes, uint64_t len, uint32_t *crc, uint64_t cap, uint64_t *n);
+
 /* HIP_VERSION the library was compiled against and hipRuntimeGetVersion() of the runtime it found in the process (0
  * when that call fails, e.g. without a driver): a binding that loads another runtime first (PyTorch's) can compare. */
 int lsq_debug_hip_versions(int *compiled, int *runtime);

@@ -42,6 +42,10 @@ class SynthSpecStruct(C.Structure):
                 ("sorted", u32), ("reserved", u32)]
 
 
+class BamReportStruct(C.Structure):       # lsq_bam_report
+    _fields_ = [(k, u64) for k in ("file_bytes", "blocks", "inflated_bytes", "header_lines", "references", "records", "reads", "read_blocks", "blocks_repaired")]
+
+
 def _sig(name, res, *args):
     f = getattr(lib, name)
     f.restype = res
@@ -82,6 +86,9 @@ _sig("lsq_sam_parse", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
 _sig("lsq_sam_to_mrf", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
 _sig("lsq_bam_parse", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
 _sig("lsq_bam_to_mrf", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
+_sig("lsq_bam_parse_checked", C.c_int, cs, vp, C.c_uint, C.c_uint, C.c_int, P(vp))
+_sig("lsq_bam_to_mrf_checked", C.c_int, cs, u64, C.c_uint, C.c_uint, P(vp), P(u64))
+_sig("lsq_bam_check_host", C.c_int, cs, C.c_int, P(BamReportStruct))
 _sig("lsq_reads_wrap", C.c_int, u64, P(u64), P(u32), P(i32), P(i32), P(u16), P(u8), P(vp))
 _sig("lsq_reads_free", None, vp)
 _sig("lsq_reads_count", u64, vp)
@@ -118,6 +125,8 @@ _sig("lsq_last_sam_paths", C.c_int, vp, P(u32), P(u32))
 _sig("lsq_last_ingest_stage_count", C.c_int, vp)
 _sig("lsq_last_bam_paths", C.c_int, vp, P(u64), P(u64))
 _sig("lsq_debug_bgzf_inflate", C.c_int, vp, cs, u64, vp, u64, P(u64))
+_sig("lsq_debug_bgzf_crc32", C.c_int, vp, cs, u64, P(u32), u64, P(u64))
+_sig("lsq_bam_check", C.c_int, vp, cs, P(BamReportStruct))
 _sig("lsq_reads_retained", u64, vp, C.c_int)
 _sig("lsq_reads_retained_blocks", u64, vp, C.c_int)
 _sig("lsq_reads_pooled", u64, vp, C.c_int)

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, check_runtime_once, SynthSpecStruct, u64, u32, i32, u16, u8, i64, vp, cs, P
+from ._lib import lib, check, check_runtime_once, SynthSpecStruct, BamReportStruct, u64, u32, i32, u16, u8, i64, vp, cs, P
 
 EVENT_TYPES = ("SE", "RI", "A5SS", "A3SS", "MXE", "AFE", "ALE", "T3")
 
@@ -179,15 +179,28 @@ def sam_to_mrf(sam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0):
         lib.lsq_free(out)
 
 
-def bam_to_mrf(bam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0):
-    """the MRF_SINGLE text (bytes) that defines what a BAM_SINGLE file means (lsq_bam_to_mrf): that of its SAM equivalent"""
+def bam_to_mrf(bam_bytes, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0, verify=False):
+    """the MRF_SINGLE text (bytes) that defines what a BAM_SINGLE file means (lsq_bam_to_mrf): that of its SAM equivalent;
+    verify: every block's CRC32 and the end-of-file marker are checked on the way (lsq_bam_to_mrf_checked)"""
     data = bytes(bam_bytes)
     out, n = vp(), u64()
-    check(lib.lsq_bam_to_mrf(data, len(data), skip_flags, min_mapq, C.byref(out), C.byref(n)))
+    check((lib.lsq_bam_to_mrf_checked if verify else lib.lsq_bam_to_mrf)(data, len(data), skip_flags, min_mapq, C.byref(out), C.byref(n)))
     try:
         return C.string_at(out.value, n.value)
     finally:
         lib.lsq_free(out)
+
+
+def _bam_report(r):
+    return {k: int(getattr(r, k)) for k, _ in r._fields_}
+
+
+def bam_check_host(path, n_threads=0):
+    """a whole BAM file checked on the host, CRC32s and end-of-file marker included, no annotation needed (lsq_bam_check_host):
+    the report's fields as a dict"""
+    r = BamReportStruct()
+    check(lib.lsq_bam_check_host(_b(path), n_threads, C.byref(r)))
+    return _bam_report(r)
 
 
 class Reads:
@@ -211,10 +224,11 @@ class Reads:
         return cls(h)
 
     @classmethod
-    def from_bam(cls, path, events, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0, n_threads=0):
-        """a BAM_SINGLE file through the host parser (lsq_bam_parse): the arrays from_sam gives for its SAM equivalent"""
+    def from_bam(cls, path, events, skip_flags=SAM_DEFAULT_SKIP_FLAGS, min_mapq=0, n_threads=0, verify=False):
+        """a BAM_SINGLE file through the host parser (lsq_bam_parse): the arrays from_sam gives for its SAM equivalent;
+        verify: every block's CRC32 and the end-of-file marker are checked on the way (lsq_bam_parse_checked)"""
         h = vp()
-        check(lib.lsq_bam_parse(_b(path), events.h, skip_flags, min_mapq, n_threads, C.byref(h)))
+        check((lib.lsq_bam_parse_checked if verify else lib.lsq_bam_parse)(_b(path), events.h, skip_flags, min_mapq, n_threads, C.byref(h)))
         return cls(h)
 
     @classmethod
@@ -345,6 +359,27 @@ class Context:
             check(st)
             return out.raw[:n.value]
 
+    def bgzf_crc32(self, data):
+        """the CRC32 the device computes for every BGZF block of a file's bytes, in file order, nothing compared (lsq_debug_bgzf_crc32)"""
+        data = bytes(data)
+        n = u64()
+        cap = 1 << 10
+        while True:
+            out = (u32 * cap)()
+            st = lib.lsq_debug_bgzf_crc32(self.h, data, len(data), out, cap, C.byref(n))
+            if st == -5 and n.value > cap:
+                cap = n.value
+                continue
+            check(st)
+            return [int(v) for v in out[:n.value]]
+
+    def bam_check(self, path):
+        """a whole BAM file checked on the device chain, CRC32s and end-of-file marker included; the context needs no events
+        (lsq_bam_check): the report's fields as a dict"""
+        r = BamReportStruct()
+        check(lib.lsq_bam_check(self.h, _b(path), C.byref(r)))
+        return _bam_report(r)
+
     def mrf_timing(self):
         a, b = C.c_float(), C.c_float()
         check(lib.lsq_last_mrf_timing(self.h, C.byref(a), C.byref(b)))
@@ -396,7 +431,7 @@ class Context:
 
     def set_option(self, name, value):
         """lsq_ctx_set_option: grid_multiplier, exception_capacity, recount_every_read, em_guard_band,
-        snap_shares, em_regroup, em_flat_min_events, compact_pools"""
+        snap_shares, em_regroup, em_flat_min_events, compact_pools, sam_skip_flags, sam_min_mapq, bam_verify"""
         check(lib.lsq_ctx_set_option(self.h, _b(name), float(value)))
 
     def count_status(self):

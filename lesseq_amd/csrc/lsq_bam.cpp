@@ -1,6 +1,8 @@
 // BAM_SINGLE on the host: the parser (lsq_bam_parse: the arrays lsq_sam_parse fills for the equivalent SAM text) and the
 // converter to the equivalent MRF_SINGLE text (lsq_bam_to_mrf, the bam2mrf executable).  The rules live in lsq_bam_record.hpp
 // and lsq_sam_line.hpp, the decoder in lsq_inflate.hpp, the file's structure in lsq_bam.hpp.  No GPU touched, no zlib.
+// The _checked entries verify every block's CRC32 and the end-of-file marker (lsq_crc32.hpp) on the way; lsq_bam_check_host is
+// the whole-file check without an annotation (the bamcheck executable with --host).
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -16,10 +18,10 @@ namespace lsq {
 int bam_fail(const BamError &e) { return fail(e.status, "%s", e.text.c_str()); }      // (declared in lsq_internal.hpp: the device chain reports through it too)
 
 // the MRF text that defines what the BAM file means: "AlignmentBlocks", '#' per header line, a line per record
-int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o) {
+int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify) {
 	BamStream S;
 	BamError e;
-	if (bam_open((const unsigned char *)bytes, len, host_threads(0), S, e)) return bam_fail(e);
+	if (bam_open((const unsigned char *)bytes, len, host_threads(0), S, e, verify)) return bam_fail(e);
 	o = "AlignmentBlocks\n";
 	for (uint64_t k = 0; k < S.H.h_lines; ++k) o += "#\n";
 	size_t keep = o.size();
@@ -38,22 +40,21 @@ int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_
 	return st ? bam_fail(e) : LSQ_OK;
 }
 
-} // namespace lsq
+// a file's bytes, a file that does not open named as the parsers name it
+static int bam_read_file(const char *path, std::string &bytes) {
+	FILE *f = fopen(path, "rb");
+	if (!f) return fail(LSQ_E_IO, "cannot open reads file %s", path);
+	fclose(f);
+	return read_all(path, bytes) ? LSQ_E_IO : LSQ_OK;
+}
 
-extern "C" {
-
-int lsq_bam_parse(const char *path, lsq_events *E, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out) LSQ_API_TRY {
+static int bam_parse_file(const char *path, lsq_events *E, unsigned skip_flags, unsigned min_mapq, int n_threads, bool verify, lsq_reads **out) {
 	if (!path || !E || !out) return fail(LSQ_E_ARG, "null argument");
 	std::string bytes;
-	{
-		FILE *f = fopen(path, "rb");
-		if (!f) return fail(LSQ_E_IO, "cannot open reads file %s", path);
-		fclose(f);
-		if (read_all(path, bytes)) return LSQ_E_IO;
-	}
+	if (const int rc = bam_read_file(path, bytes)) return rc;
 	BamStream S;
 	BamError e;
-	if (bam_open((const unsigned char *)bytes.data(), bytes.size(), host_threads(n_threads), S, e)) return bam_fail(e);
+	if (bam_open((const unsigned char *)bytes.data(), bytes.size(), host_threads(n_threads), S, e, verify)) return bam_fail(e);
 	std::string().swap(bytes);
 	// chromosome ids: only names the events know can ever pass the containment filter (as lsq_mrf.cpp's parse_chunk)
 	const uint16_t NOCHROM = 0xFFFF;
@@ -88,12 +89,12 @@ int lsq_bam_parse(const char *path, lsq_events *E, unsigned skip_flags, unsigned
 	R->adopt();
 	*out = R.release();
 	return LSQ_OK;
-} LSQ_API_CATCH
+}
 
-int lsq_bam_to_mrf(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len) LSQ_API_TRY {
+static int bam_to_mrf_text(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, bool verify, char **mrf_text, uint64_t *mrf_len) {
 	if ((!bam_bytes && len) || !mrf_text) return fail(LSQ_E_ARG, "null argument");
 	std::string o;
-	const int st = bam_to_mrf((const char *)bam_bytes, (size_t)len, skip_flags, min_mapq, o);
+	const int st = bam_to_mrf((const char *)bam_bytes, (size_t)len, skip_flags, min_mapq, o, verify);
 	if (st) return st;
 	char *p = (char *)malloc(o.size() + 1);
 	if (!p) return fail(LSQ_E_INTERNAL, "out of memory");
@@ -101,6 +102,42 @@ int lsq_bam_to_mrf(const void *bam_bytes, uint64_t len, unsigned skip_flags, uns
 	p[o.size()] = 0;
 	*mrf_text = p;
 	if (mrf_len) *mrf_len = o.size();
+	return LSQ_OK;
+}
+
+} // namespace lsq
+
+extern "C" {
+
+int lsq_bam_parse(const char *path, lsq_events *E, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out) LSQ_API_TRY {
+	return bam_parse_file(path, E, skip_flags, min_mapq, n_threads, false, out);
+} LSQ_API_CATCH
+int lsq_bam_parse_checked(const char *path, lsq_events *E, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_reads **out) LSQ_API_TRY {
+	return bam_parse_file(path, E, skip_flags, min_mapq, n_threads, true, out);
+} LSQ_API_CATCH
+
+int lsq_bam_to_mrf(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len) LSQ_API_TRY {
+	return bam_to_mrf_text(bam_bytes, len, skip_flags, min_mapq, false, mrf_text, mrf_len);
+} LSQ_API_CATCH
+int lsq_bam_to_mrf_checked(const void *bam_bytes, uint64_t len, unsigned skip_flags, unsigned min_mapq, char **mrf_text, uint64_t *mrf_len) LSQ_API_TRY {
+	return bam_to_mrf_text(bam_bytes, len, skip_flags, min_mapq, true, mrf_text, mrf_len);
+} LSQ_API_CATCH
+
+int lsq_bam_check_host(const char *path, int n_threads, lsq_bam_report *r) LSQ_API_TRY {
+	if (!path || !r) return fail(LSQ_E_ARG, "null argument");
+	std::string bytes;
+	if (const int rc = bam_read_file(path, bytes)) return rc;
+	BamStream S;
+	BamError e;
+	if (bam_open((const unsigned char *)bytes.data(), bytes.size(), host_threads(n_threads), S, e, true)) return bam_fail(e);
+	lsq_bam_report R{};
+	R.file_bytes = bytes.size(); R.blocks = S.n_blocks; R.inflated_bytes = S.bytes.size();
+	R.header_lines = S.H.h_lines; R.references = S.H.ref_names.size();
+	uint64_t nb = 0;
+	const int st = bam_for_each_record(S, SAM_DEFAULT_SKIP_FLAGS, SAM_DEFAULT_MIN_MAPQ, [&](int64_t, bool, int64_t, int64_t, int64_t, int64_t) { ++nb; },
+	                                   [&](uint64_t, int v) { ++R.records; if (v == SAM_READ) { ++R.reads; R.read_blocks += nb; } nb = 0; return (int)BAM_OK; }, e);
+	if (st) return bam_fail(e);
+	*r = R;
 	return LSQ_OK;
 } LSQ_API_CATCH
 

@@ -4,17 +4,21 @@
 // it depends on nothing of the library.  DESIGN.md 4.10.
 //
 // Errors, in the order a file meets them: the block chain (all of it), the deflate streams (first failing block in file order),
-// the BAM header, the records (first malformed record in file order).  The CRC32 of a block is not verified.
+// the BAM header, the records (first malformed record in file order).  With `verify` (bam_open, bgzf_inflate_all; off unless a
+// caller asks) two checks stand between the deflate streams and the header: every block's CRC32 (lsq_crc32.hpp) against the
+// stored one, the first differing block in file order, and the end-of-file marker as the file's last 28 bytes.
 #pragma once
 #include <algorithm>
 #include <atomic>
 #include <cstdint>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <thread>
 #include <vector>
 
 #include "lsq_bam_record.hpp"
+#include "lsq_crc32.hpp"
 #include "lsq_inflate.hpp"
 
 namespace lsq {
@@ -36,6 +40,19 @@ inline int bam_format_error(BamError &e, const std::string &what, uint64_t file_
 inline int bam_inflate_error(BamError &e, int inflate_status, uint64_t file_off) {
 	return bam_format_error(e, std::string("invalid deflate stream (") + inflate_status_text(inflate_status) + ")", file_off);
 }
+inline int bam_crc_error(BamError &e, uint32_t stored, uint32_t computed, uint64_t file_off) {
+	char what[80];
+	snprintf(what, sizeof what, "CRC32 mismatch (stored 0x%08x, computed 0x%08x)", (unsigned)stored, (unsigned)computed);
+	return bam_format_error(e, what, file_off);
+}
+// the empty block that ends a BGZF file: a file cut at a block boundary lacks it
+constexpr unsigned char BGZF_EOF_MARKER[28] = {0x1f, 0x8b, 0x08, 0x04, 0, 0, 0, 0, 0, 0xff, 0x06, 0, 0x42, 0x43, 0x02, 0, 0x1b, 0, 0x03, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+inline int bam_check_eof_marker(const unsigned char *b, uint64_t len, BamError &e) {
+	if (len >= sizeof BGZF_EOF_MARKER && memcmp(b + len - sizeof BGZF_EOF_MARKER, BGZF_EOF_MARKER, sizeof BGZF_EOF_MARKER) == 0) return BAM_OK;
+	return bam_format_error(e, "no end-of-file marker", len);
+}
+// the CRC32 a block stores: the four bytes behind its deflate stream
+inline uint32_t bgzf_stored_crc(const unsigned char *b, const BgzfBlock &B) { return bam_le32(b + B.in_off + B.in_len); }
 inline int bam_record_error(BamError &e, uint64_t line_no, uint64_t byte) {
 	e.status = BAM_E_PARSE;
 	e.text = "#" + std::to_string(line_no) + ":<BAM record at byte " + std::to_string(byte) + " of the inflated stream>";
@@ -70,17 +87,19 @@ inline int bgzf_block_table(const unsigned char *b, uint64_t len, std::vector<Bg
 	return BAM_OK;
 }
 
-// Every block of the table into out (total bytes), by n_threads threads; the first failing block in file order speaks.
-inline int bgzf_inflate_all(const unsigned char *b, const std::vector<BgzfBlock> &tab, unsigned char *out, int n_threads, BamError &e) {
-	std::atomic<uint64_t> first_bad{~0ull};
+// Every block of the table into out (total bytes), by n_threads threads; the first failing block in file order speaks.  With
+// `verify` each thread checksums the blocks it inflated: a deflate error anywhere in the file comes before a CRC32 that differs.
+inline int bgzf_inflate_all(const unsigned char *b, const std::vector<BgzfBlock> &tab, unsigned char *out, int n_threads, BamError &e, bool verify = false) {
+	std::atomic<uint64_t> first_bad{~0ull}, first_crc{~0ull};
+	auto lower = [](std::atomic<uint64_t> &word, uint64_t mine) {
+		uint64_t cur = word.load();
+		while (mine < cur && !word.compare_exchange_weak(cur, mine)) {}
+	};
 	auto work = [&](size_t t, size_t T) {
 		for (size_t k = t; k < tab.size(); k += T) {
 			const int st = inflate_block(b + tab[k].in_off, tab[k].in_len, out + tab[k].out_off, tab[k].isize);
-			if (st) {
-				const uint64_t mine = ((uint64_t)k << 8) | (uint64_t)st;
-				uint64_t cur = first_bad.load();
-				while (mine < cur && !first_bad.compare_exchange_weak(cur, mine)) {}
-			}
+			if (st) lower(first_bad, ((uint64_t)k << 8) | (uint64_t)st);
+			else if (verify && crc32_bytes(out + tab[k].out_off, tab[k].isize) != bgzf_stored_crc(b, tab[k])) lower(first_crc, (uint64_t)k);
 		}
 	};
 	const size_t T = (size_t)std::max(1, std::min<int>(n_threads, (int)std::min<size_t>(tab.size() / 16 + 1, 64)));
@@ -92,6 +111,10 @@ inline int bgzf_inflate_all(const unsigned char *b, const std::vector<BgzfBlock>
 	}
 	const uint64_t bad = first_bad.load();
 	if (bad != ~0ull) return bam_inflate_error(e, (int)(bad & 0xFFu), tab[(size_t)(bad >> 8)].file_off);
+	if (first_crc.load() != ~0ull) {
+		const BgzfBlock &B = tab[(size_t)first_crc.load()];
+		return bam_crc_error(e, bgzf_stored_crc(b, B), crc32_bytes(out + B.out_off, B.isize), B.file_off);
+	}
 	return BAM_OK;
 }
 
@@ -138,14 +161,16 @@ inline int bam_parse_header(const unsigned char *s, uint64_t avail, uint64_t tot
 }
 
 // A whole file's bytes: the inflated stream and its header.
-struct BamStream { std::vector<unsigned char> bytes; BamHeader H; };
-inline int bam_open(const unsigned char *file, uint64_t len, int n_threads, BamStream &S, BamError &e) {
+struct BamStream { std::vector<unsigned char> bytes; BamHeader H; uint64_t n_blocks = 0; };
+inline int bam_open(const unsigned char *file, uint64_t len, int n_threads, BamStream &S, BamError &e, bool verify = false) {
 	std::vector<BgzfBlock> tab;
 	uint64_t total = 0;
 	int st = bgzf_block_table(file, len, tab, total, e);
 	if (st) return st;
+	S.n_blocks = tab.size();
 	S.bytes.assign((size_t)total + 16, 0);
-	if ((st = bgzf_inflate_all(file, tab, S.bytes.data(), n_threads, e))) return st;
+	if ((st = bgzf_inflate_all(file, tab, S.bytes.data(), n_threads, e, verify))) return st;
+	if (verify && (st = bam_check_eof_marker(file, len, e))) return st;
 	S.bytes.resize((size_t)total);
 	return bam_parse_header(S.bytes.data(), total, total, S.H, e);
 }

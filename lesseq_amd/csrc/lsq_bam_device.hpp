@@ -6,6 +6,10 @@
 //   bgzf_inflate     lsq_bgzf_inflate_kernel: a lane a BGZF block runs the shared decoder (lsq_inflate.hpp) from the block's
 //                    deflate bytes into its ISIZE bytes of the inflated stream; a failing block's status to an error
 //                    word, the first in file order wins
+//   bgzf_crc32       only with the context option "bam_verify" (and always under lsq_bam_check): lsq_bgzf_crc_kernel, a wave a BGZF
+//                    block -- every lane the CRC-32 (lsq_crc32.hpp) of its slice of the block's inflated bytes, folded across the
+//                    wave; the first block in file order whose sum is not the stored one to an error word; then the host looks
+//                    at the file's last 28 bytes for the end-of-file marker
 //   header           host: l_text, the text, n_ref and the names read back -> h and the refID -> chromosome id table
 //   bam_record_starts   a record belongs to the block in which it starts.  The stream is contiguous, so only where the first
 //                    record of each block begins is unknown: proposed at the block's first byte (the header's end for the block
@@ -53,6 +57,50 @@ __global__ void __launch_bounds__(64) lsq_bgzf_inflate_kernel(const unsigned cha
 	int st = lsq::inflate_stream(src, sink, work);
 	if (!st && sink.n != B.isize) st = lsq::INF_OUTPUT_UNDER;
 	if (st) atomicMin(&err[0], ((unsigned long long)b << 8) | (unsigned long long)st);
+}
+
+// ---- CRC-32: a wave a BGZF block.  Lane l owns the bytes [l S, (l + 1) S) of the block's ISIZE, S = ceil(ISIZE / 64) rounded up
+// to 16 (at most 1 KiB), and runs the register over them -- from 0xFFFFFFFF in lane 0, from zero elsewhere -- four bytes a step
+// through the four tables in LDS.  CRC-32 is linear over GF(2): what a lane's register would be after the bytes behind its
+// slice is the register times x^(8 * those bytes) modulo the polynomial, and the block's register is the xor of the 64.  A block's
+// place in the stream is a prefix sum of ISIZEs, so of any alignment: a lane takes the bytes up to the first 16-byte boundary
+// one at a time, then aligned 16-byte words, then the tail; S is a multiple of 16, so the lanes of a wave share the split.
+// crc[b] = the computed sum; with `compare`, the first block in file order whose stored sum (the four bytes behind its deflate
+// stream in the staged file) differs goes to err[0].
+constexpr unsigned BGZF_CRC_WAVES = 4;           // waves (blocks of the file at a time) per workgroup
+__global__ void __launch_bounds__(64 * BGZF_CRC_WAVES) lsq_bgzf_crc_kernel(const unsigned char *in, const lsq::BgzfBlock *tab, unsigned nb, const unsigned char *stream, unsigned *crc,
+                                                                            unsigned compare, unsigned long long *err) {
+	__shared__ unsigned table[lsq::CRC32_TABLE_WORDS];
+	for (unsigned i = threadIdx.x; i < lsq::CRC32_TABLE_WORDS; i += 64u * BGZF_CRC_WAVES) table[i] = lsq::crc32_table_entry(i & 255u, i >> 8);
+	__syncthreads();
+	const unsigned lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+	for (unsigned long long b = (unsigned long long)blockIdx.x * BGZF_CRC_WAVES + wave; b < nb; b += (unsigned long long)gridDim.x * BGZF_CRC_WAVES) {
+		const lsq::BgzfBlock B = tab[b];
+		const unsigned isize = B.isize;                                  // (<= 65 536: the block table refuses more)
+		const unsigned S = (((isize + 63u) >> 6) + 15u) & ~15u;
+		const unsigned lo = min(lane * S, isize), hi = min(lo + S, isize);
+		const unsigned char *p = stream + B.out_off + lo, *const end = stream + B.out_off + hi;
+		unsigned c = lane == 0u ? 0xFFFFFFFFu : 0u;
+		for (; p < end && ((unsigned long long)p & 15ull) != 0ull; ++p) c = lsq::crc32_step_byte(c, *p, table);
+		for (; end - p >= 16; p += 16) {
+			const uint4 w = *reinterpret_cast<const uint4 *>(p);
+			c = lsq::crc32_step_word(c, w.x, table);
+			c = lsq::crc32_step_word(c, w.y, table);
+			c = lsq::crc32_step_word(c, w.z, table);
+			c = lsq::crc32_step_word(c, w.w, table);
+		}
+		for (; p < end; ++p) c = lsq::crc32_step_byte(c, *p, table);
+		if (c != 0u && hi < isize) c = lsq::crc32_mulmod(c, lsq::crc32_xpow8(isize - hi));
+#pragma unroll
+		for (unsigned m = 1; m < 64u; m <<= 1) c ^= (unsigned)__shfl_xor((int)c, (int)m, 64);
+		if (lane == 0u) {
+			c ^= 0xFFFFFFFFu;
+			crc[b] = c;
+			const unsigned char *q = in + B.in_off + B.in_len;
+			const unsigned stored = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16) | ((unsigned)q[3] << 24);
+			if (compare && stored != c) atomicMin(&err[0], b);
+		}
+	}
 }
 
 // ---- record starts
@@ -223,6 +271,7 @@ struct BamRecords {
 	DevBuf<lsq::BgzfBlock> d_tab;
 	DevBuf<unsigned> d_ref_cid;
 	DevBuf<unsigned long long> d_rec_off;
+	DevBuf<unsigned> d_crc;                  // per block: the CRC-32 the device computed (only when the file was verified)
 	BamView view() const { return BamView{d_stream.p, total, d_rec_off.p, d_ref_cid.p, (long long)H.ref_names.size()}; }
 	// the first malformed record of the latest pass, as the host parser names it
 	int fail_record(unsigned long long line_no, hipStream_t st) const {
@@ -237,8 +286,10 @@ struct BamRecords {
 
 using lsq::bam_fail;
 
-// the block table over the file's bytes in host memory, and every block through the inflate kernel
-static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char *host_bytes, BamRecords &B) {
+// the block table over the file's bytes in host memory, and every block through the inflate kernel; verify: 1 -- every block
+// through the CRC-32 kernel behind it, compared with the stored sum, then the end-of-file marker; 2 -- the sums computed, nothing
+// compared (lsq_debug_bgzf_crc32)
+static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char *host_bytes, BamRecords &B, int verify) {
 	hipStream_t st = c->stream;
 	int rc;
 	lsq::BamError e;
@@ -248,7 +299,7 @@ static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char
 	if (B.tab.size() > 0x7FFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^31 BGZF blocks");
 	size_t mem_free = 0, mem_total = 0;
 	HIP_TRY(hipMemGetInfo(&mem_free, &mem_total));
-	const unsigned long long want = B.total + 16ull + B.tab.size() * (sizeof(lsq::BgzfBlock) + 28ull) + (64ull << 20);
+	const unsigned long long want = B.total + 16ull + B.tab.size() * (sizeof(lsq::BgzfBlock) + 32ull) + (64ull << 20);
 	if (want > mem_free) return fail(LSQ_E_RANGE, "%s: the inflated stream (%llu bytes) beside the %llu compressed bytes does not fit the device's free memory (%llu bytes)",
 	                                 T.path.c_str(), B.total, T.len, (unsigned long long)mem_free);
 	DevBuf<unsigned long long> d_err;
@@ -265,6 +316,27 @@ static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char
 	HIP_TRY(hipMemcpyAsync(&bad, d_err.p, 8, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	if (bad != no_err) { lsq::bam_inflate_error(e, (int)(bad & 0xFFu), B.tab[(size_t)(bad >> 8)].file_off); return bam_fail(e); }
+	if (!verify) return LSQ_OK;
+	if ((rc = B.d_crc.alloc(nb))) return rc;
+	{
+		// (the error word still holds "none": the inflate left it alone)
+		StageClock k(c, st, LSQ_INGEST_STAGES + 2);
+		const unsigned grid = (unsigned)std::min<unsigned long long>(((unsigned long long)nb + BGZF_CRC_WAVES - 1) / BGZF_CRC_WAVES, (unsigned long long)c->n_cu * 16);
+		hipLaunchKernelGGL(lsq_bgzf_crc_kernel, dim3(grid), dim3(64 * BGZF_CRC_WAVES), 0, st, (const unsigned char *)T.d_text.p, (const lsq::BgzfBlock *)B.d_tab.p, nb, (const unsigned char *)B.d_stream.p,
+		                   B.d_crc.p, verify == 1 ? 1u : 0u, d_err.p);
+		HIP_TRY(hipGetLastError());
+		k.end(B.total + 8ull * nb);
+	}
+	HIP_TRY(hipMemcpyAsync(&bad, d_err.p, 8, hipMemcpyDeviceToHost, st));
+	HIP_TRY(hipStreamSynchronize(st));
+	if (verify != 1) return LSQ_OK;
+	if (bad != no_err) {
+		unsigned computed = 0;
+		HIP_TRY(hipMemcpy(&computed, B.d_crc.p + bad, 4, hipMemcpyDeviceToHost));
+		lsq::bam_crc_error(e, lsq::bgzf_stored_crc(host_bytes, B.tab[(size_t)bad]), computed, B.tab[(size_t)bad].file_off);
+		return bam_fail(e);
+	}
+	if (lsq::bam_check_eof_marker(host_bytes, T.len, e)) return bam_fail(e);
 	return LSQ_OK;
 }
 
@@ -286,15 +358,16 @@ struct BamFileMap {
 	}
 };
 
-// ReadFormat::open of BAM_SINGLE: the staged file to an inflated stream with its records' offsets
-static int bam_open_staged(lsq_ctx *c, lsq_text &T, BamRecords &B) {
+// ReadFormat::open of BAM_SINGLE: the staged file to an inflated stream with its records' offsets.  (lsq_bam_check runs it on a
+// context without events: no chromosome is known then, and every reference is one the events do not cover.)
+static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify) {
 	hipStream_t st = c->stream;
 	int rc;
-	lsq_events &E = *c->E;
+	lsq_events *E = c->E;
 	{
 		BamFileMap M;
 		const unsigned char *bytes = nullptr;
-		if ((rc = M.open_text(T, bytes)) || (rc = bam_inflate_staged(c, T, bytes, B))) return rc;
+		if ((rc = M.open_text(T, bytes)) || (rc = bam_inflate_staged(c, T, bytes, B, verify ? 1 : 0))) return rc;
 	}
 	// the header, from a prefix of the stream that grows until it holds it
 	lsq::BamError e;
@@ -311,8 +384,8 @@ static int bam_open_staged(lsq_ctx *c, lsq_text &T, BamRecords &B) {
 	}
 	std::vector<unsigned> ref_cid(B.H.ref_names.size());
 	for (size_t r = 0; r < ref_cid.size(); ++r) {
-		const int id = E.chroms.find(B.H.ref_names[r]);
-		ref_cid[r] = !B.H.ref_walks[r] ? BAM_REF_NO_READ : (id < 0 || (size_t)id >= E.covered.size()) ? MRF_NOCHROM : (unsigned)id;
+		const int id = E ? E->chroms.find(B.H.ref_names[r]) : -1;
+		ref_cid[r] = !B.H.ref_walks[r] ? BAM_REF_NO_READ : (id < 0 || (size_t)id >= E->covered.size()) ? MRF_NOCHROM : (unsigned)id;
 	}
 	// record starts
 	const unsigned nb = (unsigned)B.tab.size();
@@ -347,6 +420,7 @@ static int bam_open_staged(lsq_ctx *c, lsq_text &T, BamRecords &B) {
 	c->bam_blocks = nb; c->bam_blocks_repaired = misc[1];
 	return LSQ_OK;
 }
+static int bam_open_staged(lsq_ctx *c, lsq_text &T, BamRecords &B) { return bam_open_verified(c, T, B, c->opt_bam_verify); }
 
 static void bam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
 	if (!J.X.n_lines) return;

@@ -183,8 +183,10 @@ struct PhaseTimer {
 
 // LSQ_OPTIONS="name=value,...": tuning knobs for lsq_ctx_set_option, read once per process
 int apply_env_options(lsq_ctx *c) {
-	// which records of SAM_SINGLE read files make no read (decimal, or 0x... / 0... as strtoul reads them)
-	for (const char *const *kv : {(const char *const[]){"LSQ_SAM_SKIP_FLAGS", "sam_skip_flags"}, (const char *const[]){"LSQ_SAM_MIN_MAPQ", "sam_min_mapq"}})
+	// which records of SAM_SINGLE read files make no read (decimal, or 0x... / 0... as strtoul reads them); whether BAM_SINGLE
+	// read files are verified (0 or 1)
+	for (const char *const *kv : {(const char *const[]){"LSQ_SAM_SKIP_FLAGS", "sam_skip_flags"}, (const char *const[]){"LSQ_SAM_MIN_MAPQ", "sam_min_mapq"},
+	                              (const char *const[]){"LSQ_BAM_VERIFY", "bam_verify"}})
 		if (const char *e = getenv(kv[0])) {
 			char *end = nullptr;
 			const unsigned long v = strtoul(e, &end, 0);
@@ -205,6 +207,36 @@ int apply_env_options(lsq_ctx *c) {
 		pos = end + 1;
 	}
 	return LSQ_OK;
+}
+
+// bamcheck [--host] reads.bam: the whole-file check of a BAM file (lsq_bam_check; --host: lsq_bam_check_host, no GPU) -- a
+// "key<TAB>value" line per field of the report on standard output.  Exit status 0; 1 with the message on standard error, and
+// nothing on standard output, for a file that fails the check or does not open (as bam2mrf).
+int run_bamcheck(int argc, const char *const *argv, std::string &out) {
+	bool host = false, bad = false;
+	const char *path = nullptr;
+	for (int i = 1; i < argc && !bad; ++i) {
+		if (strcmp(argv[i], "--host") == 0) host = true;
+		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
+		else if (!path) path = argv[i];
+		else bad = true;
+	}
+	if (bad || !path) { logf(0, "Usage:\nbamcheck [--host] bam_path"); return 1; }
+	lsq_bam_report r;
+	Freer F;
+	int st;
+	if (host) st = lsq_bam_check_host(path, 0, &r);
+	else {
+		st = lsq_ctx_create(lsq::cli_device(), &F.c);
+		if (!st) st = apply_env_options(F.c);
+		if (!st) st = lsq_bam_check(F.c, path, &r);
+	}
+	if (st) { logf(0, "%s", lsq_last_error()); if (st == LSQ_E_PARSE) logf(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
+	const std::pair<const char *, uint64_t> fields[] = {{"file_bytes", r.file_bytes}, {"blocks", r.blocks}, {"inflated_bytes", r.inflated_bytes}, {"header_lines", r.header_lines},
+	                                                     {"references", r.references}, {"records", r.records}, {"reads", r.reads}, {"read_blocks", r.read_blocks},
+	                                                     {"blocks_repaired", r.blocks_repaired}};
+	for (const auto &f : fields) { out += f.first; out += '\t'; out += std::to_string(f.second); out += '\n'; }
+	return 0;
 }
 
 // ---- one job over several GPUs (LSQ_GPUS=N): the reference's scale-out -- a process per slice
@@ -829,6 +861,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "gencodeIsoformMap") == 0) rc = run_isoform_map(argc, argv, out);
 	else if (tool && strcmp(tool, "sam2mrf") == 0) rc = run_sam2mrf(false, argc, argv, out);
 	else if (tool && strcmp(tool, "bam2mrf") == 0) rc = run_sam2mrf(true, argc, argv, out);
+	else if (tool && strcmp(tool, "bamcheck") == 0) rc = run_bamcheck(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -882,6 +882,9 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 	} else if (n == "sam_min_mapq") {
 		if (!(value >= 0 && value <= 256)) return fail(LSQ_E_ARG, "sam_min_mapq must lie in 0..256");
 		c->opt_sam_min_mapq = (unsigned)value;
+	} else if (n == "bam_verify") {
+		if (!(value == 0 || value == 1)) return fail(LSQ_E_ARG, "bam_verify must be 0 or 1");
+		c->opt_bam_verify = value == 1;           // takes effect with the next BAM_SINGLE file uploaded or parsed on the device
 	} else if (n == "compact_pools") {
 		c->opt_compact_pools = value != 0;        // takes effect with the next upload of a read set
 	} else if (n == "workgroups_per_cu") {

@@ -36,7 +36,7 @@ using namespace lsq;
 constexpr unsigned P2_GROUP_PAD = LSQ_P2_PAD;      // ... and a junction group of the two-block pool (eight, with eight two-block reads per look, measured 2 % slower on C3: more padding, longer steps)
 constexpr unsigned P1_GROUP_PAD = LSQ_P1_PAD;      // records a cell's group of the one-block pool is padded to: what a lane of the count kernel takes per look
 constexpr int LSQ_INGEST_STAGES = 7;     // newline count, route, partition count, partition scatter, group classify, group offsets, group place
-constexpr int LSQ_INGEST_SLOTS = LSQ_INGEST_STAGES + 2;      // ... and the two passes ahead of a BAM file's route: inflate, record starts (lsq_bam_device.hpp)
+constexpr int LSQ_INGEST_SLOTS = LSQ_INGEST_STAGES + 3;      // ... and the passes ahead of a BAM file's route: inflate, record starts, and -- "bam_verify" -- the CRC32s (lsq_bam_device.hpp)
 constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
 
 namespace lsq {
@@ -286,7 +286,9 @@ struct lsq_ctx {
 	// SAM_SINGLE read files (lsq_sam_device.hpp): which records make no read ("sam_skip_flags", "sam_min_mapq") and what the
 	// kernels of the latest one handed on (lsq_last_sam_paths)
 	unsigned opt_sam_skip_flags = 0x904u, opt_sam_min_mapq = 0u;
+	bool opt_bam_verify = false;            // "bam_verify": BAM_SINGLE files have their blocks' CRC32s and their end-of-file marker checked (lsq_bam_device.hpp)
 	int ing_format = -1;                    // the read format of the latest ingest (lsq_ingest.hip: READ_FORMATS), -1: parsed blocks from the host
+	bool ing_verified = false;              // ... and whether it ran the CRC32 pass of a BAM file ("bam_verify")
 	unsigned sam_lines_listed = 0, sam_all_slow = 0;
 	unsigned long long bam_blocks = 0, bam_blocks_repaired = 0;      // the latest BAM_SINGLE file (lsq_last_bam_paths)
 	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_text.hip: pinned_pipeline)

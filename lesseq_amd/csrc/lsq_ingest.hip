@@ -1279,6 +1279,7 @@ static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &
 	int rc;
 	if ((rc = ensure_lanes(c))) return rc;
 	c->ing_format = (int)(fmt - READ_FORMATS);
+	c->ing_verified = fmt->open && c->opt_bam_verify;
 	c->mrf_h2d_ms = T.h2d_ms; c->mrf_parse_ms = 0;
 	stages_reset(c, T.scanned && !fmt->open);
 	BamRecords BR;                                         // (a file of records: what takes the place of the text's newline tiles)
@@ -1330,7 +1331,7 @@ static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &
 	c->reads[method].named = false;
 	if ((rc = ingest_device(c, method, F))) return rc;
 	// (device time of the parse = the newline count and the routing pass; the rest of the chain is the ingest)
-	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1] + c->ing_ms[LSQ_INGEST_STAGES] + c->ing_ms[LSQ_INGEST_STAGES + 1];
+	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1] + c->ing_ms[LSQ_INGEST_STAGES] + c->ing_ms[LSQ_INGEST_STAGES + 1] + c->ing_ms[LSQ_INGEST_STAGES + 2];
 	return LSQ_OK;
 }
 
@@ -1471,14 +1472,21 @@ static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
 int lsq_ingest_stage_count(void) { return LSQ_INGEST_STAGES; }
 const char *lsq_ingest_stage_name(int stage) { return stage >= 0 && stage < LSQ_INGEST_STAGES ? INGEST_STAGE_NAMES[stage] : nullptr; }
 // Pass k of the latest ingest -> its slot of the context's clocks.  A file of records (BAM) runs two passes of its own, kept in the
-// two slots behind the chain's seven, where a text runs the newline count.
+// slots behind the chain's seven, where a text runs the newline count -- three when it was verified: the CRC32 pass, in the
+// last slot, is reported between the two.
 static bool last_ingest_of_records(const lsq_ctx *c) { return c && c->ing_format >= 0 && READ_FORMATS[c->ing_format].open != nullptr; }
-static int last_stage_slot(const lsq_ctx *c, int k) { return !last_ingest_of_records(c) ? k : k < 2 ? LSQ_INGEST_STAGES + k : k - 1; }
-int lsq_last_ingest_stage_count(const lsq_ctx *c) { return last_ingest_of_records(c) ? LSQ_INGEST_STAGES + 1 : LSQ_INGEST_STAGES; }
+static int last_own_passes(const lsq_ctx *c) { return !last_ingest_of_records(c) ? 1 : c->ing_verified ? 3 : 2; }
+static int last_stage_slot(const lsq_ctx *c, int k) {
+	const int own = last_own_passes(c);
+	if (!last_ingest_of_records(c)) return k;
+	if (k >= own) return k - own + 1;
+	return k == 0 ? LSQ_INGEST_STAGES : k == own - 1 ? LSQ_INGEST_STAGES + 1 : LSQ_INGEST_STAGES + 2;
+}
+int lsq_last_ingest_stage_count(const lsq_ctx *c) { return LSQ_INGEST_STAGES - 1 + last_own_passes(c); }
 const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) {
 	if (stage < 0 || stage >= lsq_last_ingest_stage_count(c)) return nullptr;
 	const int slot = last_stage_slot(c, stage);
-	if (slot >= LSQ_INGEST_STAGES) return slot == LSQ_INGEST_STAGES ? "bgzf_inflate" : "bam_record_starts";
+	if (slot >= LSQ_INGEST_STAGES) return slot == LSQ_INGEST_STAGES ? "bgzf_inflate" : slot == LSQ_INGEST_STAGES + 1 ? "bam_record_starts" : "bgzf_crc32";
 	return c && c->ing_format >= 0 && slot == 1 ? READ_FORMATS[c->ing_format].stage : lsq_ingest_stage_name(slot);
 }
 int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_repaired) {
@@ -1495,12 +1503,67 @@ int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *ou
 	if ((rc = ensure_lanes(c))) return rc;
 	lsq_text T;
 	BamRecords B;
-	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B))) return rc;
+	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B, 0))) return rc;
 	*n = B.total;
 	if (B.total > cap) return fail(LSQ_E_RANGE, "the inflated stream holds %llu bytes, the buffer %llu", B.total, (unsigned long long)cap);
 	if (B.total) HIP_TRY(hipMemcpy(out, B.d_stream.p, (size_t)B.total, hipMemcpyDeviceToHost));
 	return LSQ_OK;
 } LSQ_API_CATCH
+// developer entry: ... and the CRC32 kernel behind it, its sums returned uncompared
+int lsq_debug_bgzf_crc32(lsq_ctx *c, const void *bytes, uint64_t len, uint32_t *crc, uint64_t cap, uint64_t *n) LSQ_API_TRY {
+	if (!c || (!bytes && len) || (!crc && cap) || !n) return fail(LSQ_E_ARG, "null argument");
+	HIP_TRY(hipSetDevice(c->device));
+	int rc;
+	if ((rc = ensure_lanes(c))) return rc;
+	lsq_text T;
+	BamRecords B;
+	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B, 2))) return rc;
+	*n = B.tab.size();
+	if (B.tab.size() > cap) return fail(LSQ_E_RANGE, "the file holds %llu BGZF blocks, the buffer %llu", (unsigned long long)B.tab.size(), (unsigned long long)cap);
+	if (!B.tab.empty()) HIP_TRY(hipMemcpy(crc, B.d_crc.p, B.tab.size() * 4, hipMemcpyDeviceToHost));
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+// The whole-file check (include/lesseq_hip.h): the chain's own passes, always verifying, then the record walk of
+// lsq_mrf_parse_device's first pass and two sums over what it counted.  No events needed: no record is routed.
+int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r) LSQ_API_TRY {
+	if (!c || !path || !r) return fail(LSQ_E_ARG, "null argument");
+	HIP_TRY(hipSetDevice(c->device));
+	hipStream_t st = c->stream;
+	int rc;
+	if ((rc = ensure_lanes(c))) return rc;
+	lsq_text T;
+	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
+	BamRecords BR;
+	if ((rc = bam_open_verified(c, T, BR, true))) return rc;
+	lsq_bam_report R{};
+	R.file_bytes = T.len; R.blocks = BR.tab.size(); R.inflated_bytes = BR.total;
+	R.header_lines = BR.H.h_lines; R.references = BR.H.ref_names.size();
+	R.records = BR.n_rec; R.blocks_repaired = c->bam_blocks_repaired;
+	const unsigned long long first_line = BR.H.h_lines + 1;
+	if (first_line + BR.n_rec > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
+	if (BR.n_rec) {
+		DevBuf<unsigned> d_line_nb;
+		DevBuf<unsigned long long> d_rd_idx, d_bk_off, d_err;
+		ScanScratch SS;
+		const unsigned long long no_err = MRF_NO_ERR;
+		if ((rc = d_line_nb.alloc(BR.n_rec)) || (rc = d_rd_idx.alloc(BR.n_rec + 1)) || (rc = d_bk_off.alloc(BR.n_rec + 1)) || (rc = SS.reserve(BR.n_rec)) || (rc = d_err.upload(&no_err, 1, st))) return rc;
+		const MrfText X{T.d_text.p, T.len, nullptr, 0u, first_line, BR.n_rec};
+		hipLaunchKernelGGL(lsq_bam_count_kernel, dim3((unsigned)((BR.n_rec + 255) / 256)), dim3(256), 0, st, BR.view(), X, sam_opts(c), d_line_nb.p, d_err.p);
+		HIP_TRY(hipGetLastError());
+		if ((rc = device_scan<1, true>(SS, d_line_nb.p, BR.n_rec, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, BR.n_rec, d_bk_off.p, st))) return rc;
+		unsigned long long bad = 0, n_reads = 0, n_blocks = 0;
+		HIP_TRY(hipMemcpyAsync(&bad, d_err.p, 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + BR.n_rec, 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + BR.n_rec, 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipStreamSynchronize(st));
+		if (bad != no_err) return BR.fail_record(bad, st);
+		R.reads = n_reads; R.read_blocks = n_blocks;
+	}
+	*r = R;
+	return LSQ_OK;
+} LSQ_API_CATCH
+
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {
 	if (!c) return LSQ_E_ARG;
 	if (lines_listed) *lines_listed = c->sam_lines_listed;

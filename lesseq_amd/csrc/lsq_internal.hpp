@@ -300,6 +300,6 @@ int run_test_as(int argc, const char *const *argv, std::string &out);        // 
 int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out);      // lsq_sam.cpp: the sam2mrf and bam2mrf executables
 struct BamError;
 int bam_fail(const BamError &e);                                             // lsq_bam.cpp: a BAM error (lsq_bam.hpp) as the calling thread's status and text
-int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o);      // lsq_bam.cpp
+int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify = false);      // lsq_bam.cpp (verify: CRC32s and end-of-file marker)
 
 } // namespace lsq

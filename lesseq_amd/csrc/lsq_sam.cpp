@@ -58,22 +58,23 @@ namespace lsq {
 // sam2mrf [--skip-flags N] [--min-mapq N] [file]: SAM from standard input (or the file) to the equivalent MRF on standard
 // output.  Exit status 0; 1 for a malformed line ("#<k>:<line>" and the lexical-cast line on standard error) or a file
 // that does not open; nothing on standard output then.  bam2mrf: the same for a BAM file (lsq_bam.cpp); a file that is no
-// BAM file is exit status 1 with its message alone.
+// BAM file is exit status 1 with its message alone; bam2mrf --verify also checks every block's CRC32 and the end-of-file marker.
 int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out) {
 	unsigned skip_flags = SAM_DEFAULT_SKIP_FLAGS, min_mapq = SAM_DEFAULT_MIN_MAPQ;
 	const char *path = nullptr;
-	bool bad = false;
+	bool bad = false, verify = false;
 	for (int i = 1; i < argc && !bad; ++i) {
-		if (strcmp(argv[i], "--skip-flags") == 0 && i + 1 < argc) bad = !cast_u32(argv[++i], skip_flags);
+		if (bam && strcmp(argv[i], "--verify") == 0) verify = true;
+		else if (strcmp(argv[i], "--skip-flags") == 0 && i + 1 < argc) bad = !cast_u32(argv[++i], skip_flags);
 		else if (strcmp(argv[i], "--min-mapq") == 0 && i + 1 < argc) bad = !cast_u32(argv[++i], min_mapq);
 		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
 		else if (!path) path = argv[i];
 		else bad = true;
 	}
-	if (bad) { cli_log(0, bam ? "Usage:\nbam2mrf [--skip-flags N] [--min-mapq N] [bam_path]      (standard input without a path)" : "Usage:\nsam2mrf [--skip-flags N] [--min-mapq N] [sam_path]      (standard input without a path)"); return 1; }
+	if (bad) { cli_log(0, bam ? "Usage:\nbam2mrf [--verify] [--skip-flags N] [--min-mapq N] [bam_path]      (standard input without a path)" : "Usage:\nsam2mrf [--skip-flags N] [--min-mapq N] [sam_path]      (standard input without a path)"); return 1; }
 	std::string bytes;
 	if (read_all(path, bytes)) { cli_log(0, lsq_last_error()); return 1; }
-	const int st = bam ? bam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out) : sam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out);
+	const int st = bam ? bam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out, verify) : sam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out);
 	if (st) { out.clear(); cli_log(0, lsq_last_error()); if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
 	return 0;
 }

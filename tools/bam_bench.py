@@ -2,7 +2,7 @@
 """BAM_SINGLE against SAM_SINGLE through the loader chain on the GPU box: the generator's reads of tools/sam_bench.py's shape written
 as SAM, and that SAM rewritten as BAM with Python's zlib (tests/bam_writer.py's records; at most 16 worker processes).  A developer
 aid, not a test.
-    python tools/bam_bench.py [--reads N] [--events N] [--reps K] [--out FILE]
+    python tools/bam_bench.py [--reads N] [--events N] [--reps K] [--verify] [--out FILE]
 One run, one box, the files in the page cache.  Prints (and writes to --out) one JSON object:
   bam          the BAM as htslib lays it out (every block begins with a record): file bytes, the copy to HBM, per pass of the chain
                the device milliseconds (HIP events on the library's stream, lsq_last_ingest_stages), the from-file wall clock
@@ -12,6 +12,9 @@ One run, one box, the files in the page cache.  Prints (and writes to --out) one
   sam          the SAM text of the same reads through the SAM_SINGLE path (code this change leaves as it was), measured beside it
   host         one thread inflating the file: zlib (what a `samtools view` in front of the run pays), and the library's own decoder
                and parser (Reads.from_bam, n_threads=1)
+  bam_verified (--verify) the htslib-layout BAM once more with the option "bam_verify" on -- the bgzf_crc32 pass beside the inflate of
+               the same run, the from-file wall clock against the unverified one -- and, under host, one thread of zlib.crc32 over
+               the same inflated bytes: what a check in front of the run costs
 """
 import argparse
 import json
@@ -104,6 +107,7 @@ def main():
     ap.add_argument("--reads", type=int, default=10000000)
     ap.add_argument("--events", type=int, default=5000)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--verify", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     d = tempfile.mkdtemp(prefix="lsq_bam_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
@@ -124,26 +128,47 @@ def main():
                 out[key]["paths"] = ctx.bam_paths()
             ctx.count()
             tables[key] = L.format_count(ev, ctx.counts()[0])
+        if a.verify:
+            ctx.set_option("bam_verify", 1)
+            out["bam_verified"] = measure(ctx, bam, "BAM_SINGLE", a.reads, a.reps)
+            ctx.set_option("bam_verify", 0)
+            ctx.count()
+            tables["bam_verified"] = L.format_count(ev, ctx.counts()[0])
         out["count_tables_equal"] = len(set(tables.values())) == 1
         ctx.close()
         with open(bam, "rb") as f:
             data = f.read()
         t0 = time.perf_counter()
-        o, total = 0, 0
+        o, total, payloads = 0, 0, []
         while o < len(data):
             n = struct.unpack_from("<H", data, o + 16)[0] + 1
-            total += len(zlib.decompress(data[o + 18:o + n - 8], -15))
+            payloads.append(zlib.decompress(data[o + 18:o + n - 8], -15))
+            total += len(payloads[-1])
             o += n
         t1 = time.perf_counter()
+        if not a.verify:
+            payloads = []
         r = L.Reads.from_bam(bam, ev, n_threads=1)
         t2 = time.perf_counter()
         out["host"] = {"inflated_bytes": total, "zlib_one_thread_inflate_s": t1 - t0, "library_one_thread_inflate_and_parse_s": t2 - t1, "reads": len(r)}
+        if a.verify:
+            t3 = time.perf_counter()
+            n_sums = len([zlib.crc32(p) for p in payloads])
+            out["host"]["zlib_one_thread_crc32_s"] = time.perf_counter() - t3
+            out["host"]["crc32_blocks"] = n_sums
         wall = lambda k: out[k]["best"]["from_file_wall_s"]      # noqa: E731
         out["summary"] = {"bam_from_file_ms": 1e3 * min(wall("bam"), wall("bam_again")), "sam_from_text_ms": 1e3 * min(wall("sam"), wall("sam_again")),
                           "bam_cut_from_file_ms": 1e3 * wall("bam_cut"), "bam_bytes_over_sam_bytes": out["bam"]["file_bytes"] / out["sam"]["file_bytes"],
                           "bam_stages_ms": {s["stage"]: s["ms"] for s in out["bam"]["best"]["stages"]},
                           "bam_cut_stages_ms": {s["stage"]: s["ms"] for s in out["bam_cut"]["best"]["stages"]},
                           "blocks": out["bam_cut"]["paths"]["blocks"], "blocks_repaired_in_cut_file": out["bam_cut"]["paths"]["blocks_repaired"]}
+        if a.verify:
+            v = out["bam_verified"]["best"]
+            out["summary"]["verify"] = {"bgzf_crc32_ms": next(s["ms"] for s in v["stages"] if s["stage"] == "bgzf_crc32"),
+                                        "bgzf_inflate_ms_same_run": next(s["ms"] for s in v["stages"] if s["stage"] == "bgzf_inflate"),
+                                        "bgzf_crc32_GBps": next(s["GBps"] for s in v["stages"] if s["stage"] == "bgzf_crc32"),
+                                        "from_file_ms_verified": 1e3 * v["from_file_wall_s"], "from_file_ms_unverified": out["summary"]["bam_from_file_ms"],
+                                        "zlib_one_thread_crc32_ms": 1e3 * out["host"]["zlib_one_thread_crc32_s"], "inflated_bytes": total}
         text = json.dumps(out, indent=1)
         print(json.dumps(out["summary"], indent=1))
         if a.out:
