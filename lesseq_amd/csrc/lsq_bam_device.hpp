@@ -1,4 +1,8 @@
-// BAM_SINGLE on the device (included by lsq_ingest.hip ahead of READ_FORMATS; not a public header).  DESIGN.md 4.10.
+// BAM_SINGLE on the device; not a public header.  DESIGN.md 4.10.
+// Needs: lsq_sam_device.hpp (the record filters; through it the dictionary look-ups, lsq_route.hpp, lsq_text.hpp -- StageClock -- and
+// lsq_readjob.hpp), lsq_bam.hpp (block chain, header, the shared decoder and record walk).  Gives: a staged file opened -- inflated,
+// verified on request, its header read and its records found (BamRecords, bam_open_verified) -- the routing kernel and its launch for
+// the loader chain (bam_launch), the count / write kernels of lsq_mrf_parse_device.
 //
 // The file's bytes lie in HBM as lsq_text.hip staged them.  What takes the place of the text and its newline tiles:
 //   block table      host: the BGZF chain (BSIZE to BSIZE) over a mapping of the file -- compressed offset, deflate length, ISIZE,
@@ -24,8 +28,15 @@
 //   lsq_bam_count_kernel / lsq_bam_write_kernel   the same walk for lsq_mrf_parse_device("BAM_SINGLE")
 // Record i of the file is data line i of the chain: first_line = h + 1, no header line.
 #pragma once
-// (lsq_bam.hpp -- block chain, header, the shared decoder and record walk -- is included by lsq_ingest.hip at file scope; BamView,
-// what the record kernels see of a file, is declared there beside TextJob)
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include "lsq_sam_device.hpp"
+#include "lsq_bam.hpp"
+
+namespace {
 
 constexpr unsigned BAM_REF_NO_READ = 0xFFFFFFFFu;      // a reference whose name MRF cannot write: its records make no read
 
@@ -307,7 +318,7 @@ static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char
 	if ((rc = B.d_stream.alloc((size_t)B.total + 16)) || (rc = B.d_tab.upload(B.tab.data(), B.tab.size(), st)) || (rc = d_err.upload(&no_err, 1, st))) return rc;
 	const unsigned nb = (unsigned)B.tab.size();
 	{
-		StageClock k(c, st, LSQ_INGEST_STAGES);
+		StageClock k(c, st, "bgzf_inflate");
 		hipLaunchKernelGGL(lsq_bgzf_inflate_kernel, dim3((nb + 63u) / 64u), dim3(64), 0, st, (const unsigned char *)T.d_text.p, (const lsq::BgzfBlock *)B.d_tab.p, nb, B.d_stream.p, d_err.p);
 		HIP_TRY(hipGetLastError());
 		k.end(T.len + B.total);
@@ -320,7 +331,7 @@ static int bam_inflate_staged(lsq_ctx *c, const lsq_text &T, const unsigned char
 	if ((rc = B.d_crc.alloc(nb))) return rc;
 	{
 		// (the error word still holds "none": the inflate left it alone)
-		StageClock k(c, st, LSQ_INGEST_STAGES + 2);
+		StageClock k(c, st, "bgzf_crc32");
 		const unsigned grid = (unsigned)std::min<unsigned long long>(((unsigned long long)nb + BGZF_CRC_WAVES - 1) / BGZF_CRC_WAVES, (unsigned long long)c->n_cu * 16);
 		hipLaunchKernelGGL(lsq_bgzf_crc_kernel, dim3(grid), dim3(64 * BGZF_CRC_WAVES), 0, st, (const unsigned char *)T.d_text.p, (const lsq::BgzfBlock *)B.d_tab.p, nb, (const unsigned char *)B.d_stream.p,
 		                   B.d_crc.p, verify == 1 ? 1u : 0u, d_err.p);
@@ -358,7 +369,7 @@ struct BamFileMap {
 	}
 };
 
-// ReadFormat::open of BAM_SINGLE: the staged file to an inflated stream with its records' offsets.  (lsq_bam_check runs it on a
+// What BAM_SINGLE's ReadFormat::open runs: the staged file to an inflated stream with its records' offsets.  (lsq_bam_check runs it on a
 // context without events: no chromosome is known then, and every reference is one the events do not cover.)
 static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify) {
 	hipStream_t st = c->stream;
@@ -396,7 +407,7 @@ static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify
 	if ((rc = B.d_ref_cid.upload(ref_cid.data(), ref_cid.size(), st)) || (rc = d_start.alloc(nb)) || (rc = d_next.alloc(nb)) || (rc = d_cnt.alloc(nb)) || (rc = d_base.alloc((size_t)nb + 1)) ||
 	    (rc = d_misc.upload(zero2, 2, st)) || (rc = SS.reserve(nb))) return rc;
 	const BamStarts A{B.d_tab.p, nb, B.d_stream.p, B.total, B.H.end, d_start.p, d_next.p, d_cnt.p};
-	StageClock k(c, st, LSQ_INGEST_STAGES + 1);
+	StageClock k(c, st, "bam_record_starts");
 	unsigned long long misc[2] = {0, 0};
 	hipLaunchKernelGGL(lsq_bam_starts_kernel, dim3(nb / 256u + 1u), dim3(256), 0, st, A);
 	hipLaunchKernelGGL(lsq_bam_verify_kernel, dim3(nb / 256u + 1u), dim3(256), 0, st, A, d_misc.p);
@@ -420,10 +431,11 @@ static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify
 	c->bam_blocks = nb; c->bam_blocks_repaired = misc[1];
 	return LSQ_OK;
 }
-static int bam_open_staged(lsq_ctx *c, lsq_text &T, BamRecords &B) { return bam_open_verified(c, T, B, c->opt_bam_verify); }
 
 static void bam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
 	if (!J.X.n_lines) return;
 	const unsigned grid = (unsigned)std::min<unsigned long long>((J.X.n_lines + 255) / 256, (unsigned long long)J.c->n_cu * 16);
 	hipLaunchKernelGGL(lsq_bam_route_kernel, dim3(grid), dim3(256), 0, s, J.R, J.X, sam_opts(J.c), J.D, RT, O, J.err);
 }
+
+} // namespace

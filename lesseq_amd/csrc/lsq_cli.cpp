@@ -113,7 +113,7 @@ bool named_read_format(const char *fmt) {       // the read formats only `solve`
 }
 
 // the read formats that the device parses from the file's own bytes (lsq_reads_upload_text): a read per line, or per BAM record
-bool line_text_format(const char *fmt) { return strcmp(fmt, "MRF_SINGLE") == 0 || strcmp(fmt, "SAM_SINGLE") == 0 || strcmp(fmt, "BAM_SINGLE") == 0; }
+bool line_text_format(const char *fmt) { return lsq::device_read_format(fmt); }
 
 int precheck_reads_file(const char *fmt, const char *path, bool solve) {
 	FILE *f = fopen(path, "rb");

@@ -1,5 +1,5 @@
 // Device group of the C ABI: context, event tables, count / solve entry points, result fetch (gfx950).
-// The kernels live in lsq_count.hip, lsq_em.hip and lsq_ingest.hip.
+// The kernels live in lsq_count.hip, lsq_em.hip, lsq_ingest.hip and lsq_readfile.hip.
 #include "lsq_device.hpp"
 #include <chrono>
 #include <thread>
@@ -160,7 +160,7 @@ void lsq_ctx_destroy(lsq_ctx *c) {
 	if (c->evt0) (void)hipEventDestroy(c->evt0);
 	if (c->evt1) (void)hipEventDestroy(c->evt1);
 	for (int m = 0; m < LSQ_MAX_METHODS; ++m) { if (c->evf0[m]) (void)hipEventDestroy(c->evf0[m]); if (c->evf1[m]) (void)hipEventDestroy(c->evf1[m]); }
-	for (hipEvent_t e : c->ing_ev) if (e) (void)hipEventDestroy(e);
+	for (IngestPass &p : c->ing_pass) for (hipEvent_t e : p.ev) if (e) (void)hipEventDestroy(e);
 	for (int q = 0; q < 2; ++q) { if (c->pin_buf[q]) (void)hipHostFree(c->pin_buf[q]); if (c->pin_ev[q]) (void)hipEventDestroy(c->pin_ev[q]); }
 	if (c->stream) (void)hipStreamDestroy(c->stream);
 	for (int l = 0; l < 2; ++l) { if (c->stream_em2[l]) (void)hipStreamDestroy(c->stream_em2[l]); if (c->stream_count2[l]) (void)hipStreamDestroy(c->stream_count2[l]); }

@@ -1,8 +1,8 @@
 // Shared by the HIP translation units of the device group (not part of the ABI): device buffers, the
 // per-read-file state, the context, and the entry points one unit offers the others.
 //   lsq_device.hip  context, event tables, result fetch         lsq_count.hip  count kernels
-//   lsq_ingest.hip  loader kernels (read parsers, filter, pools) lsq_em.hip     EM kernel
-//   lsq_text.hip    texts staged in HBM, their newline tiles
+//   lsq_ingest.hip  loader chain (filter, partition, pools)      lsq_em.hip     EM kernel
+//   lsq_text.hip    texts staged in HBM, their newline tiles     lsq_readfile.hip  read files parsed on the device
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -36,7 +36,7 @@ using namespace lsq;
 constexpr unsigned P2_GROUP_PAD = LSQ_P2_PAD;      // ... and a junction group of the two-block pool (eight, with eight two-block reads per look, measured 2 % slower on C3: more padding, longer steps)
 constexpr unsigned P1_GROUP_PAD = LSQ_P1_PAD;      // records a cell's group of the one-block pool is padded to: what a lane of the count kernel takes per look
 constexpr int LSQ_INGEST_STAGES = 7;     // newline count, route, partition count, partition scatter, group classify, group offsets, group place
-constexpr int LSQ_INGEST_SLOTS = LSQ_INGEST_STAGES + 3;      // ... and the passes ahead of a BAM file's route: inflate, record starts, and -- "bam_verify" -- the CRC32s (lsq_bam_device.hpp)
+constexpr int LSQ_INGEST_PASS_MAX = 16;  // ... and room for the passes a read file clocks ahead of its route (a BAM file: inflate, CRC32s, record starts)
 constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
 
 namespace lsq {
@@ -108,6 +108,16 @@ struct WgPlan {
 	VisitRec first;                          // (b == n_buckets: the share holds no packed bucket's slots)
 };
 static_assert(sizeof(WgPlan) == 144, "WgPlan layout");
+
+// one pass of the loader as the stage report knows it: its name, the events around its launches, the bytes it has to move at
+// least, its device time (read once the stream has been waited for)
+struct IngestPass {
+	const char *name = nullptr;
+	hipEvent_t ev[2] = {nullptr, nullptr};
+	unsigned long long bytes = 0;
+	float ms = 0;
+	bool clocked = false;                  // by the latest ingest (a pass it lists and does not run reports zeros)
+};
 
 struct MethodReads {
 	DevBuf<ExcEntry> exc;                  // exception lists: two halves of exc_cap entries, one per counter set
@@ -287,18 +297,15 @@ struct lsq_ctx {
 	// kernels of the latest one handed on (lsq_last_sam_paths)
 	unsigned opt_sam_skip_flags = 0x904u, opt_sam_min_mapq = 0u;
 	bool opt_bam_verify = false;            // "bam_verify": BAM_SINGLE files have their blocks' CRC32s and their end-of-file marker checked (lsq_bam_device.hpp)
-	int ing_format = -1;                    // the read format of the latest ingest (lsq_ingest.hip: READ_FORMATS), -1: parsed blocks from the host
-	bool ing_verified = false;              // ... and whether it ran the CRC32 pass of a BAM file ("bam_verify")
 	unsigned sam_lines_listed = 0, sam_all_slow = 0;
 	unsigned long long bam_blocks = 0, bam_blocks_repaired = 0;      // the latest BAM_SINGLE file (lsq_last_bam_paths)
 	// two pinned 32 MiB host buffers and their "drained" events, made at the first large host-to-device copy (lsq_text.hip: pinned_pipeline)
 	unsigned char *pin_buf[2] = {nullptr, nullptr};
 	hipEvent_t pin_ev[2] = {nullptr, nullptr};
-	// device time and bytes of the stages of the latest ingest (lsq_ingest.hip: lsq_last_ingest_stages)
-	hipEvent_t ing_ev[2 * LSQ_INGEST_SLOTS] = {};
-	float ing_ms[LSQ_INGEST_SLOTS] = {};
-	unsigned long long ing_bytes[LSQ_INGEST_SLOTS] = {};
-	bool ing_seen[LSQ_INGEST_SLOTS] = {};
+	// the passes of the latest ingest in the order in which they were first clocked (lsq_text.hpp: StageClock; lsq_ingest.hip:
+	// lsq_last_ingest_stages): the first ing_n entries, of which the latest ingest listed -- and the report shows -- ing_reported
+	IngestPass ing_pass[LSQ_INGEST_PASS_MAX];
+	int ing_n = 0, ing_reported = 0;
 };
 
 // The text of one file in HBM (lsq_text_stage).  Staging needs no event tables: the executables start it

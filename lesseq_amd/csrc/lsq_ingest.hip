@@ -1,9 +1,9 @@
-// Loader kernels of the device group: MRF text parsed in HBM, the load-time containment filter, block
-// merge and the bucket / group / pool layout (count/count.cpp:279-364), and the entry points around them.
+// The loader chain of the device group: the load-time containment filter, block merge and the bucket / group / pool layout (count/count.cpp:279-364)
+// over the reads a front end delivers (lsq_ingest.hpp: parsed blocks from the host here, a read file's own bytes in lsq_readfile.hip), and the stage report.
 //
 // Round 4 form.  The loader is a chain of streaming passes, each of which reads and writes whole cache lines:
-//   newline count   text -> newlines per 7 680-byte tile                               (lsq_mrf_device.hpp)
-//   route           text (or parsed blocks from the host) -> per read a key (bucket, pool, strand) and its merged blocks:
+//   newline count   text -> newlines per 7 680-byte tile                               (lsq_text.hip)
+//   route           text (a format's parser) or parsed blocks from the host -> per read a key (bucket, pool, strand) and its merged blocks:
 //                   the splitter, the containment filter against the covered regions of the block's own chromosome
 //                   (count/count.cpp:319, interval_list.hpp:396-422), the interval_list merge of the kept blocks (:323,
 //                   interval_list.hpp:462-503), chromosome/strand of the last kept block (:321-322), the bucket of the first
@@ -19,345 +19,10 @@
 // tables from HBM per read, two global atomics) and a second scattered 1-8-byte stores over the whole pool: 19 ms +
 // 10 ms + 6 ms of one-workgroup scans per C3 file, >= 56 GB of HBM traffic for 3.7 GB of text.
 // This replaces the reference's load-time filter and its read index (count/count.cpp:348-364).
-#include <fcntl.h>
-#include <sys/mman.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
+#include "lsq_ingest.hpp"
 #include "lsq_text.hpp"
-#include "lsq_mrf_line.hpp"
-#include "lsq_sam_line.hpp"
-#include "lsq_bam.hpp"
 
 namespace {
-
-constexpr int INGEST_MAX_BLOCKS = 16;                  // merged blocks per read the device ingest handles
-constexpr int LSQ_RETRY = 1;                           // a front end's settle(): route the file again (it has changed its own mode)
-
-// ---- what the routing pass knows and what it leaves behind ------------------------------------------------------------
-struct RouteTables {
-	const RouteChrom *chrom;       // per chromosome id (lsq_device.hpp); a kernel may point this at its own copy in LDS
-	const int2 *cov;               // covered regions: (start, end), ascending per chromosome
-	const int4 *clu;               // clusters (spans of the planned events) cut at the bucket cuts: (start, end -- inclusive --, bucket, bucket's first base)
-	const uint2 *loc;              // locator grid (lsq_ctx::loc): entries k and k + 1 are read as one 16-byte pair
-	unsigned loc_shift;
-	unsigned n_chrom;
-};
-constexpr unsigned ROUTE_CHROM_LDS = 64;      // chromosome records a kernel stages in LDS (more chromosomes: read from global memory)
-
-// A read's key: pool in bits 0-1 (0 one merged block, 1 two, 2 three or more, 3 one or two that do not fit compact
-// records), bucket in bits 2-23, strand id in bits 24-31.  Bucket 0x3FFFFF: not routed -- dropped (all ones), or
-// retained by the filter but a candidate of no planned event (low bits 01, the number of its merged blocks in bits 24-31).
-constexpr unsigned ROUTE_KEY_DROPPED = 0xFFFFFFFFu;
-constexpr unsigned ROUTE_NO_BUCKET = 0x3FFFFFu;
-__host__ __device__ inline unsigned route_key(unsigned bucket, unsigned pool, unsigned strand) { return (strand << 24) | (bucket << 2) | pool; }
-__host__ __device__ inline unsigned route_key_unrouted(unsigned n_blocks) { return (n_blocks << 24) | (ROUTE_NO_BUCKET << 2) | 1u; }
-__host__ __device__ inline bool route_key_is_routed(unsigned k) { return ((k >> 2) & ROUTE_NO_BUCKET) != ROUTE_NO_BUCKET; }
-
-struct RouteOut {
-	unsigned *key;                 // per read
-	int4 *rec;                     // per read: its first two merged blocks (s0, e0, s1, e1)
-	// reads of pools 2 and 3: a list (they are few in short-read files; a file of long reads fills it, and the ingest sizes it again)
-	unsigned long long *nb_tot;    // [0] entries wanted, [1] blocks wanted, [2] error flag (a read beyond the tables' range)
-	unsigned long long nb_cap, nbb_cap;
-	uint4 *nb_ent;                 // read index, bucket, blocks | strand << 8, first block in nb_blk
-	int2 *nb_blk;
-	unsigned *cntn, *cntnb;        // per bucket: such reads, their blocks
-	unsigned compact;              // compact pool records: one- and two-block reads that do not fit them go to pool 3
-};
-
-// The locator entry of base x on a chromosome: where, among the chromosome's covered regions and clusters, the records that
-// start inside x's bin lie.  Kept per lane from one look-up to the next: a read's blocks and its first base mostly share a bin.
-struct LocProbe {
-	int chrom; long long bin;
-	unsigned cov_a, cov_b, clu_a, clu_b;       // lower_bound(starts, x) lies in [a, b]
-};
-__device__ inline void loc_probe(const RouteTables &T, const RouteChrom &R, const int chrom, const int x, LocProbe &P) {
-	const long long d = (long long)x - (long long)R.loc_base;
-	long long k = d >> T.loc_shift;
-	if (R.loc_nb == 0u || d <= 0) k = -1;                       // at or below the first bin's first base: nothing starts left of x
-	else if (k >= (long long)R.loc_nb) k = (long long)R.loc_nb; // beyond the last bin: everything does
-	if (P.chrom == chrom && P.bin == k) return;
-	P.chrom = chrom; P.bin = k;
-	if (k < 0) { P.cov_a = P.cov_b = R.cov0; P.clu_a = P.clu_b = R.clu0; }
-	else if (k >= (long long)R.loc_nb) { P.cov_a = P.cov_b = R.cov1; P.clu_a = P.clu_b = R.clu1; }
-	else {
-		uint4 e;                                                  // (8-byte aligned: two entries in one load)
-		__builtin_memcpy(&e, T.loc + (R.loc_first + (unsigned)k), 16);
-		P.cov_a = e.x; P.clu_a = e.y; P.cov_b = e.z; P.clu_b = e.w;
-	}
-}
-
-// interval_list::contains_interval against the covered regions of the block's chromosome (interval_list.hpp:396-422):
-// lo = lower_bound(starts, start); the interval at lo (when it starts exactly there) or the one before it must reach `end`
-__device__ inline bool route_covered(const RouteTables &T, const RouteChrom &R, const int chrom, const int start, const int end, LocProbe &P) {
-	if (!(start < end)) return true;
-	loc_probe(T, R, chrom, start, P);
-	const unsigned a = P.cov_a, b = P.cov_b;
-	int2 at, before;                        // the records at lo and at lo - 1
-	bool has_at, has_before;
-	if (b - a <= 3u) {
-		// records a - 1 .. a + 3 hold both, wherever in [a, b] lo falls: five loads in flight at once, no dependent probe
-		int2 c[5];
-		unsigned below = 0;
-#pragma unroll
-		for (unsigned q = 0; q < 5; ++q) {
-			const unsigned idx = a + q - 1u;
-			const bool ok = idx + 1u > R.cov0 && idx < R.cov1 && idx <= b;     // (a - 1 may be R.cov0 - 1, or wrap below zero: both fail here)
-			c[q] = ok ? T.cov[idx] : make_int2(0, 0);
-			below += (unsigned)(ok && q >= 1u && idx < b && c[q].x < start);
-		}
-		const unsigned lo = a + below;
-		at = make_int2(0, 0); before = make_int2(0, 0);
-#pragma unroll
-		for (unsigned q = 0; q < 5; ++q) { if (a + q - 1u == lo) at = c[q]; if (a + q == lo) before = c[q]; }
-		has_at = lo < R.cov1; has_before = lo > R.cov0;
-	} else {
-		unsigned lo = a, hi = b;
-		while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (T.cov[mid].x < start) lo = mid + 1; else hi = mid; }
-		has_at = lo < R.cov1; has_before = lo > R.cov0;
-		at = has_at ? T.cov[lo] : make_int2(0, 0);
-		before = has_before ? T.cov[lo - 1u] : make_int2(0, 0);
-	}
-	if (has_at && at.x <= start && end <= at.y) return true;
-	if (has_before && before.x <= start && end <= before.y) return true;
-	return false;
-}
-
-// the cluster record of base p: the last one that starts at or left of p, if p is inside it -- its bucket is p's bucket
-// (what the reference's candidate window comes to for a read's first base: count/count.cpp:429-432,463)
-__device__ inline bool route_cluster(const RouteTables &T, const RouteChrom &R, const int chrom, const int p, LocProbe &P, int4 &rec) {
-	if (p >= 0x7FFFFFFF) return false;
-	loc_probe(T, R, chrom, p + 1, P);
-	const unsigned a = P.clu_a, b = P.clu_b;       // upper_bound(starts, p) = lower_bound(starts, p + 1) lies in [a, b]
-	if (b - a <= 3u) {
-		int4 c[4];                                   // records a - 1 .. a + 2: the one before the upper bound is among them
-		unsigned below = 0;
-#pragma unroll
-		for (unsigned q = 0; q < 4; ++q) {
-			const unsigned idx = a + q - 1u;
-			const bool ok = idx + 1u > R.clu0 && idx < R.clu1 && idx < b;      // (q = 0: a - 1 < b unless it wrapped, which the first test catches)
-			c[q] = ok ? T.clu[idx] : make_int4(0, 0, 0, 0);
-			below += (unsigned)(ok && q >= 1u && c[q].x <= p);
-		}
-		const unsigned ub = a + below;
-		if (ub == R.clu0) return false;
-		rec = make_int4(0, -1, 0, 0);
-#pragma unroll
-		for (unsigned q = 0; q < 4; ++q) if (a + q == ub) rec = c[q];
-		return p <= rec.y;
-	}
-	unsigned lo = a, hi = b;
-	while (lo < hi) { const unsigned mid = (lo + hi) >> 1; if (T.clu[mid].x <= p) lo = mid + 1; else hi = mid; }
-	if (lo == R.clu0) return false;
-	rec = T.clu[lo - 1u];
-	return p <= rec.y;
-}
-
-// the chromosome records into a workgroup's LDS when they are few (every workgroup of the routing kernels starts with this)
-__device__ inline const RouteChrom *route_stage_chroms(const RouteTables &T, RouteChrom *lds) {
-	if (T.n_chrom > ROUTE_CHROM_LDS) return T.chrom;
-	for (unsigned q = threadIdx.x; q < 2u * T.n_chrom; q += blockDim.x) reinterpret_cast<uint4 *>(lds)[q] = reinterpret_cast<const uint4 *>(T.chrom)[q];
-	__syncthreads();
-	return lds;
-}
-
-// interval_list::add_interval on a small sorted array (see lsq::IntervalList::add)
-__device__ inline bool small_add_interval(int *s, int *e, int &n, int start, int end) {
-	if (!(start < end)) return true;
-	int ss = 0, se = 0, es = 0, ee = 0;
-	for (int i = 0; i < n; ++i) { ss += s[i] < start; se += e[i] < start; es += s[i] < end; ee += e[i] < end; }
-	const bool start_inside = (ss - se == 1), end_inside = (es - ee == 1);
-	// starts: erase [ss, es), insert `start` at ss unless start_inside; ends: erase [se, ee), insert `end` at se unless end_inside
-	const int ns = n - (es - ss) + (start_inside ? 0 : 1);
-	if (ns > INGEST_MAX_BLOCKS) return false;
-	int ts[INGEST_MAX_BLOCKS], te[INGEST_MAX_BLOCKS];
-	int k = 0;
-	for (int i = 0; i < ss; ++i) ts[k++] = s[i];
-	if (!start_inside) ts[k++] = start;
-	for (int i = es; i < n; ++i) ts[k++] = s[i];
-	k = 0;
-	for (int i = 0; i < se; ++i) te[k++] = e[i];
-	if (!end_inside) te[k++] = end;
-	for (int i = ee; i < n; ++i) te[k++] = e[i];
-	n = ns;
-	for (int i = 0; i < n; ++i) { s[i] = ts[i]; e[i] = te[i]; }
-	return true;
-}
-
-__device__ inline void push3(int &a0, int &a1, int &a2, int &k, const int v) {
-	a0 = k == 0 ? v : a0; a1 = k == 1 ? v : a1; a2 = k == 2 ? v : a2;
-	++k;
-}
-
-// The kept blocks of one read as they come, merged by interval_list's rule.  Nearly every read keeps one or two merged
-// blocks: those live in registers (the rule written out for a list of at most two); a third block moves the read to arrays.
-// (the arrays are an object of their own: as members they kept the whole accumulator in the private segment -- every field a
-// scratch store and load per block, 10 GB of scratch traffic per C3 file -- where now only a read's third block touches it)
-struct ReadBig { int bs[INGEST_MAX_BLOCKS], be[INGEST_MAX_BLOCKS]; };
-struct ReadAcc {
-	int s0, e0, s1, e1;
-	int n;                          // merged blocks
-	int chrom;
-	unsigned strand;
-	bool any, ok, big;
-	__device__ inline void init() { s0 = e0 = s1 = e1 = 0; n = 0; chrom = -1; strand = 0; any = false; ok = true; big = false; }
-	// a block that passed the containment filter (count/count.cpp:319-323)
-	__device__ inline void add(ReadBig &B, const unsigned c, const unsigned sid, const int start, const int end) {
-		any = true; chrom = (int)c; strand = sid;
-		if (!(start < end)) return;
-		if (big) { ok = small_add_interval(B.bs, B.be, n, start, end) && ok; return; }
-		if (n == 0) { s0 = start; e0 = end; n = 1; return; }
-		const bool h0 = n > 0, h1 = n > 1;
-		const int ss = (int)(h0 && s0 < start) + (int)(h1 && s1 < start), se = (int)(h0 && e0 < start) + (int)(h1 && e1 < start);
-		const int es = (int)(h0 && s0 < end) + (int)(h1 && s1 < end), ee = (int)(h0 && e0 < end) + (int)(h1 && e1 < end);
-		const bool start_inside = (ss - se == 1), end_inside = (es - ee == 1);
-		int a0 = 0, a1 = 0, a2 = 0, ka = 0, b0 = 0, b1 = 0, b2 = 0, kb = 0;
-		if (h0 && 0 < ss) push3(a0, a1, a2, ka, s0);
-		if (h1 && 1 < ss) push3(a0, a1, a2, ka, s1);
-		if (!start_inside) push3(a0, a1, a2, ka, start);
-		if (h0 && 0 >= es) push3(a0, a1, a2, ka, s0);
-		if (h1 && 1 >= es) push3(a0, a1, a2, ka, s1);
-		if (h0 && 0 < se) push3(b0, b1, b2, kb, e0);
-		if (h1 && 1 < se) push3(b0, b1, b2, kb, e1);
-		if (!end_inside) push3(b0, b1, b2, kb, end);
-		if (h0 && 0 >= ee) push3(b0, b1, b2, kb, e0);
-		if (h1 && 1 >= ee) push3(b0, b1, b2, kb, e1);
-		if (ka <= 2) { s0 = a0; s1 = a1; e0 = b0; e1 = b1; n = ka; }
-		else { B.bs[0] = a0; B.bs[1] = a1; B.bs[2] = a2; B.be[0] = b0; B.be[1] = b1; B.be[2] = b2; n = 3; big = true; }
-	}
-	// the read is complete: its key and blocks to their place (index i of the pass)
-	__device__ inline void finish(const ReadBig &B, const RouteTables &T, const RouteChrom *chroms, LocProbe &P, const RouteOut &O, const unsigned i) {
-		unsigned key = ROUTE_KEY_DROPPED;
-		int4 rec = make_int4(0, 0, 0, 0);
-		if (any && n > 0) {
-			long long tot = 0;
-			if (big) {
-				s0 = B.bs[0]; e0 = B.be[0];
-				if (n > 1) { s1 = B.bs[1]; e1 = B.be[1]; }
-				for (int q = 0; q < n; ++q) tot += B.be[q] - B.bs[q];
-			} else tot = (long long)(e0 - s0) + (n > 1 ? (long long)(e1 - s1) : 0ll);
-			if (!ok || tot >= (1 << 18)) atomicMax(&O.nb_tot[2], 1ull);
-			key = route_key_unrouted((unsigned)n);
-			rec = make_int4(s0, e0, n > 1 ? s1 : 0, n > 1 ? e1 : 0);
-			const RouteChrom R = chroms[chrom];
-			// the bucket of the first merged base, if that base lies in the span of some planned event (a cluster): otherwise the
-			// read is a candidate of none of them (count/count.cpp:429-432,463) -- with a shard, the other shards' reads
-			int4 cl;
-			if (route_cluster(T, R, chrom, s0, P, cl)) {
-				const unsigned b = (unsigned)cl.z;
-				const int lo = cl.w;
-				unsigned pool = n == 1 ? 0u : (n == 2 ? 1u : 2u);
-				if (pool < 2u && O.compact) {
-					bool fits = lsq::compact_block_fits((long long)s0 - lo + lsq::COMPACT_BIAS, (long long)e0 - s0);
-					if (n == 2) fits = fits && lsq::compact_block_fits((long long)s1 - e0, (long long)e1 - s1);
-					if (!fits) pool = 3u;
-				}
-				key = route_key(b, pool, strand);
-				if (pool >= 2u) {
-					const unsigned long long idx = atomicAdd(&O.nb_tot[0], 1ull), boff = atomicAdd(&O.nb_tot[1], (unsigned long long)n);
-					atomicAdd(&O.cntn[b], 1u); atomicAdd(&O.cntnb[b], (unsigned)n);
-					if (idx < O.nb_cap && boff + (unsigned)n <= O.nbb_cap) {
-						O.nb_ent[idx] = make_uint4(i, b, (unsigned)n | (strand << 8), (unsigned)boff);
-						if (big) { for (int q = 0; q < n; ++q) O.nb_blk[boff + q] = make_int2(B.bs[q], B.be[q]); }
-						else { O.nb_blk[boff] = make_int2(s0, e0); if (n > 1) O.nb_blk[boff + 1] = make_int2(s1, e1); }
-					}
-				}
-			}
-		}
-		O.key[i] = key;
-		O.rec[i] = rec;
-	}
-};
-
-// ---- device time of the chain's stages (lsq_last_ingest_stages; StageClock, lsq_text.hpp, records them)
-static void stages_reset(lsq_ctx *c, bool keep_text_stage) {
-	for (int s = keep_text_stage ? 1 : 0; s < LSQ_INGEST_SLOTS; ++s) { c->ing_seen[s] = false; c->ing_ms[s] = 0; c->ing_bytes[s] = 0; }
-}
-static void stages_collect(lsq_ctx *c) {          // (the stream has been waited for)
-	for (int s = 0; s < LSQ_INGEST_SLOTS; ++s) {
-		if (!c->ing_seen[s] || !c->ing_ev[2 * s] || !c->ing_ev[2 * s + 1]) continue;
-		float ms = 0;
-		if (hipEventElapsedTime(&ms, c->ing_ev[2 * s], c->ing_ev[2 * s + 1]) == hipSuccess) c->ing_ms[s] = ms;
-	}
-	(void)hipGetLastError();
-}
-
-// the reads of one file as the routing pass meets them
-struct Front {
-	unsigned long long n = 0;                 // reads of the pass (text: data lines, skipped ones among them)
-	const unsigned *line_no = nullptr;        // per read (device), or null: first_line + index
-	unsigned long long first_line = 0;
-	unsigned long long in_bytes = 0;          // what the routing pass reads
-	std::function<int(const RouteTables &, const RouteOut &, hipStream_t)> launch;   // runs the routing kernel
-	std::function<int(hipStream_t)> settle;   // once the stream has been waited for: the front end's own verdict (the first failing line)
-};
-
-// ---- what the chain hands a read format's device parser (lsq_mrf_device.hpp, lsq_sam_device.hpp): the staged text, the dictionaries,
-// the lists of work a tile kernel hands on, the parsed arrays of lsq_mrf_parse_device
-struct MrfText {
-	const unsigned char *text;
-	unsigned long long len;
-	const unsigned long long *tile_base;
-	unsigned has_header;
-	unsigned long long first_line;            // the number of data line 0 in the whole file (read name "read-<L>")
-	unsigned long long n_lines;
-};
-
-struct MrfDict {
-	const unsigned *chrom_hash;             // open addressing, 0 = empty; 32-bit FNV-1a of the name
-	const unsigned *chrom_id;
-	const unsigned *name_off;               // per chromosome id, into names
-	const char *names;
-	unsigned mask, n_chrom, names_bytes;
-	unsigned long long *strand_tab;         // 256 slots
-};
-
-// A line that began more than MRF_LB bytes ahead of its tile: its data line index, first byte and length.  At most one per tile.
-struct MrfLongLine { unsigned long long i, start, n; };
-
-// lists of work the fast kernel hands on: counts[0] tiles, counts[1] lines, counts[2] set when the line list ran over
-struct MrfHandOff {
-	unsigned *counts;
-	unsigned *tiles; unsigned tile_cap;
-	MrfLongLine *lines; unsigned line_cap;
-};
-
-struct MrfOut {
-	unsigned long long *blk_off;
-	unsigned *line_no;
-	int *blk_start, *blk_end;
-	unsigned short *blk_chrom;
-	unsigned char *blk_strand;
-};
-
-// what the record kernels of a BAM file see (lsq_bam_device.hpp): the inflated stream, the records' offsets, the reference table
-struct BamView {
-	const unsigned char *s;
-	unsigned long long len;
-	const unsigned long long *rec_off;
-	const unsigned *ref_cid;                 // per refID: chromosome id, MRF_NOCHROM, or "its records make no read"
-	long long n_ref;
-};
-
-// What ingest_text hands a read format's front end, and parse_staged_text the format's count / write launches: the
-// text, the dictionaries and the error words, the hand-off lists.
-struct TextJob {
-	lsq_ctx *c;
-	MrfText X;                              // (a BAM file: no text; n_lines records, first_line the number of record 0)
-	BamView R;
-	MrfDict D;
-	unsigned long long *err;
-	MrfHandOff H;
-	unsigned n_tiles;
-	bool all_slow;                          // every tile through the format's byte-walking kernel: the front end's choice, or the line list ran over
-	unsigned counts[4];                     // H.counts as the routing pass left them (the front end's record reads them)
-	DevBuf<unsigned long long> tab64;       // tables of the format's own, made by its prepare (MRF: the fast kernel's dictionary)
-	DevBuf<unsigned short> tab16;
-};
-
-#include "lsq_mrf_device.hpp"
-
 
 // ---- routing of parsed blocks that came from the host (lsq_reads_upload: file order) -------------------------------------
 struct IngestRaw {
@@ -778,14 +443,29 @@ __global__ void __launch_bounds__(256) lsq_ingest_pad_kernel(const BucketDesc *b
 }
 
 // ---- the chain on the host ---------------------------------------------------------------------------------------------
-static RouteTables route_tables(lsq_ctx *c) {
+static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
+	"newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"};
+
+// the stage report of the ingest that has just run: the device time between every clocked pass's events (the stream has been waited for)
+void stages_collect(lsq_ctx *c) {
+	for (int k = 0; k < c->ing_n; ++k) {
+		IngestPass &p = c->ing_pass[k];
+		float ms = 0;
+		if (p.clocked && p.ev[0] && p.ev[1] && hipEventElapsedTime(&ms, p.ev[0], p.ev[1]) == hipSuccess) p.ms = ms;
+	}
+	(void)hipGetLastError();
+}
+
+} // namespace
+
+RouteTables lsq::route_tables(lsq_ctx *c) {
 	RouteTables T{};
 	T.chrom = c->route_chrom.p; T.cov = c->cov.p; T.clu = c->clu.p; T.loc = c->loc.p; T.loc_shift = c->loc_shift; T.n_chrom = c->n_chrom_tables;
 	return T;
 }
 
 // Runs the chain over the reads a front end delivers (MRF text in HBM, or parsed blocks from the host).
-static int ingest_device(lsq_ctx *c, int method, Front &F) {
+int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	HostStopwatch SW;
 	const lsq_events &E = *c->E;
 	MethodReads &mr = c->reads[method];
@@ -841,6 +521,11 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	if (place_lds > 48 * 1024) HIP_TRY(hipFuncSetAttribute((const void *)lsq_group_place_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)place_lds));
 	const unsigned part_grid = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(n / 131072ull, 2ull * (unsigned)c->n_cu));
 	SW.mark("ingest: allocations");
+	// the stage report lists the chain's passes now, run or not, behind those the front end has clocked (none: the newline count, with zeros)
+	if (!c->ing_n) (void)stage_entry(c, INGEST_STAGE_NAMES[0]);
+	(void)stage_entry(c, F.stage);
+	for (int s = 2; s < LSQ_INGEST_STAGES; ++s) (void)stage_entry(c, INGEST_STAGE_NAMES[s]);
+	c->ing_reported = c->ing_n;
 
 	unsigned compact = c->opt_compact_pools ? 1u : 0u;
 	unsigned long long nb_cap = std::max<unsigned long long>(4096, n / 32), nbb_cap = 4 * nb_cap;
@@ -855,12 +540,12 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 		O.key = d_key.p; O.rec = d_rec.p; O.nb_tot = d_tot.p + 8; O.nb_cap = nb_cap; O.nbb_cap = nbb_cap; O.nb_ent = d_nb_ent.p; O.nb_blk = d_nb_blk.p;
 		O.cntn = cntn; O.cntnb = cntnb; O.compact = compact;
 		if (n) {
-			StageClock k(c, st, 1);
+			StageClock k(c, st, F.stage);
 			if ((rc = F.launch(T, O, st))) return rc;
 			k.end(F.in_bytes + 20ull * n);
 		}
 		{
-			StageClock k(c, st, 2);
+			StageClock k(c, st, "partition_count");
 			if (part_in_lds) hipLaunchKernelGGL(lsq_part_hist_kernel<true>, dim3(part_grid), dim3(PART_WG), part_lds, st, (const unsigned *)d_key.p, n, B, part_cnt, d_tot.p);
 			else hipLaunchKernelGGL(lsq_part_hist_kernel<false>, dim3(part_grid), dim3(PART_WG), 0, st, (const unsigned *)d_key.p, n, B, part_cnt, d_tot.p);
 			HIP_TRY(hipGetLastError());
@@ -900,7 +585,7 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	if ((rc = d_part1.alloc(n1p)) || (rc = d_part2.alloc(2 * n2p)) || (rc = d_fine1.alloc(n1p)) || (rc = d_fine2.alloc(n2p)) || (rc = d_pieces.alloc(n_pieces))) return rc;
 	SW.mark("ingest: partition buffers");
 	{
-		StageClock k(c, st, 3);
+		StageClock k(c, st, "partition_scatter");
 		PartArgs A{};
 		A.key = d_key.p; A.rec = d_rec.p; A.n = n; A.B = B; A.off1 = d_part_off1.p; A.off2 = d_part_off2.p; A.cursor = part_cur;
 		A.part1 = d_part1.p; A.part2 = d_part2.p; A.line_no = F.line_no; A.first_line = F.first_line;
@@ -916,7 +601,7 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	GA.pieces = d_pieces.p; GA.off1 = d_part_off1.p; GA.off2 = d_part_off2.p; GA.part1 = d_part1.p; GA.part2 = d_part2.p;
 	GA.fine1 = d_fine1.p; GA.fine2 = d_fine2.p; GA.cnt1 = cnt1; GA.cnt2 = cnt2; GA.park1 = park1; GA.park2 = park2;
 	if (n_pieces) {
-		StageClock k(c, st, 4);
+		StageClock k(c, st, "group_classify");
 		GroupTables GT{};
 		GT.buckets = c->buckets.p; GT.images = c->images.p; GT.cell_base = c->cell_base.p; GT.jg_keys = c->jg_keys.p; GT.jg_base = c->jg_base.p; GT.jgroup_base = c->jgroup_base.p;
 		GT.B = B; GT.lds_img = (unsigned)img_max; GT.lds_keys = (unsigned)keys_lds;
@@ -926,7 +611,7 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	}
 	unsigned long long psum[2] = {0, 0};
 	{
-		StageClock k(c, st, 5);
+		StageClock k(c, st, "group_offsets");
 		if ((rc = device_scan<P1_GROUP_PAD>(SS, cnt1, FC, d_off1.p, st)) || (rc = device_scan<P2_GROUP_PAD>(SS, cnt2, FJ, d_off2.p, st))) return rc;      // groups padded to eight records, and to four
 		hipLaunchKernelGGL(lsq_ingest_offsets_kernel, dim3(B / 256 + 1), dim3(256), 0, st, c->cell_base.p, c->jgroup_base.p, B, d_off1.p, d_off2.p, mr.pn_off.p,
 		                   mr.p1_off.p, mr.p2_off.p, mr.slot_off.p);
@@ -948,7 +633,7 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	if ((rc = mr.pn_se.alloc(2 * nnb)) || (rc = mr.pn_blk_off.alloc(nn)) || (rc = mr.pn_nblk.alloc(nn)) || (rc = mr.pn_strand.alloc(nn)) ||
 	    (rc = mr.pn_line.alloc(nn)) || (rc = mr.pn_bucket.alloc(nn))) return rc;
 	{
-		StageClock k(c, st, 6);
+		StageClock k(c, st, "group_place");
 		if (n_pieces) {
 			// the pools themselves: their groups need no order inside
 			PlaceArgs P{};
@@ -1062,8 +747,10 @@ static int ingest_device(lsq_ctx *c, int method, Front &F) {
 	return LSQ_OK;
 }
 
+namespace {
+
 // the front end of parsed blocks from the host (lsq_reads_upload)
-static void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_blocks, Front &F) {
+void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_blocks, Front &F) {
 	F.n = Rw.n_reads; F.line_no = Rw.line_no; F.first_line = 0;
 	F.in_bytes = 12ull * Rw.n_reads + 11ull * n_blocks;
 	F.launch = [c, Rw](const RouteTables &T, const RouteOut &O, hipStream_t st) -> int {
@@ -1072,267 +759,6 @@ static void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_b
 		HIP_TRY(hipGetLastError());
 		return LSQ_OK;
 	};
-	F.settle = nullptr;
-}
-
-// The dictionaries of a parse: the events' chromosome names behind a hash table, the strand table seeded with the strands
-// already known.  The events' strand dictionary grows by the strings the file introduces (as it does under lsq_mrf_parse).
-struct MrfDictDev {
-	DevBuf<unsigned> d_hash, d_id, d_off;
-	DevBuf<unsigned long long> d_strand, d_err;
-	DevBuf<char> d_names;
-	size_t n_seed = 0;
-	MrfDict D{};
-	int build(lsq_ctx *c, hipStream_t st) {
-		lsq_events &E = *c->E;
-		int rc;
-		const size_t nc = E.covered.size();
-		size_t tab = 2;
-		while (tab < 4 * nc) tab <<= 1;
-		std::vector<unsigned> h_hash(tab, 0), h_id(tab, 0), h_off(nc + 1, 0);
-		std::string h_names;
-		for (size_t id = 0; id < nc; ++id) {
-			const std::string &nm = E.chroms.names[id];
-			const unsigned h = mrf_fnv32(nm.data(), nm.size());
-			size_t i = (size_t)(h & (unsigned)(tab - 1));
-			while (h_hash[i] != 0) i = (i + 1) & (tab - 1);
-			h_hash[i] = h; h_id[i] = (unsigned)id;
-			h_names += nm;
-			h_off[id + 1] = (unsigned)h_names.size();
-		}
-		if (E.strands.names.size() > 256) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
-		n_seed = E.strands.names.size();
-		std::vector<unsigned long long> h_strand(256, STRAND_EMPTY);
-		for (size_t i = 0; i < n_seed; ++i) {
-			const std::string &s = E.strands.names[i];
-			h_strand[i] = s.size() <= 7 ? mrf_strand_key(s.data(), s.size()) : STRAND_UNMATCHABLE;
-		}
-		const unsigned long long err[4] = {MRF_NO_ERR, 0, 0, 0};
-		if ((rc = d_hash.upload(h_hash.data(), tab, st)) || (rc = d_id.upload(h_id.data(), tab, st)) || (rc = d_off.upload(h_off.data(), nc + 1, st)) ||
-		    (rc = d_names.upload(h_names.data(), h_names.size(), st)) || (rc = d_strand.upload(h_strand.data(), 256, st)) || (rc = d_err.upload(err, 4, st))) return rc;
-		HIP_TRY(hipStreamSynchronize(st));            // the host vectors go out of scope
-		D.chrom_hash = d_hash.p; D.chrom_id = d_id.p; D.name_off = d_off.p; D.names = d_names.p; D.mask = (unsigned)(tab - 1);
-		D.n_chrom = (unsigned)nc; D.names_bytes = (unsigned)h_names.size(); D.strand_tab = d_strand.p;
-		return LSQ_OK;
-	}
-	int reset_errors(hipStream_t st) {
-		static const unsigned long long err0[4] = {MRF_NO_ERR, 0, 0, 0};
-		HIP_TRY(hipMemcpyAsync(d_err.p, err0, sizeof(err0), hipMemcpyHostToDevice, st));
-		return LSQ_OK;
-	}
-	// after the parse kernels have run and the stream has been waited for: the first failing line, strand strings out of range, new strands
-	// (bad_record: a format of binary records names its failing record itself)
-	int settle(lsq_ctx *c, const lsq_text &T, unsigned has_header, unsigned long long first_line, hipStream_t st, const std::function<int(unsigned long long)> &bad_record = nullptr) {
-		lsq_events &E = *c->E;
-		unsigned long long err[4];
-		std::vector<unsigned long long> h_strand(256);
-		HIP_TRY(hipMemcpyAsync(err, d_err.p, sizeof(err), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(h_strand.data(), d_strand.p, 256 * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (err[0] != MRF_NO_ERR && bad_record) return bad_record(err[0]);
-		if (err[0] != MRF_NO_ERR) {
-			// the text of the failing line, from the file: between the newline that ends the line before it and its own
-			const unsigned long long want = err[0] - first_line + has_header;      // ordinal of the newline that ends the failing line
-			std::string text;
-			const int fd = open(T.path.c_str(), O_RDONLY);
-			if (fd >= 0) {
-				// walk the file's range for the want-th newline (an error path: speed does not matter, bounded memory does)
-				std::vector<char> buf(1 << 20);
-				unsigned long long seen = 0, pos = 0;
-				bool in_line = want == 0, done = false;
-				while (!done && pos < T.len) {
-					const size_t ask = (size_t)std::min<unsigned long long>(buf.size(), T.len - pos);
-					const ssize_t got = pread(fd, buf.data(), ask, (off_t)(T.offset + pos));
-					if (got <= 0) break;
-					for (ssize_t q = 0; q < got && !done; ++q) {
-						if (buf[(size_t)q] == '\n') {
-							if (in_line) done = true;
-							else if (++seen == want) in_line = true;
-						} else if (in_line) text.push_back(buf[(size_t)q]);
-					}
-					pos += (unsigned long long)got;
-				}
-				close(fd);
-			}
-			return fail(LSQ_E_PARSE, "#%llu:%s", err[0], text.c_str());
-		}
-		if (err[1]) return fail(LSQ_E_UNSUPPORTED, "a strand string longer than 7 bytes: outside the device parser's range (lsq_mrf_parse handles it)");
-		if (err[2]) return fail(LSQ_E_RANGE, "more than 256 distinct strand strings");
-		for (size_t i = n_seed; i < 256 && h_strand[i] != STRAND_EMPTY; ++i) {
-			const unsigned long long k = h_strand[i];
-			std::string s;
-			for (unsigned j = 0; j < (unsigned)(k & 0xFF); ++j) s.push_back((char)(k >> (56 - 8 * j)));
-			const int id = E.strands.intern(s);
-			if (id != (int)i) return fail(LSQ_E_STATE, "strand dictionary changed while a reads file was being parsed");
-		}
-		n_seed = E.strands.names.size();
-		return LSQ_OK;
-	}
-};
-
-struct DevParsed {
-	uint64_t n_reads = 0, n_blocks = 0;
-	DevBuf<unsigned long long> blk_off;
-	DevBuf<unsigned> line_no;
-	DevBuf<int> bs, be;
-	DevBuf<unsigned short> bc;
-	DevBuf<unsigned char> bst;
-};
-
-#include "lsq_bam_device.hpp"
-
-// ---- the read formats: the one place that names them.  Per format: whether a whole file's first line is a header (MRF; every
-// line of a SAM file counts: "read-<k>", k from 1), the switch that shortens its line list (tests: the run-over path on a small
-// file), the routing stage's name, its front end for the chain (prepare once; launch the routing kernels, once more with
-// J.all_slow set if the line list ran over; record what they handed on), and its count / write launches for parse_staged_text
-struct ReadFormat {
-	const char *name;
-	unsigned has_header;
-	const char *line_list_env, *stage;
-	int (*open)(lsq_ctx *, lsq_text &, BamRecords &);       // a file of binary records: inflates the staged bytes and finds the records (null: text, its newlines counted)
-	int (*prepare)(TextJob &);                               // (prepare and record may be null)
-	void (*launch)(const TextJob &, const RouteTables &, const RouteOut &, hipStream_t);
-	void (*record)(const TextJob &);
-	void (*count)(const TextJob &, hipStream_t, unsigned *);
-	void (*write)(const TextJob &, hipStream_t, const unsigned *, const unsigned long long *, const unsigned long long *, const MrfOut &);
-};
-static const ReadFormat READ_FORMATS[] = {
-	{"MRF_SINGLE", 1u, "LSQ_MRF_LINE_LIST", "route", nullptr, mrf_prepare, mrf_launch, mrf_record,
-	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_mrf_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, J.err); },
-	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
-		 hipLaunchKernelGGL(lsq_mrf_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, nb, rd, bk, J.D, O, J.err); }},
-	{"SAM_SINGLE", 0u, "LSQ_SAM_LINE_LIST", "sam_route", nullptr, sam_prepare, sam_launch, sam_record,
-	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, J.err); },
-	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
-		 hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
-	{"BAM_SINGLE", 0u, nullptr, "bam_route", bam_open_staged, nullptr, bam_launch, nullptr,
-	 [](const TextJob &J, hipStream_t st, unsigned *nb) {
-		 hipLaunchKernelGGL(lsq_bam_count_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, J.err); },
-	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
-		 hipLaunchKernelGGL(lsq_bam_write_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
-};
-// the format a caller names (looked up once its file has been opened: the order in which the reference meets a bad file or literal)
-static int read_format_named(const char *name, const ReadFormat *&fmt) {
-	if (!name) return fail(LSQ_E_ARG, "null argument");
-	for (const ReadFormat &f : READ_FORMATS) if (strcmp(name, f.name) == 0) { fmt = &f; return LSQ_OK; }
-	return fail(LSQ_E_FORMAT, "Unknown file format error: %s", name);
-}
-
-// Parses staged text on the device into the arrays of lsq_mrf_parse (file order): lsq_mrf_parse_device.
-static int parse_staged_text(lsq_ctx *c, const ReadFormat *fmt, lsq_text &T, unsigned long long first_line, DevParsed &out, float *h2d_ms, float *parse_ms) {
-	const unsigned has_header = fmt->has_header;
-	BamRecords BR;                                         // (a file of records: what takes the place of the text's newline tiles)
-	hipStream_t st = c->stream;
-	int rc;
-	if ((rc = ensure_lanes(c))) return rc;                 // (c->ev1 / c->ev2 are the lanes thread's)
-	const unsigned long long zero_off = 0;
-	out.n_reads = out.n_blocks = 0;
-	auto empty_result = [&]() -> int {
-		int r2;
-		if ((r2 = out.blk_off.upload(&zero_off, 1, st)) || (r2 = out.line_no.alloc(0)) || (r2 = out.bs.alloc(0)) || (r2 = out.be.alloc(0)) ||
-		    (r2 = out.bc.alloc(0)) || (r2 = out.bst.alloc(0))) return r2;
-		HIP_TRY(hipStreamSynchronize(st));
-		return LSQ_OK;
-	};
-	if (h2d_ms) *h2d_ms = T.h2d_ms;
-	if (parse_ms) *parse_ms = 0;
-	if (T.len == 0 && !fmt->open) return empty_result();
-	HIP_TRY(hipEventRecord(c->ev1, st));
-	if (fmt->open) { if ((rc = fmt->open(c, T, BR))) return rc; first_line = BR.H.h_lines + 1; }
-	else if ((rc = scan_newlines(c, T))) return rc;
-	const unsigned long long n_nl = fmt->open ? BR.n_rec : T.n_nl;
-	if (n_nl < 1 + has_header) return empty_result();   // header only (or no terminated line at all)
-	const unsigned long long n_lines = n_nl - has_header;
-	const std::function<int(unsigned long long)> bad_record = fmt->open ? std::function<int(unsigned long long)>([&](unsigned long long k) { return BR.fail_record(k, st); }) : nullptr;
-	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
-	DevBuf<unsigned> d_line_nb;
-	DevBuf<unsigned long long> d_rd_idx, d_bk_off;
-	ScanScratch SS;
-	MrfDictDev DD;
-	if ((rc = d_line_nb.alloc(n_lines)) || (rc = d_rd_idx.alloc(n_lines + 1)) || (rc = d_bk_off.alloc(n_lines + 1)) || (rc = SS.reserve(n_lines)) || (rc = DD.build(c, st))) return rc;
-	TextJob J{};
-	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
-	J.R = BR.view();
-	J.n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
-	fmt->count(J, st, d_line_nb.p);
-	HIP_TRY(hipGetLastError());
-	if ((rc = device_scan<1, true>(SS, d_line_nb.p, n_lines, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, n_lines, d_bk_off.p, st))) return rc;
-	unsigned long long n_reads = 0, n_blocks = 0;
-	HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + n_lines, 8, hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + n_lines, 8, hipMemcpyDeviceToHost, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st, bad_record))) return rc;          // (waits for the stream) the first failing line ends the run here
-	if ((rc = out.blk_off.alloc(n_reads + 1)) || (rc = out.line_no.alloc(n_reads)) || (rc = out.bs.alloc(n_blocks)) || (rc = out.be.alloc(n_blocks)) ||
-	    (rc = out.bc.alloc(n_blocks)) || (rc = out.bst.alloc(n_blocks))) return rc;
-	const MrfOut O{out.blk_off.p, out.line_no.p, out.bs.p, out.be.p, out.bc.p, out.bst.p};
-	fmt->write(J, st, d_line_nb.p, d_rd_idx.p, d_bk_off.p, O);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c->ev2, st));
-	if ((rc = DD.settle(c, T, has_header, first_line, st, bad_record))) return rc;
-	if (parse_ms) (void)hipEventElapsedTime(parse_ms, c->ev1, c->ev2);
-	out.n_reads = n_reads; out.n_blocks = n_blocks;
-	return LSQ_OK;
-}
-
-// A read file's text in HBM through the chain: newline counts, then the format's parse as the chain's routing pass
-static int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &T, unsigned has_header, unsigned long long first_line) {
-	hipStream_t st = c->stream;
-	int rc;
-	if ((rc = ensure_lanes(c))) return rc;
-	c->ing_format = (int)(fmt - READ_FORMATS);
-	c->ing_verified = fmt->open && c->opt_bam_verify;
-	c->mrf_h2d_ms = T.h2d_ms; c->mrf_parse_ms = 0;
-	stages_reset(c, T.scanned && !fmt->open);
-	BamRecords BR;                                         // (a file of records: what takes the place of the text's newline tiles)
-	if (fmt->open) {
-		if (has_header || first_line != 1ull) return fail(LSQ_E_ARG, "a %s file is taken whole, not in byte ranges", fmt->name);
-		if ((rc = fmt->open(c, T, BR))) return rc;
-		first_line = BR.H.h_lines + 1;
-	} else if (T.len && (rc = scan_newlines(c, T))) return rc;
-	const unsigned long long n_nl = fmt->open ? BR.n_rec : T.len ? T.n_nl : 0;
-	const unsigned long long n_lines = n_nl >= 1 + has_header ? n_nl - has_header : 0;       // (header only, or no terminated line at all: no reads)
-	if (first_line + n_lines > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
-	MrfDictDev DD;
-	if ((rc = DD.build(c, st))) return rc;
-	Front F;
-	F.n = n_lines; F.line_no = nullptr; F.first_line = first_line; F.in_bytes = fmt->open ? BR.total : T.len;
-	const unsigned n_tiles = (unsigned)((T.len + TEXT_TILE - 1) / TEXT_TILE);
-	// what a format's tile kernel hands on: tiles it does not take (MRF: more delimiters than the fast kernel's tables hold), lines
-	// it does not settle (another shape than a read's; at most one a tile begins ahead of its window; the rest is whatever the
-	// file holds -- when the list runs over, the whole file goes through the format's byte-walking kernel)
-	unsigned long long list_cap = 1ull << 22;
-	if (!fmt->line_list_env) list_cap = 0;                // (records, not lines: nothing is handed on)
-	else if (const char *e = getenv(fmt->line_list_env)) { const long long v = atoll(e); if (v >= 0) list_cap = (unsigned long long)v; }
-	const unsigned line_cap = (unsigned)std::min<unsigned long long>(n_lines, list_cap) + n_tiles + 1u;
-	DevBuf<MrfLongLine> d_lines;
-	DevBuf<unsigned> d_tiles, d_counts;
-	if ((rc = d_lines.alloc(line_cap)) || (rc = d_tiles.alloc(n_tiles)) || (rc = d_counts.alloc(4))) return rc;
-	HIP_TRY(hipMemsetAsync(d_counts.p, 0, 16, st));          // (a file without lines launches nothing; the verdict below still reads these)
-	TextJob J{};
-	J.c = c; J.X = MrfText{T.d_text.p, T.len, T.d_tile_base.p, has_header, first_line, n_lines}; J.D = DD.D; J.err = DD.d_err.p;
-	J.H = MrfHandOff{d_counts.p, d_tiles.p, n_tiles, d_lines.p, line_cap}; J.n_tiles = n_tiles;
-	J.R = BR.view();
-	if (fmt->prepare && (rc = fmt->prepare(J))) return rc;
-	F.launch = [&](const RouteTables &RT, const RouteOut &O, hipStream_t s) -> int {
-		const int r2 = DD.reset_errors(s);
-		if (r2) return r2;
-		HIP_TRY(hipMemsetAsync(d_counts.p, 0, 16, s));
-		fmt->launch(J, RT, O, s);
-		HIP_TRY(hipGetLastError());
-		return LSQ_OK;
-	};
-	F.settle = [&](hipStream_t s) -> int {
-		// the line list ran over (a file of lines of another shape than a read's): once more, every tile through the byte-walking kernel
-		HIP_TRY(hipMemcpy(J.counts, d_counts.p, 16, hipMemcpyDeviceToHost));
-		if (J.counts[2] && !J.all_slow) { J.all_slow = true; return LSQ_RETRY; }
-		if (J.counts[2]) return fail(LSQ_E_INTERNAL, "the device parser's line list ran over");
-		if (fmt->record) fmt->record(J);
-		return DD.settle(c, T, has_header, first_line, s, fmt->open ? std::function<int(unsigned long long)>([&](unsigned long long k) { return BR.fail_record(k, s); }) : nullptr);
-	};
-	c->reads[method].named = false;
-	if ((rc = ingest_device(c, method, F))) return rc;
-	// (device time of the parse = the newline count and the routing pass; the rest of the chain is the ingest)
-	c->mrf_parse_ms = c->ing_ms[0] + c->ing_ms[1] + c->ing_ms[LSQ_INGEST_STAGES] + c->ing_ms[LSQ_INGEST_STAGES + 1] + c->ing_ms[LSQ_INGEST_STAGES + 2];
-	return LSQ_OK;
 }
 
 } // namespace
@@ -1378,7 +804,6 @@ int lsq_reads_upload(lsq_ctx *c, int method, const lsq_reads *R) LSQ_API_TRY {
 	SW.mark("upload: allocations, copies queued");
 	if (SW.on) { HIP_TRY(hipStreamSynchronize(st)); SW.mark("upload: copies done"); }
 	stages_reset(c, false);
-	c->ing_format = -1;
 	Front F;
 	front_of_raw(c, Rw, nblk, F);
 	if ((rc = ingest_device(c, method, F))) return rc;
@@ -1392,190 +817,19 @@ int lsq_reads_upload(lsq_ctx *c, int method, const lsq_reads *R) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
-int lsq_reads_upload_mrf(lsq_ctx *c, int method, const char *read_format, const char *path) LSQ_API_TRY {
-	if (!c) return fail(LSQ_E_ARG, "null argument");
-	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	if (method < 0 || method >= c->E->n_methods) return fail(LSQ_E_ARG, "method %d out of range", method);
-	HIP_TRY(hipSetDevice(c->device));
-	HostStopwatch SW;
-	if (!read_format || !path) return fail(LSQ_E_ARG, "null argument");
-	const ReadFormat *fmt;
-	lsq_text T;
-	int rc;
-	if ((rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
-	rc = ingest_text(c, method, fmt, T, fmt->has_header, 1ull);
-	SW.mark("upload_mrf: all");
-	return rc;
-} LSQ_API_CATCH
-
-int lsq_reads_upload_text(lsq_ctx *c, int method, const char *read_format, lsq_text *t) LSQ_API_TRY {
-	const ReadFormat *fmt = nullptr;          // (a whole file of its format: the first line as the format has it; a bad literal is reported below)
-	(void)read_format_named(read_format, fmt);
-	return lsq_reads_upload_text_at(c, method, read_format, t, fmt ? (int)fmt->has_header : 1, 1);
-} LSQ_API_CATCH
-
-int lsq_reads_upload_text_at(lsq_ctx *c, int method, const char *read_format, lsq_text *t, int has_header, uint64_t first_line) LSQ_API_TRY {
-	if (!c || !t) return fail(LSQ_E_ARG, "null argument");
-	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	if (method < 0 || method >= c->E->n_methods) return fail(LSQ_E_ARG, "method %d out of range", method);
-	HIP_TRY(hipSetDevice(c->device));
-	const ReadFormat *fmt;
-	const int rc = read_format_named(read_format, fmt);
-	return rc ? rc : ingest_text(c, method, fmt, *t, has_header ? 1u : 0u, first_line);
-} LSQ_API_CATCH
-
-int lsq_mrf_parse_device(lsq_ctx *c, const char *read_format, const char *path, lsq_reads **out) LSQ_API_TRY {
-	if (!c || !out) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
-	if (!read_format || !path) return fail(LSQ_E_ARG, "null argument");
-	const ReadFormat *fmt;
-	lsq_text T;
-	int rc;
-	if ((rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
-	DevParsed P;
-	if ((rc = parse_staged_text(c, fmt, T, 1ull, P, &c->mrf_h2d_ms, &c->mrf_parse_ms))) return rc;
-	std::unique_ptr<lsq_reads> R(new lsq_reads);
-	R->o_blk_off.resize(P.n_reads + 1); R->o_line_no.resize(P.n_reads);
-	R->o_start.resize(P.n_blocks); R->o_end.resize(P.n_blocks); R->o_chrom.resize(P.n_blocks); R->o_strand.resize(P.n_blocks);
-	HIP_TRY(hipMemcpy(R->o_blk_off.data(), P.blk_off.p, (P.n_reads + 1) * 8, hipMemcpyDeviceToHost));
-	if (P.n_reads) HIP_TRY(hipMemcpy(R->o_line_no.data(), P.line_no.p, P.n_reads * 4, hipMemcpyDeviceToHost));
-	if (P.n_blocks) {
-		HIP_TRY(hipMemcpy(R->o_start.data(), P.bs.p, P.n_blocks * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(R->o_end.data(), P.be.p, P.n_blocks * 4, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(R->o_chrom.data(), P.bc.p, P.n_blocks * 2, hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(R->o_strand.data(), P.bst.p, P.n_blocks, hipMemcpyDeviceToHost));
-	}
-	R->adopt();
-	*out = R.release();
-	return LSQ_OK;
-} LSQ_API_CATCH
-
-// developer entry (include/lesseq_hip_dev.h): which of the parse's three kernels the latest MRF text went through
-int lsq_debug_last_parse_paths(const lsq_ctx *c, unsigned *tiles_handed, unsigned *lines_listed, unsigned *all_slow) {
-	if (!c) return LSQ_E_ARG;
-	if (tiles_handed) *tiles_handed = c->parse_tiles_handed;
-	if (lines_listed) *lines_listed = c->parse_lines_listed;
-	if (all_slow) *all_slow = c->parse_all_slow;
-	return LSQ_OK;
-}
-
-int lsq_last_mrf_timing(lsq_ctx *c, float *h2d_ms, float *parse_ms) LSQ_API_TRY {
-	if (!c) return fail(LSQ_E_ARG, "null context");
-	if (h2d_ms) *h2d_ms = c->mrf_h2d_ms;
-	if (parse_ms) *parse_ms = c->mrf_parse_ms;
-	return LSQ_OK;
-} LSQ_API_CATCH
-
-static const char *const INGEST_STAGE_NAMES[LSQ_INGEST_STAGES] = {
-	"newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"};
 int lsq_ingest_stage_count(void) { return LSQ_INGEST_STAGES; }
 const char *lsq_ingest_stage_name(int stage) { return stage >= 0 && stage < LSQ_INGEST_STAGES ? INGEST_STAGE_NAMES[stage] : nullptr; }
-// Pass k of the latest ingest -> its slot of the context's clocks.  A file of records (BAM) runs two passes of its own, kept in the
-// slots behind the chain's seven, where a text runs the newline count -- three when it was verified: the CRC32 pass, in the
-// last slot, is reported between the two.
-static bool last_ingest_of_records(const lsq_ctx *c) { return c && c->ing_format >= 0 && READ_FORMATS[c->ing_format].open != nullptr; }
-static int last_own_passes(const lsq_ctx *c) { return !last_ingest_of_records(c) ? 1 : c->ing_verified ? 3 : 2; }
-static int last_stage_slot(const lsq_ctx *c, int k) {
-	const int own = last_own_passes(c);
-	if (!last_ingest_of_records(c)) return k;
-	if (k >= own) return k - own + 1;
-	return k == 0 ? LSQ_INGEST_STAGES : k == own - 1 ? LSQ_INGEST_STAGES + 1 : LSQ_INGEST_STAGES + 2;
-}
-int lsq_last_ingest_stage_count(const lsq_ctx *c) { return LSQ_INGEST_STAGES - 1 + last_own_passes(c); }
+// The passes of the latest ingest as it listed them (ingest_device); a context that has ingested nothing reports the chain's seven, with zeros.
+int lsq_last_ingest_stage_count(const lsq_ctx *c) { return c && c->ing_reported ? c->ing_reported : LSQ_INGEST_STAGES; }
 const char *lsq_last_ingest_stage_name(const lsq_ctx *c, int stage) {
 	if (stage < 0 || stage >= lsq_last_ingest_stage_count(c)) return nullptr;
-	const int slot = last_stage_slot(c, stage);
-	if (slot >= LSQ_INGEST_STAGES) return slot == LSQ_INGEST_STAGES ? "bgzf_inflate" : slot == LSQ_INGEST_STAGES + 1 ? "bam_record_starts" : "bgzf_crc32";
-	return c && c->ing_format >= 0 && slot == 1 ? READ_FORMATS[c->ing_format].stage : lsq_ingest_stage_name(slot);
-}
-int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_repaired) {
-	if (!c) return LSQ_E_ARG;
-	if (n_blocks) *n_blocks = c->bam_blocks;
-	if (blocks_repaired) *blocks_repaired = c->bam_blocks_repaired;
-	return LSQ_OK;
-}
-// developer entry (include/lesseq_hip_dev.h): the staging and the inflate kernel of the BAM chain alone
-int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *out, uint64_t cap, uint64_t *n) LSQ_API_TRY {
-	if (!c || (!bytes && len) || (!out && cap) || !n) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure_lanes(c))) return rc;
-	lsq_text T;
-	BamRecords B;
-	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B, 0))) return rc;
-	*n = B.total;
-	if (B.total > cap) return fail(LSQ_E_RANGE, "the inflated stream holds %llu bytes, the buffer %llu", B.total, (unsigned long long)cap);
-	if (B.total) HIP_TRY(hipMemcpy(out, B.d_stream.p, (size_t)B.total, hipMemcpyDeviceToHost));
-	return LSQ_OK;
-} LSQ_API_CATCH
-// developer entry: ... and the CRC32 kernel behind it, its sums returned uncompared
-int lsq_debug_bgzf_crc32(lsq_ctx *c, const void *bytes, uint64_t len, uint32_t *crc, uint64_t cap, uint64_t *n) LSQ_API_TRY {
-	if (!c || (!bytes && len) || (!crc && cap) || !n) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	int rc;
-	if ((rc = ensure_lanes(c))) return rc;
-	lsq_text T;
-	BamRecords B;
-	if ((rc = text_stage_buffer(c, bytes, len, "<bytes>", T)) || (rc = bam_inflate_staged(c, T, (const unsigned char *)bytes, B, 2))) return rc;
-	*n = B.tab.size();
-	if (B.tab.size() > cap) return fail(LSQ_E_RANGE, "the file holds %llu BGZF blocks, the buffer %llu", (unsigned long long)B.tab.size(), (unsigned long long)cap);
-	if (!B.tab.empty()) HIP_TRY(hipMemcpy(crc, B.d_crc.p, B.tab.size() * 4, hipMemcpyDeviceToHost));
-	return LSQ_OK;
-} LSQ_API_CATCH
-
-// The whole-file check (include/lesseq_hip.h): the chain's own passes, always verifying, then the record walk of
-// lsq_mrf_parse_device's first pass and two sums over what it counted.  No events needed: no record is routed.
-int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r) LSQ_API_TRY {
-	if (!c || !path || !r) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	hipStream_t st = c->stream;
-	int rc;
-	if ((rc = ensure_lanes(c))) return rc;
-	lsq_text T;
-	if ((rc = stage_text_file(c, path, 0, ~0ull, T))) return rc;
-	BamRecords BR;
-	if ((rc = bam_open_verified(c, T, BR, true))) return rc;
-	lsq_bam_report R{};
-	R.file_bytes = T.len; R.blocks = BR.tab.size(); R.inflated_bytes = BR.total;
-	R.header_lines = BR.H.h_lines; R.references = BR.H.ref_names.size();
-	R.records = BR.n_rec; R.blocks_repaired = c->bam_blocks_repaired;
-	const unsigned long long first_line = BR.H.h_lines + 1;
-	if (first_line + BR.n_rec > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 lines");
-	if (BR.n_rec) {
-		DevBuf<unsigned> d_line_nb;
-		DevBuf<unsigned long long> d_rd_idx, d_bk_off, d_err;
-		ScanScratch SS;
-		const unsigned long long no_err = MRF_NO_ERR;
-		if ((rc = d_line_nb.alloc(BR.n_rec)) || (rc = d_rd_idx.alloc(BR.n_rec + 1)) || (rc = d_bk_off.alloc(BR.n_rec + 1)) || (rc = SS.reserve(BR.n_rec)) || (rc = d_err.upload(&no_err, 1, st))) return rc;
-		const MrfText X{T.d_text.p, T.len, nullptr, 0u, first_line, BR.n_rec};
-		hipLaunchKernelGGL(lsq_bam_count_kernel, dim3((unsigned)((BR.n_rec + 255) / 256)), dim3(256), 0, st, BR.view(), X, sam_opts(c), d_line_nb.p, d_err.p);
-		HIP_TRY(hipGetLastError());
-		if ((rc = device_scan<1, true>(SS, d_line_nb.p, BR.n_rec, d_rd_idx.p, st)) || (rc = device_scan<1, false>(SS, d_line_nb.p, BR.n_rec, d_bk_off.p, st))) return rc;
-		unsigned long long bad = 0, n_reads = 0, n_blocks = 0;
-		HIP_TRY(hipMemcpyAsync(&bad, d_err.p, 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(&n_reads, d_rd_idx.p + BR.n_rec, 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(&n_blocks, d_bk_off.p + BR.n_rec, 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipStreamSynchronize(st));
-		if (bad != no_err) return BR.fail_record(bad, st);
-		R.reads = n_reads; R.read_blocks = n_blocks;
-	}
-	*r = R;
-	return LSQ_OK;
-} LSQ_API_CATCH
-
-int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {
-	if (!c) return LSQ_E_ARG;
-	if (lines_listed) *lines_listed = c->sam_lines_listed;
-	if (all_slow) *all_slow = c->sam_all_slow;
-	return LSQ_OK;
+	return c && c->ing_reported ? c->ing_pass[stage].name : lsq_ingest_stage_name(stage);
 }
 int lsq_last_ingest_stages(const lsq_ctx *c, float *ms, uint64_t *bytes, int capacity) LSQ_API_TRY {
 	if (!c) return fail(LSQ_E_ARG, "null context");
 	for (int k = 0; k < lsq_last_ingest_stage_count(c) && k < capacity; ++k) {
-		const int s = last_stage_slot(c, k);
-		if (ms) ms[k] = c->ing_seen[s] ? c->ing_ms[s] : 0.0f;
-		if (bytes) bytes[k] = c->ing_seen[s] ? c->ing_bytes[s] : 0;
+		if (ms) ms[k] = c->ing_reported ? c->ing_pass[k].ms : 0.0f;
+		if (bytes) bytes[k] = c->ing_reported ? c->ing_pass[k].bytes : 0;
 	}
 	return LSQ_OK;
 } LSQ_API_CATCH

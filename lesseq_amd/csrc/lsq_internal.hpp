@@ -299,6 +299,7 @@ int cli_device();                                                            // 
 int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
 int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out);      // lsq_sam.cpp: the sam2mrf and bam2mrf executables
 struct BamError;
+bool device_read_format(const char *name);                                   // lsq_readfile.hip: a read format the device parses from the file's own bytes (READ_FORMATS names them)
 int bam_fail(const BamError &e);                                             // lsq_bam.cpp: a BAM error (lsq_bam.hpp) as the calling thread's status and text
 int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify = false);      // lsq_bam.cpp (verify: CRC32s and end-of-file marker)
 

@@ -1,11 +1,15 @@
-// MRF_SINGLE parsed on the device (included by lsq_ingest.hip; not a public header).
+// MRF_SINGLE parsed on the device; not a public header.
+// Needs: lsq_route.hpp (the routing pass's tables and the merge of a read's blocks), lsq_text.hpp (a text's newline tiles), lsq_mrf_line.hpp
+// (the shared splitter), lsq_readjob.hpp (the kernels' parameter structs).  Gives: the three routing kernels and the format's front end
+// for the loader chain (mrf_prepare, mrf_launch, mrf_record), the count / write kernels of lsq_mrf_parse_device, and the dictionary code
+// (chromosome and strand look-ups) the SAM and BAM parsers share.
 //
 // The text lies in HBM as lsq_text.hip staged it, its newlines counted per tile (lsq_text.hpp).  A workgroup of the parse owns
 // the lines that END in its tile and sees the tile and the 512 bytes before it.  The newline ordinal of a line (tile base from
 // the prefix sum over the tile counts + its place in the tile) is its line number: the header and "read-<n>" fall out as in
 // the reference (count/count.cpp:283,286,293-295).
 //
-// The parse IS the routing pass of the loader chain (lsq_ingest.hip): per line, every block goes through the containment
+// The parse IS the routing pass of the loader chain (lsq_ingest.hip: ingest_device): per line, every block goes through the containment
 // filter and the merge as it is split off, and nothing but the routed read leaves the kernel -- no parsed array exists in HBM
 // either.  Three kernels, launched by the format's front end (mrf_launch, at the end of this file):
 //   lsq_mrf_route_fast_kernel   every tile: delimiter tables from byte-parallel zero-byte tests, lines walk table entries,
@@ -25,8 +29,14 @@
 //     with byte-wise verification for the byte-walking kernels); strand strings against a 256-slot table seeded with the
 //     strands already known, grown with atomicCAS (strings of at most 7 bytes; longer ones give LSQ_E_UNSUPPORTED -- use
 //     lsq_mrf_parse)
-// The SAM parser (lsq_sam_device.hpp, included behind this file) resolves chromosomes and strands with the dictionary code here.
+// The SAM parser (lsq_sam_device.hpp) resolves chromosomes and strands with the dictionary code here.
 #pragma once
+#include "lsq_route.hpp"
+#include "lsq_text.hpp"
+#include "lsq_mrf_line.hpp"
+#include "lsq_readjob.hpp"
+
+namespace {      // (the device code of the unit that includes it: internal linkage)
 
 constexpr unsigned MRF_LB = 512;                    // bytes ahead of the tile that are staged with it: a window of 8 KiB (tiles of 7 680 bytes) or 4 KiB (3 584)
 constexpr unsigned long long MRF_NO_ERR = ~0ull;
@@ -576,7 +586,7 @@ __global__ void __launch_bounds__(256) lsq_mrf_write_kernel(MrfText X, const uns
 	});
 }
 
-// ---- the front end (READ_FORMATS, lsq_ingest.hip): the fast kernel's dictionary, the routing launches, what they handed on
+// ---- the front end (READ_FORMATS, lsq_readfile.hip): the fast kernel's dictionary, the routing launches, what they handed on
 static int mrf_prepare(TextJob &J) {
 	hipStream_t st = J.c->stream;
 	int rc;
@@ -616,4 +626,4 @@ static void mrf_record(const TextJob &J) {
 	J.c->parse_tiles_handed = J.all_slow ? 0u : J.counts[0]; J.c->parse_lines_listed = J.counts[1]; J.c->parse_all_slow = J.all_slow ? 1u : 0u;
 }
 
-#include "lsq_sam_device.hpp"
+} // namespace

@@ -1,4 +1,8 @@
-// SAM_SINGLE parsed on the device (included by lsq_ingest.hip behind lsq_mrf_device.hpp; not a public header).
+// SAM_SINGLE parsed on the device; not a public header.
+// Needs: lsq_mrf_device.hpp (the tile's LDS, the dictionary look-ups, the byte tests; through it lsq_route.hpp, lsq_text.hpp and
+// lsq_readjob.hpp), lsq_sam_line.hpp (the shared splitter).  Gives: the routing kernels and the format's front end for the loader chain
+// (sam_prepare, sam_launch, sam_record), the count / write kernels of lsq_mrf_parse_device, and the record filters (SamOpts, sam_opts)
+// the BAM parser shares.
 //
 // The text lies in HBM as lsq_text.hip staged it and its newline-count pass has numbered its tiles (lsq_text.hpp), as for MRF.  What differs is the shape of a line: a record with SEQ and QUAL is 200-400 bytes of which only the
 // first six fields, 40-90 bytes, are ever read, so a 7 680-byte tile holds about 25 lines.  Hence another form than MRF's:
@@ -18,11 +22,14 @@
 //   lsq_sam_route_lines_kernel    the listed lines
 //   lsq_sam_count_kernel / lsq_sam_write_kernel   the same walk for lsq_mrf_parse_device("SAM_SINGLE"): blocks per line,
 //                                 then the parsed arrays, around two prefix sums
-// The format's front end (sam_launch, at the end of this file) launches the route kernels; READ_FORMATS (lsq_ingest.hip) the other two.
+// The format's front end (sam_launch, at the end of this file) launches the route kernels; READ_FORMATS (lsq_readfile.hip) the other two.
 // Line numbers: the ordinal of the newline ahead of a line (tile base + place in the tile) is the line's 0-based number;
 // "read-<k>" counts every line from 1, so has_header = 0 and first_line = 1 for a whole file.
 #pragma once
-// (lsq_sam_line.hpp, the shared splitter, is included by lsq_ingest.hip at file scope)
+#include "lsq_mrf_device.hpp"
+#include "lsq_sam_line.hpp"
+
+namespace {
 
 constexpr unsigned SAM_TAIL = MRF_LB;               // bytes behind the tile that are staged with it
 constexpr unsigned SAM_HEAD_MAX = 256;              // bytes of a line (through the CIGAR field) the tile kernel walks at most
@@ -239,7 +246,7 @@ __global__ void __launch_bounds__(256) lsq_sam_write_kernel(MrfText X, SamOpts Q
 	});
 }
 
-// ---- the front end (READ_FORMATS, lsq_ingest.hip)
+// ---- the front end (READ_FORMATS, lsq_readfile.hip)
 static SamOpts sam_opts(const lsq_ctx *c) { return SamOpts{c->opt_sam_skip_flags, c->opt_sam_min_mapq}; }
 static int sam_prepare(TextJob &J) {
 	J.all_slow = getenv("LSQ_SAM_SLOW") != nullptr;       // (LSQ_SAM_SLOW: the tests run the byte-walking form over whole files with it)
@@ -255,3 +262,5 @@ static void sam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &
 	}
 }
 static void sam_record(const TextJob &J) { J.c->sam_lines_listed = J.all_slow ? 0u : J.counts[1]; J.c->sam_all_slow = J.all_slow ? 1u : 0u; }
+
+} // namespace

@@ -1,6 +1,6 @@
 // The staged-text layer of the device parsers: a file, a byte range of one, or bytes in host memory into HBM as they are (lsq_text,
 // lsq_device.hpp), the pinned-buffer copy pipeline behind it, and the newline counts of the text's tiles (lsq_text.hpp: what a
-// parser's workgroup does with a tile).  The loader (lsq_ingest.hip) and the GTF parser (lsq_gtf.hip) stage through here.
+// parser's workgroup does with a tile).  The read files (lsq_readfile.hip) and the GTF parser (lsq_gtf.hip) stage through here.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -172,7 +172,7 @@ int scan_newlines(lsq_ctx *c, lsq_text &T) {
 		DevBuf<unsigned> d_tile_cnt;
 		ScanScratch SS;
 		if ((rc = d_tile_cnt.alloc(n_tiles)) || (rc = T.d_tile_base.alloc(n_tiles + 1)) || (rc = SS.reserve(n_tiles))) return rc;
-		StageClock k(c, st, 0);
+		StageClock k(c, st, "newline_count");
 		hipLaunchKernelGGL(lsq_mrf_newline_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, T.d_text.p, len, d_tile_cnt.p);
 		HIP_TRY(hipGetLastError());
 		if ((rc = device_scan<1>(SS, d_tile_cnt.p, n_tiles, T.d_tile_base.p, st))) return rc;

@@ -35,16 +35,35 @@ struct HostStopwatch {
 	}
 };
 
-// device time of the loader chain's stages (lsq_last_ingest_stages): events around each stage's launches
+// Device time of the loader's passes (lsq_last_ingest_stages): events around each pass's launches.  The context lists the passes
+// of the latest ingest (lsq_ctx::ing_pass) in the order in which they were first named; naming one again -- a route that runs a
+// second time -- overwrites its entry.  An entry keeps its pair of events: they are made once and used again by whatever pass comes
+// to stand there.
+inline IngestPass *stage_entry(lsq_ctx *c, const char *name) {
+	for (int k = 0; k < c->ing_n; ++k) if (strcmp(c->ing_pass[k].name, name) == 0) return &c->ing_pass[k];
+	if (c->ing_n == LSQ_INGEST_PASS_MAX) return nullptr;
+	IngestPass &p = c->ing_pass[c->ing_n++];
+	p.name = name; p.bytes = 0; p.ms = 0; p.clocked = false;
+	return &p;
+}
+// a new ingest begins: the list is empty again -- but for the newline count, if the text at hand was counted before the ingest took it
+inline void stages_reset(lsq_ctx *c, bool keep_newline_count) {
+	int n = 0;
+	for (int k = 0; keep_newline_count && k < c->ing_n && !n; ++k)
+		if (strcmp(c->ing_pass[k].name, "newline_count") == 0) { std::swap(c->ing_pass[0], c->ing_pass[k]); n = 1; }
+	c->ing_n = n; c->ing_reported = 0;
+}
 struct StageClock {
-	lsq_ctx *c; hipStream_t st; int s;
-	StageClock(lsq_ctx *c_, hipStream_t st_, int s_) : c(c_), st(st_), s(s_) {
-		for (int q = 0; q < 2; ++q) if (!c->ing_ev[2 * s + q]) (void)hipEventCreate(&c->ing_ev[2 * s + q]);
-		if (c->ing_ev[2 * s]) (void)hipEventRecord(c->ing_ev[2 * s], st);
+	IngestPass *p; hipStream_t st;
+	StageClock(lsq_ctx *c, hipStream_t st_, const char *name) : p(stage_entry(c, name)), st(st_) {
+		if (!p) return;
+		for (hipEvent_t &e : p->ev) if (!e) (void)hipEventCreate(&e);
+		if (p->ev[0]) (void)hipEventRecord(p->ev[0], st);
 	}
 	void end(unsigned long long bytes) {
-		if (c->ing_ev[2 * s + 1]) (void)hipEventRecord(c->ing_ev[2 * s + 1], st);
-		c->ing_bytes[s] = bytes; c->ing_seen[s] = true;
+		if (!p) return;
+		if (p->ev[1]) (void)hipEventRecord(p->ev[1], st);
+		p->bytes = bytes; p->clocked = true;
 	}
 };
 } // namespace lsq

@@ -179,3 +179,70 @@ def test_executables_verify_when_asked(tmp_path):
     assert p.returncode == 0 and [ln.split("\t") for ln in p.stdout.split("\n")[:-1]] == [[k, str(v)] for k, v in want.items()], p.stderr
     p = subprocess.run([os.path.join(BIN, "bamcheck"), bad], capture_output=True, text=True, timeout=CHILD_TIMEOUT)
     assert p.returncode == 1 and p.stdout == "" and msg in p.stderr
+
+
+def mixed_bam(d, n=300, bad=None, payload=300):
+    """(header lines, BGZF bytes) of n records on the basic case's first reference -- reads of one, two and three blocks, unmapped
+    and secondary records among them -- in payload blocks of 300 bytes, which cut most records in two; bad: that record's
+    l_read_name set to zero"""
+    sam = bw.terminated(read_file(os.path.join(d, "in.sam")))
+    head_text, refs, _ = bw.parse_sam(sam)
+    recs = []
+    for k in range(n):
+        flag = 4 if k % 7 == 0 else 0x100 if k % 11 == 0 else 16 if k % 2 else 0
+        cigar = "30M200N20M" if k % 3 == 0 else "10M50N20M60N20M" if k % 5 == 0 else "50M"
+        recs.append("r%d\t%d\t%s\t%d\t60\t%s\t*\t0\t0\t*\t*\n" % (k, flag, refs[0][0], 1000 + 10 * k, cigar))
+    head, rs = bw.bam_stream((head_text + "".join(recs)).encode("latin-1"))
+    if bad is not None:
+        body = bytearray(rs[bad][4:])
+        body[8] = 0
+        rs[bad] = struct.pack("<I", len(body)) + bytes(body)
+    stream = head + b"".join(rs)
+    return head_text.count("\n"), bw.bgzf_file([stream[i:i + payload] for i in range(0, len(stream), payload)] or [b""])
+
+
+def read_file(path):
+    with open(path, "rb") as f:
+        return f.read()
+
+
+def test_check_and_parse_are_one_walk(tmp_path, ctx0):
+    """lsq_bam_check's record walk is the first pass of lsq_mrf_parse_device: the same counts on a file of filtered records,
+    multi-block reads and records that straddle the BGZF blocks; the same first malformed record, by status and message, from
+    the check, the parse and the ingest; nothing and no error from a file that is its header alone"""
+    _, d = load("basic")
+    ev, ctx = context_for(d)
+    h, data = mixed_bam(d)
+    path = str(tmp_path / "mixed.bam")
+    with open(path, "wb") as f:
+        f.write(data)
+    rep = ctx0.bam_check(path)
+    dev = ctx.parse_bam_device(path)
+    assert rep["records"] == 300 and rep["blocks_repaired"] > 0 and ctx.bam_paths()["blocks_repaired"] > 0
+    assert 150 < rep["reads"] < 300 and rep["read_blocks"] > rep["reads"]
+    assert (rep["reads"], rep["read_blocks"]) == (len(dev), dev.num_blocks)
+    same_reads(ev, L.Reads.from_bam(path, ev), dev)
+    ctx.upload_reads_bam(0, path)
+    # one malformed record, late in the file
+    _, data = mixed_bam(d, bad=200)
+    bad = str(tmp_path / "bad.bam")
+    with open(bad, "wb") as f:
+        f.write(data)
+    seen = []
+    for run in (lambda: ctx0.bam_check(bad), lambda: ctx.parse_bam_device(bad), lambda: ctx.upload_reads_bam(0, bad)):
+        with pytest.raises(L.LsqError) as e:
+            run()
+        seen.append((e.value.status, str(e.value)))
+    assert seen[0] == seen[1] == seen[2] and seen[0][0] == -4 and ("#%d:<BAM record at byte " % (h + 201)) in seen[0][1], seen
+    # the header alone
+    _, data = mixed_bam(d, n=0)
+    empty = str(tmp_path / "empty.bam")
+    with open(empty, "wb") as f:
+        f.write(data)
+    rep = ctx0.bam_check(empty)
+    assert (rep["records"], rep["reads"], rep["read_blocks"]) == (0, 0, 0)
+    dev = ctx.parse_bam_device(empty)
+    assert (len(dev), dev.num_blocks) == (0, 0)
+    ctx.upload_reads_bam(0, empty)
+    assert ctx.retained(0) == 0
+    ctx.close()

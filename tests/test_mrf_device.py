@@ -444,3 +444,72 @@ def test_ingest_stage_report(tmp_path):
     st = ctx.ingest_stages()
     assert st[0]["ms"] == 0 and st[0]["bytes"] == 0 and all(s["ms"] > 0 for s in st[1:])
     ctx.close()
+
+
+SEVEN_STAGES = ["newline_count", "route", "partition_count", "partition_scatter", "group_classify", "group_offsets", "group_place"]
+
+
+def parse_time_is_the_sum_up_to_the_route(ctx, route):
+    """lsq_last_mrf_timing's parse time: the reported passes up to and including the route, to float rounding"""
+    st = ctx.ingest_stages()
+    k = [s["stage"] for s in st].index(route)
+    assert abs(ctx.mrf_timing()["parse_ms"] - sum(s["ms"] for s in st[:k + 1])) <= 1e-3, (ctx.mrf_timing(), st)
+
+
+def test_stage_report_across_formats_on_one_context(tmp_path, monkeypatch):
+    """one context, one read set in every form the loader takes, one after the other: the report lists the passes the latest
+    ingest ran, each once and in the order it ran them -- a newline count inherited from lsq_text_lines, a route that ran twice
+    (the line list ran over), a BAM file's own passes with and without the CRC32 pass, SAM text, parsed arrays -- and the parse
+    time of a read file is the sum of its passes up to and including the route.  (Parsed arrays are no file: their upload leaves
+    lsq_last_mrf_timing as the file before left it.)"""
+    import bam_writer as bw
+    spec = L.SynthSpec(43, 50, 2000, 100, 3, L.EVENT_TYPES)
+    L.synth_write(spec, str(tmp_path), "f")
+    L.synth_write_sam(spec, str(tmp_path), "f")
+    mrf, sam, bam = str(tmp_path / "f.mrf"), str(tmp_path / "f.sam"), str(tmp_path / "f.bam")
+    with open(sam, "rb") as f:
+        sam_bytes = f.read()
+    with open(bam, "wb") as f:
+        f.write(bw.sam_to_bam(bw.terminated(sam_bytes)))
+    ev, ctx = setup(str(tmp_path / "f.interval"), str(tmp_path / "f.map"), 100)
+    shared = SEVEN_STAGES[2:]
+    # (a) the newlines counted ahead of the upload
+    text = ctx.stage_text(mrf)
+    assert ctx.text_lines(text) == 2001
+    ctx.upload_reads_text(0, text)
+    st = ctx.ingest_stages()
+    assert [s["stage"] for s in st] == SEVEN_STAGES
+    assert st[0]["ms"] > 0 and st[0]["bytes"] >= os.path.getsize(mrf)
+    parse_time_is_the_sum_up_to_the_route(ctx, "route")
+    # (b) the line list runs over: the route and the partition count are clocked twice, and listed once
+    # (the list holds a line a tile and one more with LSQ_MRF_LINE_LIST=0: three lines of another shape, five times each, are more)
+    lines = open(mrf).read().split("\n")
+    for k in range(15):
+        lines.insert(100 + 120 * k, ODD_LINES[8 + k % 3])
+    (tmp_path / "o.mrf").write_text("\n".join(lines))
+    assert 15 > (os.path.getsize(tmp_path / "o.mrf") + 7679) // 7680 + 1
+    monkeypatch.setenv("LSQ_MRF_LINE_LIST", "0")
+    ctx.upload_reads_mrf(0, str(tmp_path / "o.mrf"))
+    monkeypatch.delenv("LSQ_MRF_LINE_LIST")
+    assert parse_paths(ctx)[2]
+    st = ctx.ingest_stages()
+    assert [s["stage"] for s in st] == SEVEN_STAGES and all(s["ms"] > 0 for s in st)
+    parse_time_is_the_sum_up_to_the_route(ctx, "route")
+    # (c) the formats in turn
+    ctx.set_option("bam_verify", 1)
+    ctx.upload_reads_bam(0, bam)
+    assert [s["stage"] for s in ctx.ingest_stages()] == ["bgzf_inflate", "bgzf_crc32", "bam_record_starts", "bam_route"] + shared
+    parse_time_is_the_sum_up_to_the_route(ctx, "bam_route")
+    ctx.upload_reads_sam(0, sam)
+    assert [s["stage"] for s in ctx.ingest_stages()] == ["newline_count", "sam_route"] + shared
+    parse_time_is_the_sum_up_to_the_route(ctx, "sam_route")
+    of_the_sam_file = ctx.mrf_timing()
+    ctx.upload_reads(0, L.Reads.from_mrf(mrf, ev))
+    st = ctx.ingest_stages()
+    assert [s["stage"] for s in st] == SEVEN_STAGES and st[0]["ms"] == 0 and st[0]["bytes"] == 0
+    assert ctx.mrf_timing() == of_the_sam_file
+    ctx.set_option("bam_verify", 0)
+    ctx.upload_reads_bam(0, bam)
+    assert [s["stage"] for s in ctx.ingest_stages()] == ["bgzf_inflate", "bam_record_starts", "bam_route"] + shared
+    parse_time_is_the_sum_up_to_the_route(ctx, "bam_route")
+    ctx.close()

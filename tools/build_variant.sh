@@ -7,7 +7,7 @@ cd "$(dirname "$0")/../lesseq_amd/csrc"
 name=$1; shift
 B=../_build
 OBJS=""
-for f in lsq_device lsq_count lsq_em lsq_text lsq_ingest lsq_replay; do
+for f in lsq_device lsq_count lsq_em lsq_text lsq_ingest lsq_readfile lsq_replay; do
 	/opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -DLSQ_DEV "$@" -c -o $B/${f}_$name.o $f.hip &
 	OBJS="$OBJS $B/${f}_$name.o"
 done
