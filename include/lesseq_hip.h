@@ -96,6 +96,35 @@ int64_t lsq_annotation_num_genes_loaded(const lsq_annotation *a);
  * otherwise, the reference's unknown_readtype_err). */
 int lsq_events_compile(const lsq_annotation *a, int n_methods, const char *const *read_types,
                        const uint64_t *expected_read_lengths, lsq_events **out);
+/* The library type of a job.  Unstranded: a read counts for every event it overlaps, whatever their strands --
+ * the reference's behaviour, and what lsq_events_compile gives.  Forward and reverse: a read has a transcript strand
+ *   t = s XOR (library == reverse) XOR mate2
+ * (s: the alignment strand -- the strand column of an MRF block, which must be exactly "+" or "-", FLAG & 0x10 of a SAM / BAM
+ * record; mate2: (FLAG & 0x1) && (FLAG & 0x80) of a SAM / BAM record, false for every other format) and counts only for events
+ * of that strand: the job's table is, row by row, the table of the unstranded job of the plus genes on the t = "+" reads and of
+ * the unstranded job of the minus genes on the t = "-" reads.  A read without a transcript strand (a strand string that is
+ * neither "+" nor "-") makes no read.  forward is htseq-count's -s yes, reverse its -s reverse (the dUTP protocols). */
+#define LSQ_LIBRARY_UNSTRANDED 0
+#define LSQ_LIBRARY_FORWARD 1
+#define LSQ_LIBRARY_REVERSE 2
+/* "unstranded", "forward" or "reverse" to its number; -1 for any other string. */
+int lsq_library_from_name(const char *name);
+/* lsq_events_compile for a job of the given library type.  The library type is a property of the compiled events: in a
+ * stranded compile the covered regions, the clusters, the buckets and the loader's tables are kept per (chromosome, strand),
+ * so that events of opposite strands never share a bucket and everything behind the loader runs as it does unstranded.  A
+ * selected gene whose isoforms do not all carry the same one of "+" / "-" cannot be placed: LSQ_E_UNSUPPORTED, the message
+ * names the first such gene and says how many there are (an unstranded compile takes them).  LSQ_E_RANGE beyond 32 767
+ * chromosomes.  LSQ_LIBRARY_UNSTRANDED: exactly lsq_events_compile.
+ * Every upload call of a context that holds stranded events (lsq_reads_upload, lsq_reads_upload_mrf, lsq_reads_upload_text...)
+ * routes by transcript strand; wherever the pipeline uses a read's strand, the read then carries its transcript strand's string.
+ * Parsed arrays have no room for the mate bits, so under stranded events lsq_sam_parse, lsq_bam_parse(_checked) and
+ * lsq_mrf_parse_device write s XOR mate2 as a SAM / BAM record's strand -- what the record's MRF form holds -- and
+ * lsq_reads_upload derives t from the strand id of a read's first block (an id other than those of "+" and "-": no read).
+ * lsq_reads_parse drops, for the name-keyed formats, the lines the containment filter of the line's transcript strand drops, and
+ * makes a name whose lines lie on both transcript strands a read per strand (an upload routes a read by one strand). */
+int lsq_events_compile_library(const lsq_annotation *a, int n_methods, const char *const *read_types,
+                               const uint64_t *expected_read_lengths, int library, lsq_events **out);
+int lsq_events_library(const lsq_events *e);
 void lsq_events_free(lsq_events *e);
 
 /* read-only views into compiled events, in output order (bytewise-sorted gene names) */
@@ -304,6 +333,11 @@ int lsq_last_bam_paths(const lsq_ctx *c, uint64_t *n_blocks, uint64_t *blocks_re
  * context needs no events. */
 int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r);
 uint64_t lsq_reads_retained(const lsq_ctx *c, int method);      /* "loaded N reads" log line */
+/* The library report of the latest read file of `method` in a stranded job: out[0] / out[1] the reads the file made with
+ * transcript strand "+" / "-", out[2] the records that would have made a read but have no transcript strand, out[3] / out[4]
+ * how many of the first two the load-time filter retained.  A library type chosen wrongly shows here: nearly every read of
+ * one strand is then tested against the other strand's genes and dropped.  LSQ_E_STATE for unstranded events. */
+int lsq_last_library_report(const lsq_ctx *c, int method, uint64_t out[5]);
 uint64_t lsq_reads_retained_blocks(const lsq_ctx *c, int method);
 /* Of the retained reads, those kept in the pools: reads whose first base lies in the span of an event planned on this
  * context.  Without a shard that is every retained read; with lsq_events_set_shard the slice's share (a read that starts

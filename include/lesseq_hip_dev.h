@@ -72,6 +72,12 @@ int lsq_debug_bgzf_crc32(lsq_ctx *c, const void *bytes, uint64_t len, uint32_t *
  * when that call fails, e.g. without a driver): a binding that loads another runtime first (PyTorch's) can compare. */
 int lsq_debug_hip_versions(int *compiled, int *runtime);
 
+/* The covered regions the load-time filter tests a block against, as [start, end) pairs in ascending order: those of the
+ * chromosome (unstranded events; `minus` is ignored), or of the chromosome's plus (minus = 0) or minus (minus = 1) genes
+ * (stranded events, lsq_events_compile_library).  Returns their number and writes at most `capacity` of them; -1 for a bad
+ * argument.  The tests hold a stranded compile's regions against those of the two split compiles with it. */
+int64_t lsq_debug_events_covered(const lsq_events *e, const char *chrom, int minus, int64_t *starts, int64_t *ends, int64_t capacity);
+
 #ifdef __cplusplus
 }
 #endif

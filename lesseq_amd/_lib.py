@@ -62,6 +62,10 @@ _sig("lsq_annotation_num_genes", i64, vp)
 _sig("lsq_annotation_num_isoforms_loaded", i64, vp)
 _sig("lsq_annotation_num_genes_loaded", i64, vp)
 _sig("lsq_events_compile", C.c_int, vp, C.c_int, P(cs), P(u64), P(vp))
+_sig("lsq_events_compile_library", C.c_int, vp, C.c_int, P(cs), P(u64), C.c_int, P(vp))
+_sig("lsq_events_library", C.c_int, vp)
+_sig("lsq_library_from_name", C.c_int, cs)
+_sig("lsq_debug_events_covered", C.c_int64, vp, cs, C.c_int, P(C.c_int64), P(C.c_int64), C.c_int64)
 _sig("lsq_events_free", None, vp)
 _sig("lsq_events_count", i64, vp)
 _sig("lsq_events_total_isoforms", i64, vp)
@@ -128,6 +132,7 @@ _sig("lsq_debug_bgzf_inflate", C.c_int, vp, cs, u64, vp, u64, P(u64))
 _sig("lsq_debug_bgzf_crc32", C.c_int, vp, cs, u64, P(u32), u64, P(u64))
 _sig("lsq_bam_check", C.c_int, vp, cs, P(BamReportStruct))
 _sig("lsq_reads_retained", u64, vp, C.c_int)
+_sig("lsq_last_library_report", C.c_int, vp, C.c_int, P(u64))
 _sig("lsq_reads_retained_blocks", u64, vp, C.c_int)
 _sig("lsq_reads_pooled", u64, vp, C.c_int)
 _sig("lsq_reads_pooled_blocks", u64, vp, C.c_int)

@@ -44,16 +44,34 @@ class Annotation:
 
 
 class Events:
-    """lsq_events_compile: segments, isoform masks, ARS per read file, covered regions, device plan"""
+    """lsq_events_compile: segments, isoform masks, ARS per read file, covered regions, device plan.
+    library: "unstranded" (the default), "forward" or "reverse" -- the job's library type (lsq_events_compile_library)."""
 
-    def __init__(self, annotation, read_types=("SHORT_READ",), read_lengths=(100,)):
+    def __init__(self, annotation, read_types=("SHORT_READ",), read_lengths=(100,), library="unstranded"):
         M = len(read_types)
         rt = (cs * max(M, 1))(*[_b(t) for t in read_types])
         rl = (u64 * max(M, 1))(*read_lengths)
         h = vp()
-        check(lib.lsq_events_compile(annotation.h, M, rt, rl, C.byref(h)))
+        code = lib.lsq_library_from_name(_b(library))
+        if code < 0:
+            raise ValueError("library is 'unstranded', 'forward' or 'reverse', not %r" % (library,))
+        check(lib.lsq_events_compile_library(annotation.h, M, rt, rl, code, C.byref(h)))
         self.h = h
         self.n_methods = M
+
+    @property
+    def library(self):
+        return ("unstranded", "forward", "reverse")[lib.lsq_events_library(self.h)]
+
+    def covered(self, chrom, minus=False):
+        """the covered regions the load-time filter uses: the chromosome's (unstranded events), or those of its plus /
+        minus genes (stranded events), as (start, end) pairs (a developer entry: lsq_debug_events_covered)"""
+        n = lib.lsq_debug_events_covered(self.h, _b(chrom), int(minus), None, None, 0)
+        if n < 0:
+            raise ValueError("bad argument")
+        s, e = (C.c_int64 * max(n, 1))(), (C.c_int64 * max(n, 1))()
+        lib.lsq_debug_events_covered(self.h, _b(chrom), int(minus), s, e, n)
+        return [(s[q], e[q]) for q in range(n)]
 
     def __del__(self):
         if getattr(self, "h", None):
@@ -403,6 +421,13 @@ class Context:
 
     def retained(self, method):
         return lib.lsq_reads_retained(self.h, method)
+
+    def library_report(self, method=0):
+        """stranded jobs: (reads of the + strand, of the - strand, records without a strand, + reads retained, - reads
+        retained) of the latest read file of `method` (lsq_last_library_report)"""
+        out = (u64 * 5)()
+        check(lib.lsq_last_library_report(self.h, method, out))
+        return tuple(out)
 
     def pooled(self, method):
         """retained reads kept in the pools: those that start in the span of an event planned on this context"""

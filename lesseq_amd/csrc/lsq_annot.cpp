@@ -508,17 +508,19 @@ int plan_device(lsq_events &E) {
 	E.buckets.clear(); E.images.clear(); E.dev2out.clear(); E.ties.clear();
 	E.jg_keys.clear(); E.jg_base.clear();
 	E.dev_cls_base.clear(); E.dev_iso_base.clear(); E.dev_K.clear();
-	E.cut_lo.assign(E.chroms.names.size(), {});
-	E.clu_s.assign(E.chroms.names.size(), {});
-	E.clu_e.assign(E.chroms.names.size(), {});
-	E.chrom_first_bucket.assign(E.chroms.names.size(), -1);
+	// (per table id: lsq_events::library)
+	const size_t n_tab = E.table_of(E.chroms.names.size(), 0);
+	E.cut_lo.assign(n_tab, {});
+	E.clu_s.assign(n_tab, {});
+	E.clu_e.assign(n_tab, {});
+	E.chrom_first_bucket.assign(n_tab, -1);
 	E.n_cls_total = E.n_iso_total = 0;
 	E.max_lds_bytes = 0;
 
-	// events per chromosome, ordered by span start
-	std::vector<std::vector<int32_t>> per_chrom(E.chroms.names.size());
+	// events per chromosome (stranded: and strand), ordered by span start
+	std::vector<std::vector<int32_t>> per_chrom(n_tab);
 	for (size_t i = 0; i < n; ++i)
-		if (i >= E.shard_first && i - E.shard_first < E.shard_count) per_chrom[E.ev[i].chrom_id].push_back((int32_t)i);
+		if (i >= E.shard_first && i - E.shard_first < E.shard_count) per_chrom[E.ev[i].table_id].push_back((int32_t)i);
 	auto ev_bytes = [&](const Event &e) -> uint32_t {
 		// packed bucket: record 48 B, ~2 cell records of 32 B per segment (the segment's stretches and the gap behind it),
 		// 8 bin records of 16 B, class histogram
@@ -734,7 +736,7 @@ int plan_device(lsq_events &E) {
 			d.img_bytes = off;
 			d.hist_off = off; off += 8 * HIST_REPLICAS * hist_stride(ncls);
 			d.n_cls = ncls;
-			if (off > 128u * 1024u) return fail(LSQ_E_UNSUPPORTED, "bucket of %u events on %s needs %u bytes of LDS tables", d.n_events, E.chroms.names[c].c_str(), off);
+			if (off > 128u * 1024u) return fail(LSQ_E_UNSUPPORTED, "bucket of %u events on %s needs %u bytes of LDS tables", d.n_events, E.chroms.names[E.stranded() ? c / 2 : c].c_str(), off);
 			E.max_lds_bytes = std::max(E.max_lds_bytes, off);
 			d.img_off = (uint32_t)E.images.size();
 			d.cls_base = E.n_cls_total;
@@ -849,10 +851,24 @@ namespace lsq {
 // count/count.cpp:231-258 and :394-416.  device_plan = false (classify) skips the device
 // limits and the bucket/LDS-image plan.
 int compile_events(const lsq_annotation *a, int n_methods, const char *const *read_types,
-                   const uint64_t *expected_read_lengths, bool device_plan, lsq_events **out) {
+                   const uint64_t *expected_read_lengths, bool device_plan, int library, lsq_events **out) {
 	if (!a || !out || n_methods < 0 || n_methods > LSQ_MAX_METHODS) return fail(LSQ_E_ARG, "bad argument (1..%d methods)", LSQ_MAX_METHODS);
+	if (library != LSQ_LIBRARY_UNSTRANDED && library != LSQ_LIBRARY_FORWARD && library != LSQ_LIBRARY_REVERSE) return fail(LSQ_E_ARG, "unknown library type %d", library);
 	std::unique_ptr<lsq_events> E(new lsq_events);
 	E->n_methods = n_methods;
+	E->library = library;
+	if (E->stranded()) {
+		// a gene lies in the tables of its strand: every isoform must name the same one of "+" / "-" 
+		const Gene *first_bad = nullptr;
+		size_t n_bad = 0;
+		for (const Gene &g : a->selected) {
+			bool good = !g.isos.empty() && (g.isos[0]->strand == "+" || g.isos[0]->strand == "-");
+			for (const IsoRec *r : g.isos) good = good && r->strand == g.isos[0]->strand;
+			if (!good) { if (!first_bad) first_bad = &g; ++n_bad; }
+		}
+		if (first_bad) return fail(LSQ_E_UNSUPPORTED, "gene %s has no strand of its own (its isoforms do not all carry the same one of + / -): a stranded job cannot place it; %zu such gene(s) selected",
+		                           first_bad->name.c_str(), n_bad);
+	}
 	std::vector<bool> is_short(n_methods);
 	for (int m = 0; m < n_methods; ++m) {
 		E->read_types.push_back(read_types[m]);
@@ -870,11 +886,13 @@ int compile_events(const lsq_annotation *a, int n_methods, const char *const *re
 		if (!g.isos.empty()) { e.chrom = g.isos[0]->chrom; e.strand = g.isos[0]->strand; }   // splicing_graph.h:239-242
 		e.chrom_id = E->chroms.intern(e.chrom);
 		e.strand_id = E->strands.intern(e.strand);
+		const unsigned e_minus = e.strand == "-" ? 1u : 0u;
+		e.table_id = (int)E->table_of((size_t)e.chrom_id, e_minus);
 		for (const IsoRec *r : g.isos) {
 			if (r->exonStarts.size() < r->exonCount || r->exonEnds.size() < r->exonCount)
 				return fail(LSQ_E_ARG, "isoform %s: exonCount %llu exceeds the listed exons (the reference reads past its vectors here)", r->name.c_str(), (unsigned long long)r->exonCount);
-			int cid = E->chroms.intern(r->chrom);
-			if ((size_t)cid >= E->covered.size()) E->covered.resize(cid + 1);
+			const size_t cid = E->table_of((size_t)E->chroms.intern(r->chrom), e_minus);
+			if (cid >= E->covered.size()) E->covered.resize(cid + 1);
 			for (uint64_t i = 0; i < r->exonCount; ++i) {
 				int64_t s = r->exonStarts[i], t = r->exonEnds[i];
 				if (s <= -COORD_LIMIT || s >= COORD_LIMIT || t <= -COORD_LIMIT || t >= COORD_LIMIT)
@@ -941,8 +959,14 @@ int compile_events(const lsq_annotation *a, int n_methods, const char *const *re
 		else e.tie_mode = ((unsigned char)pfx[p] < (unsigned char)e.gname[p]) ? 1 : 0;
 		E->ev.push_back(std::move(e));
 	}
-	if (E->covered.size() < E->chroms.names.size()) E->covered.resize(E->chroms.names.size());
+	if (E->covered.size() < E->table_of(E->chroms.names.size(), 0)) E->covered.resize(E->table_of(E->chroms.names.size(), 0));
 	if (E->chroms.names.size() > 65000) return fail(LSQ_E_RANGE, "too many chromosomes");
+	if (E->stranded()) {
+		// (a block's chromosome id is 16 bits wide, and its table id is twice that and one)
+		if (E->chroms.names.size() > 32767) return fail(LSQ_E_RANGE, "more than 32767 chromosomes in a stranded job");
+		E->strand_plus = E->strands.intern("+");
+		E->strand_minus = E->strands.intern("-");
+	}
 	if (E->strands.names.size() > 255) return fail(LSQ_E_RANGE, "more than 255 distinct strand strings");
 	if (!device_plan) { *out = E.release(); return LSQ_OK; }
 	E->class_off.assign(E->ev.size() + 1, 0);
@@ -957,13 +981,39 @@ int compile_events(const lsq_annotation *a, int n_methods, const char *const *re
 	return LSQ_OK;
 }
 
+// (the unstranded form, as classify and the local-event detection call it)
+int compile_events(const lsq_annotation *a, int n_methods, const char *const *read_types,
+                   const uint64_t *expected_read_lengths, bool device_plan, lsq_events **out) {
+	return compile_events(a, n_methods, read_types, expected_read_lengths, device_plan, LSQ_LIBRARY_UNSTRANDED, out);
+}
+
 } // namespace lsq
 
 extern "C" {
 
 int lsq_events_compile(const lsq_annotation *a, int n_methods, const char *const *read_types,
                        const uint64_t *expected_read_lengths, lsq_events **out) LSQ_API_TRY {
-	return lsq::compile_events(a, n_methods, read_types, expected_read_lengths, true, out);
+	return lsq::compile_events(a, n_methods, read_types, expected_read_lengths, true, LSQ_LIBRARY_UNSTRANDED, out);
+} LSQ_API_CATCH
+int lsq_events_compile_library(const lsq_annotation *a, int n_methods, const char *const *read_types,
+                               const uint64_t *expected_read_lengths, int library, lsq_events **out) LSQ_API_TRY {
+	return lsq::compile_events(a, n_methods, read_types, expected_read_lengths, true, library, out);
+} LSQ_API_CATCH
+int lsq_events_library(const lsq_events *e) { return e ? e->library : LSQ_LIBRARY_UNSTRANDED; }
+int lsq_library_from_name(const char *name) {
+	if (!name) return -1;
+	if (strcmp(name, "unstranded") == 0) return LSQ_LIBRARY_UNSTRANDED;
+	if (strcmp(name, "forward") == 0) return LSQ_LIBRARY_FORWARD;
+	if (strcmp(name, "reverse") == 0) return LSQ_LIBRARY_REVERSE;
+	return -1;
+}
+int64_t lsq_debug_events_covered(const lsq_events *e, const char *chrom, int minus, int64_t *starts, int64_t *ends, int64_t capacity) LSQ_API_TRY {
+	if (!e || !chrom || capacity < 0 || (capacity && (!starts || !ends))) return -1;
+	const int id = e->chroms.find(chrom);
+	if (id < 0 || (size_t)id >= e->n_table_chroms()) return 0;
+	const lsq::IntervalList &il = e->covered[e->table_of((size_t)id, minus ? 1u : 0u)];
+	for (size_t q = 0; q < il.size() && (int64_t)q < capacity; ++q) { starts[q] = il.s[q]; ends[q] = il.e[q]; }
+	return (int64_t)il.size();
 } LSQ_API_CATCH
 void lsq_events_free(lsq_events *e) { delete e; }
 

@@ -18,7 +18,7 @@ namespace lsq {
 int bam_fail(const BamError &e) { return fail(e.status, "%s", e.text.c_str()); }      // (declared in lsq_internal.hpp: the device chain reports through it too)
 
 // the MRF text that defines what the BAM file means: "AlignmentBlocks", '#' per header line, a line per record
-int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify) {
+int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify, int library) {
 	BamStream S;
 	BamError e;
 	if (bam_open((const unsigned char *)bytes, len, host_threads(0), S, e, verify)) return bam_fail(e);
@@ -29,14 +29,14 @@ int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_
 	const int st = bam_for_each_record(S, skip_flags, min_mapq, [&](int64_t ref, bool minus, int64_t bs, int64_t be, int64_t qs, int64_t qe) {
 		if (o.size() > keep) o += ',';
 		o += S.H.ref_names[(size_t)ref];
-		o += minus ? ":-:" : ":+:";
+		o += (minus != (library == LSQ_LIBRARY_REVERSE)) ? ":-:" : ":+:";      // (a library given: the transcript strand)
 		put(bs); o += ':'; put(be); o += ':'; put(qs); o += ':'; put(qe);
 	}, [&](uint64_t, int v) {
 		if (v != SAM_READ) { o.resize(keep); o += '#'; }
 		o += '\n';
 		keep = o.size();
 		return BAM_OK;
-	}, e);
+	}, e, library != LSQ_LIBRARY_UNSTRANDED);
 	return st ? bam_fail(e) : LSQ_OK;
 }
 
@@ -61,7 +61,7 @@ static int bam_parse_file(const char *path, lsq_events *E, unsigned skip_flags, 
 	std::vector<uint16_t> ref_chrom(S.H.ref_names.size(), NOCHROM);
 	for (size_t r = 0; r < ref_chrom.size(); ++r) {
 		const int id = E->chroms.find(S.H.ref_names[r]);
-		if (id >= 0 && (size_t)id < E->covered.size()) ref_chrom[r] = (uint16_t)id;
+		if (id >= 0 && (size_t)id < E->n_table_chroms()) ref_chrom[r] = (uint16_t)id;
 	}
 	int strand_id[2] = {-1, -1};
 	const int64_t LIM = (int64_t)1 << 30;
@@ -84,7 +84,7 @@ static int bam_parse_file(const char *path, lsq_events *E, unsigned skip_flags, 
 		R->o_blk_off.push_back(keep);
 		R->o_line_no.push_back((uint32_t)line_no);
 		return (int)BAM_OK;
-	}, e);
+	}, e, E->stranded());       // (stranded events: the strand of the fragment's first mate, as lsq_sam_parse writes it)
 	if (st) return bam_fail(e);
 	R->adopt();
 	*out = R.release();

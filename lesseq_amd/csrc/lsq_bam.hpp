@@ -178,14 +178,14 @@ inline int bam_open(const unsigned char *file, uint64_t len, int n_threads, BamS
 // Every record in file order: on_block(ref_id, minus, start, end, qstart, qend) as bam_split_record calls it, then
 // on_record(line_no, verdict) -- SAM_NO_READ or SAM_READ; the first malformed record ends the loop with its error.
 template <class OnBlock, class OnRecord>
-inline int bam_for_each_record(const BamStream &S, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block, OnRecord &&on_record, BamError &e) {
+inline int bam_for_each_record(const BamStream &S, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block, OnRecord &&on_record, BamError &e, const bool mate_strand = false) {
 	const unsigned char *s = S.bytes.data();
 	const uint64_t total = S.bytes.size();
 	const int64_t n_ref = (int64_t)S.H.ref_names.size();
 	uint64_t line_no = S.H.h_lines;
 	for (uint64_t p = S.H.end; p < total; p = bam_next_record(s, total, p)) {
 		++line_no;
-		const int v = bam_split_record(s + p, total - p, n_ref, skip_flags, min_mapq, [&](int64_t r) { return S.H.ref_walks[(size_t)r] != 0u; }, on_block);
+		const int v = bam_split_record(s + p, total - p, n_ref, skip_flags, min_mapq, [&](int64_t r) { return S.H.ref_walks[(size_t)r] != 0u; }, on_block, mate_strand);
 		if (v == SAM_MALFORMED) return bam_record_error(e, line_no, p);
 		const int st = on_record(line_no, v);
 		if (st) return st;

@@ -197,7 +197,10 @@ __global__ void __launch_bounds__(256) lsq_bam_offsets_kernel(BamStarts A, const
 #ifndef LSQ_BAM_WAVES
 #define LSQ_BAM_WAVES 6
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_BAM_WAVES))) lsq_bam_route_kernel(BamView R, MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err) {
+// (STRANDED: as the SAM kernels, lsq_sam_device.hpp)
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_BAM_WAVES))) lsq_bam_route_kernel(BamView R, MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	__shared__ RouteChrom chrom_lds[ROUTE_CHROM_LDS];
 	__shared__ unsigned long long strand_lds[256];
 	strand_lds[threadIdx.x & 255u] = __hip_atomic_load(&G.strand_tab[threadIdx.x & 255u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -205,6 +208,8 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_BA
 	__syncthreads();
 	const long long LIM = 1ll << 30;
 	const unsigned long long gsz = (unsigned long long)gridDim.x * blockDim.x;
+	LibTally L;
+	L.init();
 	for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < X.n_lines; i += gsz) {
 		const unsigned long long p = R.rec_off[i];
 		ReadAcc A;
@@ -212,7 +217,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_BA
 		A.init();
 		LocProbe P;
 		P.chrom = -1; P.bin = 0;
-		unsigned cid = MRF_NOCHROM, sid = 0;
+		unsigned cid = MRF_NOCHROM, sid = 0, t = 0;
 		bool looked = false;
 		const int verdict = lsq::bam_split_record(R.s + p, R.len - p, R.n_ref, Q.skip_flags, Q.min_mapq, [&](const int64_t ref) { return R.ref_cid[ref] != BAM_REF_NO_READ; },
 		                                          [&](const int64_t ref, const bool minus, const int64_t start, const int64_t end, int64_t, int64_t) {
@@ -220,18 +225,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_BA
 				// (one reference and one strand a record)
 				looked = true;
 				cid = R.ref_cid[ref];
-				const char sc = minus ? '-' : '+';
+				if constexpr (STRANDED) { t = route_transcript(lib, minus ? 1u : 0u); if (cid != MRF_NOCHROM) cid = route_table(cid, t); }
+				const char sc = (STRANDED ? t != 0u : minus) ? '-' : '+';
 				sid = mrf_strand_slot(strand_lds, G.strand_tab, lsq::MrfView{&sc, 1}, err);
 			}
 			const long long s0 = start - 1, e0 = end;
 			if (cid >= T.n_chrom || e0 >= LIM || s0 >= LIM) return;
 			if (!route_covered(T, chroms[cid], (int)cid, (int)s0, (int)e0, P)) return;
 			A.add(B, cid, sid, (int)s0, (int)e0);
-		});
+		}, STRANDED);
 		if (verdict == lsq::SAM_MALFORMED) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; continue; }
 		if (verdict != lsq::SAM_READ) { O.key[i] = ROUTE_KEY_DROPPED; continue; }
+		if constexpr (STRANDED) L.note(t, A.kept());
 		A.finish(B, T, chroms, P, O, (unsigned)i);
 	}
+	if constexpr (STRANDED) L.flush(O);
 }
 
 // ---- lsq_mrf_parse_device("BAM_SINGLE"): pass 1, blocks per record (0 for records that make no read), first malformed record
@@ -248,7 +256,7 @@ __global__ void __launch_bounds__(256) lsq_bam_count_kernel(BamView R, MrfText X
 
 // pass 2: every read's blocks to their place (as lsq_sam_write_kernel)
 __global__ void __launch_bounds__(256) lsq_bam_write_kernel(BamView R, MrfText X, SamOpts Q, const unsigned *line_nb, const unsigned long long *rd_idx, const unsigned long long *bk_off,
-                                                            MrfDict G, MrfOut O, unsigned long long *err) {
+                                                            MrfDict G, MrfOut O, unsigned long long *err, unsigned mate_strand) {
 	const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
 	if (i >= X.n_lines) return;
 	const long long LIM = 1ll << 30;
@@ -270,7 +278,7 @@ __global__ void __launch_bounds__(256) lsq_bam_write_kernel(BamView R, MrfText X
 		O.blk_start[w] = (int)s0; O.blk_end[w] = (int)e0;
 		O.blk_chrom[w] = (unsigned short)cid; O.blk_strand[w] = (unsigned char)sid;
 		++w;
-	});
+	}, mate_strand != 0u);
 }
 
 // ---- the host side of the chain: a staged file inflated, its header read, its records found
@@ -396,7 +404,7 @@ static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify
 	std::vector<unsigned> ref_cid(B.H.ref_names.size());
 	for (size_t r = 0; r < ref_cid.size(); ++r) {
 		const int id = E ? E->chroms.find(B.H.ref_names[r]) : -1;
-		ref_cid[r] = !B.H.ref_walks[r] ? BAM_REF_NO_READ : (id < 0 || (size_t)id >= E->covered.size()) ? MRF_NOCHROM : (unsigned)id;
+		ref_cid[r] = !B.H.ref_walks[r] ? BAM_REF_NO_READ : (id < 0 || (size_t)id >= E->n_table_chroms()) ? MRF_NOCHROM : (unsigned)id;
 	}
 	// record starts
 	const unsigned nb = (unsigned)B.tab.size();
@@ -435,7 +443,8 @@ static int bam_open_verified(lsq_ctx *c, lsq_text &T, BamRecords &B, bool verify
 static void bam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
 	if (!J.X.n_lines) return;
 	const unsigned grid = (unsigned)std::min<unsigned long long>((J.X.n_lines + 255) / 256, (unsigned long long)J.c->n_cu * 16);
-	hipLaunchKernelGGL(lsq_bam_route_kernel, dim3(grid), dim3(256), 0, s, J.R, J.X, sam_opts(J.c), J.D, RT, O, J.err);
+	if (J.c->E->stranded()) hipLaunchKernelGGL((lsq_bam_route_kernel<true, unsigned>), dim3(grid), dim3(256), 0, s, J.R, J.X, sam_opts(J.c), J.D, RT, O, J.err, lsq::route_lib(J.c));
+	else hipLaunchKernelGGL(lsq_bam_route_kernel<false>, dim3(grid), dim3(256), 0, s, J.R, J.X, sam_opts(J.c), J.D, RT, O, J.err);
 }
 
 } // namespace

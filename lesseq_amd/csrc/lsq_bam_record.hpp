@@ -37,9 +37,9 @@ LSQ_HD inline uint64_t bam_next_record(const unsigned char *s, uint64_t len, uin
 
 // One record: `r` points at its block_size field, `avail` bytes of the stream lie from there on.  ref_walks(refID) says
 // whether the reference's name can be an MRF chromosome (not "*", no ':' or ',', no leading '#').  Calls
-// on_block(refID, minus, start, end, qstart, qend) for every block, in order (1-based inclusive).  Verdicts as sam_split_fields.
+// on_block(refID, minus, start, end, qstart, qend) for every block, in order (1-based inclusive).  Verdicts, and mate_strand, as sam_split_fields.
 template <class RefWalks, class OnBlock>
-LSQ_HD inline int bam_split_record(const unsigned char *r, uint64_t avail, int64_t n_ref, unsigned skip_flags, unsigned min_mapq, RefWalks &&ref_walks, OnBlock &&on_block) {
+LSQ_HD inline int bam_split_record(const unsigned char *r, uint64_t avail, int64_t n_ref, unsigned skip_flags, unsigned min_mapq, RefWalks &&ref_walks, OnBlock &&on_block, const bool mate_strand = false) {
 	if (avail < 4u) return SAM_MALFORMED;
 	const uint64_t block_size = bam_le32(r);
 	if (block_size > avail - 4u || block_size < 32u) return SAM_MALFORMED;
@@ -57,7 +57,7 @@ LSQ_HD inline int bam_split_record(const unsigned char *r, uint64_t avail, int64
 	if (pos < 0 || pos > SAM_POS_MAX) return SAM_MALFORMED;
 	if (n_cigar == 0u) return SAM_NO_READ;
 	if (ref_id < 0 || pos == 0 || !ref_walks(ref_id)) return SAM_NO_READ;
-	const bool minus = (flag & 0x10u) != 0u;
+	const bool minus = ((flag & 0x10u) != 0u) != (mate_strand && sam_flag_mate2(flag));
 	auto emit = [&](int64_t s, int64_t e, int64_t qs, int64_t qe) { on_block(ref_id, minus, s, e, qs, qe); };
 	SamBlockWalk W;
 	W.begin(pos);

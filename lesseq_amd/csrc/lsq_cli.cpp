@@ -247,7 +247,7 @@ int run_bamcheck(int argc, const char *const *argv, std::string &out) {
 // on demand; LSQ_GATHER=host moves the blocks through host memory instead -- for boxes where the "GPUs" are one device)
 // puts the blocks together and thread 0 prints the table, byte-identical to the single-GPU run.
 struct ShardedJob {
-	bool solve; int G; int M;
+	bool solve; int G; int M; int library;
 	const lsq_annotation *ann;
 	std::vector<const char *> fmts, types, paths;
 	std::vector<uint64_t> lens;
@@ -315,7 +315,7 @@ struct SliceContext {
 	int create(const ShardedJob &J, int r) {
 		int q = lsq_ctx_create(J.devices[(size_t)r], &c);
 		if (!q) q = apply_env_options(c);
-		return q ? q : lsq_events_compile(J.ann, J.M, J.types.data(), J.lens.data(), &e);
+		return q ? q : lsq_events_compile_library(J.ann, J.M, J.types.data(), J.lens.data(), J.library, &e);
 	}
 };
 // the developer's way to see the meeting at work: a slice whose number this variable holds fails where its job asks this
@@ -330,6 +330,13 @@ int report_failure(const SliceTeam &team, const std::vector<int> &devices) {
 	if (team.status(r) == LSQ_E_PARSE) { logf(0, "%s", team.error(r).c_str()); logf(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
 	logf(0, "GPU %d: %s", devices[(size_t)r], team.error(r).c_str());
 	return 3;
+}
+// the library report of a stranded job's read file (lsq_last_library_report): how a wrongly chosen library type shows
+void log_library_report(lsq_ctx *c, lsq_events *e, int m) {
+	uint64_t r[5];
+	if (lsq_events_library(e) == LSQ_LIBRARY_UNSTRANDED || lsq_last_library_report(c, m, r) != LSQ_OK) return;
+	logf(2, "Sampling method #%d: %s library: %llu reads of the + strand, %llu retained; %llu of the - strand, %llu retained; %llu without a strand", m,
+	     lsq_events_library(e) == LSQ_LIBRARY_REVERSE ? "reverse" : "forward", (unsigned long long)r[0], (unsigned long long)r[3], (unsigned long long)r[1], (unsigned long long)r[4], (unsigned long long)r[2]);
 }
 // One read file into method m of a context: the staged text where there is one, else the file's text through the device
 // parser, else -- name-keyed formats, strand strings beyond the device parser's 7 bytes -- the host parser.
@@ -544,6 +551,12 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	}
 	const int M = (int)paths.size();
 	if (M > LSQ_MAX_METHODS) { logf(0, "more than %d read files", LSQ_MAX_METHODS); return 2; }
+	// LSQ_LIBRARY=unstranded|forward|reverse: the job's library type; the argv stays the reference's
+	int library = LSQ_LIBRARY_UNSTRANDED;
+	if (const char *e = getenv("LSQ_LIBRARY")) {
+		library = lsq_library_from_name(e);
+		if (library < 0) { logf(0, "LSQ_LIBRARY=%s: the library type is unstranded, forward or reverse", e); return 1; }
+	}
 	// LSQ_DEVICE picks the GPU (cli_device); LSQ_GPUS=N runs the job over N of them (LSQ_DEVICES="a,b,..." names them, default 0..N-1)
 	int G = 1;
 	if (const char *e = getenv("LSQ_GPUS")) G = std::max(1, atoi(e));
@@ -558,6 +571,10 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	bool shard_reads = false;
 	if (const char *e = getenv("LSQ_SHARD")) shard_reads = strcmp(e, "reads") == 0 && G > 1 && !want_fim;
 	for (const char *f : fmts) if (strcmp(f, "MRF_SINGLE") != 0) shard_reads = false;
+	if (shard_reads && library != LSQ_LIBRARY_UNSTRANDED) {
+		logf(1, "LSQ_SHARD=reads: a stranded job (LSQ_LIBRARY=%s) is sharded by events instead", getenv("LSQ_LIBRARY"));
+		shard_reads = false;
+	}
 	Freer F;
 	// the device context (HIP start-up, a tenth of a second or more) is created on a second thread while
 	// this one reads the annotation; its status is looked at only where the reference would be past
@@ -615,7 +632,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 			if (!bad_type) bad_type_name = types[m];
 			bad_type = true; use_types[m] = "SHORT_READ";
 		}
-	st = lsq_events_compile(F.a, M, use_types.data(), lens.data(), &F.e);
+	st = lsq_events_compile_library(F.a, M, use_types.data(), lens.data(), library, &F.e);
 	if (st) { logf(0, "%s", lsq_last_error()); return status_to_exit(st); }
 	const int64_t n_ev = lsq_events_count(F.e);
 	logf(2, "Built isoform structures for the %lld selected gene(s)", (long long)n_ev);
@@ -658,13 +675,14 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 		if (st == LSQ_E_PARSE) { logf(0, "%s", lsq_last_error()); logf(0, "Lexical_cast error when converting arguments to numeric values"); return status_to_exit(st); }
 		if (st) { logf(0, "%s", lsq_last_error()); return st == LSQ_E_DEVICE ? 3 : (st == LSQ_E_IO || st == LSQ_E_FORMAT ? status_to_exit(st) : 2); }
 		logf(2, "Sampling method #%d: loaded %llu reads associated with the selected gene regions", m, (unsigned long long)lsq_reads_retained(F.c, m));
+		log_library_report(F.c, F.e, m);
 		T.mark("reads: copy, parse, ingest");
 		if (T.on) { float h2d = 0, parse = 0; lsq_last_mrf_timing(F.c, &h2d, &parse); fprintf(stderr, "[timing] %-28s %.3f s\n[timing] %-28s %.3f s\n", "  of which text copy", h2d * 1e-3, "  of which parse kernels", parse * 1e-3); }
 	}
 	// (read-sharded: the reads are loaded below, and a line that fails the cast there comes first, as in the reference)
 	if (bad_type && n_ev > 0 && !shard_reads) { logf(0, "Unknown read type error: %s", bad_type_name.c_str()); return 1; }
 	logf(2, "Processing reads info for genes");
-	ShardedJob J{solve, G, M, F.a, fmts, use_types, paths, lens, devices};
+	ShardedJob J{solve, G, M, library, F.a, fmts, use_types, paths, lens, devices};
 	if (shard_reads && n_ev > 0) {
 		const int rc = run_read_sharded_job(J, F.c, F.e);
 		T.mark("read-sharded ingest + count + sum");

@@ -124,6 +124,7 @@ struct MethodReads {
 	size_t exc_cap = 0;
 	bool present = false;
 	uint64_t n_retained = 0, n_retained_blocks = 0, total_slots = 0;
+	uint64_t lib_report[5] = {0, 0, 0, 0, 0};      // stranded jobs: lsq_last_library_report
 	// one- and two-block pools: wide records (2 / 4 ints a read), or compact ones (1 / 2 ints a read, see COMPACT_*) when
 	// at least 15 of 16 such reads fit them; compact pools are padded to whole 16-byte words
 	DevBuf<int32_t> p1, p2, pn_se;

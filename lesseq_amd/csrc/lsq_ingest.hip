@@ -37,25 +37,50 @@ struct IngestRaw {
 #ifndef LSQ_RAW_WAVES
 #define LSQ_RAW_WAVES 8
 #endif
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_RAW_WAVES))) lsq_route_raw_kernel(RouteTables T, IngestRaw R, RouteOut O) {
+// (STRANDED: lsq_route.hpp -- the read's transcript strand is that of its first block's strand id)
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LSQ_RAW_WAVES))) lsq_route_raw_kernel(RouteTables T, IngestRaw R, RouteOut O, Lib... lib_arg) {
 	__shared__ RouteChrom chrom_lds[ROUTE_CHROM_LDS];
 	const RouteChrom *chroms = route_stage_chroms(T, chrom_lds);
 	const unsigned long long gsz = (unsigned long long)gridDim.x * blockDim.x;
 	LocProbe P;
 	P.chrom = -1; P.bin = 0;
-	for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < R.n_reads; i += gsz) {
-		const unsigned long long b0 = R.blk_off[i], b1 = R.blk_off[i + 1];
-		ReadAcc A;
-		ReadBig B;
-		A.init();
-		for (unsigned long long j = b0; j < b1; ++j) {
-			const unsigned c = R.blk_chrom[j];
-			if (c >= T.n_chrom) continue;
-			const int bs = R.blk_start[j], be = R.blk_end[j];
-			if (!route_covered(T, chroms[c], (int)c, bs, be, P)) continue;
-			A.add(B, c, R.blk_strand[j], bs, be);
+	if constexpr (!STRANDED) {
+		for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < R.n_reads; i += gsz) {
+			const unsigned long long b0 = R.blk_off[i], b1 = R.blk_off[i + 1];
+			ReadAcc A;
+			ReadBig B;
+			A.init();
+			for (unsigned long long j = b0; j < b1; ++j) {
+				const unsigned c = R.blk_chrom[j];
+				if (c >= T.n_chrom) continue;
+				const int bs = R.blk_start[j], be = R.blk_end[j];
+				if (!route_covered(T, chroms[c], (int)c, bs, be, P)) continue;
+				A.add(B, c, R.blk_strand[j], bs, be);
+			}
+			A.finish(B, T, chroms, P, O, (unsigned)i);
 		}
-		A.finish(B, T, chroms, P, O, (unsigned)i);
+	} else {
+		const unsigned lib = route_lib_arg(lib_arg...);
+		LibTally L;
+		L.init();
+		for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < R.n_reads; i += gsz) {
+			const unsigned long long b0 = R.blk_off[i], b1 = R.blk_off[i + 1];
+			ReadAcc A;
+			ReadBig B;
+			A.init();
+			const unsigned t = b0 < b1 ? route_transcript_of_id(lib, R.blk_strand[b0]) : ROUTE_NO_STRAND;
+			for (unsigned long long j = b0; j < b1 && t < ROUTE_NO_STRAND; ++j) {
+				const unsigned c = route_table(R.blk_chrom[j], t);       // (a chromosome the events lack, 0xFFFF: its table id lies beyond the tables too)
+				if (c >= T.n_chrom) continue;
+				const int bs = R.blk_start[j], be = R.blk_end[j];
+				if (!route_covered(T, chroms[c], (int)c, bs, be, P)) continue;
+				A.add(B, c, route_strand_id(lib, t), bs, be);
+			}
+			if (b0 < b1) L.note(t, A.kept());
+			A.finish(B, T, chroms, P, O, (unsigned)i);
+		}
+		L.flush(O);
 	}
 }
 
@@ -458,6 +483,10 @@ void stages_collect(lsq_ctx *c) {
 
 } // namespace
 
+unsigned lsq::route_lib(const lsq_ctx *c) {
+	const lsq_events &E = *c->E;
+	return E.stranded() ? route_lib_word(E.library == LSQ_LIBRARY_REVERSE, (unsigned)E.strand_plus, (unsigned)E.strand_minus) : 0u;
+}
 RouteTables lsq::route_tables(lsq_ctx *c) {
 	RouteTables T{};
 	T.chrom = c->route_chrom.p; T.cov = c->cov.p; T.clu = c->clu.p; T.loc = c->loc.p; T.loc_shift = c->loc_shift; T.n_chrom = c->n_chrom_tables;
@@ -487,13 +516,16 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	// counters, one allocation (zeroed per attempt): part_cnt[2B] | part_cur[2B] | piece_cnt[2B] | cntn[B] | cntnb[B] | curn[B] | curnb[B] |
 	// cnt1[FC] | cnt2[FJ] | cur1[FC] | cur2[FJ] | park1[FC] | park2[FJ]
 	const size_t n_cnt = 10 * (size_t)B + 3 * (FC + FJ);
+	// totals: tot[8] | nb_tot[8] | stranded events: the library report's places (lsq_route.hpp)
+	const size_t n_tot = 8 + ROUTE_LIB_WORD0 + (E.stranded() ? 8 * (size_t)ROUTE_LIB_SLOTS : 0);
+	std::vector<unsigned long long> lib_places(E.stranded() ? 8 * (size_t)ROUTE_LIB_SLOTS : 0);
 	DevBuf<unsigned> d_key, d_cnt, d_fine1, d_fine2;
 	DevBuf<int4> d_rec;
 	DevBuf<unsigned long long> d_tot, d_part_off1, d_part_off2, d_piece_off, d_off1, d_off2;
 	DevBuf<uint4> d_nb_ent, d_part1, d_part2, d_pieces;
 	DevBuf<int2> d_nb_blk;
 	ScanScratch SS;
-	if ((rc = d_key.alloc(n)) || (rc = d_rec.alloc(n)) || (rc = d_cnt.alloc(n_cnt)) || (rc = d_tot.alloc(12)) || (rc = d_part_off1.alloc(B + 1)) || (rc = d_part_off2.alloc(B + 1)) ||
+	if ((rc = d_key.alloc(n)) || (rc = d_rec.alloc(n)) || (rc = d_cnt.alloc(n_cnt)) || (rc = d_tot.alloc(n_tot)) || (rc = d_part_off1.alloc(B + 1)) || (rc = d_part_off2.alloc(B + 1)) ||
 	    (rc = d_piece_off.alloc(2 * (size_t)B + 1)) || (rc = d_off1.alloc(FC + 1)) || (rc = d_off2.alloc(FJ + 1)) || (rc = SS.reserve(std::max<size_t>(std::max(FC, FJ), 2 * (size_t)B)))) return rc;
 	unsigned *part_cnt = d_cnt.p, *part_cur = part_cnt + 2 * (size_t)B, *piece_cnt = part_cur + 2 * (size_t)B;
 	unsigned *cntn = piece_cnt + 2 * (size_t)B, *cntnb = cntn + B, *curn = cntnb + B, *curnb = curn + B;
@@ -530,12 +562,12 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	unsigned compact = c->opt_compact_pools ? 1u : 0u;
 	unsigned long long nb_cap = std::max<unsigned long long>(4096, n / 32), nbb_cap = 4 * nb_cap;
 	if (const char *e = getenv("LSQ_NB_LIST")) { const long long v = atoll(e); if (v > 0) { nb_cap = (unsigned long long)v; nbb_cap = 2 * nb_cap; } }      // tests: the list runs over and is sized again
-	unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nb_tot[4] = {0, 0, 0, 0}, sums[5] = {0, 0, 0, 0, 0};      // sums: reads of pool 0 / pool 1 partitions, pieces, n-block reads, their blocks
+	unsigned long long tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, nb_tot[8] = {0, 0, 0, 0, 0, 0, 0, 0}, sums[5] = {0, 0, 0, 0, 0};      // sums: reads of pool 0 / pool 1 partitions, pieces, n-block reads, their blocks
 	for (;;) {
 		if (d_nb_ent.n < nb_cap) { if ((rc = d_nb_ent.alloc((size_t)nb_cap))) return rc; }
 		if (d_nb_blk.n < nbb_cap) { if ((rc = d_nb_blk.alloc((size_t)nbb_cap))) return rc; }
 		HIP_TRY(hipMemsetAsync(d_cnt.p, 0, std::max<size_t>(n_cnt, 1) * 4, st));
-		HIP_TRY(hipMemsetAsync(d_tot.p, 0, 12 * 8, st));
+		HIP_TRY(hipMemsetAsync(d_tot.p, 0, n_tot * 8, st));
 		RouteOut O{};
 		O.key = d_key.p; O.rec = d_rec.p; O.nb_tot = d_tot.p + 8; O.nb_cap = nb_cap; O.nbb_cap = nbb_cap; O.nb_ent = d_nb_ent.p; O.nb_blk = d_nb_blk.p;
 		O.cntn = cntn; O.cntnb = cntnb; O.compact = compact;
@@ -557,7 +589,8 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 			k.end(4ull * n);
 		}
 		HIP_TRY(hipMemcpyAsync(tot, d_tot.p, 8 * 8, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipMemcpyAsync(nb_tot, d_tot.p + 8, 4 * 8, hipMemcpyDeviceToHost, st));
+		HIP_TRY(hipMemcpyAsync(nb_tot, d_tot.p + 8, 8 * 8, hipMemcpyDeviceToHost, st));
+		if (!lib_places.empty()) HIP_TRY(hipMemcpyAsync(lib_places.data(), d_tot.p + 8 + ROUTE_LIB_WORD0, lib_places.size() * 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(&sums[0], d_part_off1.p + B, 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(&sums[1], d_part_off2.p + B, 8, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(&sums[2], d_piece_off.p + 2 * (size_t)B, 8, hipMemcpyDeviceToHost, st));
@@ -671,6 +704,10 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	}
 	if ((rc = upload_strand_ranks(c))) return rc;      // the reads may have introduced new strand strings
 	mr.n_retained = tot[0];
+	for (int q = 0; q < 5; ++q) {          // (the latest routing pass's: LibTally)
+		mr.lib_report[q] = 0;
+		for (size_t k = 0; k < lib_places.size(); k += 8) mr.lib_report[q] += lib_places[k + q];
+	}
 	mr.n_retained_blocks = tot[1] + nb_tot[1];
 	mr.total_slots = n1 + n2 + nn;
 	mr.wg_grid = 0;
@@ -755,7 +792,8 @@ void front_of_raw(lsq_ctx *c, const IngestRaw &Rw, unsigned long long n_blocks, 
 	F.in_bytes = 12ull * Rw.n_reads + 11ull * n_blocks;
 	F.launch = [c, Rw](const RouteTables &T, const RouteOut &O, hipStream_t st) -> int {
 		const unsigned igrid = (unsigned)std::min<unsigned long long>((Rw.n_reads + 255) / 256 + 1, (unsigned long long)c->n_cu * 16);
-		hipLaunchKernelGGL(lsq_route_raw_kernel, dim3(igrid), dim3(256), 0, st, T, Rw, O);
+		if (c->E->stranded()) hipLaunchKernelGGL((lsq_route_raw_kernel<true, unsigned>), dim3(igrid), dim3(256), 0, st, T, Rw, O, route_lib(c));
+		else hipLaunchKernelGGL(lsq_route_raw_kernel<false>, dim3(igrid), dim3(256), 0, st, T, Rw, O);
 		HIP_TRY(hipGetLastError());
 		return LSQ_OK;
 	};
@@ -845,6 +883,13 @@ uint64_t lsq_reads_pooled_blocks(const lsq_ctx *c, int method) {
 	const MethodReads &mr = c->reads[method];
 	return mr.n1_reads + 2 * mr.n2_reads + mr.pn_se.n / 2;
 }
+int lsq_last_library_report(const lsq_ctx *c, int method, uint64_t out[5]) LSQ_API_TRY {
+	if (!c || !out || method < 0 || method >= LSQ_MAX_METHODS) return fail(LSQ_E_ARG, "bad context or method");
+	if (!c->E || !c->E->stranded()) return fail(LSQ_E_STATE, "the events of this context are unstranded: there is no library report");
+	if (!c->reads[method].present) return fail(LSQ_E_STATE, "no reads uploaded for method %d", method);
+	for (int q = 0; q < 5; ++q) out[q] = c->reads[method].lib_report[q];
+	return LSQ_OK;
+} LSQ_API_CATCH
 uint64_t lsq_reads_retained_blocks(const lsq_ctx *c, int method) { return (c && method >= 0 && method < LSQ_MAX_METHODS) ? c->reads[method].n_retained_blocks : 0; }
 
 int lsq_reads_pool_format(const lsq_ctx *c, int method, int *compact, uint64_t *pool_bytes, uint64_t *pool_reads) LSQ_API_TRY {

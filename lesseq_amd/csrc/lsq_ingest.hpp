@@ -21,6 +21,7 @@ struct Front {
 };
 
 RouteTables route_tables(lsq_ctx *c);
+unsigned route_lib(const lsq_ctx *c);          // the `lib` word of the stranded routing kernels (lsq_route.hpp); 0 for unstranded events
 // Runs the chain over the reads a front end delivers.  The stage report (StageClock, lsq_text.hpp) lists the passes the front end has
 // clocked since stages_reset, then the chain's own.
 int ingest_device(lsq_ctx *c, int method, Front &F);

@@ -89,6 +89,7 @@ struct Gene {
 struct Event {
 	std::string gname, chrom, strand;
 	int chrom_id = -1, strand_id = -1;
+	int table_id = -1;                             // the loader tables the event lies in (lsq_events::table_of): its chromosome's, or its (chromosome, strand)'s
 	int K = 0, N = 0;
 	std::vector<int64_t> seg_s, seg_e;             // atomic segments, ascending
 	std::vector<std::string> iso_names;
@@ -236,7 +237,22 @@ struct lsq_events {
 	std::vector<std::string> read_types;
 	std::vector<uint64_t> read_lengths;
 	lsq::Dict chroms, strands;
-	std::vector<lsq::IntervalList> covered;        // by chrom id (events' chromosomes)
+	// The library type (LSQ_LIBRARY_*).  Every table of the loader below -- covered, clu_s / clu_e, cut_lo,
+	// chrom_first_bucket, BucketDesc::chrom_id, the RouteChrom records and the locator grid made from them (lsq_device.hip) -- is
+	// indexed by a TABLE id: the chromosome id in an unstranded job; 2 * chromosome id + (1 for the minus strand) in a stranded
+	// one, where plus and minus genes of a chromosome share nothing.  Chromosome ids themselves (lsq_events_chrom_id, the ids of
+	// lsq_reads arrays) stay one per name.
+	int library = LSQ_LIBRARY_UNSTRANDED;
+	bool stranded() const { return library != LSQ_LIBRARY_UNSTRANDED; }
+	size_t table_of(size_t chrom_id, unsigned minus) const { return stranded() ? 2 * chrom_id + (minus & 1u) : chrom_id; }
+	size_t n_table_chroms() const { return stranded() ? covered.size() / 2 : covered.size(); }      // chromosome ids that have tables
+	int strand_plus = -1, strand_minus = -1;       // stranded: the ids of "+" and "-" in `strands`
+	// The transcript strand (0 plus, 1 minus) of a record whose alignment strand is `minus`, in this job's library; mate2: the
+	// record is the second mate of a pair (SAM / BAM only)
+	unsigned transcript_minus(bool minus, bool mate2) const { return (unsigned)(minus != mate2) ^ (unsigned)(library == LSQ_LIBRARY_REVERSE); }
+	// ... of a strand string: 0, 1, or 2 when it is neither "+" nor "-" (no transcript strand: the record makes no read)
+	unsigned transcript_of(const char *p, size_t n) const { return n == 1 && (p[0] == '+' || p[0] == '-') ? transcript_minus(p[0] == '-', false) : 2u; }
+	std::vector<lsq::IntervalList> covered;        // by table id (events' chromosomes)
 	// ---- device plan
 	uint64_t shard_first = 0, shard_count = UINT64_MAX;   // events (output order) this process works on
 	uint32_t lds_budget = 0;
@@ -257,8 +273,8 @@ struct lsq_events {
 	std::vector<uint8_t> dev_K;                    // device order
 	uint32_t n_cls_total = 0, n_iso_total = 0;
 	uint32_t max_lds_bytes = 0;                    // image + histogram, max over buckets
-	// bucket lookup: per chrom id, ascending cut coordinates and the bucket of each range
-	// per chrom id: the merged spans of the planned events (clusters of transitively overlapping spans), ascending.  A read
+	// bucket lookup: per table id, ascending cut coordinates and the bucket of each range
+	// per table id: the merged spans of the planned events (clusters of transitively overlapping spans), ascending.  A read
 	// is a candidate of an event only if its first base lies in the event's span (count/count.cpp:429-432,463), so a read
 	// that starts outside every cluster is dropped at ingest -- with a shard (lsq_events_set_shard) those are the reads of
 	// the other shards' events, which pass the load-time filter of the whole range but concern no event planned here
@@ -293,6 +309,7 @@ struct lsq_reads {
 namespace lsq {
 
 int plan_device(lsq_events &E);
+int compile_events(const lsq_annotation *a, int n_methods, const char *const *read_types, const uint64_t *expected_read_lengths, bool device_plan, int library, lsq_events **out);
 int host_threads(int requested);
 void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
 int cli_device();                                                            // lsq_cli.cpp: the GPU the environment picks for an executable (default 0)
@@ -301,6 +318,6 @@ int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out); 
 struct BamError;
 bool device_read_format(const char *name);                                   // lsq_readfile.hip: a read format the device parses from the file's own bytes (READ_FORMATS names them)
 int bam_fail(const BamError &e);                                             // lsq_bam.cpp: a BAM error (lsq_bam.hpp) as the calling thread's status and text
-int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify = false);      // lsq_bam.cpp (verify: CRC32s and end-of-file marker)
+int bam_to_mrf(const char *bytes, size_t len, unsigned skip_flags, unsigned min_mapq, std::string &o, bool verify = false, int library = LSQ_LIBRARY_UNSTRANDED);      // lsq_bam.cpp (verify: CRC32s and end-of-file marker; library: the strand column holds the transcript strand)
 
 } // namespace lsq

@@ -72,7 +72,7 @@ void parse_chunk(Chunk &ck, lsq_events *E, const SamOpts *sam) {
 			if (last_chrom_id == -2 || last_chrom.size() != chr.n || memcmp(last_chrom.data(), chr.p, chr.n) != 0) {
 				last_chrom.assign(chr.p, chr.n);
 				int id = E->chroms.find(last_chrom);
-				last_chrom_id = (id < 0 || (size_t)id >= E->covered.size()) ? (int)NOCHROM : id;
+				last_chrom_id = (id < 0 || (size_t)id >= E->n_table_chroms()) ? (int)NOCHROM : id;
 			}
 			int sid = -1;
 			for (auto &c : sc) if (c.id >= 0 && c.s.size() == strand.n && memcmp(c.s.data(), strand.p, strand.n) == 0) { sid = c.id; break; }
@@ -96,7 +96,7 @@ void parse_chunk(Chunk &ck, lsq_events *E, const SamOpts *sam) {
 			const size_t keep = ck.bs.size();
 			const int v = sam_split_line(line, sam->skip_flags, sam->min_mapq, [&](MrfView chr, bool minus, int64_t start, int64_t end, int64_t, int64_t) {
 				take(chr, MrfView{minus ? "-" : "+", 1}, start, end);
-			});
+			}, E->stranded());       // (stranded events: the strand of the fragment's first mate -- lsq_reads_upload derives the transcript strand from it)
 			ok = v != SAM_MALFORMED;
 			if (ok && v != SAM_READ) { ck.bs.resize(keep); ck.be.resize(keep); ck.bc.resize(keep); ck.bst.resize(keep); continue; }
 		} else ok = mrf_split_line(line, take);
@@ -250,16 +250,21 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 	std::unordered_map<std::string, uint32_t> by_name;
 	std::vector<std::string> names;
 	const int64_t LIM = (int64_t)1 << 30;
-	auto chrom_of = [&](const std::string &c) -> int { int id = E->chroms.find(c); return (id < 0 || (size_t)id >= E->covered.size()) ? -1 : id; };
-	auto covered = [&](int chrom, int64_t s, int64_t e) -> bool {
+	auto chrom_of = [&](const std::string &c) -> int { int id = E->chroms.find(c); return (id < 0 || (size_t)id >= E->n_table_chroms()) ? -1 : id; };
+	// (stranded events: against the covered regions of the line's transcript strand; a line without one is dropped beforehand)
+	auto covered = [&](int chrom, unsigned t, int64_t s, int64_t e) -> bool {
 		if (!(s < e)) return true;                       // contains_interval of an empty interval (interval_list.hpp:396-422)
-		return chrom >= 0 && E->covered[chrom].contains(s, e);
+		return chrom >= 0 && E->covered[E->table_of((size_t)chrom, t)].contains(s, e);
 	};
+	auto transcript = [&](const std::string &strand) -> unsigned { return E->stranded() ? E->transcript_of(strand.data(), strand.size()) : 0u; };
 	auto strand_of = [&](const std::string &st, int &sid) -> bool { sid = E->strands.intern(st); return sid <= 255; };
-	auto push = [&](const std::string &name, int chrom, int sid, int nblk, const int64_t *bs, const int64_t *be) {
-		auto it = by_name.find(name);
+	// (stranded events: a name whose lines lie on both transcript strands is a read per strand, as it is in the two split jobs that
+	// define the stranded one -- lsq_reads_upload routes a read by one strand)
+	auto push = [&](const std::string &name, unsigned t, int chrom, int sid, int nblk, const int64_t *bs, const int64_t *be) {
+		const std::string key = E->stranded() ? name + (t ? "\x01-" : "\x01+") : name;
+		auto it = by_name.find(key);
 		uint32_t r;
-		if (it == by_name.end()) { r = (uint32_t)names.size(); by_name.emplace(name, r); names.push_back(name); } else r = it->second;
+		if (it == by_name.end()) { r = (uint32_t)names.size(); by_name.emplace(key, r); names.push_back(name); } else r = it->second;
 		for (int k = 0; k < nblk; k += 2) {
 			Line l; l.read = r; l.strand = (uint8_t)sid; l.n = (uint8_t)std::min(2, nblk - k);
 			l.chrom = chrom < 0 ? NOCHROM : (uint16_t)chrom;
@@ -302,17 +307,19 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 			iss >> chr >> tmp >> tmp >> start >> end >> tmp >> strand >> tmp >> rname;
 			if (iss.fail()) { status = LSQ_E_ARG; err = "line " + std::to_string(line_no) + " does not have the UCSC_GFF columns (the reference reads uninitialised coordinates here)"; break; }
 			const int chrom = chrom_of(chr);
-			if (!covered(chrom, (int64_t)start - 1, end)) continue;
+			const unsigned t = transcript(strand);
+			if (t > 1u || !covered(chrom, t, (int64_t)start - 1, end)) continue;
 			if (!strand_of(strand, sid)) { status = LSQ_E_RANGE; err = "more than 256 distinct strand strings"; break; }
 			const int64_t bs[1] = {(int64_t)start - 1}, be[1] = {end};
-			push(rname, chrom, sid, 1, bs, be);
+			push(rname, t, chrom, sid, 1, bs, be);
 		} else if (fmt == "UCSC_BED") {
 			int64_t start, end, nb;
 			size_t b, e;
 			if (!cast_field(ln, 1, start) || !cast_field(ln, 2, end)) { status = LSQ_E_PARSE; err = "#" + std::to_string(line_no) + ":" + ln; break; }
 			std::string chr = field(ln, 0, b, e) ? ln.substr(b, e - b) : std::string();
 			const int chrom = chrom_of(chr);
-			if (!covered(chrom, start, end)) continue;
+			const unsigned t = transcript(field(ln, 5, b, e) ? ln.substr(b, e - b) : std::string());
+			if (t > 1u || !covered(chrom, t, start, end)) continue;
 			if (!cast_field(ln, 9, nb)) { status = LSQ_E_PARSE; err = "#" + std::to_string(line_no) + ":" + ln; break; }
 			std::string rname = field(ln, 3, b, e) ? ln.substr(b, e - b) : std::string();
 			std::string strand = field(ln, 5, b, e) ? ln.substr(b, e - b) : std::string();
@@ -333,7 +340,7 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 				ps = qs + 1; pz = qz + 1;
 			}
 			if (status != LSQ_OK) break;
-			push(rname, chrom, sid, (int)bs.size(), bs.data(), be.data());
+			push(rname, t, chrom, sid, (int)bs.size(), bs.data(), be.data());
 		} else {
 			int64_t start, end;
 			size_t b, e;
@@ -368,10 +375,11 @@ int lsq_reads_parse(const char *read_format, const char *path, lsq_events *E, in
 			}
 			if (status != LSQ_OK) break;
 			const int chrom = chrom_of(chr);
-			if (!covered(chrom, start - 1, end)) continue;
+			const unsigned t = transcript(strand);
+			if (t > 1u || !covered(chrom, t, start - 1, end)) continue;
 			if (!strand_of(strand, sid)) { status = LSQ_E_RANGE; err = "more than 256 distinct strand strings"; break; }
-			if (!found_parent) { const int64_t bs[1] = {start - 1}, be[1] = {end}; push(rname, chrom, sid, 1, bs, be); }
-			else { const int64_t bs[2] = {start - 1, end2}, be[2] = {start2 - 1, end}; push(rname, chrom, sid, 2, bs, be); }
+			if (!found_parent) { const int64_t bs[1] = {start - 1}, be[1] = {end}; push(rname, t, chrom, sid, 1, bs, be); }
+			else { const int64_t bs[2] = {start - 1, end2}, be[2] = {start2 - 1, end}; push(rname, t, chrom, sid, 2, bs, be); }
 		}
 	}
 	if (status != LSQ_OK) return fail(status, "%s", err.c_str());

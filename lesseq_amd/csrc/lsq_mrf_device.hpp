@@ -185,9 +185,16 @@ __device__ inline unsigned mrf_strand_slot(const unsigned long long *lds_tab, un
 
 // ---- the parse that feeds the load-time filter (the product path): per line, every block through the covered regions and
 // the merge as it is split off; the routed read to key[i] / rec[i], i the data line's index
+// t of an MRF strand column: exactly "+" or "-" (lsq_route.hpp)
 template <class V>
+__device__ inline unsigned mrf_transcript(const unsigned lib, const V strand) {
+	if (strand.n != 1 || (strand.p[0] != '+' && strand.p[0] != '-')) return ROUTE_NO_STRAND;
+	return route_transcript(lib, strand.p[0] == '-' ? 1u : 0u);
+}
+// (STRANDED: the read's transcript strand is that of its first block's strand column; every block of it goes by that one)
+template <bool STRANDED, class V>
 __device__ inline void mrf_route_line(const MrfText &X, const MrfDict &D, const unsigned long long *lds_strand, const RouteTables &T, const RouteChrom *chroms, const RouteOut &O,
-                                      unsigned long long *err, const unsigned long long i, const V line) {
+                                      unsigned long long *err, const unsigned long long i, const V line, const unsigned lib, LibTally &L) {
 	const long long LIM = 1ll << 30;
 	if (lsq::mrf_line_is_skipped(line)) { O.key[i] = ROUTE_KEY_DROPPED; return; }
 	ReadAcc A;
@@ -195,34 +202,51 @@ __device__ inline void mrf_route_line(const MrfText &X, const MrfDict &D, const 
 	A.init();
 	LocProbe P;
 	P.chrom = -1; P.bin = 0;
+	unsigned t = 3u;                        // (STRANDED; 3: no block seen yet)
 	const bool ok = lsq::mrf_split_line(line, [&](const V chr, const V strand, const int64_t start, const int64_t end) {
-		const unsigned cid = mrf_chrom_lookup(D, chr);
+		unsigned cid = mrf_chrom_lookup(D, chr);
 		const long long s0 = start - 1, e0 = end;
+		if constexpr (STRANDED) {
+			if (t == 3u) t = mrf_transcript(lib, strand);
+			if (t >= ROUTE_NO_STRAND || cid == MRF_NOCHROM) return;
+			cid = route_table(cid, t);
+		}
 		if (cid >= T.n_chrom || s0 <= -LIM || e0 >= LIM || s0 >= LIM || e0 <= -LIM) return;
 		if (!route_covered(T, chroms[cid], (int)cid, (int)s0, (int)e0, P)) return;
-		A.add(B, cid, mrf_strand_slot(lds_strand, D.strand_tab, strand, err), (int)s0, (int)e0);
+		if constexpr (STRANDED) { const char tc = t ? '-' : '+'; A.add(B, cid, mrf_strand_slot(lds_strand, D.strand_tab, lsq::MrfView{&tc, 1}, err), (int)s0, (int)e0); }
+		else A.add(B, cid, mrf_strand_slot(lds_strand, D.strand_tab, strand, err), (int)s0, (int)e0);
 	});
 	if (!ok) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; return; }
+	if constexpr (STRANDED) { if (t != 3u) L.note(t, A.kept()); }
 	A.finish(B, T, chroms, P, O, (unsigned)i);
 }
 
-__global__ void __launch_bounds__(256) lsq_mrf_route_kernel(MrfText X, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles, unsigned listed) {
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) lsq_mrf_route_kernel(MrfText X, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles, unsigned listed, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	__shared__ MrfTileLds S;
 	const MrfDict D = mrf_stage_dict(S, G);
 	const RouteChrom *chroms = route_stage_chroms(T, S.chrom);
 	const unsigned n = listed ? min(H.counts[0], H.tile_cap) : n_tiles;
+	LibTally L;
+	L.init();
 	for (unsigned t = blockIdx.x; t < n; t += gridDim.x) {
 		const unsigned tile = listed ? H.tiles[t] : t;
 		mrf_tile_lines<true>(S, tile, X.text, X.len, X.tile_base, X.has_header, H.lines, H.counts + 1, H.line_cap, H.counts + 2, [&](const unsigned long long i, const MrfLdsView line) {
-			mrf_route_line(X, D, S.strand, T, chroms, O, err, i, line);
+			mrf_route_line<STRANDED>(X, D, S.strand, T, chroms, O, err, i, line, lib, L);
 		});
 		__syncthreads();
 	}
+	if constexpr (STRANDED) L.flush(O);
 }
 // listed lines, one lane each, straight from HBM.  A line listed without its start (n = ~0: it began ahead of a tile's
 // window) is walked back to the newline before it first.
-__global__ void __launch_bounds__(256) lsq_mrf_route_lines_kernel(MrfText X, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H) {
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) lsq_mrf_route_lines_kernel(MrfText X, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	const unsigned n = min(H.counts[1], H.line_cap);
+	LibTally LT;
+	LT.init();
 	for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
 		MrfLongLine L = H.lines[t];
 		if (L.n == ~0ull) {
@@ -231,8 +255,9 @@ __global__ void __launch_bounds__(256) lsq_mrf_route_lines_kernel(MrfText X, Mrf
 			while (a > 0 && X.text[a - 1] != '\n') --a;
 			L.n = L.start - a; L.start = a;
 		}
-		mrf_route_line(X, G, nullptr, T, T.chrom, O, err, L.i, lsq::MrfView{reinterpret_cast<const char *>(X.text) + L.start, (size_t)L.n});
+		mrf_route_line<STRANDED>(X, G, nullptr, T, T.chrom, O, err, L.i, lsq::MrfView{reinterpret_cast<const char *>(X.text) + L.start, (size_t)L.n}, lib, LT);
 	}
+	if constexpr (STRANDED) LT.flush(O);
 }
 
 // ---- the fast kernel.  A workgroup takes a window of 8 KiB of text -- a tile of 7 680 bytes and the 512 ahead of it -- 32
@@ -322,9 +347,16 @@ __device__ inline bool fp_number8(const unsigned long long w, const unsigned len
 	return digits;
 }
 
-__global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_kernel(MrfText X, MrfDict G, MrfFastDict FD, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles) {
+// (STRANDED, lsq_route.hpp: step (2) filters a block against the tables of its own strand column's t and notes t for the blocks it
+// passes over; step (3) takes the read's t from its first block, and a line whose blocks disagree goes to the list, where
+// mrf_route_line settles it)
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_kernel(MrfText X, MrfDict G, MrfFastDict FD, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	__shared__ MrfFastLds S;
 	const unsigned tid = threadIdx.x;
+	LibTally L;
+	L.init();
 	// ---- the dictionaries
 	if (tid < FP_STRANDS) S.strand[tid] = __hip_atomic_load(&G.strand_tab[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 	S.ckey[tid] = FD.ckey[tid]; S.cid[tid] = FD.cid[tid];
@@ -497,7 +529,13 @@ __global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_ke
 				if (l_e == 9u) { good = good && e9 <= 9u; ve += e9 * 100000000u; }
 				if (good) {
 					out.w = 1u;
-					if (l_chr != 0u) {
+					unsigned tb = 0u;
+					if constexpr (STRANDED) {
+						const unsigned char c0 = (unsigned char)wt;
+						tb = l_str == 1u && (c0 == '+' || c0 == '-') ? route_transcript(lib, c0 == '-' ? 1u : 0u) : ROUTE_NO_STRAND;
+						out.x = tb;
+					}
+					if (l_chr != 0u && tb < ROUTE_NO_STRAND) {
 						const unsigned long long kb = wc & ((1ull << (8u * l_chr)) - 1ull);
 						const unsigned long long key = ((unsigned long long)__builtin_bswap32((unsigned)kb) << 32) | (unsigned long long)__builtin_bswap32((unsigned)(kb >> 32)) | (unsigned long long)l_chr;
 						unsigned cid = MRF_NOCHROM;
@@ -509,12 +547,15 @@ __global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_ke
 						const int s0 = (int)vs - 1, e0 = (int)ve;
 						LocProbe P;
 						P.chrom = -1; P.bin = 0;
+						if constexpr (STRANDED) { if (cid != MRF_NOCHROM) cid = route_table(cid, tb); }
 						if (cid < T.n_chrom && route_covered(T, S.chrom[cid], (int)cid, s0, e0, P)) {
-							const unsigned long long tb = wt & ((1ull << (8u * l_str)) - 1ull);
-							const unsigned long long tkey = ((unsigned long long)__builtin_bswap32((unsigned)tb) << 32) | (unsigned long long)__builtin_bswap32((unsigned)(tb >> 32)) | (unsigned long long)l_str;
+							const unsigned long long sb = wt & ((1ull << (8u * l_str)) - 1ull);
+							unsigned long long tkey = ((unsigned long long)__builtin_bswap32((unsigned)sb) << 32) | (unsigned long long)__builtin_bswap32((unsigned)(sb >> 32)) | (unsigned long long)l_str;
+							if constexpr (STRANDED) tkey = ((unsigned long long)(tb ? '-' : '+') << 56) | 1ull;       // (the read carries t's string)
 							unsigned sid = 256u;
 							for (unsigned z = 0; z < FP_STRANDS; ++z) { const unsigned long long cur = S.strand[z]; if (cur == tkey) { sid = z; break; } if (cur == STRAND_EMPTY) break; }
-							if (sid == 256u) sid = mrf_strand_slot(nullptr, G.strand_tab, MrfLdsView{text + (p1 + 1u), l_str}, err);
+							if constexpr (STRANDED) { if (sid == 256u) { const char tc = tb ? '-' : '+'; sid = mrf_strand_slot(nullptr, G.strand_tab, lsq::MrfView{&tc, 1}, err); } }
+							else if (sid == 256u) sid = mrf_strand_slot(nullptr, G.strand_tab, MrfLdsView{text + (p1 + 1u), l_str}, err);
 							out = make_uint4(cid | (sid << 16), (unsigned)s0, (unsigned)e0, 0u);
 						}
 					}
@@ -530,21 +571,30 @@ __global__ void __launch_bounds__(256) LSQ_FAST_WAVES_ATTR lsq_mrf_route_fast_ke
 				ReadAcc A;
 				ReadBig B;
 				A.init();
+				unsigned t = ROUTE_NO_STRAND;
 				for (unsigned q = 0; q < nb; ++q) {
 					const uint4 r = S.blk[first + q];
 					if (r.w == 2u) { odd = true; break; }
+					if constexpr (STRANDED) {
+						// (a kept block's table id is odd for t = minus; a block passed over holds t itself)
+						const unsigned tq = r.w == 0u ? (r.x & 1u) : r.x;
+						if (q == 0u) t = tq;
+						else if (tq != t) { odd = true; break; }
+					}
 					if (r.w == 0u) A.add(B, r.x & 0xFFFFu, r.x >> 16, (int)r.y, (int)r.z);
 				}
 				if (odd) defer(i, w0 + start, eol - start);
 				else {
 					LocProbe P;
 					P.chrom = -1; P.bin = 0;
+					if constexpr (STRANDED) L.note(t, A.kept());
 					A.finish(B, T, S.chrom, P, O, (unsigned)i);
 				}
 			}
 		}
 	}
 	}
+	if constexpr (STRANDED) L.flush(O);
 }
 
 // ---- the same walk for lsq_mrf_parse_device: pass 1, blocks per data line (0 for skipped lines), first failing line
@@ -592,10 +642,10 @@ static int mrf_prepare(TextJob &J) {
 	int rc;
 	// the chromosomes' names as 64-bit keys (names of at most seven bytes; a longer one has no slot and its lines go to the list)
 	const lsq_events &E = *J.c->E;
-	const size_t nc = E.covered.size();
+	const size_t nc = E.n_table_chroms();          // (chromosome ids that have tables)
 	std::vector<unsigned long long> ck(FP_DICT, 0);
 	std::vector<unsigned short> ci(FP_DICT, 0);
-	const bool usable = nc <= ROUTE_CHROM_LDS && getenv("LSQ_MRF_SLOW") == nullptr;       // (LSQ_MRF_SLOW: the tests run the byte-walking kernel over whole files with it)
+	const bool usable = E.covered.size() <= ROUTE_CHROM_LDS && getenv("LSQ_MRF_SLOW") == nullptr;       // (the fast kernel keeps every table's record in LDS; LSQ_MRF_SLOW: the tests run the byte-walking kernel over whole files with it)
 	for (size_t id = 0; usable && id < nc; ++id) {
 		const std::string &nm = E.chroms.names[id];
 		if (nm.empty() || nm.size() > 7) continue;
@@ -616,11 +666,21 @@ static void mrf_launch(const TextJob &J, const RouteTables &RT, const RouteOut &
 	unsigned fast_grid = std::max(J.n_tiles, 1u);
 	if (const char *e = getenv("LSQ_FAST_GRID")) { const int v = atoi(e); if (v > 0) fast_grid = (unsigned)v * n_cu; }
 	const MrfFastDict FD{J.tab64.p, J.tab16.p, 1u};        // (usable, or J.all_slow is set)
+	const unsigned lib = lsq::route_lib(J.c);
+	const dim3 lines_grid(std::min(J.H.line_cap / 256u + 1u, 1024u));
+	if (J.c->E->stranded()) {
+		if (!J.all_slow) {
+			hipLaunchKernelGGL((lsq_mrf_route_fast_kernel<true, unsigned>), dim3(std::min(J.n_tiles, fast_grid)), dim3(256), 0, s, J.X, J.D, FD, RT, O, J.err, J.H, J.n_tiles, lib);
+			hipLaunchKernelGGL((lsq_mrf_route_kernel<true, unsigned>), dim3(std::min(side_grid, 256u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 1u, lib);
+		} else hipLaunchKernelGGL((lsq_mrf_route_kernel<true, unsigned>), dim3(J.n_tiles), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 0u, lib);
+		hipLaunchKernelGGL((lsq_mrf_route_lines_kernel<true, unsigned>), lines_grid, dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, lib);
+		return;
+	}
 	if (!J.all_slow) {
-		hipLaunchKernelGGL(lsq_mrf_route_fast_kernel, dim3(std::min(J.n_tiles, fast_grid)), dim3(256), 0, s, J.X, J.D, FD, RT, O, J.err, J.H, J.n_tiles);
-		hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(std::min(side_grid, 256u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 1u);
-	} else hipLaunchKernelGGL(lsq_mrf_route_kernel, dim3(J.n_tiles), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 0u);
-	hipLaunchKernelGGL(lsq_mrf_route_lines_kernel, dim3(std::min(J.H.line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H);
+		hipLaunchKernelGGL(lsq_mrf_route_fast_kernel<false>, dim3(std::min(J.n_tiles, fast_grid)), dim3(256), 0, s, J.X, J.D, FD, RT, O, J.err, J.H, J.n_tiles);
+		hipLaunchKernelGGL(lsq_mrf_route_kernel<false>, dim3(std::min(side_grid, 256u)), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 1u);
+	} else hipLaunchKernelGGL(lsq_mrf_route_kernel<false>, dim3(J.n_tiles), dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H, J.n_tiles, 0u);
+	hipLaunchKernelGGL(lsq_mrf_route_lines_kernel<false>, lines_grid, dim3(256), 0, s, J.X, J.D, RT, O, J.err, J.H);
 }
 static void mrf_record(const TextJob &J) {
 	J.c->parse_tiles_handed = J.all_slow ? 0u : J.counts[0]; J.c->parse_lines_listed = J.counts[1]; J.c->parse_all_slow = J.all_slow ? 1u : 0u;

@@ -23,7 +23,7 @@ struct MrfDictDev {
 	int build(lsq_ctx *c, hipStream_t st) {
 		lsq_events &E = *c->E;
 		int rc;
-		const size_t nc = E.covered.size();
+		const size_t nc = E.n_table_chroms();          // (chromosome ids that have tables)
 		size_t tab = 2;
 		while (tab < 4 * nc) tab <<= 1;
 		std::vector<unsigned> h_hash(tab, 0), h_id(tab, 0), h_off(nc + 1, 0);
@@ -204,12 +204,12 @@ const ReadFormat READ_FORMATS[] = {
 	{"SAM_SINGLE", 0u, "LSQ_SAM_LINE_LIST", "sam_route", text_open, text_fail_line, sam_prepare, sam_launch, sam_record,
 	 [](const TextJob &J, hipStream_t st, unsigned *nb) { hipLaunchKernelGGL(lsq_sam_count_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, J.err); },
 	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
-		 hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
+		 hipLaunchKernelGGL(lsq_sam_write_kernel, dim3(J.n_tiles), dim3(256), 0, st, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err, J.c->E->stranded() ? 1u : 0u); }},
 	{"BAM_SINGLE", 0u, nullptr, "bam_route", bam_open, bam_fail_record, nullptr, bam_launch, nullptr,
 	 [](const TextJob &J, hipStream_t st, unsigned *nb) {
 		 hipLaunchKernelGGL(lsq_bam_count_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, J.err); },
 	 [](const TextJob &J, hipStream_t st, const unsigned *nb, const unsigned long long *rd, const unsigned long long *bk, const MrfOut &O) {
-		 hipLaunchKernelGGL(lsq_bam_write_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err); }},
+		 hipLaunchKernelGGL(lsq_bam_write_kernel, dim3((unsigned)((J.X.n_lines + 255) / 256)), dim3(256), 0, st, J.R, J.X, sam_opts(J.c), nb, rd, bk, J.D, O, J.err, J.c->E->stranded() ? 1u : 0u); }},
 };
 // the format a caller names (looked up once its file has been opened: the order in which the reference meets a bad file or literal)
 int read_format_named(const char *name, const ReadFormat *&fmt) {

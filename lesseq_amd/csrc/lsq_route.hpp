@@ -32,7 +32,7 @@ struct RouteOut {
 	unsigned *key;                 // per read
 	int4 *rec;                     // per read: its first two merged blocks (s0, e0, s1, e1)
 	// reads of pools 2 and 3: a list (they are few in short-read files; a file of long reads fills it, and the ingest sizes it again)
-	unsigned long long *nb_tot;    // [0] entries wanted, [1] blocks wanted, [2] error flag (a read beyond the tables' range)
+	unsigned long long *nb_tot;    // [0] entries wanted, [1] blocks wanted, [2] error flag (a read beyond the tables' range); from [ROUTE_LIB_WORD0] on: a stranded pass's library report (LibTally)
 	unsigned long long nb_cap, nbb_cap;
 	uint4 *nb_ent;                 // read index, bucket, blocks | strand << 8, first block in nb_blk
 	int2 *nb_blk;
@@ -40,7 +40,56 @@ struct RouteOut {
 	unsigned compact;              // compact pool records: one- and two-block reads that do not fit them go to pool 3
 };
 
+// ---- stranded jobs.  Every routing kernel has a stranded form, a template parameter: it derives the transcript
+// strand t of a record (0 plus, 1 minus, ROUTE_NO_STRAND none), and everything it does with the record's chromosome -- the
+// chromosome record, route_covered, ReadAcc::add / finish, route_cluster -- it does with the TABLE id route_table(chromosome, t)
+// instead (lsq_events::table_of); a record without t makes no read; the read carries t's string as its strand.  The word `lib`
+// such a kernel takes as its last argument (route_lib_word): bit 0 -- the library is `reverse`; bits 8-15 / 16-23 -- the strand
+// ids of "+" / "-".  The argument is a parameter pack, empty in the unstranded form (kernel<false>; kernel<true, unsigned>): that
+// form's arguments, and so its code, are what they were before there was a stranded one.
+constexpr unsigned ROUTE_NO_STRAND = 2u;
+constexpr unsigned ROUTE_LIB_SLOTS = 1024u, ROUTE_LIB_WORD0 = 8u;      // the library report's places behind RouteOut::nb_tot: eight words each, five used
+__host__ __device__ inline unsigned route_lib_word(bool reverse, unsigned plus_id, unsigned minus_id) { return (reverse ? 1u : 0u) | (plus_id << 8) | (minus_id << 16); }
+__host__ __device__ inline unsigned route_lib_arg() { return 0u; }
+__host__ __device__ inline unsigned route_lib_arg(unsigned lib) { return lib; }
+__host__ __device__ inline unsigned route_table(unsigned chrom, unsigned t) { return 2u * chrom + t; }
+// t of an alignment strand (minus: 0 / 1; SAM and BAM: already XOR mate2)
+__host__ __device__ inline unsigned route_transcript(unsigned lib, unsigned minus) { return (minus ^ lib) & 1u; }
+// ... of a strand id
+__host__ __device__ inline unsigned route_transcript_of_id(unsigned lib, unsigned sid) {
+	return sid == ((lib >> 8) & 0xFFu) ? route_transcript(lib, 0u) : sid == ((lib >> 16) & 0xFFu) ? route_transcript(lib, 1u) : ROUTE_NO_STRAND;
+}
+__host__ __device__ inline unsigned route_strand_id(unsigned lib, unsigned t) { return (lib >> (t ? 16 : 8)) & 0xFFu; }
+
 namespace {      // (device code of the unit that includes it: internal linkage, as the kernels that call it)
+
+// The library report of a stranded pass: per lane what its records came to, summed over the wave when the kernel ends, one atomic a
+// wave and counter -- reads made with t = plus / minus, records without t, and of the first two those the filter retained.  The
+// waves spread their sums over ROUTE_LIB_SLOTS places of 64 bytes behind RouteOut::nb_tot (the host adds the places up): a tile
+// kernel runs a workgroup a tile, and that many atomics on five addresses took twelve times the routing itself.
+struct LibTally {
+	unsigned made0, made1, none, kept0, kept1;
+	__device__ inline void init() { made0 = made1 = none = kept0 = kept1 = 0u; }
+	__device__ inline void note(const unsigned t, const bool kept) {
+		made0 += (unsigned)(t == 0u); made1 += (unsigned)(t == 1u); none += (unsigned)(t >= ROUTE_NO_STRAND);
+		kept0 += (unsigned)(t == 0u && kept); kept1 += (unsigned)(t == 1u && kept);
+	}
+	// (every lane of the wave comes here: the end of the kernel, outside its loops)
+	__device__ inline void flush(const RouteOut &O) const {
+		unsigned v[5] = {made0, made1, none, kept0, kept1};
+#pragma unroll
+		for (int q = 0; q < 5; ++q) {
+			unsigned x = v[q];
+			for (int d = 32; d > 0; d >>= 1) x += (unsigned)__shfl_down((int)x, d);
+			const unsigned slot = (blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (ROUTE_LIB_SLOTS - 1u);
+			if ((threadIdx.x & 63u) == 0u && x) atomicAdd(&O.nb_tot[ROUTE_LIB_WORD0 + 8u * slot + q], (unsigned long long)x);
+		}
+	}
+};
+// (a helper of a stranded kernel takes the word and the kernel's tally as its pack)
+__device__ inline unsigned route_helper_lib() { return 0u; }
+__device__ inline unsigned route_helper_lib(unsigned lib, LibTally *) { return lib; }
+__device__ inline LibTally *route_tally_arg(unsigned, LibTally *tally) { return tally; }
 
 // The locator entry of base x on a chromosome: where, among the chromosome's covered regions and clusters, the records that
 // start inside x's bin lie.  Kept per lane from one look-up to the next: a read's blocks and its first base mostly share a bin.
@@ -202,6 +251,7 @@ struct ReadAcc {
 		if (ka <= 2) { s0 = a0; s1 = a1; e0 = b0; e1 = b1; n = ka; }
 		else { B.bs[0] = a0; B.bs[1] = a1; B.bs[2] = a2; B.be[0] = b0; B.be[1] = b1; B.be[2] = b2; n = 3; big = true; }
 	}
+	__device__ inline bool kept() const { return any && n > 0; }          // (finish gives such a read a key other than ROUTE_KEY_DROPPED)
 	// the read is complete: its key and blocks to their place (index i of the pass)
 	__device__ inline void finish(const ReadBig &B, const RouteTables &T, const RouteChrom *chroms, LocProbe &P, const RouteOut &O, const unsigned i) {
 		unsigned key = ROUTE_KEY_DROPPED;

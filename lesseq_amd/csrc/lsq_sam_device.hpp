@@ -120,41 +120,48 @@ __device__ inline lsq::MrfView sam_hbm_line(const MrfText &X, const unsigned lon
 }
 
 // one record through the containment filter and the merge, as mrf_route_line does for an MRF line
-template <class V>
+// (STRANDED, lsq_route.hpp: the splitter hands over the strand of the fragment's first mate; the library turns that into t)
+// (the stranded form's two arguments -- the `lib` word and the kernel's tally -- are a parameter pack, empty in the unstranded form, as
+// the kernels' own: with them in its signature the unstranded helper lay beyond the inliner's threshold, and the byte-walking kernel
+// called sam_route_whole_line where it had held it)
+template <bool STRANDED, class V, class... Lib>
 __device__ inline void sam_route_fields(const MrfText &X, const SamOpts Q, const MrfDict &D, const unsigned long long *lds_strand, const RouteTables &T, const RouteChrom *chroms,
-                                        const RouteOut &O, unsigned long long *err, const unsigned long long i, const V line, const typename V::index_type *b) {
+                                        const RouteOut &O, unsigned long long *err, const unsigned long long i, const V line, const typename V::index_type *b, Lib... lib_arg) {
+	const unsigned lib = route_helper_lib(lib_arg...);
 	const long long LIM = 1ll << 30;
 	ReadAcc A;
 	ReadBig B;
 	A.init();
 	LocProbe P;
 	P.chrom = -1; P.bin = 0;
-	unsigned cid = MRF_NOCHROM, sid = 0;
+	unsigned cid = MRF_NOCHROM, sid = 0, t = 0;
 	bool looked = false;
 	const int verdict = lsq::sam_split_fields(line, b, Q.skip_flags, Q.min_mapq, [&](const V chr, const bool minus, const int64_t start, const int64_t end, int64_t, int64_t) {
 		if (!looked) {
 			// (one RNAME and one strand a record)
 			looked = true;
 			cid = mrf_chrom_lookup(D, chr);
-			const char sc = minus ? '-' : '+';
+			if constexpr (STRANDED) { t = route_transcript(lib, minus ? 1u : 0u); if (cid != MRF_NOCHROM) cid = route_table(cid, t); }
+			const char sc = (STRANDED ? t != 0u : minus) ? '-' : '+';
 			sid = mrf_strand_slot(lds_strand, D.strand_tab, lsq::MrfView{&sc, 1}, err);
 		}
 		const long long s0 = start - 1, e0 = end;
 		if (cid >= T.n_chrom || e0 >= LIM || s0 >= LIM) return;
 		if (!route_covered(T, chroms[cid], (int)cid, (int)s0, (int)e0, P)) return;
 		A.add(B, cid, sid, (int)s0, (int)e0);
-	});
+	}, STRANDED);
 	if (verdict == lsq::SAM_MALFORMED) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; return; }
 	if (verdict != lsq::SAM_READ) { O.key[i] = ROUTE_KEY_DROPPED; return; }
+	if constexpr (STRANDED) route_tally_arg(lib_arg...)->note(t, A.kept());
 	A.finish(B, T, chroms, P, O, (unsigned)i);
 }
-template <class V>
+template <bool STRANDED, class V, class... Lib>
 __device__ inline void sam_route_whole_line(const MrfText &X, const SamOpts Q, const MrfDict &D, const unsigned long long *lds_strand, const RouteTables &T, const RouteChrom *chroms,
-                                            const RouteOut &O, unsigned long long *err, const unsigned long long i, const V line) {
+                                            const RouteOut &O, unsigned long long *err, const unsigned long long i, const V line, Lib... lib_arg) {
 	typename V::index_type b[7];
 	if (line.n >= 1 && line.p[0] == '@') { O.key[i] = ROUTE_KEY_DROPPED; return; }
 	if (lsq::sam_field_bounds(line, true, b) != lsq::SAM_BOUNDS_OK) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; return; }
-	sam_route_fields(X, Q, D, lds_strand, T, chroms, O, err, i, line, b);
+	sam_route_fields<STRANDED>(X, Q, D, lds_strand, T, chroms, O, err, i, line, b, lib_arg...);
 }
 
 // Waves a SIMD the compiler is asked to leave room for in the tile kernel.  Left alone (0) it takes 181 registers -- two
@@ -169,16 +176,23 @@ __device__ inline void sam_route_whole_line(const MrfText &X, const SamOpts Q, c
 #define LSQ_SAM_WAVES_ATTR
 #endif
 
-template <bool ALL_HBM>
-__global__ void __launch_bounds__(256) LSQ_SAM_WAVES_ATTR lsq_sam_route_kernel(MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles) {
+template <bool ALL_HBM, bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) LSQ_SAM_WAVES_ATTR lsq_sam_route_kernel(MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, unsigned n_tiles, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	__shared__ MrfTileLds S;
+	LibTally L;
+	L.init();
 	const MrfDict D = mrf_stage_dict(S, G);
 	const RouteChrom *chroms = route_stage_chroms(T, S.chrom);
 	const mrf_lds_cptr lds_text = (mrf_lds_cptr)(const char *)S.text;
 	for (unsigned tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
 		const unsigned long long t0 = (unsigned long long)tile * TEXT_TILE;
 		sam_tile_lines(S, tile, X, [&](const unsigned long long i, const unsigned start, const unsigned n, const bool whole) {
-			if constexpr (ALL_HBM) sam_route_whole_line(X, Q, D, S.strand, T, chroms, O, err, i, sam_hbm_line(X, t0 + start));
+			if constexpr (ALL_HBM) {
+				if constexpr (STRANDED) [[clang::always_inline]] sam_route_whole_line<true>(X, Q, D, S.strand, T, chroms, O, err, i, sam_hbm_line(X, t0 + start), lib, &L);
+				// (held here, as it was before the helper had a stranded sibling: left to itself the inliner now calls it from this kernel)
+				else [[clang::always_inline]] sam_route_whole_line<false>(X, Q, D, S.strand, T, chroms, O, err, i, sam_hbm_line(X, t0 + start));
+			}
 			else {
 				if (n >= 1u && lds_text[start] == '@') { O.key[i] = ROUTE_KEY_DROPPED; return; }
 				const MrfLdsView head{lds_text + start, n < SAM_HEAD_MAX ? n : SAM_HEAD_MAX};
@@ -190,20 +204,28 @@ __global__ void __launch_bounds__(256) LSQ_SAM_WAVES_ATTR lsq_sam_route_kernel(M
 					if (at < H.line_cap) H.lines[at] = MrfLongLine{i, t0 + start, ~0ull}; else H.counts[2] = 1u;
 				}
 				else if (fb == lsq::SAM_BOUNDS_SHORT_LINE) { atomicMin(&err[0], X.first_line + i); O.key[i] = ROUTE_KEY_DROPPED; }
-				else sam_route_fields(X, Q, D, S.strand, T, chroms, O, err, i, head, b);
+				else if constexpr (STRANDED) sam_route_fields<true>(X, Q, D, S.strand, T, chroms, O, err, i, head, b, lib, &L);
+				else sam_route_fields<false>(X, Q, D, S.strand, T, chroms, O, err, i, head, b);
 			}
 		});
 		__syncthreads();
 	}
+	if constexpr (STRANDED) L.flush(O);
 }
 
 // the listed lines, one lane each, straight from HBM
-__global__ void __launch_bounds__(256) lsq_sam_route_lines_kernel(MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H) {
+template <bool STRANDED, class... Lib>
+__global__ void __launch_bounds__(256) lsq_sam_route_lines_kernel(MrfText X, SamOpts Q, MrfDict G, RouteTables T, RouteOut O, unsigned long long *err, MrfHandOff H, Lib... lib_arg) {
+	const unsigned lib = route_lib_arg(lib_arg...);
 	const unsigned n = min(H.counts[1], H.line_cap);
+	LibTally LT;
+	LT.init();
 	for (unsigned t = blockIdx.x * blockDim.x + threadIdx.x; t < n; t += gridDim.x * blockDim.x) {
 		const MrfLongLine L = H.lines[t];
-		sam_route_whole_line(X, Q, G, nullptr, T, T.chrom, O, err, L.i, sam_hbm_line(X, L.start));
+		if constexpr (STRANDED) sam_route_whole_line<true>(X, Q, G, nullptr, T, T.chrom, O, err, L.i, sam_hbm_line(X, L.start), lib, &LT);
+		else sam_route_whole_line<false>(X, Q, G, nullptr, T, T.chrom, O, err, L.i, sam_hbm_line(X, L.start));
 	}
+	if constexpr (STRANDED) LT.flush(O);
 }
 
 // ---- lsq_mrf_parse_device("SAM_SINGLE"): pass 1, blocks per data line (0 for lines that make no read), first malformed line
@@ -219,8 +241,9 @@ __global__ void __launch_bounds__(256) lsq_sam_count_kernel(MrfText X, SamOpts Q
 }
 
 // pass 2: every read's blocks to their place (as lsq_mrf_write_kernel)
+// (mate_strand: stranded events -- the strand written is that of the fragment's first mate, as lsq_sam_parse writes it)
 __global__ void __launch_bounds__(256) lsq_sam_write_kernel(MrfText X, SamOpts Q, const unsigned *line_nb, const unsigned long long *rd_idx, const unsigned long long *bk_off,
-                                                            MrfDict G, MrfOut O, unsigned long long *err) {
+                                                            MrfDict G, MrfOut O, unsigned long long *err, unsigned mate_strand) {
 	__shared__ MrfTileLds S;
 	const MrfDict D = mrf_stage_dict(S, G);
 	const long long LIM = 1ll << 30;
@@ -242,7 +265,7 @@ __global__ void __launch_bounds__(256) lsq_sam_write_kernel(MrfText X, SamOpts Q
 			O.blk_start[w] = (int)s0; O.blk_end[w] = (int)e0;
 			O.blk_chrom[w] = (unsigned short)cid; O.blk_strand[w] = (unsigned char)sid;
 			++w;
-		});
+		}, mate_strand != 0u);
 	});
 }
 
@@ -255,10 +278,19 @@ static int sam_prepare(TextJob &J) {
 static void sam_launch(const TextJob &J, const RouteTables &RT, const RouteOut &O, hipStream_t s) {
 	const SamOpts Q = sam_opts(J.c);
 	// a workgroup a tile, as the MRF kernel is launched; the listed lines behind it
-	if (J.n_tiles && J.all_slow) hipLaunchKernelGGL(lsq_sam_route_kernel<true>, dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
-	else if (J.n_tiles) {
-		hipLaunchKernelGGL(lsq_sam_route_kernel<false>, dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
-		hipLaunchKernelGGL(lsq_sam_route_lines_kernel, dim3(std::min(J.H.line_cap / 256u + 1u, 1024u)), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H);
+	const unsigned lib = lsq::route_lib(J.c);
+	const dim3 lines_grid(std::min(J.H.line_cap / 256u + 1u, 1024u));
+	if (!J.n_tiles) return;
+	if (J.c->E->stranded()) {
+		if (J.all_slow) hipLaunchKernelGGL((lsq_sam_route_kernel<true, true, unsigned>), dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles, lib);
+		else {
+			hipLaunchKernelGGL((lsq_sam_route_kernel<false, true, unsigned>), dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles, lib);
+			hipLaunchKernelGGL((lsq_sam_route_lines_kernel<true, unsigned>), lines_grid, dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, lib);
+		}
+	} else if (J.all_slow) hipLaunchKernelGGL((lsq_sam_route_kernel<true, false>), dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
+	else {
+		hipLaunchKernelGGL((lsq_sam_route_kernel<false, false>), dim3(J.n_tiles), dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H, J.n_tiles);
+		hipLaunchKernelGGL(lsq_sam_route_lines_kernel<false>, lines_grid, dim3(256), 0, s, J.X, Q, J.D, RT, O, J.err, J.H);
 	}
 }
 static void sam_record(const TextJob &J) { J.c->sam_lines_listed = J.all_slow ? 0u : J.counts[1]; J.c->sam_all_slow = J.all_slow ? 1u : 0u; }

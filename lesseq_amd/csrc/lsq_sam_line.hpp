@@ -103,11 +103,15 @@ struct SamBlockWalk {
 	LSQ_HD inline void end(Emit &&emit) { if (ref > bs) { emit(bs, ref - 1, qs, qe); ++n_blocks; } }
 };
 
+// the record is the second mate of a pair: its fragment came from the strand opposite to the one it aligned to
+LSQ_HD inline bool sam_flag_mate2(unsigned flag) { return (flag & 0x1u) != 0u && (flag & 0x80u) != 0u; }
+
 // Calls on_block(rname, minus, start, end, qstart, qend) for every block of the record, in order (1-based inclusive).
+// minus: FLAG & 0x10; with mate_strand set (stranded jobs), that XOR sam_flag_mate2 -- the strand the fragment's first mate lies on.
 // SAM_MALFORMED may come after blocks have been delivered; SAM_READ only when at least one was.  `b`: sam_field_bounds
 // of a line that does not begin with '@'.
 template <class V, class OnBlock>
-LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block) {
+LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block, const bool mate_strand = false) {
 	typedef typename V::index_type Idx;
 	auto field = [&](int k) { return V{line.p + b[k], (Idx)(b[k + 1] - 1 - b[k])}; };
 	int64_t flag, mapq, pos;
@@ -123,7 +127,7 @@ LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsi
 	for (Idx j = 0; walk && j < rname.n; ++j) if (rname.p[j] == ':' || rname.p[j] == ',') walk = false;
 	if (no_cigar) return SAM_NO_READ;
 	if (cigar.n == 0) return SAM_MALFORMED;
-	const bool minus = ((unsigned)flag & 0x10u) != 0u;
+	const bool minus = (((unsigned)flag & 0x10u) != 0u) != (mate_strand && sam_flag_mate2((unsigned)flag));
 	auto emit = [&](int64_t s, int64_t e, int64_t qs, int64_t qe) { on_block(rname, minus, s, e, qs, qe); };
 	SamBlockWalk W;
 	W.begin(pos);
@@ -146,11 +150,11 @@ LSQ_HD inline int sam_split_fields(V line, const typename V::index_type *b, unsi
 
 // a whole line
 template <class V, class OnBlock>
-LSQ_HD inline int sam_split_line(V line, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block) {
+LSQ_HD inline int sam_split_line(V line, unsigned skip_flags, unsigned min_mapq, OnBlock &&on_block, const bool mate_strand = false) {
 	typename V::index_type b[7];
 	if (line.n >= 1 && line.p[0] == '@') return SAM_NO_READ;
 	if (sam_field_bounds(line, true, b) != SAM_BOUNDS_OK) return SAM_MALFORMED;
-	return sam_split_fields(line, b, skip_flags, min_mapq, on_block);
+	return sam_split_fields(line, b, skip_flags, min_mapq, on_block, mate_strand);
 }
 
 } // namespace lsq

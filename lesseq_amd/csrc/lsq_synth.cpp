@@ -415,7 +415,7 @@ int lsq_synth_reads(const lsq_synth_spec *S, lsq_events *E, int n_threads, lsq_r
 	std::vector<int> cid(S->n_chrom);
 	for (uint32_t c = 0; c < S->n_chrom; ++c) {
 		int id = E->chroms.find(chrom_name((int)c));
-		cid[c] = (id < 0 || (size_t)id >= E->covered.size()) ? 0xFFFF : id;
+		cid[c] = (id < 0 || (size_t)id >= E->n_table_chroms()) ? 0xFFFF : id;
 	}
 	int plus = lsq_events_strand_id(E, "+"), minus = lsq_events_strand_id(E, "-");
 	if (plus < 0 || minus < 0) return LSQ_E_RANGE;

@@ -11,6 +11,8 @@ log-likelihood) in output order on the device (lsq_results_pack_device), and one
 process group -- RCCL over xGMI with backend "nccl", gloo on host copies in the tests -- gives every rank
 the blocks of all; lsq_gathered_unpack lays them out as the whole job's tables.
 """
+import os
+
 import numpy as np
 
 from . import api
@@ -128,7 +130,7 @@ def run_sharded(tool, argv, rank, world, device_index=0, group=None, comm_device
     import torch
     a = parse_cli(tool, argv)
     ann = api.Annotation(a["isoforms"], a["g2i"], a["begin"], a["end"], a["isoform_format"], a["g2i_format"])
-    ev = api.Events(ann, a["read_types"], a["read_lengths"])
+    ev = api.Events(ann, a["read_types"], a["read_lengths"], library=os.environ.get("LSQ_LIBRARY", "unstranded"))
     ctx = api.Context(device_index)
     staged = StagedReads(ctx, ev, a)
     try:
@@ -206,6 +208,9 @@ def run_read_sharded(tool, argv, rank, world, device_index=0, group=None, comm_d
     for fmt in a["read_formats"]:
         if fmt != "MRF_SINGLE":
             raise ValueError("the read-sharded run takes MRF_SINGLE read files only (got %s); use --shard events" % fmt)
+    if os.environ.get("LSQ_LIBRARY", "unstranded") != "unstranded":
+        # (as the executables, which shard a stranded job by events whatever LSQ_SHARD says)
+        raise ValueError("the read-sharded run takes unstranded jobs only (LSQ_LIBRARY=%s); use --shard events" % os.environ["LSQ_LIBRARY"])
     ann = api.Annotation(a["isoforms"], a["g2i"], a["begin"], a["end"], a["isoform_format"], a["g2i_format"])
     ev = api.Events(ann, a["read_types"], a["read_lengths"])
     ctx = api.Context(device_index)
@@ -294,7 +299,9 @@ def main(args=None):
         dev = torch.device("cuda", local)
         dist.init_process_group("nccl", device_id=dev)
     try:
-        run = run_read_sharded if a.shard == "reads" else run_sharded
+        # (a stranded job is sharded by events whatever --shard says, as the executables do under LSQ_SHARD=reads)
+        stranded = os.environ.get("LSQ_LIBRARY", "unstranded") != "unstranded"
+        run = run_read_sharded if a.shard == "reads" and not stranded else run_sharded
         text = run(a.tool, argv, rank, world, device_index=local, comm_device=dev)
         if rank == 0:
             sys.stdout.write(text)

@@ -3,7 +3,7 @@
     python tools/ingest_bench.py [workload c3|c2|c5s] [reps] [sorted 0|1]
 Prints one JSON object: per pass the device milliseconds (HIP events on the library's stream), the bytes the pass has to
 move at least, GB/s and the fraction of the 8 TB/s HBM peak; wall-clock of stage + upload; LSQ_CLI_TIMING=1 adds the
-host-side phase clock on stderr."""
+host-side phase clock on stderr; LSQ_LIBRARY=forward|reverse runs the file as a stranded job."""
 import json
 import os
 import sys
@@ -30,10 +30,11 @@ t_write = time.time() - t0
 mrf = os.path.join(d, "s.mrf")
 size = os.path.getsize(mrf)
 a = L.Annotation(os.path.join(d, "s.interval"), os.path.join(d, "s.map"), 0, 10 ** 9)
-ev = L.Events(a, ("SHORT_READ",), (W["R"],))
+library = os.environ.get("LSQ_LIBRARY", "unstranded")      # forward / reverse: the stranded routing kernels
+ev = L.Events(a, ("SHORT_READ",), (W["R"],), library=library)
 ctx = L.Context(0)
 ctx.upload_events(ev)
-out = {"workload": wl, "sorted": want_sorted, "n_reads": n_reads, "text_bytes": size, "write_s": round(t_write, 2), "runs": []}
+out = {"workload": wl, "library": library, "sorted": want_sorted, "n_reads": n_reads, "text_bytes": size, "write_s": round(t_write, 2), "runs": []}
 for rep in range(reps):
     ctx.synchronize()
     t0 = time.perf_counter()
