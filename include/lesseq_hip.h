@@ -526,7 +526,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck" or "junctions" (lsq_jn_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -582,6 +582,64 @@ uint64_t lsq_as_input_left_out(const lsq_as_input *in);
 /* R's as.character(v): 15 significant digits, trailing zeros dropped, fixed unless scientific is strictly shorter
  * ("1e-04", "0.001", "1e+05", "123456"), NaN as "NA".  32 bytes always suffice. */
 int lsq_as_format_number(double v, char *buf, size_t cap);
+
+/* ------------------------------------------------------------------------------------
+ * Splice junctions of a read file: the table step 1 of the pipeline ("refining gene models using RNA-Seq data") starts from
+ * (DESIGN.md 4.12); what STAR writes as SJ.out.tab and `regtools junctions extract` prints
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition, on the arrays the parsers above give (lsq_reads_parse / lsq_sam_parse / lsq_bam_parse, lsq_mrf_parse_device):
+ *   chromosomes  the distinct chromosome strings of the annotation's isoform lines (every line it loaded, selected or not).  A
+ *                block on another chromosome, or with a coordinate outside +-2^30, has no chromosome (the parsers' own rule).
+ *   occurrence   two consecutive blocks k, k+1 of one read, unmerged, file order, 0-based half-open: both with the same chromosome
+ *                (not none), start[k+1] > end[k], and min(end[k]-start[k], end[k+1]-start[k+1]) >= min_overhang.  The junction is
+ *                (chromosome, end[k], start[k+1]).  Abutting, overlapping or descending blocks, and a pair across two chromosomes, make none.
+ *   per junction reads: its occurrences; plus / minus: those whose block k carries the strand string "+" / "-"; max_overhang:
+ *                the largest of the minima above.
+ *   ann          per isoform line the union of its exons with end > start (the first exonCount of the line; order, overlap and
+ *                empty exons do not matter); its introns are the gaps between consecutive maximal intervals of that union.  '.': no
+ *                isoform on the chromosome has the junction as an intron; '+' / '-': every isoform that has it carries that strand
+ *                string; '*' otherwise.
+ *   rows         ascending in chromosome name (bytewise), start, end.  Text: chrom TAB start+1 TAB end TAB ann TAB reads TAB plus
+ *                TAB minus TAB max_overhang NL -- the intron's first and last base, 1-based inclusive, as STAR prints it; no header.
+ *   report       reads in the file, blocks in the file, occurrences counted, block pairs dropped by the overhang (same chromosome,
+ *                a gap, a flank too short), block pairs in which a block has no chromosome.
+ * Events are not involved and none of lsq_events_compile's limits applies.  More than 2^32-1 occurrences: LSQ_E_RANGE. */
+typedef struct lsq_jn_index lsq_jn_index;       /* chromosome and strand dictionaries ("+" = 0, "-" = 1), the sorted distinct introns with their ann */
+typedef struct lsq_jn_table lsq_jn_table;
+int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out);      /* LSQ_E_RANGE beyond 65 535 chromosomes */
+void lsq_jn_index_free(lsq_jn_index *ix);
+int64_t lsq_jn_index_num_chroms(const lsq_jn_index *ix);
+const char *lsq_jn_index_chrom_name(const lsq_jn_index *ix, int64_t chrom);      /* NULL when out of range */
+int64_t lsq_jn_index_num_introns(const lsq_jn_index *ix);
+/* The index's dictionaries as the lsq_events the host parsers intern against (owned by the index; it holds no event and cannot be
+ * uploaded): lsq_reads_parse(..., lsq_jn_index_dictionaries(ix), ...) gives the arrays lsq_jn_host_reads takes. */
+lsq_events *lsq_jn_index_dictionaries(lsq_jn_index *ix);
+/* Host-only: the table from the host parsers' arrays.  read_format: whatever lsq_reads_parse takes (the name-keyed formats: the
+ * lines of one name, in file order, are the blocks of one read; a line on a chromosome the annotation does not name is dropped by
+ * that parser); skip_flags / min_mapq apply to SAM_SINGLE and BAM_SINGLE.  Statuses and messages are the parser's.  The index's
+ * strand dictionary grows by the strings the file introduces.  lsq_jn_host_reads: the same from arrays parsed against the index
+ * (tools: the host path without the parse). */
+int lsq_jn_host(lsq_jn_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq,
+                uint32_t min_overhang, int n_threads, lsq_jn_table **out);
+int lsq_jn_host_reads(lsq_jn_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_jn_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed from the file's own bytes as lsq_mrf_parse_device parses
+ * it (the context's "sam_skip_flags" / "sam_min_mapq" / "bam_verify"; the statuses and messages of lsq_reads_upload_mrf for a
+ * malformed file), then extract, sort, reduce, annotate on device arrays; the distinct rows alone come back.  The context needs
+ * no events, and its events, reads and counters are as they were afterwards. */
+int lsq_jn_device(lsq_ctx *c, lsq_jn_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_jn_table **out);
+void lsq_jn_table_free(lsq_jn_table *t);
+int64_t lsq_jn_table_rows(const lsq_jn_table *t);
+/* The rows' arrays (they live as long as the table; any pointer may be null): chrom indexes lsq_jn_index_chrom_name. */
+int lsq_jn_table_arrays(const lsq_jn_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint8_t **ann,
+                        const uint32_t **reads, const uint32_t **plus, const uint32_t **minus, const uint32_t **max_overhang);
+int lsq_jn_table_report(const lsq_jn_table *t, uint64_t report[5]);
+/* Device milliseconds per phase of the lsq_jn_device call that made the table -- extract, sort, reduce, annotate, copy-back --
+ * from HIP events on the library's stream (zeros from the host path); the parse ahead of them: lsq_last_mrf_timing. */
+int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]);
+/* The text of the rows with reads >= min_reads and, with novel_only, ann '.'; malloc'd, NUL-terminated (lsq_free). */
+int lsq_jn_format(const lsq_jn_table *t, uint32_t min_reads, int novel_only, char **out_text);
+int lsq_jn_sort_tile(void);      /* records a workgroup of the device sort takes (tests place their cases around it) */
 
 /* ------------------------------------------------------------------------------------
  * Local events: step 2 of the pipeline, bin/Events.r

@@ -219,6 +219,22 @@ _sig("lsq_gtf_format", C.c_int, vp, P(vp), P(vp))
 _sig("lsq_gtf_result_times", C.c_int, vp, P(C.c_double))
 _sig("lsq_gtf_isoform_map", C.c_int, cs, u64, P(vp))
 _sig("lsq_le_load_gtf", C.c_int, vp, cs, P(vp))
+_sig("lsq_jn_index_build", C.c_int, vp, P(vp))
+_sig("lsq_jn_index_free", None, vp)
+_sig("lsq_jn_index_num_chroms", i64, vp)
+_sig("lsq_jn_index_chrom_name", cs, vp, i64)
+_sig("lsq_jn_index_num_introns", i64, vp)
+_sig("lsq_jn_index_dictionaries", vp, vp)
+_sig("lsq_jn_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, u32, C.c_int, P(vp))
+_sig("lsq_jn_host_reads", C.c_int, vp, vp, u32, C.c_int, P(vp))
+_sig("lsq_jn_device", C.c_int, vp, vp, cs, cs, u32, P(vp))
+_sig("lsq_jn_table_free", None, vp)
+_sig("lsq_jn_table_rows", i64, vp)
+_sig("lsq_jn_table_arrays", C.c_int, vp, P(P(u32)), P(P(i32)), P(P(i32)), P(P(u8)), P(P(u32)), P(P(u32)), P(P(u32)), P(P(u32)))
+_sig("lsq_jn_table_report", C.c_int, vp, P(u64))
+_sig("lsq_jn_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_jn_format", C.c_int, vp, u32, C.c_int, P(vp))
+_sig("lsq_jn_sort_tile", C.c_int)
 
 
 def _warn_on_runtime_mismatch():

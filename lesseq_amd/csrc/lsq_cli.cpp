@@ -20,6 +20,7 @@
 #include "lsq_internal.hpp"
 #include "lsq_localev.hpp"
 #include "lsq_gtf.hpp"
+#include "lsq_junc.hpp"
 #include "lsq_team.hpp"
 
 using namespace lsq;
@@ -788,6 +789,7 @@ std::string format_events_parallel(size_t n, F &&one) {
 } // namespace
 
 void lsq::cli_log(int level, const char *text) { logf(level, "%s", text); }
+int lsq::cli_env_options(lsq_ctx *c) { return apply_env_options(c); }
 int lsq::cli_device() { const char *e = getenv("LSQ_DEVICE"); return e ? atoi(e) : 0; }
 
 extern "C" {
@@ -880,6 +882,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "sam2mrf") == 0) rc = run_sam2mrf(false, argc, argv, out);
 	else if (tool && strcmp(tool, "bam2mrf") == 0) rc = run_sam2mrf(true, argc, argv, out);
 	else if (tool && strcmp(tool, "bamcheck") == 0) rc = run_bamcheck(argc, argv, out);
+	else if (tool && strcmp(tool, "junctions") == 0) rc = run_junctions(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -1,0 +1,295 @@
+// Splice junctions of a read file (include/lesseq_hip.h, lsq_jn_*): the index made from an annotation, the host
+// path over the host parsers' arrays, the table's text and the junctions executable.  The device passes are lsq_junc.hip, the
+// entry that opens a read file on the device is lsq_readfile.hip's lsq_jn_device.
+#include <algorithm>
+#include <cerrno>
+#include <cstdlib>
+#include <cstring>
+#include <numeric>
+
+#include "lsq_junc.hpp"
+
+using namespace lsq;
+
+namespace {
+
+struct Row { uint32_t chrom; uint64_t key; uint32_t reads, plus, minus, max_ov; };
+inline bool row_less(const Row &a, const Row &b) { return a.chrom != b.chrom ? a.chrom < b.chrom : a.key < b.key; }
+
+// sorted rows with equal keys -> one row each
+void fold_rows(std::vector<Row> &v) {
+	size_t o = 0;
+	for (size_t i = 0; i < v.size(); ++i) {
+		if (o && v[o - 1].chrom == v[i].chrom && v[o - 1].key == v[i].key) {
+			Row &r = v[o - 1];
+			r.reads += v[i].reads; r.plus += v[i].plus; r.minus += v[i].minus; r.max_ov = std::max(r.max_ov, v[i].max_ov);
+		} else v[o++] = v[i];
+	}
+	v.resize(o);
+}
+
+char *dup_text(const std::string &s) {
+	char *p = (char *)malloc(s.size() + 1);
+	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
+	return p;
+}
+
+} // namespace
+
+void lsq::jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t) {
+	t.chrom_names = ix.E.chroms.names;
+	const size_t n = t.chrom.size(), nc = t.chrom_names.size();
+	// rows arrive ascending in (chromosome index, start, end): the chromosomes' groups reordered by name
+	std::vector<size_t> first(nc + 1, 0);
+	for (size_t i = 0; i < n; ++i) ++first[t.chrom[i] + 1];
+	for (size_t c = 0; c < nc; ++c) first[c + 1] += first[c];
+	std::vector<uint32_t> order(nc);
+	std::iota(order.begin(), order.end(), 0u);
+	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t.chrom_names[a] < t.chrom_names[b]; });
+	std::vector<size_t> from;
+	from.reserve(n);
+	for (uint32_t c : order) for (size_t i = first[c]; i < first[c + 1]; ++i) from.push_back(i);
+	auto permute = [&](auto &v) { auto w = v; for (size_t i = 0; i < n; ++i) w[i] = v[from[i]]; v.swap(w); };
+	permute(t.chrom); permute(t.start); permute(t.end); permute(t.ann); permute(t.reads); permute(t.plus); permute(t.minus); permute(t.max_overhang);
+}
+
+int lsq::jn_host_reads(const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t) {
+	int T = host_threads(n_threads);
+	if (R.n_reads < (1u << 16)) T = 1;
+	std::vector<std::vector<Row>> part((size_t)T);
+	std::vector<uint64_t> dropped((size_t)T, 0), nochrom((size_t)T, 0), occ((size_t)T, 0);
+	{
+		ThreadGroup th;
+		for (int k = 0; k < T; ++k) th.spawn([&, k] {
+			std::vector<Row> &v = part[(size_t)k];
+			const uint64_t r0 = R.n_reads * (uint64_t)k / (uint64_t)T, r1 = R.n_reads * (uint64_t)(k + 1) / (uint64_t)T;
+			for (uint64_t r = r0; r < r1; ++r)
+				for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
+					const unsigned c0 = R.bc[b], c1 = R.bc[b + 1];
+					if (c0 == JN_NOCHROM || c1 == JN_NOCHROM) { ++nochrom[(size_t)k]; continue; }
+					if (c0 != c1 || R.bs[b + 1] <= R.be[b]) continue;
+					const int64_t ov = std::min((int64_t)R.be[b] - R.bs[b], (int64_t)R.be[b + 1] - R.bs[b + 1]);
+					if (ov < (int64_t)min_overhang) { ++dropped[(size_t)k]; continue; }
+					v.push_back(Row{c0, jn_key(R.be[b], R.bs[b + 1]), 1u, R.bst[b] == 0 ? 1u : 0u, R.bst[b] == 1 ? 1u : 0u, (uint32_t)ov});
+				}
+			occ[(size_t)k] = v.size();
+			std::sort(v.begin(), v.end(), row_less);
+			fold_rows(v);
+		});
+		th.join();
+		if (th.failed()) return fail(LSQ_E_INTERNAL, "%s", th.error().c_str());
+	}
+	uint64_t n_occ = 0;
+	for (uint64_t o : occ) n_occ += o;
+	if (n_occ > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32-1 junction occurrences");
+	std::vector<Row> all = std::move(part[0]);
+	for (int k = 1; k < T; ++k) {
+		std::vector<Row> m(all.size() + part[(size_t)k].size());
+		std::merge(all.begin(), all.end(), part[(size_t)k].begin(), part[(size_t)k].end(), m.begin(), row_less);
+		fold_rows(m);
+		all.swap(m);
+	}
+	t.resize(all.size());
+	for (size_t i = 0; i < all.size(); ++i) {
+		const Row &r = all[i];
+		t.chrom[i] = r.chrom; t.start[i] = jn_key_start(r.key); t.end[i] = jn_key_end(r.key);
+		t.reads[i] = r.reads; t.plus[i] = r.plus; t.minus[i] = r.minus; t.max_overhang[i] = r.max_ov;
+		size_t lo = 0, hi = ix.in_key.size();
+		while (lo < hi) {
+			const size_t mid = lo + (hi - lo) / 2;
+			if (ix.in_chrom[mid] < r.chrom || (ix.in_chrom[mid] == r.chrom && ix.in_key[mid] < r.key)) lo = mid + 1; else hi = mid;
+		}
+		t.ann[i] = (lo < ix.in_key.size() && ix.in_chrom[lo] == r.chrom && ix.in_key[lo] == r.key) ? ix.in_ann[lo] : (uint8_t)'.';
+	}
+	t.report[0] = R.n_reads; t.report[1] = R.n_blocks; t.report[2] = n_occ; t.report[3] = t.report[4] = 0;
+	for (int k = 0; k < T; ++k) { t.report[3] += dropped[(size_t)k]; t.report[4] += nochrom[(size_t)k]; }
+	for (float &m : t.ms) m = 0;
+	jn_finish_table(ix, t);
+	return LSQ_OK;
+}
+
+extern "C" {
+
+int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY {
+	if (!a || !out) return fail(LSQ_E_ARG, "null argument");
+	std::unique_ptr<lsq_jn_index> ix(new lsq_jn_index);
+	lsq_events &E = ix->E;
+	E.strands.intern("+"); E.strands.intern("-");
+	struct Intron { uint32_t chrom; uint64_t key; uint8_t ann; };
+	std::vector<Intron> in;
+	std::vector<std::pair<int64_t, int64_t>> ex;
+	for (const auto &rp : a->recs) {
+		const IsoRec &r = *rp;
+		const int cid = E.chroms.intern(r.chrom);
+		if (cid >= (int)JN_NOCHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
+		// the union of the line's exons: its maximal intervals, and the gaps between them
+		ex.clear();
+		const size_t ne = std::min<size_t>({(size_t)r.exonCount, r.exonStarts.size(), r.exonEnds.size()});
+		for (size_t i = 0; i < ne; ++i) if (r.exonEnds[i] > r.exonStarts[i]) ex.emplace_back(r.exonStarts[i], r.exonEnds[i]);
+		std::sort(ex.begin(), ex.end());
+		const uint8_t ann = r.strand == "+" ? '+' : r.strand == "-" ? '-' : '*';
+		int64_t reach = 0;
+		for (size_t i = 0; i < ex.size(); ++i) {
+			if (i && ex[i].first > reach && reach > -JN_BIAS && ex[i].first < JN_BIAS) in.push_back(Intron{(uint32_t)cid, jn_key(reach, ex[i].first), ann});
+			reach = i ? std::max(reach, ex[i].second) : ex[i].second;
+		}
+	}
+	std::sort(in.begin(), in.end(), [](const Intron &x, const Intron &y) { return x.chrom != y.chrom ? x.chrom < y.chrom : x.key < y.key; });
+	for (const Intron &i : in) {
+		if (!ix->in_key.empty() && ix->in_chrom.back() == i.chrom && ix->in_key.back() == i.key) {
+			if (ix->in_ann.back() != i.ann) ix->in_ann.back() = '*';
+		} else { ix->in_chrom.push_back(i.chrom); ix->in_key.push_back(i.key); ix->in_ann.push_back(i.ann); }
+	}
+	E.covered.resize(E.chroms.names.size());
+	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
+	*out = ix.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+void lsq_jn_index_free(lsq_jn_index *ix) { delete ix; }
+int64_t lsq_jn_index_num_chroms(const lsq_jn_index *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
+const char *lsq_jn_index_chrom_name(const lsq_jn_index *ix, int64_t chrom) {
+	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
+}
+lsq_events *lsq_jn_index_dictionaries(lsq_jn_index *ix) { return ix ? &ix->E : nullptr; }
+int64_t lsq_jn_index_num_introns(const lsq_jn_index *ix) { return ix ? (int64_t)ix->in_key.size() : 0; }
+
+int lsq_jn_host_reads(lsq_jn_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_jn_table **out) LSQ_API_TRY {
+	if (!ix || !r || !out) return fail(LSQ_E_ARG, "null argument");
+	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
+	std::unique_ptr<lsq_jn_table> t(new lsq_jn_table);
+	const JnReads R{r->n_reads, r->n_blocks, (const unsigned long long *)r->blk_off, r->blk_start, r->blk_end, r->blk_chrom, r->blk_strand};
+	const int rc = jn_host_reads(*ix, R, min_overhang, n_threads, *t);
+	if (rc) return rc;
+	*out = t.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+int lsq_jn_host(lsq_jn_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, int n_threads,
+                lsq_jn_table **out) LSQ_API_TRY {
+	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
+	lsq_reads *r = nullptr;
+	int rc;
+	if (strcmp(read_format, "SAM_SINGLE") == 0) rc = lsq_sam_parse(path, &ix->E, skip_flags, min_mapq, n_threads, &r);
+	else if (strcmp(read_format, "BAM_SINGLE") == 0) rc = lsq_bam_parse(path, &ix->E, skip_flags, min_mapq, n_threads, &r);
+	else rc = lsq_reads_parse(read_format, path, &ix->E, n_threads, &r);
+	if (rc) return rc;
+	rc = lsq_jn_host_reads(ix, r, min_overhang, n_threads, out);
+	lsq_reads_free(r);
+	return rc;
+} LSQ_API_CATCH
+
+void lsq_jn_table_free(lsq_jn_table *t) { delete t; }
+int64_t lsq_jn_table_rows(const lsq_jn_table *t) { return t ? (int64_t)t->chrom.size() : 0; }
+int lsq_jn_table_arrays(const lsq_jn_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint8_t **ann,
+                        const uint32_t **reads, const uint32_t **plus, const uint32_t **minus, const uint32_t **max_overhang) {
+	if (!t) return fail(LSQ_E_ARG, "null argument");
+	if (chrom) *chrom = t->chrom.data();
+	if (start) *start = t->start.data();
+	if (end) *end = t->end.data();
+	if (ann) *ann = t->ann.data();
+	if (reads) *reads = t->reads.data();
+	if (plus) *plus = t->plus.data();
+	if (minus) *minus = t->minus.data();
+	if (max_overhang) *max_overhang = t->max_overhang.data();
+	return LSQ_OK;
+}
+int lsq_jn_table_report(const lsq_jn_table *t, uint64_t report[5]) {
+	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
+	memcpy(report, t->report, sizeof(t->report));
+	return LSQ_OK;
+}
+int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]) {
+	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
+	memcpy(ms, t->ms, sizeof(t->ms));
+	return LSQ_OK;
+}
+
+int lsq_jn_format(const lsq_jn_table *t, uint32_t min_reads, int novel_only, char **out_text) LSQ_API_TRY {
+	if (!t || !out_text) return fail(LSQ_E_ARG, "null argument");
+	std::string o;
+	char buf[96];
+	for (size_t i = 0; i < t->chrom.size(); ++i) {
+		if (t->reads[i] < min_reads || (novel_only && t->ann[i] != '.')) continue;
+		o += t->chrom_names[t->chrom[i]];
+		snprintf(buf, sizeof buf, "\t%lld\t%lld\t%c\t%u\t%u\t%u\t%u\n", (long long)t->start[i] + 1, (long long)t->end[i], (char)t->ann[i], t->reads[i], t->plus[i], t->minus[i], t->max_overhang[i]);
+		o += buf;
+	}
+	*out_text = dup_text(o);
+	return *out_text ? LSQ_OK : fail(LSQ_E_INTERNAL, "out of memory");
+} LSQ_API_CATCH
+
+} // extern "C"
+
+// junctions [--host] [--min-overhang N] [--min-reads N] [--novel] <isoform_format> <isoforms_path> <g2i_format> <g2i_path>
+//           <read_format> <reads_path> [<out>]
+// The table on standard output (or in <out>; "-": standard output), the report in the log.  Exit status 1, nothing on standard
+// output, for a file that does not open or parse.
+int lsq::run_junctions(int argc, const char *const *argv, std::string &out) {
+	static const char *USAGE = "Usage:\njunctions [--host] [--min-overhang N] [--min-reads N] [--novel] isoform_format isoforms_path g2i_format g2i_path read_format reads_path [out_path]";
+	bool host = false, novel = false, bad = false;
+	unsigned long min_ov = 1, min_reads = 0;
+	std::vector<const char *> pos;
+	auto number = [&](int &i, unsigned long &v) {
+		char *end = nullptr;
+		if (i + 1 >= argc) { bad = true; return; }
+		errno = 0;
+		v = strtoul(argv[++i], &end, 10);
+		if (end == argv[i] || *end || errno || v > 0xFFFFFFFFul || argv[i][0] == '-') bad = true;
+	};
+	for (int i = 1; i < argc && !bad; ++i) {
+		if (strcmp(argv[i], "--host") == 0) host = true;
+		else if (strcmp(argv[i], "--novel") == 0) novel = true;
+		else if (strcmp(argv[i], "--min-overhang") == 0) number(i, min_ov);
+		else if (strcmp(argv[i], "--min-reads") == 0) number(i, min_reads);
+		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
+		else pos.push_back(argv[i]);
+	}
+	if (bad || pos.size() < 6 || pos.size() > 7 || min_ov < 1) { cli_log(0, USAGE); return 1; }
+	struct Owned {
+		lsq_annotation *a = nullptr; lsq_jn_index *ix = nullptr; lsq_jn_table *t = nullptr; lsq_ctx *c = nullptr; char *text = nullptr;
+		~Owned() { lsq_jn_table_free(t); if (c) lsq_ctx_destroy(c); lsq_jn_index_free(ix); lsq_annotation_free(a); lsq_free(text); }
+	} O;
+	auto failed = [&](int st) {
+		cli_log(0, lsq_last_error());
+		if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
+		return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
+	};
+	int st = lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &O.a);
+	if (!st) st = lsq_jn_index_build(O.a, &O.ix);
+	if (st) return failed(st);
+	if (host) {
+		unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
+		const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
+		for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
+			char *end = nullptr;
+			opt[k] = strtoul(e, &end, 0);
+			if (end == e || *end) { fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e); return failed(LSQ_E_ARG); }
+		}
+		if (opt[2] && strcmp(pos[4], "BAM_SINGLE") == 0) {
+			lsq_reads *r = nullptr;
+			st = lsq_bam_parse_checked(pos[5], &O.ix->E, (unsigned)opt[0], (unsigned)opt[1], 0, &r);
+			if (!st) st = lsq_jn_host_reads(O.ix, r, (uint32_t)min_ov, 0, &O.t);
+			lsq_reads_free(r);
+		} else st = lsq_jn_host(O.ix, pos[4], pos[5], (unsigned)opt[0], (unsigned)opt[1], (uint32_t)min_ov, 0, &O.t);
+	} else {
+		st = lsq_ctx_create(cli_device(), &O.c);
+		if (!st) st = cli_env_options(O.c);
+		if (!st) st = lsq_jn_device(O.c, O.ix, pos[4], pos[5], (uint32_t)min_ov, &O.t);
+	}
+	if (!st) st = lsq_jn_format(O.t, (uint32_t)min_reads, novel ? 1 : 0, &O.text);
+	if (st) return failed(st);
+	char msg[256];
+	snprintf(msg, sizeof msg, "junctions: %llu read(s), %llu block(s), %llu occurrence(s) of %lld junction(s); %llu block pair(s) below the overhang, %llu with a block on no chromosome of the annotation",
+	         (unsigned long long)O.t->report[0], (unsigned long long)O.t->report[1], (unsigned long long)O.t->report[2], (long long)lsq_jn_table_rows(O.t),
+	         (unsigned long long)O.t->report[3], (unsigned long long)O.t->report[4]);
+	cli_log(1, msg);
+	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) {
+		FILE *fp = fopen(pos[6], "wb");
+		const size_t n = strlen(O.text);
+		const bool ok = fp && fwrite(O.text, 1, n, fp) == n;
+		if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", pos[6]); return failed(LSQ_E_IO); }
+	} else out = O.text;
+	return 0;
+}

@@ -1,7 +1,8 @@
 // The read files of the loader: the formats the device parses from a file's own bytes (READ_FORMATS), a file of one of them opened
 // (ReadSource), and the entry points that take one -- through the chain (lsq_ingest.hip) for count and solve, into the arrays of
 // lsq_mrf_parse for tests and tools, or over its records alone (lsq_bam_check).  The parsers themselves are lsq_mrf_device.hpp,
-// lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only.
+// lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only, this unit and the
+// junction passes (lsq_junc.hip) through lsq_junc.hpp.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -9,6 +10,7 @@
 #include "lsq_mrf_device.hpp"
 #include "lsq_sam_device.hpp"
 #include "lsq_bam_device.hpp"
+#include "lsq_junc.hpp"
 
 namespace {
 
@@ -448,6 +450,31 @@ int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r) LSQ_API_TRY {
 	R.records = S.BR.n_rec; R.blocks_repaired = c->bam_blocks_repaired;
 	R.reads = P.n_reads; R.read_blocks = P.n_blocks;
 	*r = R;
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+// The splice junctions of a read file (include/lesseq_hip.h): the file parsed as lsq_mrf_parse_device parses it, against the
+// index's dictionaries instead of the events' -- for the length of the call the index's lsq_events stands where the context's
+// does, so every parser finds its chromosomes, its strand table and its library type (unstranded) where it always looks -- and the
+// device arrays handed to lsq_junc.hip.  The context's events, reads and counters are not touched.
+int lsq_jn_device(lsq_ctx *c, lsq_jn_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_jn_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
+	HIP_TRY(hipSetDevice(c->device));
+	const ReadFormat *fmt;
+	lsq_text T;
+	int rc;
+	if ((rc = ensure_lanes(c)) || (rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
+	struct Stand { lsq_ctx *c; lsq_events *own; ~Stand() { c->E = own; } } stand{c, c->E};
+	c->E = &ix->E;
+	DevParsed P;
+	if ((rc = parse_staged_text(c, fmt, T, P))) return rc;
+	T.d_text.alloc(0); T.d_tile_base.alloc(0);          // (the text has been read: its room is the sort's)
+	std::unique_ptr<lsq_jn_table> t(new lsq_jn_table);
+	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
+	if ((rc = jn_device_reads(c, *ix, R, min_overhang, *t))) return rc;
+	jn_finish_table(*ix, *t);
+	*out = t.release();
 	return LSQ_OK;
 } LSQ_API_CATCH
 
