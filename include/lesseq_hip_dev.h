@@ -1,7 +1,7 @@
 /* lesseq_hip_dev.h -- developer entry points of liblesseq_hip.so, beside the product ABI of
  * lesseq_hip.h.  Nothing here replaces anything in the reference; the tools under tools/ and a
  * few tests use them to look inside a run (tools/kbench.py, tools/step_bench.py,
- * tests/test_parity_gpu.py).  They may change without notice. */
+ * tests/test_parity_gpu.py, tests/test_em_direct_gpu.py).  They may change without notice. */
 #ifndef LESSEQ_HIP_DEV_H
 #define LESSEQ_HIP_DEV_H
 
@@ -42,6 +42,19 @@ int lsq_debug_offsets(lsq_ctx *c, int method, int which, unsigned long long *out
  * isoforms and one (method, class) pair per lane.  Results do not depend on the placement
  * (tests/test_parity_gpu.py::test_em_numbers_do_not_depend_on_which_events_share_a_wave). */
 int lsq_debug_set_em_order(lsq_ctx *c, const uint32_t *order, unsigned n_small_places, unsigned n_places);
+
+/* Which kernels the latest lsq_solve launched for the EM, from the launch code's own bookkeeping -- so that a test of one form of the
+ * EM can hold that this form ran, and a silent choice of another cannot pass as it (tests/test_em_direct_gpu.py).  Waits for the
+ * context's streams.  out[0]: the form the lean group (events with at most two isoforms and four (method, class) pairs) went through --
+ * 0: there is none, 1: four lanes an event, 2: four lanes an event with a cap on the passes, then lsq_em_tail_kernel (option em_quad_cap),
+ * 3: lsq_em_head_kernel, then the closed form in lsq_em_tail_kernel (option em_closed_form), 4 / 5: four lanes an event below the split
+ * and one lane an event from it on, with three / four slots an event (one / several read files);
+ * out[1]: the places of the lean group (events and holes; sixteen to a wave of the four-lane form);
+ * out[2]: the split -- the first place solved one lane per event, read back from the device; out[1] when no place was;
+ * out[3]: the places of the general kernel (lsq_em_kernel);
+ * out[4]: 1 when the lean places were in an order learnt from an earlier solve's iteration counts (option em_regroup);
+ * out[5]: the cap of form 2, else 0;  out[6]: 1 when a new order was learnt behind this solve;  out[7]: the step lane (0 / 1). */
+int lsq_debug_last_em_launch(lsq_ctx *c, unsigned out[8]);
 
 /* The rate a plain streaming read of `bytes` of device memory reaches on this device, in GB/s (best launch over
  * eight grid / unroll combinations): the practical ceiling bench.py reports beside the nominal HBM peak. */

@@ -105,6 +105,7 @@ _sig("lsq_ctx_stream", vp, vp)
 _sig("lsq_ctx_synchronize", C.c_int, vp)
 _sig("lsq_ctx_synchronize_for", C.c_int, vp, C.c_double)
 _sig("lsq_debug_throw", C.c_int, C.c_int)
+_sig("lsq_debug_last_em_launch", C.c_int, vp, P(C.c_uint))
 _sig("lsq_debug_hip_versions", C.c_int, P(C.c_int), P(C.c_int))
 _sig("lsq_events_upload", C.c_int, vp, vp)
 _sig("lsq_reads_upload", C.c_int, vp, C.c_int, vp)

@@ -493,6 +493,17 @@ class Context:
         check(lib.lsq_solve_finalize(self.h, C.byref(n)))
         return n.value
 
+    EM_LEAN_FORMS = ("none", "four_lane", "four_lane_capped_tail", "head_tail", "four_lane_flat3", "four_lane_flat4")
+
+    def em_launch(self):
+        """what the latest solve() launched for the EM (lsq_debug_last_em_launch): the form the lean group went through, its
+        places, the first place solved one lane per event (the lean places when none was), the general kernel's places, and
+        whether the lean places were in an order learnt from an earlier solve"""
+        out = (C.c_uint * 8)()
+        check(lib.lsq_debug_last_em_launch(self.h, out))
+        return {"lean_form": self.EM_LEAN_FORMS[out[0]], "lean_places": int(out[1]), "split": int(out[2]), "general_places": int(out[3]),
+                "learnt_placement": bool(out[4]), "quad_cap": int(out[5]), "placement_learnt_after": bool(out[6]), "lane": int(out[7])}
+
     def synchronize(self):
         check(lib.lsq_ctx_synchronize(self.h))
 

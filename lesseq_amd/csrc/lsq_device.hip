@@ -230,7 +230,11 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 			for (size_t d = 0; d < n_dev; ++d) {
 				const int K = E->dev_K[d];
 				if (host_event[d]) continue;            // solved on the host (host_solve)
-				const bool small = K <= 2 && E->n_methods * ((1 << K) - 1) <= EM_LANES;
+				// (an isoform with ONE accessible start, G = 1: the general kernel's loop with the reference's own quotients,
+				// lsq_em.hip em_quad_body)
+				bool unit_g = false;
+				for (int m = 0; m < E->n_methods; ++m) for (int j = 0; j < K; ++j) unit_g = unit_g || E->ev[E->dev2out[d]].ars[m][j] == 1;
+				const bool small = K <= 2 && E->n_methods * ((1 << K) - 1) <= EM_LANES && !unit_g;
 				if (small == (pass == 0)) order.push_back((uint32_t)d);
 			}
 			while (order.size() % (64 / EM_LANES)) order.push_back(0xFFFFFFFFu);
@@ -245,8 +249,10 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 			for (int l = 0; l < 2; ++l)
 				if ((rc = c->em_tail_u32[l].alloc(2 * np)) || (rc = c->em_tail_flag[l].alloc(np)) || (rc = c->em_tail_f64[l].alloc(3 * np))) return rc;
 		}
-		if (c->em_split.n != 3) { if ((rc = c->em_split.alloc(3))) return rc; }
-		HIP_TRY(hipMemsetAsync(c->em_split.p, 0xFF, 3 * sizeof(uint32_t), c->stream));
+		if (c->em_split.n != 4) { if ((rc = c->em_split.alloc(4))) return rc; }
+		HIP_TRY(hipMemsetAsync(c->em_split.p, 0xFF, 4 * sizeof(uint32_t), c->stream));
+		c->em_last_form = c->em_last_lean = c->em_last_general = c->em_last_cap = c->em_last_lane = 0; c->em_last_split_word = 2;
+		c->em_last_learnt = c->em_last_regrouped = false;
 		if ((rc = c->em_order.upload(order.data(), order.size(), c->stream))) return rc;
 		// gene names for span-start ties against named reads
 		std::string blob;
@@ -850,6 +856,24 @@ int lsq_debug_set_em_order(lsq_ctx *c, const uint32_t *order, unsigned n_small_p
 	c->em_small_places = n_small_places; c->em_places = n_places;
 	c->em_order_lane_valid[0] = c->em_order_lane_valid[1] = false;
 	c->opt_em_regroup = false;            // a placement given by hand stays
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+// developer aid (include/lesseq_hip_dev.h): which kernels the latest lsq_solve launched, from run_solve's own bookkeeping; the split
+// is the one device value, read after the streams have drained
+int lsq_debug_last_em_launch(lsq_ctx *c, unsigned out[8]) LSQ_API_TRY {
+	if (!c || !out) return fail(LSQ_E_ARG, "null argument");
+	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
+	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = sync_all(c); if (rc) return rc; }
+	unsigned split = c->em_last_lean;
+	if (c->em_last_form >= 4u) {
+		uint32_t w = 0;
+		HIP_TRY(hipMemcpy(&w, c->em_split.p + c->em_last_split_word, sizeof w, hipMemcpyDeviceToHost));
+		split = std::min<unsigned>(w, c->em_last_lean);
+	}
+	out[0] = c->em_last_form; out[1] = c->em_last_lean; out[2] = split; out[3] = c->em_last_general;
+	out[4] = c->em_last_learnt ? 1u : 0u; out[5] = c->em_last_cap; out[6] = c->em_last_regrouped ? 1u : 0u; out[7] = c->em_last_lane;
 	return LSQ_OK;
 } LSQ_API_CATCH
 

@@ -209,7 +209,7 @@ struct lsq_ctx {
 	// on the same lane sorts the lean group's places by the iteration counts that solve just wrote; the lane's next solve
 	// (two steps later) and the fifteen after it use that order.  A prediction, nothing more: an event's numbers do not depend on its wave mates.
 	DevBuf<uint32_t> em_order_lane[2];
-	DevBuf<uint32_t> em_split;             // per lane the first place of the one-lane-per-event kernel (lsq_em.hip), then a word that says "none"
+	DevBuf<uint32_t> em_split;             // per lane the first place of the one-lane-per-event kernel (lsq_em.hip), then a word that says "none" and one for lsq_debug_last_em_launch
 	bool em_order_lane_valid[2] = {false, false};
 	unsigned em_regroup_age[2] = {0, 0};    // solves since the lane's order was last refreshed (every 16th solve refreshes it)
 	bool opt_em_regroup = true;
@@ -222,6 +222,11 @@ struct lsq_ctx {
 	DevBuf<uint32_t> em_tail_count, em_tail_u32[2];
 	DevBuf<uint8_t> em_tail_flag[2];
 	DevBuf<double> em_tail_f64[2];
+	// what the latest run_solve launched (lsq_debug_last_em_launch, lesseq_hip_dev.h): host bookkeeping, no kernel knows of it.
+	// em_last_split_word: the word of em_split the lean launch read (2: "none"; 3: the copy taken of a lane's word before the
+	// regroup kernel behind that launch wrote the next split into it)
+	unsigned em_last_form = 0, em_last_lean = 0, em_last_general = 0, em_last_cap = 0, em_last_lane = 0, em_last_split_word = 2;
+	bool em_last_learnt = false, em_last_regrouped = false;
 	unsigned opt_em_flat_min = 16384;      // "em_flat_min_events": lean events from which on the fast ones run one lane per event
 	unsigned em_places = 0;
 	unsigned em_small_places = 0;           // the first of them: events of the lean EM kernel

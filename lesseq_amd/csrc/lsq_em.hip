@@ -120,34 +120,8 @@ __device__ inline double fast_log(double s) {
 	return fma(ed, 0.69314718055994528623, fma(ed, 2.3190468138462995584e-17, lm));
 }
 
-__device__ inline void em_pass_cached(const EmCache &E, const double *th, bool on, double &ll, double *z) {
-	double l = 0, zz[EM_CACHED_K] = {0, 0, 0};
-#pragma unroll
-	for (int t = 0; t < EM_CACHED_PAIRS; ++t) {
-		const double kd = E.kd[t];
-		if (on && kd != 0) {
-			const int c = E.cls[t];
-			double s = 0;
-#pragma unroll
-			for (int j = 0; j < EM_CACHED_K; ++j) if (c >> j & 1) s += th[j] * E.g[t][j];
-			l += kd * fast_log(s);
-			if (s > 0) {
-				const double kr = kd * fast_recip(s);
-#pragma unroll
-				for (int j = 0; j < EM_CACHED_K; ++j) if (c >> j & 1) {
-					const double local = th[j] * E.g[t][j];
-					if (local > 0) zz[j] += local * kr;
-				}
-			}
-		}
-	}
-	ll = group_sum(l);
-#pragma unroll
-	for (int j = 0; j < EM_CACHED_K; ++j) z[j] = group_sum(zz[j]);
-}
-
 // The register-cached pass with the class masks folded into G (an isoform outside the class has
-// G = 0: its term adds an exact zero, so sums and their order are those of em_pass_cached).
+// G = 0: its term adds an exact zero).
 // What a pass leaves behind per pair for the next one: the mixture s, its reciprocal and its
 // logarithm.  Passes follow one another with small steps in s (that is what makes slow events
 // slow), so log s(t+1) = log s(t) + log1p(d) with d = (s(t+1) - s(t)) / s(t), and for |d| < 2^-5 a
@@ -344,7 +318,18 @@ __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const
 	const unsigned cb = ev_ok ? A.cls_base[e] : 0, ib = ev_ok ? A.iso_base[e] : 0;
 	const int nc = (1 << K) - 1;
 	const int n_pairs = (int)A.n_methods * nc;
-	const bool cached = K <= EM_CACHED_K && n_pairs <= EM_LANES * EM_CACHED_PAIRS;
+	// An event with an isoform of G = 1 (one accessible start) is never "cached": only there can a mixture reach 1 and the
+	// log-likelihood 0, and then read.h's loop does not end on its 1e-6 test -- the test value tends to a constant far above
+	// it -- but at the iteration at which theta rounds to (1, 0): theta's last bit decides.  The register forms' local * (k / s)
+	// and z * (1 / n), an ulp off each, held theta_0 at 1 - 2^-53 .. 1 - 3 * 2^-53 for one or two iterations longer than the
+	// reference's k * (local / s) and z / n (12 and 13 iterations against 11: tests/test_em_direct_gpu.py::
+	// test_lean_stops_decided_by_rounding).  The loop that reads memory has the reference's operations: IEEE division, the
+	// library's logarithm, ll / nll as a division.  lsq_events_upload places such events with this kernel, never with the lean ones.
+	bool unit_g = false;
+	if (!SMALL && ev_ok)
+		for (unsigned m = 0; m < A.n_methods; ++m)
+			for (int j = 0; j < K; ++j) unit_g = unit_g || A.G[(size_t)m * A.n_iso + ib + (unsigned)j] == 1.0;
+	const bool cached = K <= EM_CACHED_K && n_pairs <= EM_LANES * EM_CACHED_PAIRS && !unit_g;
 	double th[LSQ_MAX_ISOFORMS], z[LSQ_MAX_ISOFORMS];
 #pragma unroll
 	for (int j = 0; j < LSQ_MAX_ISOFORMS; ++j) z[j] = 0;
@@ -386,14 +371,35 @@ __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const
 	if (SMALL) { em_lean<1, 2>(A, C, e, sub, ev_ok, K, ib, inv_n, any_reads, run, cap, T); return; }
 	if (__all(!ev_ok || (cached && K <= 2 && n_pairs <= EM_LANES))) { em_lean<1, 2>(A, C, e, sub, ev_ok, K, ib, inv_n, any_reads, run); return; }
 	if (__all(!ev_ok || cached)) { em_lean<EM_CACHED_PAIRS, EM_CACHED_K>(A, C, e, sub, ev_ok, K, ib, inv_n, any_reads, run); return; }
-	if (cached) em_pass_cached(C, th, any_reads, ll, z);
+	// A wave that mixes the two kinds: the register-cached events run the lean pass here too, with the state it carries from
+	// pass to pass -- the arithmetic of em_lean operation for operation, so that such an event's numbers are the same bit for
+	// bit whether its wave mates are cached or not (a pass with a logarithm of its own every time gave another last bit of
+	// the log-likelihood than the carried one: tests/test_em_direct_gpu.py::test_general_set_placements)
+	double ckd[EM_CACHED_PAIRS], cgm[EM_CACHED_PAIRS][EM_CACHED_K];
+	EmPairState<EM_CACHED_PAIRS> P;
+#pragma unroll
+	for (int t = 0; t < EM_CACHED_PAIRS; ++t) {
+		ckd[t] = C.kd[t];
+		P.s[t] = 1.0; P.r[t] = 1.0; P.lg[t] = 0.0;
+#pragma unroll
+		for (int j = 0; j < EM_CACHED_K; ++j) cgm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
+	}
+	auto cached_pass = [&](const double *at, const bool on, double &l, double *zv) __attribute__((always_inline)) {
+		double t3[EM_CACHED_K], z3[EM_CACHED_K];
+#pragma unroll
+		for (int j = 0; j < EM_CACHED_K; ++j) t3[j] = at[j];
+		em_pass_lean<EM_CACHED_PAIRS, EM_CACHED_K>(ckd, cgm, t3, on, P, l, z3);
+#pragma unroll
+		for (int j = 0; j < EM_CACHED_K; ++j) zv[j] = z3[j];
+	};
+	if (cached) cached_pass(th, any_reads, ll, z);
 	else em_pass(A, cb, ib, K, nc, sub, any_reads, th, ll, z);
 	while (__any(run)) {
 		// theta' = z(theta) / n; then one pass at theta' gives ll(theta') and z(theta')
 		double nth[LSQ_MAX_ISOFORMS], nll, nz[LSQ_MAX_ISOFORMS];
 #pragma unroll
 		for (int j = 0; j < LSQ_MAX_ISOFORMS; ++j) { nth[j] = cached ? z[j] * inv_n : z[j] / n_total; nz[j] = 0; }
-		if (cached) em_pass_cached(C, nth, run, nll, nz);
+		if (cached) cached_pass(nth, run, nll, nz);
 		else em_pass(A, cb, ib, K, nc, sub, run, nth, nll, nz);
 		if (run) {
 			// read.h:659, floating abs; the quotient through the reciprocal when the passes are the
@@ -921,6 +927,9 @@ int run_solve(lsq_ctx *c) {
 	hipStream_t st = c->stream_em;
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev2, st));
 	const unsigned n_ev = (unsigned)E.dev2out.size();
+	// (lsq_debug_last_em_launch: 0 nothing, 1 four-lane, 2 four-lane capped + tail, 3 head + tail, 4 / 5 four-lane + one-lane<3> / <4>)
+	c->em_last_form = 0; c->em_last_lean = 0; c->em_last_general = 0; c->em_last_cap = 0; c->em_last_lane = (unsigned)c->flip;
+	c->em_last_split_word = 2; c->em_last_learnt = false; c->em_last_regrouped = false;
 	if (n_ev) {
 		EmArgs A{};
 		A.n_events = n_ev; A.n_methods = (unsigned)E.n_methods; A.n_cls = E.n_cls_total; A.n_iso = E.n_iso_total;
@@ -949,6 +958,7 @@ int run_solve(lsq_ctx *c) {
 			hipLaunchKernelGGL(lsq_em_head_kernel<3>, dim3(n_wg), dim3(blk), 0, st, A, T);
 			hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3(n_wg), dim3(blk), 0, st, A, T);
 			HIP_TRY(hipGetLastError());
+			c->em_last_form = 3; c->em_last_lean = c->em_small_places;
 		} else if (c->em_small_places) {
 			const int lane = c->flip;
 			A.place0 = 0; A.n_places = c->em_small_places;
@@ -967,12 +977,20 @@ int run_solve(lsq_ctx *c) {
 				T.t0 = c->em_tail_f64[lane].p; T.t1 = T.t0 + c->em_small_places; T.ll = T.t1 + c->em_small_places;
 				hipLaunchKernelGGL(lsq_em_lean_quad_capped_kernel, dim3(n_quad), dim3(blk), 0, st, A, T, c->opt_em_quad_cap);
 				hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3((c->em_small_places + blk - 1) / blk), dim3(blk), 0, st, A, T);
+				c->em_last_form = 2; c->em_last_cap = c->opt_em_quad_cap;
 			} else if (!n_flat) hipLaunchKernelGGL(lsq_em_lean_quad_kernel, dim3(n_quad), dim3(blk), 0, st, A);
 			else if (E.n_methods == 1) hipLaunchKernelGGL(lsq_em_lean_kernel<3>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
 			else hipLaunchKernelGGL(lsq_em_lean_kernel<4>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
 			HIP_TRY(hipGetLastError());
+			if (!c->em_last_form) c->em_last_form = !n_flat ? 1u : E.n_methods == 1 ? 4u : 5u;
+			c->em_last_lean = c->em_small_places; c->em_last_learnt = regrouped; c->em_last_split_word = flat ? (unsigned)lane : 2u;
 			if (c->opt_em_regroup && (!c->em_order_lane_valid[lane] || ++c->em_regroup_age[lane] >= 16)) {
 				c->em_regroup_age[lane] = 0;
+				c->em_last_regrouped = true;
+				if (flat) {           // the split this launch read, kept for lsq_debug_last_em_launch: the kernel below writes the next one
+					HIP_TRY(hipMemcpyAsync(c->em_split.p + 3, c->em_split.p + lane, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
+					c->em_last_split_word = 3;
+				}
 				if (c->em_order_lane[lane].n != c->em_small_places) { int rc = c->em_order_lane[lane].alloc(c->em_small_places); if (rc) return rc; }
 				hipLaunchKernelGGL(lsq_em_regroup_kernel, dim3(1), dim3(1024), 0, st, c->em_order.p, c->iters.p, c->em_small_places, c->em_order_lane[lane].p, c->em_split.p + lane);
 				HIP_TRY(hipGetLastError());
@@ -984,6 +1002,7 @@ int run_solve(lsq_ctx *c) {
 			A.place0 = c->em_small_places; A.n_places = c->em_places;
 			hipLaunchKernelGGL(lsq_em_kernel, dim3(((c->em_places - c->em_small_places) * EM_LANES + 255) / 256), dim3(256), 0, st, A);
 			HIP_TRY(hipGetLastError());
+			c->em_last_general = c->em_places - c->em_small_places;
 		}
 	}
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev3, st));
