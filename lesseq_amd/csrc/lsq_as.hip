@@ -6,11 +6,12 @@
 //   lsq_as_fisher_kernel   one wave per table: the hypergeometric pmf walked outward from its mode, 64 terms a step
 //   lsq_as_lrt_kernel      one lane per row: two IRLS fits (R's glm.fit), normal equations in registers, Cholesky
 //   lsq_as_wilcox_kernel   one lane per row: W and the tie groups by counting over the row; exact tables from the host
-//   correction             NA compaction (lsq_scan.hpp, flag mode), stable LSD radix sort of (p bits, index), reverse min-scan
+//   correction             NA compaction (lsq_scan.hpp, flag mode), stable LSD radix sort of (p bits, index) (lsq_sort.hpp), reverse min-scan
 #include <cfloat>
 
 #include "lsq_device.hpp"
 #include "lsq_scan.hpp"
+#include "lsq_sort.hpp"
 
 namespace {
 
@@ -347,59 +348,14 @@ __global__ void __launch_bounds__(256) lsq_as_flag_kernel(const double *p, unsig
 	}
 }
 
+// the sort's records (lsq_sort.hpp): w0 = the p-value's bits (non-negative doubles sort as their bit patterns), w1 = its index
 __global__ void __launch_bounds__(256) lsq_as_compact_kernel(const double *p, unsigned long long n, const unsigned *flag, const unsigned long long *pos,
-                                                              unsigned long long *key, unsigned *idx) {
+                                                              unsigned long long *key, unsigned long long *idx) {
 	for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * blockDim.x) {
 		if (!flag[i]) continue;
 		const double v = p[i];
 		key[pos[i]] = v == 0.0 ? 0ull : (unsigned long long)__double_as_longlong(v);     // -0 sorts as +0
-		idx[pos[i]] = (unsigned)i;
-	}
-}
-
-constexpr unsigned RADIX_TILE = 256;      // values per workgroup of a radix pass: one per lane
-
-// per tile the count of each 8-bit digit, digit-major: hist[digit * n_tiles + tile]
-__global__ void __launch_bounds__(256) lsq_as_radix_hist_kernel(const unsigned long long *key, unsigned long long n, unsigned shift,
-                                                                 unsigned *hist, unsigned n_tiles) {
-	__shared__ unsigned h[256];
-	h[threadIdx.x] = 0;
-	__syncthreads();
-	const unsigned long long i = (unsigned long long)blockIdx.x * RADIX_TILE + threadIdx.x;
-	if (i < n) atomicAdd(&h[(unsigned)(key[i] >> shift) & 255u], 1u);
-	__syncthreads();
-	hist[(unsigned long long)threadIdx.x * n_tiles + blockIdx.x] = h[threadIdx.x];
-}
-
-// stable scatter: a value goes to the exclusive prefix of (digit, tile) plus the values of its digit ahead of it in the tile
-// (lanes of its wave with the same digit, found by eight ballots, then the earlier waves' counts)
-__global__ void __launch_bounds__(256) lsq_as_radix_scatter_kernel(const unsigned long long *key_in, const unsigned *idx_in, unsigned long long n,
-                                                                    unsigned shift, const unsigned long long *off, unsigned n_tiles,
-                                                                    unsigned long long *key_out, unsigned *idx_out) {
-	__shared__ unsigned wave_cnt[4][256];
-	const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-	for (unsigned q = threadIdx.x; q < 4 * 256; q += blockDim.x) (&wave_cnt[0][0])[q] = 0;
-	__syncthreads();
-	const unsigned long long i = (unsigned long long)blockIdx.x * RADIX_TILE + threadIdx.x;
-	const bool valid = i < n;
-	const unsigned long long k = valid ? key_in[i] : 0ull;
-	const unsigned d = (unsigned)(k >> shift) & 255u;
-	unsigned long long peers = __ballot(valid);
-#pragma unroll
-	for (unsigned b = 0; b < 8; ++b) {
-		const unsigned long long bb = __ballot((d >> b) & 1u);
-		peers &= ((d >> b) & 1u) ? bb : ~bb;
-	}
-	const unsigned long long lt = lane ? (~0ull >> (64u - lane)) : 0ull;
-	const unsigned ahead = (unsigned)__popcll(peers & lt);
-	if (valid && ahead == 0) wave_cnt[w][d] = (unsigned)__popcll(peers);
-	__syncthreads();
-	if (valid) {
-		unsigned before = 0;
-		for (unsigned q = 0; q < w; ++q) before += wave_cnt[q][d];
-		const unsigned long long dst = off[(unsigned long long)d * n_tiles + blockIdx.x] + before + ahead;
-		key_out[dst] = k;
-		idx_out[dst] = idx_in[i];
+		idx[pos[i]] = i;
 	}
 }
 
@@ -433,7 +389,7 @@ __global__ void lsq_as_minspine_kernel(double *bmin, unsigned long long n_blocks
 }
 
 // the sorted values again: BH = min(1, running minimum from the largest down), Bonferroni = min(1, n p), scattered back
-__global__ void __launch_bounds__(256) lsq_as_minapply_kernel(const unsigned long long *key, const unsigned *idx, unsigned long long n,
+__global__ void __launch_bounds__(256) lsq_as_minapply_kernel(const unsigned long long *key, const unsigned long long *idx, unsigned long long n,
                                                                const double *bcarry, double *bon, double *bh) {
 	__shared__ double lds[4];
 	const unsigned lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
@@ -459,15 +415,10 @@ __global__ void __launch_bounds__(256) lsq_as_minapply_kernel(const unsigned lon
 		if (k >= n) continue;
 		const double pv = __longlong_as_double((long long)key[k]);
 		run = fmin(run, bh_value(key, k, nd));
-		const unsigned i = idx[k];
+		const unsigned i = (unsigned)idx[k];
 		bh[i] = fmin(1.0, run);
 		bon[i] = fmin(1.0, nd * pv);
 	}
-}
-
-unsigned grid_for(const lsq_ctx *c, unsigned long long items, unsigned per_block, unsigned per_cu) {
-	const unsigned long long want = (items + per_block - 1) / per_block, cap = (unsigned long long)c->n_cu * per_cu;
-	return (unsigned)std::max<unsigned long long>(1, std::min(want, cap));
 }
 
 // [n][cols] row-major (the ABI's layout) -> [cols][n] sample-major, so that lane r reading sample j is a coalesced load
@@ -515,7 +466,7 @@ int lsq_as_fisher(lsq_ctx *c, uint64_t n_tables, const double *cells, double *p)
 	DevBuf<double> d_cells, d_p;
 	int rc;
 	if ((rc = d_cells.upload(cells, (size_t)n_tables * 4, c->stream)) || (rc = d_p.alloc((size_t)n_tables))) return rc;
-	hipLaunchKernelGGL(lsq_as_fisher_kernel, dim3(grid_for(c, n_tables, 4, 32)), dim3(256), 0, c->stream, d_cells.p, (unsigned long long)n_tables, d_p.p);
+	hipLaunchKernelGGL(lsq_as_fisher_kernel, dim3(grid_for(c->n_cu, n_tables, 4, 32)), dim3(256), 0, c->stream, d_cells.p, (unsigned long long)n_tables, d_p.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_tables * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	return finish(c);
@@ -533,7 +484,7 @@ int lsq_as_lrt(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count,
 	const std::vector<double> hc = sample_major(count, n_rows, n), ht = sample_major(total, n_rows, n);
 	if ((rc = d_count.upload(hc.data(), hc.size(), c->stream)) || (rc = d_total.upload(ht.data(), ht.size(), c->stream)) ||
 	    (rc = d_stat.alloc((size_t)n_rows)) || (rc = d_p.alloc((size_t)n_rows))) return rc;
-	hipLaunchKernelGGL(lsq_as_lrt_kernel, dim3(grid_for(c, n_rows, 256, 8)), dim3(256), 0, c->stream, d_count.p, d_total.p, (unsigned long long)n_rows, n1, n2, d_stat.p, d_p.p);
+	hipLaunchKernelGGL(lsq_as_lrt_kernel, dim3(grid_for(c->n_cu, n_rows, 256, 8)), dim3(256), 0, c->stream, d_count.p, d_total.p, (unsigned long long)n_rows, n1, n2, d_stat.p, d_p.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(stat, d_stat.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -566,7 +517,7 @@ int lsq_as_wilcox(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *val
 	const std::vector<double> hv = sample_major(value, n_rows, n);
 	if ((rc = d_value.upload(hv.data(), hv.size(), c->stream)) || (rc = d_off.upload(off.data(), off.size(), c->stream)) ||
 	    (rc = d_cdf.upload(cdf.data(), cdf.size(), c->stream)) || (rc = d_diff.alloc((size_t)n_rows)) || (rc = d_p.alloc((size_t)n_rows))) return rc;
-	hipLaunchKernelGGL(lsq_as_wilcox_kernel, dim3(grid_for(c, n_rows, 256, 8)), dim3(256), 0, c->stream, d_value.p, (unsigned long long)n_rows, n1, n2,
+	hipLaunchKernelGGL(lsq_as_wilcox_kernel, dim3(grid_for(c->n_cu, n_rows, 256, 8)), dim3(256), 0, c->stream, d_value.p, (unsigned long long)n_rows, n1, n2,
 	                   (const long long *)d_off.p, (const double *)d_cdf.p, d_diff.p, d_p.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(diff, d_diff.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
@@ -590,36 +541,26 @@ int lsq_as_adjust(lsq_ctx *c, uint64_t n, const double *p, double *p_bonferroni,
 	}
 	HIP_TRY(hipSetDevice(c->device));
 	hipStream_t st = c->stream;
-	const unsigned n_tiles = (unsigned)((n_valid + RADIX_TILE - 1) / RADIX_TILE);
-	const unsigned long long n_hist = (unsigned long long)n_tiles * 256ull;
+	const unsigned nb = grid_for(n_valid, MIN_BLOCK);
 	DevBuf<double> d_p, d_bon, d_bh, d_bmin;
-	DevBuf<unsigned> d_flag, d_idx[2], d_hist;
-	DevBuf<unsigned long long> d_pos, d_key[2], d_off;
-	ScanScratch S;
+	DevBuf<unsigned> d_flag;
+	DevBuf<unsigned long long> d_pos;
+	ScanScratch S;            // of the flag scan over all n values; the sort's scans (over its digit table) have B's own
+	SortBuf B;
 	int rc;
 	if ((rc = d_p.upload(p, (size_t)n, st)) || (rc = d_bon.alloc((size_t)n)) || (rc = d_bh.alloc((size_t)n)) || (rc = d_flag.alloc((size_t)n)) ||
-	    (rc = d_pos.alloc((size_t)n + 1)) || (rc = d_key[0].alloc((size_t)n_valid)) || (rc = d_key[1].alloc((size_t)n_valid)) ||
-	    (rc = d_idx[0].alloc((size_t)n_valid)) || (rc = d_idx[1].alloc((size_t)n_valid)) || (rc = d_hist.alloc((size_t)n_hist)) ||
-	    (rc = d_off.alloc((size_t)n_hist + 1)) || (rc = d_bmin.alloc((size_t)((n_valid + MIN_BLOCK - 1) / MIN_BLOCK))) ||
-	    (rc = S.reserve(std::max<unsigned long long>(n, n_hist)))) return rc;
-	const unsigned g = grid_for(c, n, 256, 16);
+	    (rc = d_pos.alloc((size_t)n + 1)) || (rc = B.reserve(n_valid)) || (rc = d_bmin.alloc(nb)) || (rc = S.reserve(n))) return rc;
+	const unsigned g = grid_for(c->n_cu, n, 256, 16);
 	hipLaunchKernelGGL(lsq_as_flag_kernel, dim3(g), dim3(256), 0, st, (const double *)d_p.p, (unsigned long long)n, d_flag.p, d_bon.p, d_bh.p);
 	if ((rc = device_scan<1, true>(S, d_flag.p, n, d_pos.p, st))) return rc;
 	hipLaunchKernelGGL(lsq_as_compact_kernel, dim3(g), dim3(256), 0, st, (const double *)d_p.p, (unsigned long long)n, (const unsigned *)d_flag.p,
-	                   (const unsigned long long *)d_pos.p, d_key[0].p, d_idx[0].p);
-	// stable LSD radix sort, 8 bits a pass; non-negative doubles sort as their bit patterns
-	for (unsigned pass = 0; pass < 8; ++pass) {
-		const unsigned a = pass & 1u, shift = 8u * pass;
-		hipLaunchKernelGGL(lsq_as_radix_hist_kernel, dim3(n_tiles), dim3(256), 0, st, (const unsigned long long *)d_key[a].p, (unsigned long long)n_valid, shift, d_hist.p, n_tiles);
-		if ((rc = device_scan<1, false>(S, d_hist.p, n_hist, d_off.p, st))) return rc;
-		hipLaunchKernelGGL(lsq_as_radix_scatter_kernel, dim3(n_tiles), dim3(256), 0, st, (const unsigned long long *)d_key[a].p, (const unsigned *)d_idx[a].p,
-		                   (unsigned long long)n_valid, shift, (const unsigned long long *)d_off.p, n_tiles, d_key[a ^ 1u].p, d_idx[a ^ 1u].p);
-	}
-	const unsigned nb = (unsigned)((n_valid + MIN_BLOCK - 1) / MIN_BLOCK);
-	hipLaunchKernelGGL(lsq_as_minblock_kernel, dim3(nb), dim3(256), 0, st, (const unsigned long long *)d_key[0].p, (unsigned long long)n_valid, d_bmin.p);
+	                   (const unsigned long long *)d_pos.p, B.w0[B.cur].p, B.w1[B.cur].p);
+	static const unsigned KEY_DIGITS[8] = {0, 8, 16, 24, 32, 40, 48, 56};      // all of w0; the index in w1 rides along
+	if ((rc = device_radix_sort(B, KEY_DIGITS, 8, st))) return rc;
+	const unsigned long long *key = B.w0[B.cur].p, *idx = B.w1[B.cur].p;
+	hipLaunchKernelGGL(lsq_as_minblock_kernel, dim3(nb), dim3(256), 0, st, key, (unsigned long long)n_valid, d_bmin.p);
 	hipLaunchKernelGGL(lsq_as_minspine_kernel, dim3(1), dim3(64), 0, st, d_bmin.p, (unsigned long long)nb);
-	hipLaunchKernelGGL(lsq_as_minapply_kernel, dim3(nb), dim3(256), 0, st, (const unsigned long long *)d_key[0].p, (const unsigned *)d_idx[0].p,
-	                   (unsigned long long)n_valid, (const double *)d_bmin.p, d_bon.p, d_bh.p);
+	hipLaunchKernelGGL(lsq_as_minapply_kernel, dim3(nb), dim3(256), 0, st, key, idx, (unsigned long long)n_valid, (const double *)d_bmin.p, d_bon.p, d_bh.p);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(p_bonferroni, d_bon.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipMemcpyAsync(p_bh, d_bh.p, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, st));

@@ -80,6 +80,27 @@ struct DevBuf {
 template <class T>
 struct DevView { T *p = nullptr; size_t n = 0; };     // a slice of somebody else's allocation
 
+// The device times of a tool's N phases: N + 1 events, phase k between marks k and k + 1 (once the stream has been waited for).
+// mark and ms hand on the runtime's status, for the caller to check or to ignore.
+template <int N>
+struct PhaseClock {
+	hipEvent_t ev[N + 1] = {};
+	~PhaseClock() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+	int make() { for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e)); return LSQ_OK; }
+	hipError_t mark(int k, hipStream_t st) { return hipEventRecord(ev[k], st); }
+	hipError_t ms(int k, float *out) { return hipEventElapsedTime(out, ev[k], ev[k + 1]); }
+};
+
+// workgroups of a launch over `items` at `per_block` a workgroup (at least one) ...
+inline unsigned grid_for(unsigned long long items, unsigned per_block) {
+	return (unsigned)std::max<unsigned long long>(1, (items + per_block - 1) / per_block);
+}
+// ... and no more than `per_cu` a compute unit (kernels that stride over their items)
+inline unsigned grid_for(int n_cu, unsigned long long items, unsigned per_block, unsigned per_cu) {
+	const unsigned long long want = (items + per_block - 1) / per_block, cap = (unsigned long long)n_cu * per_cu;
+	return (unsigned)std::max<unsigned long long>(1, std::min(want, cap));
+}
+
 // what the loader's routing pass knows about one chromosome: its stretch of the locator grid, of the covered regions and of the clusters
 struct RouteChrom {
 	unsigned loc_first, loc_nb;              // its bins of the grid

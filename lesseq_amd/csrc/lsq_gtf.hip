@@ -243,8 +243,6 @@ __global__ void __launch_bounds__(256) lsq_gtf_emit_heads_kernel(const GtfRec *o
 	heads[place[k]] = r;
 }
 
-struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } };
-
 const char *const KIND_TEXT[] = {"", "", "PROBLEM: Expected to find attribute: gene_id", "", "PROBLEM: Expected to find attribute: transcript_id", ""};
 
 int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, const char *label, lsq_gtf **out) {
@@ -255,12 +253,12 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 	hipStream_t st = c->stream;
 	lsq_text T;
 	int rc;
-	Ev ev[5];
-	for (Ev &x : ev) HIP_TRY(hipEventCreate(&x.e));
+	PhaseClock<4> PC;            // marks 2 -> 3, the host's look at the status, are not reported
+	if ((rc = PC.make())) return rc;
 	if ((rc = text_stage_buffer(c, bytes, len, label, T))) return rc;
-	HIP_TRY(hipEventRecord(ev[0].e, st));
+	HIP_TRY(PC.mark(0, st));
 	if ((rc = scan_newlines(c, T))) return rc;
-	HIP_TRY(hipEventRecord(ev[1].e, st));
+	HIP_TRY(PC.mark(1, st));
 	const unsigned long long n_lines = T.n_nl + 1;                 // lines that may exist (the last one may be empty: the text ends in a newline)
 	if (n_lines >= 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "%s: more than 2^32 lines", label);
 	const unsigned long long n_tiles = (len + TEXT_TILE - 1) / TEXT_TILE;
@@ -275,7 +273,7 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 	const GtfStatus clean{GTF_NO_ERR, 0};
 	HIP_TRY(hipMemcpyAsync(d_status.p, &clean, sizeof clean, hipMemcpyHostToDevice, st));
 	HIP_TRY(hipMemsetAsync(d_keep.p, 0, n_lines * sizeof(unsigned), st));
-	const unsigned lb = (unsigned)((n_lines + 255) / 256);
+	const unsigned lb = grid_for(n_lines, 256);
 	hipLaunchKernelGGL(lsq_gtf_lines_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, (const unsigned char *)T.d_text.p, len, (const unsigned long long *)T.d_tile_base.p,
 	                   d_rec.p, d_keep.p, d_status.p);
 	if ((rc = device_scan<1, true>(S, d_keep.p, n_lines, d_kplace.p, st))) return rc;
@@ -285,7 +283,7 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 	hipLaunchKernelGGL(lsq_gtf_emit_heads_kernel, dim3(lb), dim3(256), 0, st, (const GtfRec *)d_out.p, (const unsigned *)d_head.p, (const unsigned long long *)d_hplace.p,
 	                   (const unsigned long long *)(d_kplace.p + n_lines), d_heads.p);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ev[2].e, st));
+	HIP_TRY(PC.mark(2, st));
 	GtfStatus status;
 	unsigned long long n_kept = 0, n_heads = 0;
 	HIP_TRY(hipMemcpyAsync(&status, d_status.p, sizeof status, hipMemcpyDeviceToHost, st));
@@ -303,20 +301,20 @@ int parse_bytes(lsq_ctx *c, const unsigned char *bytes, unsigned long long len, 
 		return fail(LSQ_E_PARSE, "PROBLEM: Unexpected token: %s", item.c_str());
 	}
 	if (n_kept > n_lines || n_heads > n_kept) return fail(LSQ_E_INTERNAL, "%s: %llu kept lines and %llu runs of %llu lines", label, n_kept, n_heads, n_lines);
-	HIP_TRY(hipEventRecord(ev[3].e, st));
+	HIP_TRY(PC.mark(3, st));
 	std::vector<GtfRec> heads((size_t)n_heads);
 	std::vector<int32_t> se((size_t)n_kept * 2);
 	if (n_kept) {
 		HIP_TRY(hipMemcpyAsync(heads.data(), d_heads.p, (size_t)n_heads * sizeof(GtfRec), hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(se.data(), d_se.p, (size_t)n_kept * sizeof(int2), hipMemcpyDeviceToHost, st));
 	}
-	HIP_TRY(hipEventRecord(ev[4].e, st));
+	HIP_TRY(PC.mark(4, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	float t;
 	G->ms[0] = T.h2d_ms;
-	HIP_TRY(hipEventElapsedTime(&t, ev[0].e, ev[1].e)); G->ms[1] = t;
-	HIP_TRY(hipEventElapsedTime(&t, ev[1].e, ev[2].e)); G->ms[2] = t;
-	HIP_TRY(hipEventElapsedTime(&t, ev[3].e, ev[4].e)); G->ms[3] = t;
+	HIP_TRY(PC.ms(0, &t)); G->ms[1] = t;
+	HIP_TRY(PC.ms(1, &t)); G->ms[2] = t;
+	HIP_TRY(PC.ms(3, &t)); G->ms[3] = t;
 	G->n_lines = T.n_nl + (bytes[len - 1] != '\n' ? 1 : 0);
 	G->n_kept = n_kept; G->n_skipped = status.skipped;
 	if (status.skipped)

@@ -139,18 +139,10 @@ __global__ void __launch_bounds__(256) lsq_jn_annotate_kernel(const unsigned lon
 	O.reads[r] = (unsigned)(i1 - i0);
 }
 
-struct PhaseEvents {
-	hipEvent_t ev[JN_PHASES + 1] = {};
-	int make() { for (hipEvent_t &e : ev) HIP_TRY(hipEventCreate(&e)); return LSQ_OK; }
-	~PhaseEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-};
-
-inline unsigned grid_of(unsigned long long n) { return (unsigned)((n + 255) / 256); }
 // workgroups of the extract: eight a compute unit at most (LSQ_JN_EXTRACT_GRID: another bound -- tests: the stride on a small file)
 inline unsigned extract_grid(const lsq_ctx *c, unsigned long long n_reads) {
-	unsigned long long cap = (unsigned long long)c->n_cu * 8ull;
-	if (const char *e = getenv("LSQ_JN_EXTRACT_GRID")) { const long long v = atoll(e); if (v >= 1 && v <= 1 << 20) cap = (unsigned long long)v; }
-	return (unsigned)std::min<unsigned long long>((n_reads + 255) / 256, cap);
+	if (const char *e = getenv("LSQ_JN_EXTRACT_GRID")) { const long long v = atoll(e); if (v >= 1 && v <= 1 << 20) return std::min(grid_for(n_reads, 256), (unsigned)v); }
+	return grid_for(c->n_cu, n_reads, 256, 8);
 }
 
 } // namespace
@@ -158,8 +150,8 @@ inline unsigned extract_grid(const lsq_ctx *c, unsigned long long n_reads) {
 int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, lsq_jn_table &t) {
 	hipStream_t st = c->stream;
 	int rc;
-	PhaseEvents PE;
-	if ((rc = PE.make())) return rc;
+	PhaseClock<JN_PHASES> PC;
+	if ((rc = PC.make())) return rc;
 	if (R.n_reads > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 reads");
 	t.resize(0);
 	t.report[0] = R.n_reads; t.report[1] = R.n_blocks; t.report[2] = t.report[3] = t.report[4] = 0;
@@ -167,7 +159,7 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 	if (!R.n_reads) return LSQ_OK;
 
 	// ---- extract
-	HIP_TRY(hipEventRecord(PE.ev[0], st));
+	HIP_TRY(PC.mark(0, st));
 	DevBuf<unsigned> d_cnt;
 	DevBuf<unsigned long long> d_off;
 	DevBuf<JnAcc> d_acc;
@@ -191,7 +183,7 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 		HIP_TRY(hipGetLastError());
 	}
 	HIP_TRY(hipMemcpyAsync(&acc, d_acc.p, sizeof(acc), hipMemcpyDeviceToHost, st));
-	HIP_TRY(hipEventRecord(PE.ev[1], st));
+	HIP_TRY(PC.mark(1, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	d_cnt.alloc(0); d_off.alloc(0);
 	t.report[2] = n_occ; t.report[3] = acc.dropped; t.report[4] = acc.nochrom;
@@ -208,13 +200,13 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 		const unsigned long long any[2] = {acc.any0, acc.any1}, all[2] = {acc.all0, acc.all1};
 		const unsigned n_digits = sort_digits(any, all, ALL_DIGITS, 10, digits);
 		if ((rc = device_radix_sort(B, digits, n_digits, st))) return rc;
-		HIP_TRY(hipEventRecord(PE.ev[2], st));
+		HIP_TRY(PC.mark(2, st));
 
 		// ---- reduce
 		const unsigned long long *w0 = B.w0[B.cur].p, *w1 = B.w1[B.cur].p;
 		unsigned long long n_heads = 0;
 		if ((rc = d_head.alloc((size_t)n_occ)) || (rc = d_rid.alloc((size_t)n_occ + 1)) || (rc = SS.reserve(n_occ))) return rc;
-		hipLaunchKernelGGL(lsq_jn_heads_kernel, dim3(grid_of(n_occ)), dim3(256), 0, st, w0, w1, n_occ, d_head.p);
+		hipLaunchKernelGGL(lsq_jn_heads_kernel, dim3(grid_for(n_occ, 256)), dim3(256), 0, st, w0, w1, n_occ, d_head.p);
 		HIP_TRY(hipGetLastError());
 		if ((rc = device_scan<1, true>(SS, d_head.p, n_occ, d_rid.p, st))) return rc;
 		HIP_TRY(hipMemcpyAsync(&n_heads, d_rid.p + n_occ, 8, hipMemcpyDeviceToHost, st));
@@ -224,10 +216,10 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 		HIP_TRY(hipMemsetAsync(d_plus.p, 0, (size_t)n_rows * 4, st));
 		HIP_TRY(hipMemsetAsync(d_minus.p, 0, (size_t)n_rows * 4, st));
 		HIP_TRY(hipMemsetAsync(d_maxov.p, 0, (size_t)n_rows * 4, st));
-		hipLaunchKernelGGL(lsq_jn_reduce_kernel, dim3(grid_of(n_occ)), dim3(256), 0, st, w1, (const unsigned *)d_head.p, (const unsigned long long *)d_rid.p, n_occ,
+		hipLaunchKernelGGL(lsq_jn_reduce_kernel, dim3(grid_for(n_occ, 256)), dim3(256), 0, st, w1, (const unsigned *)d_head.p, (const unsigned long long *)d_rid.p, n_occ,
 		                   d_first.p, d_plus.p, d_minus.p, d_maxov.p);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(PE.ev[3], st));
+		HIP_TRY(PC.mark(3, st));
 
 		// ---- annotate
 		const size_t ni = ix.in_key.size();
@@ -235,9 +227,9 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 		    (rc = d_chrom.alloc(n_rows)) || (rc = d_start.alloc(n_rows)) || (rc = d_end.alloc(n_rows)) || (rc = d_ann.alloc(n_rows)) || (rc = d_reads.alloc(n_rows))) return rc;
 		const JnIntrons I{d_ichrom.p, d_ikey.p, d_iann.p, (unsigned)ni};
 		const JnRows O{d_chrom.p, d_start.p, d_end.p, d_ann.p, d_reads.p};
-		hipLaunchKernelGGL(lsq_jn_annotate_kernel, dim3(grid_of(n_rows)), dim3(256), 0, st, w0, w1, n_occ, (const unsigned *)d_first.p, n_rows, I, O);
+		hipLaunchKernelGGL(lsq_jn_annotate_kernel, dim3(grid_for(n_rows, 256)), dim3(256), 0, st, w0, w1, n_occ, (const unsigned *)d_first.p, n_rows, I, O);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(PE.ev[4], st));
+		HIP_TRY(PC.mark(4, st));
 
 		// ---- copy-back: the distinct rows
 		t.resize(n_rows);
@@ -249,11 +241,11 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 		HIP_TRY(hipMemcpyAsync(t.plus.data(), d_plus.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(t.minus.data(), d_minus.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
 		HIP_TRY(hipMemcpyAsync(t.max_overhang.data(), d_maxov.p, (size_t)n_rows * 4, hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipEventRecord(PE.ev[5], st));
+		HIP_TRY(PC.mark(5, st));
 		HIP_TRY(hipStreamSynchronize(st));
-		for (int k = 1; k < JN_PHASES; ++k) (void)hipEventElapsedTime(&t.ms[k], PE.ev[k], PE.ev[k + 1]);
+		for (int k = 1; k < JN_PHASES; ++k) (void)PC.ms(k, &t.ms[k]);
 	}
-	(void)hipEventElapsedTime(&t.ms[0], PE.ev[0], PE.ev[1]);
+	(void)PC.ms(0, &t.ms[0]);
 	return LSQ_OK;
 }
 

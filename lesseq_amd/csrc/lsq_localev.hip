@@ -154,21 +154,21 @@ int lsq_le_detect(lsq_ctx *c, const lsq_le_graphs *g, lsq_le_result **out) LSQ_A
 	DevBuf<unsigned long long> d_bits, d_slot, d_base, d_rec;
 	DevBuf<unsigned> d_hits;
 	ScanScratch S;
-	struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } } ev[5];
-	for (Ev &x : ev) HIP_TRY(hipEventCreate(&x.e));
-	HIP_TRY(hipEventRecord(ev[0].e, st));
+	PhaseClock<4> PC;
 	int rc;
+	if ((rc = PC.make())) return rc;
+	HIP_TRY(PC.mark(0, st));
 	if ((rc = d_genes.upload(desc.data(), G, st)) || (rc = d_pos.upload(g->pos.data(), g->pos.size(), st)) ||
 	    (rc = d_bits.upload((const unsigned long long *)g->bits.data(), g->bits.size(), st)) || (rc = d_hits.alloc(n_hits)) ||
 	    (rc = d_slot.alloc((size_t)n_hits + 1)) || (rc = d_base.alloc(LE_TYPES + 1)) || (rc = S.reserve(n_hits))) return rc;
-	HIP_TRY(hipEventRecord(ev[1].e, st));
-	const unsigned blocks = (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>((G + 3) / 4, (unsigned long long)c->n_cu * 8));
+	HIP_TRY(PC.mark(1, st));
+	const unsigned blocks = grid_for(c->n_cu, G, 4, 8);
 	hipLaunchKernelGGL((lsq_le_kernel<false>), dim3(blocks), dim3(256), 0, st, (const LeGene *)d_genes.p, n, (const int *)d_pos.p,
 	                   (const unsigned long long *)d_bits.p, d_hits.p, (const unsigned long long *)nullptr, (unsigned long long *)nullptr);
 	if ((rc = device_scan<1, false>(S, d_hits.p, n_hits, d_slot.p, st))) return rc;
 	hipLaunchKernelGGL(lsq_le_bases_kernel, dim3(1), dim3(64), 0, st, (const unsigned long long *)d_slot.p, n, d_base.p);
 	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(ev[2].e, st));
+	HIP_TRY(PC.mark(2, st));
 	unsigned long long base[LE_TYPES + 1];
 	HIP_TRY(hipMemcpyAsync(base, d_base.p, sizeof base, hipMemcpyDeviceToHost, st));
 	HIP_TRY(hipStreamSynchronize(st));
@@ -178,13 +178,13 @@ int lsq_le_detect(lsq_ctx *c, const lsq_le_graphs *g, lsq_le_result **out) LSQ_A
 		hipLaunchKernelGGL((lsq_le_kernel<true>), dim3(blocks), dim3(256), 0, st, (const LeGene *)d_genes.p, n, (const int *)d_pos.p,
 		                   (const unsigned long long *)d_bits.p, (unsigned *)nullptr, (const unsigned long long *)d_slot.p, d_rec.p);
 		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(ev[3].e, st));
+		HIP_TRY(PC.mark(3, st));
 		std::vector<unsigned long long> all((size_t)total);
 		HIP_TRY(hipMemcpyAsync(all.data(), d_rec.p, (size_t)total * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-		HIP_TRY(hipEventRecord(ev[4].e, st));
+		HIP_TRY(PC.mark(4, st));
 		HIP_TRY(hipStreamSynchronize(st));
 		float t[4];
-		for (int q = 0; q < 4; ++q) HIP_TRY(hipEventElapsedTime(&t[q], ev[q].e, ev[q + 1].e));
+		for (int q = 0; q < 4; ++q) HIP_TRY(PC.ms(q, &t[q]));
 		for (int q = 0; q < 4; ++q) r->ms[q] = t[q];
 		for (int t = 0; t < LE_TYPES; ++t) r->rec[t].assign(all.begin() + (ptrdiff_t)base[t], all.begin() + (ptrdiff_t)base[t + 1]);
 	}

@@ -10,8 +10,7 @@
 //               so that ONE exclusive prefix sum over the table (lsq_scan.hpp) gives every (digit value, tile) its first place;
 //   scatter     the tile again: a wave takes a quarter of the tile, in order; its records' ranks among equals come from wave
 //               ballots (no atomics: the order of equals is the input's, so the sort is stable and the same from run to run).
-// The digit table is 1 KiB a tile against 64 KiB of records (lsq_as.hip's sort of 1e5 p-values histograms 256 values at a
-// time, a table as large as its data).
+// The digit table is 1 KiB a tile against 64 KiB of records.
 #pragma once
 
 namespace {

@@ -10,6 +10,7 @@ import pytest
 
 import lesseq_amd as L
 from lesseq_amd import diffsplice as ds
+from lesseq_amd.junctions import SORT_TILE
 
 pytestmark = pytest.mark.gpu
 
@@ -317,6 +318,42 @@ def test_adjust_bit_identical(gpu_ctx, n):
     if n == 2:
         q = np.array([0.5, np.nan])
         assert ds.adjust(gpu_ctx, q)[1].tobytes() == q.tobytes()
+
+
+# The correction sorts with the shared device sort: a workgroup takes a tile of SORT_TILE records, a wave a quarter of it.
+# The counts of valid values sit on both sides of a tile's end, of two tiles' end and of a wave's span; with NaNs between
+# them the flag scan (over all values) and the sort's scans (over its digit table) differ in length.
+_T = SORT_TILE
+ADJUST_EDGE_COUNTS = [_T - 1, _T, _T + 1, 2 * _T + 1, _T // 4 - 1, _T // 4, _T // 4 + 1]
+
+
+def _adjust_edge_values(kind, n_valid):
+    rng = np.random.default_rng(n_valid)
+    if kind == "mixed":
+        q = rng.uniform(size=n_valid) ** 3
+        q[rng.integers(0, n_valid, n_valid // 50)] = 0.0
+        q[rng.integers(0, n_valid, n_valid // 20)] = 1.0
+        q[rng.integers(0, n_valid, n_valid // 20)] = q[rng.integers(0, n_valid, n_valid // 20)]      # ties
+        return q
+    if kind == "three":             # a wave's records share three counters of every digit
+        return rng.choice(np.array([1e-3, 0.04, 0.7]), size=n_valid)
+    return np.full(n_valid, 0.03)   # "equal": one counter takes a wave's whole span
+
+
+@pytest.mark.parametrize("kind,n_valid,nans",
+                         [("mixed", k, nans) for k in ADJUST_EDGE_COUNTS for nans in (False, True)] + [("three", 2 * _T + 1, False), ("equal", 2 * _T + 1, False)])
+def test_adjust_at_sort_edges(gpu_ctx, kind, n_valid, nans):
+    q = _adjust_edge_values(kind, n_valid)
+    if nans:                        # a NaN after every second value
+        p = np.full(n_valid + n_valid // 2, np.nan)
+        p[np.arange(n_valid) + np.arange(n_valid) // 2] = q
+    else:
+        p = q
+    assert int((~np.isnan(p)).sum()) == n_valid and (len(p) > n_valid) == nans
+    bon, bh = ds.adjust(gpu_ctx, p)
+    rb, rh = adjust_ref(p)
+    assert bon.tobytes() == rb.tobytes()
+    assert bh.tobytes() == rh.tobytes()
 
 
 # ---- end to end ---------------------------------------------------------------------------------------------------------
