@@ -45,10 +45,11 @@ int lsq_debug_set_em_order(lsq_ctx *c, const uint32_t *order, unsigned n_small_p
 
 /* Which kernels the latest lsq_solve launched for the EM, from the launch code's own bookkeeping -- so that a test of one form of the
  * EM can hold that this form ran, and a silent choice of another cannot pass as it (tests/test_em_direct_gpu.py).  Waits for the
- * context's streams.  out[0]: the form the lean group (events with at most two isoforms and four (method, class) pairs) went through --
- * 0: there is none, 1: four lanes an event, 2: four lanes an event with a cap on the passes, then lsq_em_tail_kernel (option em_quad_cap),
- * 3: lsq_em_head_kernel, then the closed form in lsq_em_tail_kernel (option em_closed_form), 4 / 5: four lanes an event below the split
- * and one lane an event from it on, with three / four slots an event (one / several read files);
+ * context's streams.  out[0]: the form the lean group (events with at most two isoforms and four (method, class) pairs) went through,
+ * the library's EmForm (csrc/lsq_device.hpp) -- 0 EM_FORM_NONE: there is none, 1 EM_FORM_QUAD: four lanes an event, 2 EM_FORM_QUAD_CAPPED:
+ * four lanes an event with a cap on the passes, then lsq_em_tail_kernel (option em_quad_cap), 3 EM_FORM_HEAD_TAIL: lsq_em_head_kernel, then
+ * the closed form in lsq_em_tail_kernel (option em_closed_form), 4 EM_FORM_QUAD_FLAT3 / 5 EM_FORM_QUAD_FLAT4: four lanes an event below the
+ * split and one lane an event from it on, with three / four slots an event (one / several read files);
  * out[1]: the places of the lean group (events and holes; sixteen to a wave of the four-lane form);
  * out[2]: the split -- the first place solved one lane per event, read back from the device; out[1] when no place was;
  * out[3]: the places of the general kernel (lsq_em_kernel);

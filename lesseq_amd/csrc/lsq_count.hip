@@ -1611,7 +1611,7 @@ int run_count(lsq_ctx *c) {
 	// fit, n = n.
 	double max_skew = 0.0;
 	for (int m = 0; m < M; ++m) max_skew = std::max(max_skew, c->reads[m].skew);
-	const unsigned cap = c->opt_wg_per_cu >= 0 ? (unsigned)c->opt_wg_per_cu : (c->em_small_places >= c->opt_em_flat_min && max_skew < 4.0 ? 5u : 0u);
+	const unsigned cap = c->opt_wg_per_cu >= 0 ? (unsigned)c->opt_wg_per_cu : (c->em.small_places >= c->em.opt_flat_min && max_skew < 4.0 ? 5u : 0u);
 	const unsigned lds_bytes = std::max(tables_bytes + WAVES * WAVE_QUEUE_WORDS * 16, cap ? 160u * 1024u / (cap + 1u) + 16u : 0u);
 	if (lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables + read tile exceed the CU's LDS");
 	// (That is how the rule was found, with the 80-register kernel.  The launches it holds to five now run the 96-register

@@ -238,22 +238,17 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 				if (small == (pass == 0)) order.push_back((uint32_t)d);
 			}
 			while (order.size() % (64 / EM_LANES)) order.push_back(0xFFFFFFFFu);
-			if (pass == 0) c->em_small_places = (unsigned)order.size();
+			if (pass == 0) c->em.small_places = (unsigned)order.size();
 		}
-		c->em_places = (unsigned)order.size();
-		c->em_order_lane_valid[0] = c->em_order_lane_valid[1] = false;
-		{
-			const size_t np = std::max<size_t>(c->em_small_places, 1);
-			if ((rc = c->em_tail_count.alloc(4))) return rc;
-			HIP_TRY(hipMemsetAsync(c->em_tail_count.p, 0, 4 * sizeof(uint32_t), c->stream));
-			for (int l = 0; l < 2; ++l)
-				if ((rc = c->em_tail_u32[l].alloc(2 * np)) || (rc = c->em_tail_flag[l].alloc(np)) || (rc = c->em_tail_f64[l].alloc(3 * np))) return rc;
-		}
-		if (c->em_split.n != 4) { if ((rc = c->em_split.alloc(4))) return rc; }
-		HIP_TRY(hipMemsetAsync(c->em_split.p, 0xFF, 4 * sizeof(uint32_t), c->stream));
-		c->em_last_form = c->em_last_lean = c->em_last_general = c->em_last_cap = c->em_last_lane = 0; c->em_last_split_word = 2;
-		c->em_last_learnt = c->em_last_regrouped = false;
-		if ((rc = c->em_order.upload(order.data(), order.size(), c->stream))) return rc;
+		c->em.places = (unsigned)order.size();
+		for (EmLane &l : c->em.lane) l.order_valid = false;
+		if ((rc = c->em.tail_count.alloc(4))) return rc;
+		HIP_TRY(hipMemsetAsync(c->em.tail_count.p, 0, 4 * sizeof(uint32_t), c->stream));
+		if ((rc = c->em.reserve_tails(c->em.small_places))) return rc;
+		if (c->em.split.n != EM_SPLIT_WORDS) { if ((rc = c->em.split.alloc(EM_SPLIT_WORDS))) return rc; }
+		HIP_TRY(hipMemsetAsync(c->em.split.p, 0xFF, EM_SPLIT_WORDS * sizeof(uint32_t), c->stream));
+		c->em.last = {};
+		if ((rc = c->em.order.upload(order.data(), order.size(), c->stream))) return rc;
 		// gene names for span-start ties against named reads
 		std::string blob;
 		std::vector<uint32_t> goff(n_dev + 1, 0);
@@ -844,18 +839,14 @@ int lsq_debug_set_em_order(lsq_ctx *c, const uint32_t *order, unsigned n_small_p
 	HIP_TRY(hipSetDevice(c->device));
 	{ int rc = sync_all(c); if (rc) return rc; }
 	if (n_small_places > n_places) return fail(LSQ_E_ARG, "more small places than places");
-	int rc = c->em_order.upload(order, n_places, c->stream);
+	int rc = c->em.order.upload(order, n_places, c->stream);
 	if (rc) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	{
-		// the closed form's lists are sized by the lean group (lsq_events_upload): a placement that makes the group larger takes larger lists
-		const size_t np = std::max<size_t>(n_small_places, 1);
-		for (int l = 0; l < 2; ++l)
-			if (c->em_tail_flag[l].n < np && ((rc = c->em_tail_u32[l].alloc(2 * np)) || (rc = c->em_tail_flag[l].alloc(np)) || (rc = c->em_tail_f64[l].alloc(3 * np)))) return rc;
-	}
-	c->em_small_places = n_small_places; c->em_places = n_places;
-	c->em_order_lane_valid[0] = c->em_order_lane_valid[1] = false;
-	c->opt_em_regroup = false;            // a placement given by hand stays
+	// the closed form's lists are sized by the lean group (lsq_events_upload): a placement that makes the group larger takes larger lists
+	if ((rc = c->em.reserve_tails(n_small_places))) return rc;
+	c->em.small_places = n_small_places; c->em.places = n_places;
+	for (EmLane &l : c->em.lane) l.order_valid = false;
+	c->em.opt_regroup = false;            // a placement given by hand stays
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -866,14 +857,15 @@ int lsq_debug_last_em_launch(lsq_ctx *c, unsigned out[8]) LSQ_API_TRY {
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
 	HIP_TRY(hipSetDevice(c->device));
 	{ int rc = sync_all(c); if (rc) return rc; }
-	unsigned split = c->em_last_lean;
-	if (c->em_last_form >= 4u) {
+	const EmLaunch &last = c->em.last;
+	unsigned split = last.lean;
+	if (last.form == EM_FORM_QUAD_FLAT3 || last.form == EM_FORM_QUAD_FLAT4) {
 		uint32_t w = 0;
-		HIP_TRY(hipMemcpy(&w, c->em_split.p + c->em_last_split_word, sizeof w, hipMemcpyDeviceToHost));
-		split = std::min<unsigned>(w, c->em_last_lean);
+		HIP_TRY(hipMemcpy(&w, c->em.split.p + last.split_word, sizeof w, hipMemcpyDeviceToHost));
+		split = std::min<unsigned>(w, last.lean);
 	}
-	out[0] = c->em_last_form; out[1] = c->em_last_lean; out[2] = split; out[3] = c->em_last_general;
-	out[4] = c->em_last_learnt ? 1u : 0u; out[5] = c->em_last_cap; out[6] = c->em_last_regrouped ? 1u : 0u; out[7] = c->em_last_lane;
+	out[0] = last.form; out[1] = last.lean; out[2] = split; out[3] = last.general;
+	out[4] = last.learnt ? 1u : 0u; out[5] = last.cap; out[6] = last.regrouped ? 1u : 0u; out[7] = last.lane;
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -923,16 +915,16 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 		c->opt_two_count_streams = value >= 2;
 	} else if (n == "em_flat_min_events") {
 		if (!(value >= 0 && value <= 4e9)) return fail(LSQ_E_ARG, "em_flat_min_events must lie in 0..4e9");
-		c->opt_em_flat_min = (unsigned)value;
+		c->em.opt_flat_min = (unsigned)value;
 	} else if (n == "em_closed_form") {
 		{ int rc = sync_all(c); if (rc) return rc; }
-		c->opt_em_closed = value != 0;
+		c->em.opt_closed = value != 0;
 	} else if (n == "em_quad_cap") {
 		if (value < 0 || value > 1e6) return fail(LSQ_E_ARG, "em_quad_cap out of range");
-		c->opt_em_quad_cap = (unsigned)value;
+		c->em.opt_quad_cap = (unsigned)value;
 	} else if (n == "em_regroup") {
-		c->opt_em_regroup = value != 0;
-		c->em_order_lane_valid[0] = c->em_order_lane_valid[1] = false;
+		c->em.opt_regroup = value != 0;
+		for (EmLane &l : c->em.lane) l.order_valid = false;
 	} else if (n == "recount_every_read") {
 		c->opt_recount = value != 0;
 	} else if (n == "cleanup_workgroups") {

@@ -177,6 +177,54 @@ struct MethodReads {
 
 } // namespace lsq
 
+// how the lean group ran: out[0] of lsq_debug_last_em_launch, each form described there (include/lesseq_hip_dev.h)
+enum EmForm : unsigned { EM_FORM_NONE = 0, EM_FORM_QUAD = 1, EM_FORM_QUAD_CAPPED = 2, EM_FORM_HEAD_TAIL = 3, EM_FORM_QUAD_FLAT3 = 4, EM_FORM_QUAD_FLAT4 = 5 };
+// EmState::split: per step lane the first place of the one-lane-per-event form, written by the lane's regroup kernel; then a word that stays 0xFFFFFFFF
+// (every place to the four-lane form) and the copy of a lane's word taken before the regroup kernel behind a launch wrote the next split into it
+enum : unsigned { EM_SPLIT_NONE = 2, EM_SPLIT_KEPT = 3, EM_SPLIT_WORDS = 4 };
+struct EmLane {                         // per step lane
+	// Regrouping (option "em_regroup", on by default): a wave of the lean EM kernel runs until the slowest of its sixteen
+	// events has converged, so events that take about as many iterations should share waves.  After a solve, a small kernel
+	// on the same lane sorts the lean group's places by the iteration counts that solve just wrote; the lane's next solve
+	// (two steps later) and the fifteen after it use that order.  A prediction, nothing more: an event's numbers do not depend on its wave mates.
+	lsq::DevBuf<uint32_t> order;
+	bool order_valid = false;
+	unsigned age = 0;                   // solves since the order was last refreshed (every 16th solve refreshes it)
+	// the list a capped or headed EM leaves for lsq_em_tail_kernel: event | iterations, flag, theta_0 | theta_1 | log-likelihood
+	lsq::DevBuf<uint32_t> tail_u32;
+	lsq::DevBuf<uint8_t> tail_flag;
+	lsq::DevBuf<double> tail_f64;
+};
+// what the latest run_solve launched (lsq_debug_last_em_launch): host bookkeeping, no kernel knows of it
+struct EmLaunch {
+	unsigned form = EM_FORM_NONE, lean = 0, general = 0, cap = 0, lane = 0, split_word = EM_SPLIT_NONE;      // lean, general: places; split_word: the word of EmState::split the lean launch read
+	bool learnt = false, regrouped = false;
+};
+struct EmState {                        // the EM of a context: placement, options, bookkeeping (lsq_em.hip: run_solve; lsq_device.hip: lsq_events_upload, options, developer aids)
+	EmLane lane[2];
+	EmLaunch last;
+	lsq::DevBuf<uint32_t> order;        // device event per place of the EM grid, as lsq_events_upload laid them out
+	lsq::DevBuf<uint32_t> split;        // EM_SPLIT_WORDS words
+	lsq::DevBuf<uint32_t> tail_count;   // per lane: events on its tail list, tail workgroups done
+	unsigned places = 0;
+	unsigned small_places = 0;          // the first of them: events of the lean EM kernels
+	bool opt_regroup = true;
+	// "em_closed_form" (default off): two-isoform events with one read file run a few ordinary iterations and finish in the
+	// closed form of their EM map (lsq_em.hip: lsq_em_head_kernel / lsq_em_tail_kernel)
+	bool opt_closed = false;
+	// "em_quad_cap" (0: off): the four-lane lean kernel hands events that still run after that many iterations to lsq_em_tail_kernel
+	// (two-isoform events with one read file, where no placement by earlier iteration counts is in use: lsq_em.hip)
+	unsigned opt_quad_cap = 0;
+	unsigned opt_flat_min = 16384;      // "em_flat_min_events": lean events from which on the fast ones run one lane per event
+	// room on both lanes' tail lists for `np` lean places (they only grow)
+	int reserve_tails(size_t np) {
+		np = std::max<size_t>(np, 1);
+		for (EmLane &l : lane)
+			if (l.tail_flag.n < np) { int rc; if ((rc = l.tail_u32.alloc(2 * np)) || (rc = l.tail_flag.alloc(np)) || (rc = l.tail_f64.alloc(3 * np))) return rc; }
+		return LSQ_OK;
+	}
+};
+
 struct lsq_ctx {
 	// lsq_ctx_create_with(LSQ_CTX_LANES_IN_BACKGROUND): the helper thread that makes the lanes' streams and events, and how it ended
 	std::thread lanes_thread;
@@ -222,35 +270,10 @@ struct lsq_ctx {
 	DevBuf<BucketDesc> buckets;
 	DevBuf<uint8_t> images, strand_rank, dK;
 	DevBuf<TieRec> ties;
-	DevBuf<uint32_t> cls_base, iso_base, em_order, gene_name_off;
+	DevBuf<uint32_t> cls_base, iso_base, gene_name_off;
 	DevBuf<char> gene_names;                // device event order
 	DevBuf<uint32_t> pack_cls, pack_iso, pack_ev;      // lsq_results_pack_device: device index of every class / isoform / event of the shard, in output order
-	// Regrouping (option "em_regroup", on by default): a wave of the lean EM kernel runs until the slowest of its sixteen
-	// events has converged, so events that take about as many iterations should share waves.  After a solve, a small kernel
-	// on the same lane sorts the lean group's places by the iteration counts that solve just wrote; the lane's next solve
-	// (two steps later) and the fifteen after it use that order.  A prediction, nothing more: an event's numbers do not depend on its wave mates.
-	DevBuf<uint32_t> em_order_lane[2];
-	DevBuf<uint32_t> em_split;             // per lane the first place of the one-lane-per-event kernel (lsq_em.hip), then a word that says "none" and one for lsq_debug_last_em_launch
-	bool em_order_lane_valid[2] = {false, false};
-	unsigned em_regroup_age[2] = {0, 0};    // solves since the lane's order was last refreshed (every 16th solve refreshes it)
-	bool opt_em_regroup = true;
-	// "em_closed_form" (default off): two-isoform events with one read file run a few ordinary iterations and finish in the
-	// closed form of their EM map (lsq_em.hip: lsq_em_head_kernel / lsq_em_tail_kernel); the tail's list per step lane
-	bool opt_em_closed = false;
-	// "em_quad_cap" (0: off): the four-lane lean kernel hands events that still run after that many iterations to lsq_em_tail_kernel
-	// (two-isoform events with one read file, where no placement by earlier iteration counts is in use: lsq_em.hip)
-	unsigned opt_em_quad_cap = 0;
-	DevBuf<uint32_t> em_tail_count, em_tail_u32[2];
-	DevBuf<uint8_t> em_tail_flag[2];
-	DevBuf<double> em_tail_f64[2];
-	// what the latest run_solve launched (lsq_debug_last_em_launch, lesseq_hip_dev.h): host bookkeeping, no kernel knows of it.
-	// em_last_split_word: the word of em_split the lean launch read (2: "none"; 3: the copy taken of a lane's word before the
-	// regroup kernel behind that launch wrote the next split into it)
-	unsigned em_last_form = 0, em_last_lean = 0, em_last_general = 0, em_last_cap = 0, em_last_lane = 0, em_last_split_word = 2;
-	bool em_last_learnt = false, em_last_regrouped = false;
-	unsigned opt_em_flat_min = 16384;      // "em_flat_min_events": lean events from which on the fast ones run one lane per event
-	unsigned em_places = 0;
-	unsigned em_small_places = 0;           // the first of them: events of the lean EM kernel
+	EmState em;
 	DevBuf<double> G, theta2[2], logll2[2];
 	DevBuf<uint32_t> iters2[2];
 	DevBuf<uint8_t> flags2[2];

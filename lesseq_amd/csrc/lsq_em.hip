@@ -135,10 +135,20 @@ struct EmTail {
 	unsigned *ev, *iters;
 	unsigned char *flag;
 	double *t0, *t1, *ll;          // theta and log-likelihood after `iters` accepted iterations
+	__device__ inline void push(const unsigned e, const unsigned it, const unsigned char fl, const double th0, const double th1, const double l) const {
+		const unsigned at = atomicAdd(&count[0], 1u);
+		ev[at] = e; iters[at] = it; flag[at] = fl; t0[at] = th0; t1[at] = th1; ll[at] = l;
+	}
 };
 
 template <int SLOTS>
-struct EmPairState { double s[SLOTS], r[SLOTS], lg[SLOTS]; };
+struct EmPairState {
+	double s[SLOTS], r[SLOTS], lg[SLOTS];
+	__device__ inline EmPairState() {
+#pragma unroll
+		for (int t = 0; t < SLOTS; ++t) { s[t] = 1.0; r[t] = 1.0; lg[t] = 0.0; }
+	}
+};
 
 __device__ inline double log1p_small(double d) {
 	// d (1 - d/2 + d^2/3 - ... - d^11/12), |d| < 2^-5: the first term left out is below 1e-19
@@ -215,6 +225,57 @@ __device__ inline void em_pass_lean(const double (&kd)[SLOTS], const double (&gm
 	else ll = group_sum(l);
 }
 
+// An event in registers as em_pass_lean takes it: per slot the count and G with the class mask folded in, theta at its
+// start 1/K (solve/solve.cpp:798-802, read.h:642) and what the passes carry.  Arrays that only unrolled loops index.
+template <int SLOTS, int KK>
+struct EmRegs {
+	double kd[SLOTS], gm[SLOTS][KK], th[KK];
+	EmPairState<SLOTS> P;
+	template <class CacheT>
+	__device__ inline void load(const CacheT &C, const int K) {
+#pragma unroll
+		for (int t = 0; t < SLOTS; ++t) {
+			kd[t] = C.kd[t];
+#pragma unroll
+			for (int j = 0; j < KK; ++j) gm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
+		}
+#pragma unroll
+		for (int j = 0; j < KK; ++j) th[j] = (K == 1) ? 1.0 : 1.0 / (double)K;
+	}
+};
+
+// an event's result, written by the one lane that holds it
+template <int KK>
+__device__ inline void em_store(const EmArgs &A, const unsigned e, const unsigned ib, const int K, const double (&th)[KK], const double ll, const unsigned iters, const unsigned char flag) {
+#pragma unroll
+	for (int j = 0; j < KK; ++j) if (j < K) A.theta[ib + j] = th[j];
+	A.logll[e] = ll;
+	A.iters[e] = iters;
+	A.flags[e] = flag;
+}
+
+// The next count's streaming kernel may share the SIMDs (lsq_device.hpp: the result stream); the EM kernels are
+// a few dependent chains, that one thousands of independent ones: these waves go first.
+__device__ inline void em_waves_first() {
+#ifndef LSQ_EM_NO_PRIO
+	__builtin_amdgcn_s_setprio(3);
+#endif
+}
+
+// the stop test of read.h:659 as the register forms take it: floating abs, the quotient through the reciprocal (1 ulp; the guard band is 1e-11); -inf, nan, zero keep the division's own answers
+__device__ inline double em_crit(const double ll, const double nll) {
+	const unsigned ex = (unsigned)((unsigned long long)__double_as_longlong(nll) >> 52) & 0x7FFu;
+	return (ex - 1u < 0x7FEu) ? fabs(1.0 - ll * fast_recip(nll)) : fabs(1.0 - ll / nll);
+}
+
+// ... and what its value means for an accepted iteration: counted, flagged inside the guard band, the event stopped at the threshold or at max_iters
+__device__ inline void em_accepted(const EmArgs &A, const double crit, unsigned &iters, unsigned char &flag, bool &run) {
+	++iters;
+	if (fabs(crit - 1E-6) < A.band) flag |= 1;
+	if (!(crit > 1E-6)) run = false;
+	else if (iters >= A.max_iters) { flag |= 2; run = false; }
+}
+
 // The whole EM of a wave whose events all fit SLOTS (method, class) pairs per lane and KK isoforms,
 // in registers.  The pass for theta(t+2) starts from z(t+1) as soon as that exists, without waiting
 // for the stop test on ll(t+1): the test (a reciprocal, a compare, a ballot) runs beside the next
@@ -224,27 +285,18 @@ __device__ inline void em_pass_lean(const double (&kd)[SLOTS], const double (&gm
 template <int SLOTS, int KK, bool FLAT = false, class CacheT = EmCache>
 __device__ inline void em_lean(const EmArgs &A, const CacheT &C, const unsigned e, const unsigned sub, const bool ev_ok, const int K, const unsigned ib,
                                const double inv_n, const bool any_reads, bool run, const unsigned cap = 0u, const EmTail *T = nullptr) {
-	double kd[SLOTS], gm[SLOTS][KK], t3[KK], z3[KK];
-#pragma unroll
-	for (int t = 0; t < SLOTS; ++t) {
-		kd[t] = C.kd[t];
-#pragma unroll
-		for (int j = 0; j < KK; ++j) gm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
-	}
-#pragma unroll
-	for (int j = 0; j < KK; ++j) t3[j] = (K == 1) ? 1.0 : 1.0 / (double)K;   // solve/solve.cpp:798-802, read.h:642
-	EmPairState<SLOTS> P;
-#pragma unroll
-	for (int t = 0; t < SLOTS; ++t) { P.s[t] = 1.0; P.r[t] = 1.0; P.lg[t] = 0.0; }
+	EmRegs<SLOTS, KK> R;
+	R.load(C, K);
+	double (&t3)[KK] = R.th, z3[KK];
 	unsigned iters = 0;
 	unsigned char flag = 0;
 	bool handed_on = false;
 	double ll = 0;
-	em_pass_lean<SLOTS, KK, FLAT>(kd, gm, t3, any_reads, P, ll, z3);
+	em_pass_lean<SLOTS, KK, FLAT>(R.kd, R.gm, t3, any_reads, R.P, ll, z3);
 	double c3[KK], cll, cz3[KK];           // candidate: theta(t+1), its log-likelihood and numerators
 #pragma unroll
 	for (int j = 0; j < KK; ++j) c3[j] = z3[j] * inv_n;
-	em_pass_lean<SLOTS, KK, FLAT>(kd, gm, c3, run, P, cll, cz3);
+	em_pass_lean<SLOTS, KK, FLAT>(R.kd, R.gm, c3, run, R.P, cll, cz3);
 	// One turn of the loop: the candidate c = theta(t+1) with its log-likelihood and numerators exists; the pass for
 	// n = theta(t+2) starts from c's numerators at once, and beside it c is tested against the accepted theta(t) and, for
 	// the events still running, accepted.  The loop body is written out twice with c and n in swapped roles, so that
@@ -252,7 +304,7 @@ __device__ inline void em_lean(const EmArgs &A, const CacheT &C, const unsigned 
 	auto turn = [&](const double (&c3)[KK], const double cll, const double (&cz3)[KK], double (&n3)[KK], double &nll, double (&nz3)[KK]) {
 #pragma unroll
 		for (int j = 0; j < KK; ++j) n3[j] = cz3[j] * inv_n;
-		em_pass_lean<SLOTS, KK, FLAT>(kd, gm, n3, run, P, nll, nz3);         // speculative: theta(t+2)
+		em_pass_lean<SLOTS, KK, FLAT>(R.kd, R.gm, n3, run, R.P, nll, nz3);   // speculative: theta(t+2)
 		const unsigned cll_ex = (unsigned)((unsigned long long)__double_as_longlong(cll) >> 52) & 0x7FFu;
 		// read.h:659, floating abs; -inf, nan, zero keep the division's own answers
 		const bool plain = cll_ex - 1u < 0x7FEu;
@@ -262,6 +314,7 @@ __device__ inline void em_lean(const EmArgs &A, const CacheT &C, const unsigned 
 			const double by_division = fabs(1.0 - ll / cll);
 			crit = plain ? crit : by_division;
 		}
+		// (selects on `go`, no branch: the loop of the benchmark's path; a copy of em_accepted, with which it must agree)
 		const bool go = run;
 #pragma unroll
 		for (int j = 0; j < KK; ++j) t3[j] = go ? c3[j] : t3[j];
@@ -281,19 +334,10 @@ __device__ inline void em_lean(const EmArgs &A, const CacheT &C, const unsigned 
 		}
 	}
 	if (handed_on) {
-		if (ev_ok && sub == 0) {
-			const unsigned at = atomicAdd(&T->count[0], 1u);
-			T->ev[at] = e; T->iters[at] = iters; T->flag[at] = flag; T->t0[at] = t3[0]; T->t1[at] = KK > 1 ? t3[KK > 1 ? 1 : 0] : 0.0; T->ll[at] = ll;
-		}
+		if (ev_ok && sub == 0) T->push(e, iters, flag, t3[0], KK > 1 ? t3[KK > 1 ? 1 : 0] : 0.0, ll);
 		return;
 	}
-	if (ev_ok && sub == 0) {
-#pragma unroll
-		for (int j = 0; j < KK; ++j) if (j < K) A.theta[ib + j] = t3[j];
-		A.logll[e] = ll;
-		A.iters[e] = iters;
-		A.flags[e] = flag;
-	}
+	if (ev_ok && sub == 0) em_store(A, e, ib, K, t3, ll, iters, flag);
 }
 
 // SMALL: every event of the launch has at most two isoforms and one (method, class) pair per lane
@@ -301,11 +345,7 @@ __device__ inline void em_lean(const EmArgs &A, const CacheT &C, const unsigned 
 // kernel shares the compute units with the next count's streaming kernel (lsq_device.hpp).
 template <bool SMALL>
 __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const unsigned cap = 0u, const EmTail *T = nullptr) {
-	// The next count's streaming kernel may share the SIMDs (lsq_device.hpp: the result stream); this
-	// kernel is a few dependent chains, that one thousands of independent ones: these waves go first.
-#ifndef LSQ_EM_NO_PRIO
-	__builtin_amdgcn_s_setprio(3);
-#endif
+	em_waves_first();
 	const unsigned gid = block * blockDim.x + threadIdx.x;
 	const unsigned place = A.place0 + gid / EM_LANES, sub = gid % EM_LANES;
 	// events in the order of A.order: the small ones (two isoforms, one pair per lane) first, then the
@@ -375,20 +415,13 @@ __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const
 	// pass to pass -- the arithmetic of em_lean operation for operation, so that such an event's numbers are the same bit for
 	// bit whether its wave mates are cached or not (a pass with a logarithm of its own every time gave another last bit of
 	// the log-likelihood than the carried one: tests/test_em_direct_gpu.py::test_general_set_placements)
-	double ckd[EM_CACHED_PAIRS], cgm[EM_CACHED_PAIRS][EM_CACHED_K];
-	EmPairState<EM_CACHED_PAIRS> P;
-#pragma unroll
-	for (int t = 0; t < EM_CACHED_PAIRS; ++t) {
-		ckd[t] = C.kd[t];
-		P.s[t] = 1.0; P.r[t] = 1.0; P.lg[t] = 0.0;
-#pragma unroll
-		for (int j = 0; j < EM_CACHED_K; ++j) cgm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
-	}
+	EmRegs<EM_CACHED_PAIRS, EM_CACHED_K> R;        // (its theta is not used: th below)
+	R.load(C, K);
 	auto cached_pass = [&](const double *at, const bool on, double &l, double *zv) __attribute__((always_inline)) {
 		double t3[EM_CACHED_K], z3[EM_CACHED_K];
 #pragma unroll
 		for (int j = 0; j < EM_CACHED_K; ++j) t3[j] = at[j];
-		em_pass_lean<EM_CACHED_PAIRS, EM_CACHED_K>(ckd, cgm, t3, on, P, l, z3);
+		em_pass_lean<EM_CACHED_PAIRS, EM_CACHED_K>(R.kd, R.gm, t3, on, R.P, l, z3);
 #pragma unroll
 		for (int j = 0; j < EM_CACHED_K; ++j) zv[j] = z3[j];
 	};
@@ -402,26 +435,15 @@ __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const
 		if (cached) cached_pass(nth, run, nll, nz);
 		else em_pass(A, cb, ib, K, nc, sub, run, nth, nll, nz);
 		if (run) {
-			// read.h:659, floating abs; the quotient through the reciprocal when the passes are the
-			// register-cached ones (1 ulp, against a guard band of 1e-11 around the threshold)
-			const unsigned nll_ex = (unsigned)((unsigned long long)__double_as_longlong(nll) >> 52) & 0x7FFu;
-			const bool nll_normal = nll_ex - 1u < 0x7FEu;     // -inf, nan, zero keep the division's own answers
-			const double crit = (cached && nll_normal) ? fabs(1.0 - ll * fast_recip(nll)) : fabs(1.0 - ll / nll);
+			// read.h:659, floating abs; the register forms' test value when the passes are theirs
+			const double crit = cached ? em_crit(ll, nll) : fabs(1.0 - ll / nll);
 #pragma unroll
 			for (int j = 0; j < LSQ_MAX_ISOFORMS; ++j) { th[j] = nth[j]; z[j] = nz[j]; }
 			ll = nll;
-			++iters;
-			if (fabs(crit - 1E-6) < A.band) flag |= 1;
-			if (!(crit > 1E-6)) run = false;
-			else if (iters >= A.max_iters) { flag |= 2; run = false; }
+			em_accepted(A, crit, iters, flag, run);
 		}
 	}
-	if (ev_ok && sub == 0) {
-		for (int j = 0; j < K; ++j) A.theta[ib + j] = th[j];
-		A.logll[e] = ll;
-		A.iters[e] = iters;
-		A.flags[e] = flag;
-	}
+	if (ev_ok && sub == 0) em_store(A, e, ib, K, th, ll, iters, flag);
 }
 
 // The lean group (two isoforms, at most four (method, class) pairs: LESSeq's local events with one read file) with one
@@ -430,20 +452,12 @@ __device__ inline void em_quad_body(const EmArgs &A, const unsigned block, const
 template <int FS> struct EmCacheFlat { double kd[FS]; double g[FS][2]; int cls[FS]; };
 // FS: slots of an event -- 3 when every event of the group has at most three pairs (one read file), else 4
 template <int FS>
-__device__ inline void em_flat_body(const EmArgs &A, const unsigned block) {
-#ifndef LSQ_EM_NO_PRIO
-	__builtin_amdgcn_s_setprio(3);
-#endif
-	const unsigned place = A.place0 + block * blockDim.x + threadIdx.x;
-	const unsigned first = *A.split;                  // a multiple of 64: the places below it are the four-lane form's
-	if (A.place0 + (block + 1u) * blockDim.x <= first) return;
-	const unsigned e = (place < A.n_places && place >= first) ? A.order[place] : 0xFFFFFFFFu;
-	const bool ev_ok = e != 0xFFFFFFFFu;
-	const int K = ev_ok ? A.K[e] : 1;
-	const unsigned cb = ev_ok ? A.cls_base[e] : 0, ib = ev_ok ? A.iso_base[e] : 0;
+__device__ inline void em_load_flat(const EmArgs &A, const unsigned e, const bool ev_ok, int &K, unsigned &ib, EmCacheFlat<FS> &C, double &n_total, double &inv_n) {
+	K = ev_ok ? A.K[e] : 1;
+	const unsigned cb = ev_ok ? A.cls_base[e] : 0;
+	ib = ev_ok ? A.iso_base[e] : 0;
 	const int nc = (1 << K) - 1;
 	const int n_pairs = (int)A.n_methods * nc;        // <= FS for every event of this group
-	EmCacheFlat<FS> C;
 #pragma unroll
 	for (int q = 0; q < FS; ++q) {
 		const bool has = ev_ok && q < n_pairs;
@@ -453,8 +467,20 @@ __device__ inline void em_flat_body(const EmArgs &A, const unsigned block) {
 #pragma unroll
 		for (int j = 0; j < 2; ++j) C.g[q][j] = (has && j < K) ? A.G[(size_t)m * A.n_iso + ib + j] : 0.0;
 	}
-	const double n_total = ((0.0 + C.kd[0]) + (0.0 + C.kd[1])) + ((0.0 + C.kd[2]) + (0.0 + (FS == 4 ? C.kd[FS - 1] : 0.0)));
-	const double inv_n = 1.0 / n_total;
+	n_total = ((0.0 + C.kd[0]) + (0.0 + C.kd[1])) + ((0.0 + C.kd[2]) + (0.0 + (FS == 4 ? C.kd[FS - 1] : 0.0)));
+	inv_n = 1.0 / n_total;
+}
+
+template <int FS>
+__device__ inline void em_flat_body(const EmArgs &A, const unsigned block) {
+	em_waves_first();
+	const unsigned place = A.place0 + block * blockDim.x + threadIdx.x;
+	const unsigned first = *A.split;                  // a multiple of 64: the places below it are the four-lane form's
+	if (A.place0 + (block + 1u) * blockDim.x <= first) return;
+	const unsigned e = (place < A.n_places && place >= first) ? A.order[place] : 0xFFFFFFFFu;
+	const bool ev_ok = e != 0xFFFFFFFFu;
+	int K; unsigned ib; EmCacheFlat<FS> C; double n_total, inv_n;
+	em_load_flat<FS>(A, e, ev_ok, K, ib, C, n_total, inv_n);
 	// no reads: theta stays 1/K, log-likelihood 0; one isoform: theta = 1 (solve/solve.cpp:798-802)
 	const bool run = ev_ok && n_total > 0 && K > 1, any_reads = ev_ok && n_total > 0;
 	em_lean<FS, 2, true, EmCacheFlat<FS>>(A, C, e, 0u, ev_ok, K, ib, inv_n, any_reads, run);
@@ -480,95 +506,47 @@ __device__ inline void em_flat_body(const EmArgs &A, const unsigned block) {
 // through hundreds of passes, and nothing is learnt from an earlier solve.
 constexpr unsigned EM_HEAD_PASSES = 6;
 
-template <int FS>
-__device__ inline void em_load_flat(const EmArgs &A, const unsigned e, const bool ev_ok, int &K, unsigned &ib, EmCacheFlat<FS> &C, double &n_total) {
-	K = ev_ok ? A.K[e] : 1;
-	const unsigned cb = ev_ok ? A.cls_base[e] : 0;
-	ib = ev_ok ? A.iso_base[e] : 0;
-	const int nc = (1 << K) - 1;
-	const int n_pairs = (int)A.n_methods * nc;        // <= FS for every event of this group
-#pragma unroll
-	for (int q = 0; q < FS; ++q) {
-		const bool has = ev_ok && q < n_pairs;
-		const int m = has ? q / nc : 0, c = has ? q - m * nc : 0;
-		C.kd[q] = has ? (double)A.cnt[(size_t)m * A.n_cls + cb + (unsigned)c] : 0.0;      // exact: counts are far below 2^53
-		C.cls[q] = has ? c + 1 : 0;
-#pragma unroll
-		for (int j = 0; j < 2; ++j) C.g[q][j] = (has && j < K) ? A.G[(size_t)m * A.n_iso + ib + j] : 0.0;
-	}
-	n_total = ((0.0 + C.kd[0]) + (0.0 + C.kd[1])) + ((0.0 + C.kd[2]) + (0.0 + (FS == 4 ? C.kd[FS - 1] : 0.0)));
-}
-
-// the stop test of read.h:659 as the kernels form it: floating abs; -inf, nan, zero keep the division's own answers
-__device__ inline double em_crit(const double ll, const double nll) {
-	const unsigned ex = (unsigned)((unsigned long long)__double_as_longlong(nll) >> 52) & 0x7FFu;
-	return (ex - 1u < 0x7FEu) ? fabs(1.0 - ll * fast_recip(nll)) : fabs(1.0 - ll / nll);
-}
-
-// ordinary iterations from (t3, ll, z3 = numerators at t3) until the stop test holds, `budget` iterations are done or the
+// ordinary iterations from (R.th, ll, z3 = numerators at R.th) until the stop test holds, `budget` iterations are done or the
 // cap is reached; the lanes of a wave run together
 template <int FS>
-__device__ inline void em_iterate(const EmArgs &A, const double (&kd)[FS], const double (&gm)[FS][2], const double inv_n, EmPairState<FS> &P,
-                                  double (&t3)[2], double &ll, double (&z3)[2], unsigned &iters, unsigned char &flag, bool &run, const unsigned budget) {
+__device__ inline void em_iterate(const EmArgs &A, EmRegs<FS, 2> &R, const double inv_n, double &ll, double (&z3)[2], unsigned &iters, unsigned char &flag,
+                                  bool &run, const unsigned budget) {
 	for (unsigned it = 0; it < budget && __any(run); ++it) {
 		double n3[2], nll, nz3[2];
 #pragma unroll
 		for (int j = 0; j < 2; ++j) n3[j] = z3[j] * inv_n;
-		em_pass_lean<FS, 2, true>(kd, gm, n3, run, P, nll, nz3);
+		em_pass_lean<FS, 2, true>(R.kd, R.gm, n3, run, R.P, nll, nz3);
 		const double crit = em_crit(ll, nll);
 		if (run) {
 #pragma unroll
-			for (int j = 0; j < 2; ++j) { t3[j] = n3[j]; z3[j] = nz3[j]; }
+			for (int j = 0; j < 2; ++j) { R.th[j] = n3[j]; z3[j] = nz3[j]; }
 			ll = nll;
-			++iters;
-			if (fabs(crit - 1E-6) < A.band) flag |= 1;
-			if (!(crit > 1E-6)) run = false;
-			else if (iters >= A.max_iters) { flag |= 2; run = false; }
+			em_accepted(A, crit, iters, flag, run);
 		}
 	}
 }
 
 template <int FS>
 __global__ void __launch_bounds__(64) lsq_em_head_kernel(EmArgs A, EmTail T) {
-#ifndef LSQ_EM_NO_PRIO
-	__builtin_amdgcn_s_setprio(3);
-#endif
+	em_waves_first();
 	const unsigned place = A.place0 + blockIdx.x * blockDim.x + threadIdx.x;
 	const unsigned e = place < A.n_places ? A.order[place] : 0xFFFFFFFFu;
 	const bool ev_ok = e != 0xFFFFFFFFu;
-	int K; unsigned ib; EmCacheFlat<FS> C; double n_total;
-	em_load_flat<FS>(A, e, ev_ok, K, ib, C, n_total);
-	const double inv_n = 1.0 / n_total;
+	int K; unsigned ib; EmCacheFlat<FS> C; double n_total, inv_n;
+	em_load_flat<FS>(A, e, ev_ok, K, ib, C, n_total, inv_n);
 	// no reads: theta stays 1/K, log-likelihood 0; one isoform: theta = 1 (solve/solve.cpp:798-802)
 	bool run = ev_ok && n_total > 0 && K > 1;
 	const bool any_reads = ev_ok && n_total > 0;
-	double kd[FS], gm[FS][2], t3[2], z3[2], ll = 0;
-#pragma unroll
-	for (int t = 0; t < FS; ++t) {
-		kd[t] = C.kd[t];
-#pragma unroll
-		for (int j = 0; j < 2; ++j) gm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
-	}
-#pragma unroll
-	for (int j = 0; j < 2; ++j) t3[j] = (K == 1) ? 1.0 : 1.0 / (double)K;   // solve/solve.cpp:798-802, read.h:642
-	EmPairState<FS> P;
-#pragma unroll
-	for (int t = 0; t < FS; ++t) { P.s[t] = 1.0; P.r[t] = 1.0; P.lg[t] = 0.0; }
+	EmRegs<FS, 2> R;
+	R.load(C, K);
+	double z3[2], ll = 0;
 	unsigned iters = 0;
 	unsigned char flag = 0;
-	em_pass_lean<FS, 2, true>(kd, gm, t3, any_reads, P, ll, z3);
-	em_iterate<FS>(A, kd, gm, inv_n, P, t3, ll, z3, iters, flag, run, EM_HEAD_PASSES);
+	em_pass_lean<FS, 2, true>(R.kd, R.gm, R.th, any_reads, R.P, ll, z3);
+	em_iterate<FS>(A, R, inv_n, ll, z3, iters, flag, run, EM_HEAD_PASSES);
 	if (!ev_ok) return;
-	if (run) {            // still running: the tail's
-		const unsigned at = atomicAdd(&T.count[0], 1u);
-		T.ev[at] = e; T.iters[at] = iters; T.flag[at] = flag; T.t0[at] = t3[0]; T.t1[at] = t3[1]; T.ll[at] = ll;
-		return;
-	}
-#pragma unroll
-	for (int j = 0; j < 2; ++j) if (j < K) A.theta[ib + j] = t3[j];
-	A.logll[e] = ll;
-	A.iters[e] = iters;
-	A.flags[e] = flag;
+	if (run) T.push(e, iters, flag, R.th[0], R.th[1], ll);            // still running: the tail's
+	else em_store(A, e, ib, K, R.th, ll, iters, flag);
 }
 
 // theta after m more iterations of the map, from the state the closed form was set up at: x = theta_0 and y = theta_1 = 1 - x,
@@ -588,30 +566,20 @@ struct EmMoebius {
 
 template <int FS>
 __global__ void __launch_bounds__(64) lsq_em_tail_kernel(EmArgs A, EmTail T) {
-#ifndef LSQ_EM_NO_PRIO
-	__builtin_amdgcn_s_setprio(3);
-#endif
+	em_waves_first();
 	const unsigned n_list = __builtin_amdgcn_readfirstlane((int)*(volatile unsigned *)&T.count[0]);
 	const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
 	if (blockIdx.x * blockDim.x < n_list) {
 		const bool ev_ok = i < n_list;
 		const unsigned e = ev_ok ? T.ev[i] : 0xFFFFFFFFu;
-		int K; unsigned ib; EmCacheFlat<FS> C; double n_total;
-		em_load_flat<FS>(A, e, ev_ok, K, ib, C, n_total);
-		const double inv_n = 1.0 / n_total;
-		double kd[FS], gm[FS][2], t3[2], z3[2], ll = ev_ok ? T.ll[i] : 0.0;
-#pragma unroll
-		for (int t = 0; t < FS; ++t) {
-			kd[t] = C.kd[t];
-#pragma unroll
-			for (int j = 0; j < 2; ++j) gm[t][j] = (C.cls[t] >> j & 1) ? C.g[t][j] : 0.0;
-		}
-		t3[0] = ev_ok ? T.t0[i] : 0.5; t3[1] = ev_ok ? T.t1[i] : 0.5;
+		int K; unsigned ib; EmCacheFlat<FS> C; double n_total, inv_n;
+		em_load_flat<FS>(A, e, ev_ok, K, ib, C, n_total, inv_n);
+		EmRegs<FS, 2> R;
+		R.load(C, K);
+		double (&kd)[FS] = R.kd, (&t3)[2] = R.th, z3[2], ll = ev_ok ? T.ll[i] : 0.0;
+		t3[0] = ev_ok ? T.t0[i] : 0.5; t3[1] = ev_ok ? T.t1[i] : 0.5;            // theta as the list has it, not 1/K
 		unsigned iters = ev_ok ? T.iters[i] : 0u;
 		unsigned char flag = ev_ok ? T.flag[i] : (unsigned char)0;
-		EmPairState<FS> P;
-#pragma unroll
-		for (int t = 0; t < FS; ++t) { P.s[t] = 1.0; P.r[t] = 1.0; P.lg[t] = 0.0; }
 		// ---- the closed form, where it applies: classes {0}, {1}, {0, 1} in the slots 0, 1, 2 (one read file).  Reads on both
 		// isoforms alone: always.  On one of them alone (the fixed point may then lie on the boundary): only with at least two
 		// accessible starts per isoform (G < 1) -- with G = 1 the log-likelihood itself runs to 0 there, and the test, a ratio
@@ -734,12 +702,12 @@ __global__ void __launch_bounds__(64) lsq_em_tail_kernel(EmArgs A, EmTail T) {
 		}
 		// the numerators at t3; then: closed form -- exactly one more iteration; otherwise ordinary iterations to the end
 		bool run = ev_ok;
-		em_pass_lean<FS, 2, true>(kd, gm, t3, run, P, ll, z3);
+		em_pass_lean<FS, 2, true>(R.kd, R.gm, t3, run, R.P, ll, z3);
 		if (closed) {
 			double n3v[2], nll, nz3[2];
 #pragma unroll
 			for (int j = 0; j < 2; ++j) n3v[j] = z3[j] * inv_n;
-			em_pass_lean<FS, 2, true>(kd, gm, n3v, run, P, nll, nz3);
+			em_pass_lean<FS, 2, true>(R.kd, R.gm, n3v, run, R.P, nll, nz3);
 			const double crit = em_crit(ll, nll);
 			// the ordinary arithmetic must agree with the search about this iteration; where it does not, the value sits on the
 			// threshold within rounding: flagged (the replay decides)
@@ -749,15 +717,9 @@ __global__ void __launch_bounds__(64) lsq_em_tail_kernel(EmArgs A, EmTail T) {
 		}
 		{
 			bool seq = run && !closed;
-			em_iterate<FS>(A, kd, gm, inv_n, P, t3, ll, z3, iters, flag, seq, 0xFFFFFFFFu);
+			em_iterate<FS>(A, R, inv_n, ll, z3, iters, flag, seq, 0xFFFFFFFFu);
 		}
-		if (ev_ok) {
-#pragma unroll
-			for (int j = 0; j < 2; ++j) if (j < K) A.theta[ib + j] = t3[j];
-			A.logll[e] = ll;
-			A.iters[e] = iters;
-			A.flags[e] = flag;
-		}
+		if (ev_ok) em_store(A, e, ib, K, t3, ll, iters, flag);
 	}
 	// the last workgroup to finish clears the list for the lane's next solve
 	if (threadIdx.x == 0) {
@@ -922,88 +884,110 @@ int run_fim(lsq_ctx *c) {
 	return LSQ_OK;
 }
 
+// the tail list of a step lane, laid out for the lean group as it stands
+static EmTail em_tail_of(lsq_ctx *c, const int lane) {
+	const EmLane &L = c->em.lane[lane];
+	const unsigned np = c->em.small_places;
+	EmTail T{};
+	T.count = c->em.tail_count.p + 2 * lane;
+	T.ev = L.tail_u32.p; T.iters = T.ev + np;
+	T.flag = L.tail_flag.p;
+	T.t0 = L.tail_f64.p; T.t1 = T.t0 + np; T.ll = T.t1 + np;
+	return T;
+}
+
+// behind a lean launch on `lane`, every 16th time and the first: its places sorted by the iteration counts it wrote, for the lane's next solves
+static int schedule_regroup(lsq_ctx *c, const int lane, const bool flat) {
+	EmState &S = c->em;
+	EmLane &L = S.lane[lane];
+	if (!S.opt_regroup || (L.order_valid && ++L.age < 16)) return LSQ_OK;
+	L.age = 0;
+	S.last.regrouped = true;
+	if (flat) {           // the split this launch read, kept for lsq_debug_last_em_launch
+		HIP_TRY(hipMemcpyAsync(S.split.p + EM_SPLIT_KEPT, S.split.p + lane, sizeof(uint32_t), hipMemcpyDeviceToDevice, c->stream_em));
+		S.last.split_word = EM_SPLIT_KEPT;
+	}
+	if (L.order.n != S.small_places) { int rc = L.order.alloc(S.small_places); if (rc) return rc; }
+	hipLaunchKernelGGL(lsq_em_regroup_kernel, dim3(1), dim3(1024), 0, c->stream_em, S.order.p, c->iters.p, S.small_places, L.order.p, S.split.p + lane);
+	HIP_TRY(hipGetLastError());
+	L.order_valid = true;
+	return LSQ_OK;
+}
+
+// the lean group: the places below em.small_places (A: the launch's arguments but for places, order and split)
+static int launch_lean(lsq_ctx *c, EmArgs A) {
+	const lsq_events &E = *c->E;
+	EmState &S = c->em;
+	hipStream_t st = c->stream_em;
+	const int lane = c->flip;
+	// one wave per workgroup: beside a streaming kernel that fills the device, a wave that is done gives its
+	// registers back without waiting for three others (measured 0.259 -> 0.254 ms per pipelined step)
+	const unsigned blk = 64, np = S.small_places, n_lane_wg = (np + blk - 1) / blk;
+	A.place0 = 0; A.n_places = np;
+	if (S.opt_closed && E.n_methods == 1) {
+		// two isoforms, one read file: a head of ordinary iterations for everybody, the closed form for what is left
+		// (no placement by earlier iteration counts, no chain of hundreds of passes)
+		const EmTail T = em_tail_of(c, lane);
+		hipLaunchKernelGGL(lsq_em_head_kernel<3>, dim3(n_lane_wg), dim3(blk), 0, st, A, T);
+		hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3(n_lane_wg), dim3(blk), 0, st, A, T);
+		HIP_TRY(hipGetLastError());
+		S.last.form = EM_FORM_HEAD_TAIL; S.last.lean = np;
+		return LSQ_OK;
+	}
+	const bool regrouped = S.opt_regroup && S.lane[lane].order_valid;
+	if (regrouped) A.order = S.lane[lane].order.p;
+	// one lane per event only for a job's worth of events: with a few thousand (configs[1], a rank's eighth of configs[2])
+	// a step waits for the EM's chain, not for its instructions (C2: 0.0485 ms per step without, 0.0497 with)
+	const bool flat = regrouped && np >= S.opt_flat_min;
+	const unsigned split_word = flat ? (unsigned)lane : EM_SPLIT_NONE;
+	A.split = S.split.p + split_word;
+	const unsigned n_quad = (np * EM_LANES + blk - 1) / blk, n_flat = flat ? n_lane_wg : 0u;
+	const bool capped = !flat && S.opt_quad_cap && E.n_methods == 1;
+	if (capped) {
+		const EmTail T = em_tail_of(c, lane);
+		hipLaunchKernelGGL(lsq_em_lean_quad_capped_kernel, dim3(n_quad), dim3(blk), 0, st, A, T, S.opt_quad_cap);
+		hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3(n_lane_wg), dim3(blk), 0, st, A, T);
+	} else if (!flat) hipLaunchKernelGGL(lsq_em_lean_quad_kernel, dim3(n_quad), dim3(blk), 0, st, A);
+	else if (E.n_methods == 1) hipLaunchKernelGGL(lsq_em_lean_kernel<3>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
+	else hipLaunchKernelGGL(lsq_em_lean_kernel<4>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
+	HIP_TRY(hipGetLastError());
+	S.last.form = capped ? EM_FORM_QUAD_CAPPED : !flat ? EM_FORM_QUAD : E.n_methods == 1 ? EM_FORM_QUAD_FLAT3 : EM_FORM_QUAD_FLAT4;
+	S.last.cap = capped ? S.opt_quad_cap : 0u;
+	S.last.lean = np; S.last.learnt = regrouped; S.last.split_word = split_word;
+	return schedule_regroup(c, lane, flat);
+}
+
+// the other events: the places from em.small_places on, in the order of lsq_events_upload
+static int launch_general(lsq_ctx *c, EmArgs A) {
+	A.place0 = c->em.small_places; A.n_places = c->em.places;
+	const unsigned n = A.n_places - A.place0;
+	hipLaunchKernelGGL(lsq_em_kernel, dim3((n * EM_LANES + 255) / 256), dim3(256), 0, c->stream_em, A);
+	HIP_TRY(hipGetLastError());
+	c->em.last.general = n;
+	return LSQ_OK;
+}
+
 int run_solve(lsq_ctx *c) {
 	const lsq_events &E = *c->E;
 	hipStream_t st = c->stream_em;
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev2, st));
 	const unsigned n_ev = (unsigned)E.dev2out.size();
-	// (lsq_debug_last_em_launch: 0 nothing, 1 four-lane, 2 four-lane capped + tail, 3 head + tail, 4 / 5 four-lane + one-lane<3> / <4>)
-	c->em_last_form = 0; c->em_last_lean = 0; c->em_last_general = 0; c->em_last_cap = 0; c->em_last_lane = (unsigned)c->flip;
-	c->em_last_split_word = 2; c->em_last_learnt = false; c->em_last_regrouped = false;
+	c->em.last = {};
+	c->em.last.lane = (unsigned)c->flip;
 	if (n_ev) {
 		EmArgs A{};
 		A.n_events = n_ev; A.n_methods = (unsigned)E.n_methods; A.n_cls = E.n_cls_total; A.n_iso = E.n_iso_total;
 		A.K = c->dK.p; A.cls_base = c->cls_base.p; A.iso_base = c->iso_base.p;
-		A.order = c->em_order.p;
+		A.order = c->em.order.p;
 		A.max_iters = 1000000u;
 		A.band = c->em_band;
 #ifdef LSQ_DEV
 		if (const char *e = getenv("LSQ_EM_CAP")) { const int v = atoi(e); if (v > 0) A.max_iters = (unsigned)v; }      // timing experiments
 #endif
 		A.cnt = c->cnt.p; A.G = c->G.p; A.theta = c->theta.p; A.logll = c->logll.p; A.iters = c->iters.p; A.flags = c->flags.p;
-		// one wave per workgroup: beside a streaming kernel that fills the device, a wave that is done gives its
-		// registers back without waiting for three others (measured 0.259 -> 0.254 ms per pipelined step)
-		const unsigned blk = 64;
-		if (c->em_small_places && c->opt_em_closed && E.n_methods == 1) {
-			// two isoforms, one read file: a head of ordinary iterations for everybody, the closed form for what is left
-			// (no placement by earlier iteration counts, no chain of hundreds of passes)
-			const int lane = c->flip;
-			A.place0 = 0; A.n_places = c->em_small_places;
-			EmTail T{};
-			T.count = c->em_tail_count.p + 2 * lane;
-			T.ev = c->em_tail_u32[lane].p; T.iters = T.ev + c->em_small_places;
-			T.flag = c->em_tail_flag[lane].p;
-			T.t0 = c->em_tail_f64[lane].p; T.t1 = T.t0 + c->em_small_places; T.ll = T.t1 + c->em_small_places;
-			const unsigned n_wg = (c->em_small_places + blk - 1) / blk;
-			hipLaunchKernelGGL(lsq_em_head_kernel<3>, dim3(n_wg), dim3(blk), 0, st, A, T);
-			hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3(n_wg), dim3(blk), 0, st, A, T);
-			HIP_TRY(hipGetLastError());
-			c->em_last_form = 3; c->em_last_lean = c->em_small_places;
-		} else if (c->em_small_places) {
-			const int lane = c->flip;
-			A.place0 = 0; A.n_places = c->em_small_places;
-			const bool regrouped = c->opt_em_regroup && c->em_order_lane_valid[lane];
-			if (regrouped) A.order = c->em_order_lane[lane].p;
-			// one lane per event only for a job's worth of events: with a few thousand (configs[1], a rank's eighth of configs[2])
-			// a step waits for the EM's chain, not for its instructions (C2: 0.0485 ms per step without, 0.0497 with)
-			const bool flat = regrouped && c->em_small_places >= c->opt_em_flat_min;
-			A.split = c->em_split.p + (flat ? lane : 2);          // (word 2: every place to the four-lane kernel)
-			const unsigned n_quad = (c->em_small_places * EM_LANES + blk - 1) / blk, n_flat = flat ? (c->em_small_places + 63u) / 64u : 0u;
-			if (!n_flat && c->opt_em_quad_cap && E.n_methods == 1) {
-				EmTail T{};
-				T.count = c->em_tail_count.p + 2 * lane;
-				T.ev = c->em_tail_u32[lane].p; T.iters = T.ev + c->em_small_places;
-				T.flag = c->em_tail_flag[lane].p;
-				T.t0 = c->em_tail_f64[lane].p; T.t1 = T.t0 + c->em_small_places; T.ll = T.t1 + c->em_small_places;
-				hipLaunchKernelGGL(lsq_em_lean_quad_capped_kernel, dim3(n_quad), dim3(blk), 0, st, A, T, c->opt_em_quad_cap);
-				hipLaunchKernelGGL(lsq_em_tail_kernel<3>, dim3((c->em_small_places + blk - 1) / blk), dim3(blk), 0, st, A, T);
-				c->em_last_form = 2; c->em_last_cap = c->opt_em_quad_cap;
-			} else if (!n_flat) hipLaunchKernelGGL(lsq_em_lean_quad_kernel, dim3(n_quad), dim3(blk), 0, st, A);
-			else if (E.n_methods == 1) hipLaunchKernelGGL(lsq_em_lean_kernel<3>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
-			else hipLaunchKernelGGL(lsq_em_lean_kernel<4>, dim3(n_quad + n_flat), dim3(blk), 0, st, A, n_quad);
-			HIP_TRY(hipGetLastError());
-			if (!c->em_last_form) c->em_last_form = !n_flat ? 1u : E.n_methods == 1 ? 4u : 5u;
-			c->em_last_lean = c->em_small_places; c->em_last_learnt = regrouped; c->em_last_split_word = flat ? (unsigned)lane : 2u;
-			if (c->opt_em_regroup && (!c->em_order_lane_valid[lane] || ++c->em_regroup_age[lane] >= 16)) {
-				c->em_regroup_age[lane] = 0;
-				c->em_last_regrouped = true;
-				if (flat) {           // the split this launch read, kept for lsq_debug_last_em_launch: the kernel below writes the next one
-					HIP_TRY(hipMemcpyAsync(c->em_split.p + 3, c->em_split.p + lane, sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
-					c->em_last_split_word = 3;
-				}
-				if (c->em_order_lane[lane].n != c->em_small_places) { int rc = c->em_order_lane[lane].alloc(c->em_small_places); if (rc) return rc; }
-				hipLaunchKernelGGL(lsq_em_regroup_kernel, dim3(1), dim3(1024), 0, st, c->em_order.p, c->iters.p, c->em_small_places, c->em_order_lane[lane].p, c->em_split.p + lane);
-				HIP_TRY(hipGetLastError());
-				c->em_order_lane_valid[lane] = true;
-			}
-		}
-		if (c->em_places > c->em_small_places) {
-			A.order = c->em_order.p;
-			A.place0 = c->em_small_places; A.n_places = c->em_places;
-			hipLaunchKernelGGL(lsq_em_kernel, dim3(((c->em_places - c->em_small_places) * EM_LANES + 255) / 256), dim3(256), 0, st, A);
-			HIP_TRY(hipGetLastError());
-			c->em_last_general = c->em_places - c->em_small_places;
-		}
+		int rc = LSQ_OK;
+		if (c->em.small_places && (rc = launch_lean(c, A))) return rc;
+		if (c->em.places > c->em.small_places && (rc = launch_general(c, A))) return rc;
 	}
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev3, st));
 	c->solve_timed = c->time_events;
