@@ -526,7 +526,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck" or "junctions" (lsq_jn_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*) or "coverage" (lsq_cov_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -640,6 +640,65 @@ int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]);
 /* The text of the rows with reads >= min_reads and, with novel_only, ann '.'; malloc'd, NUL-terminated (lsq_free). */
 int lsq_jn_format(const lsq_jn_table *t, uint32_t min_reads, int novel_only, char **out_text);
 int lsq_jn_sort_tile(void);      /* records a workgroup of the device sort takes (tests place their cases around it) */
+
+/* ------------------------------------------------------------------------------------
+ * Per-base read depth of a read file: what `bedtools genomecov -bg -split` prints, and the depth of every
+ * isoform line of the annotation passed (an events .interval file: of every event form)
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition, on the arrays the parsers above give (per read blk_off; per block start, end, chromosome, strand):
+ *   chromosomes    as for lsq_jn_index: the distinct chromosome strings of the annotation's isoform lines.  A block on another
+ *                  chromosome, or with a coordinate outside +-2^30, has no chromosome (the parsers' own rule).
+ *   counted block  a block with a chromosome and end > start; with strand '+' or '-' its strand string must be that one too (the
+ *                  alignment strand, as the parsers deliver it).  Every block is classified by the first rule it fails, in this order.
+ *   depth          at base x of a chromosome: the number of counted blocks, 0-based half-open, that contain x.  Every block counts on
+ *                  its own: two overlapping blocks of one read count twice, mates are two reads.  A uint32.
+ *   rows           the maximal intervals [start, end) of constant depth > 0: two adjacent intervals of equal depth are one row (a
+ *                  position where as many blocks end as begin is no boundary).  Ascending in chromosome name (bytewise), start.
+ *                  Text (bedGraph): chrom TAB start TAB end TAB depth NL, 0-based half-open; no header.
+ *   regions        one per isoform line of the annotation, every line loaded, in file order: the union of the line's exons with
+ *                  end > start (the first exonCount of the line).  bases: the size of the union; covered: its bases with depth >=
+ *                  min_depth; depth_sum: the sum of depth over its bases (64 bits).  Text: name TAB chrom TAB strand TAB bases TAB
+ *                  covered TAB depth_sum TAB mean NL, mean = depth_sum / bases as %.4f, 0.0000 when bases is 0.
+ *   report         reads in the file, blocks in the file, counted blocks, blocks without a chromosome, empty or descending blocks,
+ *                  blocks of the other strand, bases: the summed length of the counted blocks = the sum of (end - start) * depth
+ *                  over the rows.  With an annotation that names every chromosome of the file, bases is solve's total_read_bases.
+ * More than 2^32-1 sort records (two per counted block): LSQ_E_RANGE. */
+typedef struct lsq_cov_index lsq_cov_index;     /* chromosome and strand dictionaries ("+" = 0, "-" = 1), every line's exon union */
+typedef struct lsq_cov_table lsq_cov_table;
+int lsq_cov_index_build(const lsq_annotation *a, lsq_cov_index **out);    /* LSQ_E_RANGE beyond 65 535 chromosomes */
+void lsq_cov_index_free(lsq_cov_index *ix);
+int64_t lsq_cov_index_num_chroms(const lsq_cov_index *ix);
+const char *lsq_cov_index_chrom_name(const lsq_cov_index *ix, int64_t chrom);    /* NULL when out of range */
+int64_t lsq_cov_index_num_regions(const lsq_cov_index *ix);
+lsq_events *lsq_cov_index_dictionaries(lsq_cov_index *ix);                /* as lsq_jn_index_dictionaries */
+/* Host-only, threaded: the tables from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  strand: 0 (every block), '+' or '-'.  lsq_cov_host_reads: from arrays parsed
+ * against the index. */
+int lsq_cov_host(lsq_cov_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq,
+                 int strand, uint32_t min_depth, int n_threads, lsq_cov_table **out);
+int lsq_cov_host_reads(lsq_cov_index *ix, const lsq_reads *r, int strand, uint32_t min_depth, int n_threads, lsq_cov_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed exactly as lsq_jn_device parses it, then extract, sort,
+ * reduce and scan, emit, regions on device arrays; the rows and the regions' sums alone come back.  The context needs no events,
+ * and its events, reads and counters are as they were afterwards.  LSQ_COV_EXTRACT_GRID in the environment bounds the extract's
+ * workgroups (tests). */
+int lsq_cov_device(lsq_ctx *c, lsq_cov_index *ix, const char *read_format, const char *path, int strand, uint32_t min_depth, lsq_cov_table **out);
+void lsq_cov_table_free(lsq_cov_table *t);
+int64_t lsq_cov_table_rows(const lsq_cov_table *t);
+int64_t lsq_cov_table_regions(const lsq_cov_table *t);
+/* The arrays (they live as long as the table; any pointer may be null): chrom indexes lsq_cov_index_chrom_name. */
+int lsq_cov_table_arrays(const lsq_cov_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint32_t **depth);
+int lsq_cov_table_region_arrays(const lsq_cov_table *t, const uint32_t **chrom, const uint64_t **bases, const uint64_t **covered, const uint64_t **depth_sum);
+const char *lsq_cov_table_region_name(const lsq_cov_table *t, int64_t region);      /* NULL when out of range */
+const char *lsq_cov_table_region_strand(const lsq_cov_table *t, int64_t region);
+int lsq_cov_table_report(const lsq_cov_table *t, uint64_t report[7]);
+/* Device milliseconds per phase of the lsq_cov_device call that made the table -- extract, sort, reduce and scan, emit, regions,
+ * copy-back -- from HIP events on the library's stream (zeros from the host path); the parse ahead of them: lsq_last_mrf_timing. */
+int lsq_cov_table_times(const lsq_cov_table *t, float ms[6]);
+/* The bedGraph text of the rows with depth >= min_depth; the regions' text; malloc'd, NUL-terminated (lsq_free). */
+int lsq_cov_format(const lsq_cov_table *t, uint32_t min_depth, char **out_text);
+int lsq_cov_format_regions(const lsq_cov_table *t, char **out_text);
+int lsq_cov_sort_tile(void);     /* records a workgroup of the device sort takes (tests place their cases around it) */
 
 /* ------------------------------------------------------------------------------------
  * Local events: step 2 of the pipeline, bin/Events.r

@@ -236,6 +236,27 @@ _sig("lsq_jn_table_report", C.c_int, vp, P(u64))
 _sig("lsq_jn_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_jn_format", C.c_int, vp, u32, C.c_int, P(vp))
 _sig("lsq_jn_sort_tile", C.c_int)
+_sig("lsq_cov_index_build", C.c_int, vp, P(vp))
+_sig("lsq_cov_index_free", None, vp)
+_sig("lsq_cov_index_num_chroms", i64, vp)
+_sig("lsq_cov_index_chrom_name", cs, vp, i64)
+_sig("lsq_cov_index_num_regions", i64, vp)
+_sig("lsq_cov_index_dictionaries", vp, vp)
+_sig("lsq_cov_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, C.c_int, u32, C.c_int, P(vp))
+_sig("lsq_cov_host_reads", C.c_int, vp, vp, C.c_int, u32, C.c_int, P(vp))
+_sig("lsq_cov_device", C.c_int, vp, vp, cs, cs, C.c_int, u32, P(vp))
+_sig("lsq_cov_table_free", None, vp)
+_sig("lsq_cov_table_rows", i64, vp)
+_sig("lsq_cov_table_regions", i64, vp)
+_sig("lsq_cov_table_arrays", C.c_int, vp, P(P(u32)), P(P(i32)), P(P(i32)), P(P(u32)))
+_sig("lsq_cov_table_region_arrays", C.c_int, vp, P(P(u32)), P(P(u64)), P(P(u64)), P(P(u64)))
+_sig("lsq_cov_table_region_name", cs, vp, i64)
+_sig("lsq_cov_table_region_strand", cs, vp, i64)
+_sig("lsq_cov_table_report", C.c_int, vp, P(u64))
+_sig("lsq_cov_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_cov_format", C.c_int, vp, u32, P(vp))
+_sig("lsq_cov_format_regions", C.c_int, vp, P(vp))
+_sig("lsq_cov_sort_tile", C.c_int)
 
 
 def _warn_on_runtime_mismatch():

@@ -21,6 +21,7 @@
 #include "lsq_localev.hpp"
 #include "lsq_gtf.hpp"
 #include "lsq_junc.hpp"
+#include "lsq_cov.hpp"
 #include "lsq_team.hpp"
 
 using namespace lsq;
@@ -883,6 +884,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "bam2mrf") == 0) rc = run_sam2mrf(true, argc, argv, out);
 	else if (tool && strcmp(tool, "bamcheck") == 0) rc = run_bamcheck(argc, argv, out);
 	else if (tool && strcmp(tool, "junctions") == 0) rc = run_junctions(argc, argv, out);
+	else if (tool && strcmp(tool, "coverage") == 0) rc = run_coverage(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);
 	return rc;

@@ -36,19 +36,56 @@ char *dup_text(const std::string &s) {
 
 } // namespace
 
-void lsq::jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t) {
-	t.chrom_names = ix.E.chroms.names;
-	const size_t n = t.chrom.size(), nc = t.chrom_names.size();
-	// rows arrive ascending in (chromosome index, start, end): the chromosomes' groups reordered by name
+// rows ascending in chromosome index -> where each row of the tables' order (chromosome names bytewise) comes from: the
+// chromosomes' groups reordered, every group as it is
+std::vector<size_t> lsq::rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom) {
+	const size_t n = chrom.size(), nc = names.size();
 	std::vector<size_t> first(nc + 1, 0);
-	for (size_t i = 0; i < n; ++i) ++first[t.chrom[i] + 1];
+	for (size_t i = 0; i < n; ++i) ++first[chrom[i] + 1];
 	for (size_t c = 0; c < nc; ++c) first[c + 1] += first[c];
 	std::vector<uint32_t> order(nc);
 	std::iota(order.begin(), order.end(), 0u);
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return t.chrom_names[a] < t.chrom_names[b]; });
+	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
 	std::vector<size_t> from;
 	from.reserve(n);
 	for (uint32_t c : order) for (size_t i = first[c]; i < first[c + 1]; ++i) from.push_back(i);
+	return from;
+}
+
+// The dictionaries a read file is parsed against without events (lsq_jn_index, lsq_cov_index): "+" and "-" as strands 0 and 1, the
+// distinct chromosome strings of the annotation's isoform lines in file order, one whole-line interval a chromosome
+int lsq::annotation_dictionaries(const lsq_annotation &a, lsq_events &E) {
+	E.strands.intern("+"); E.strands.intern("-");
+	for (const auto &rp : a.recs) if (E.chroms.intern(rp->chrom) >= (int)JN_NOCHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
+	E.covered.resize(E.chroms.names.size());
+	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
+	return LSQ_OK;
+}
+
+// A read file through the host parser of its format, against dictionaries E; verify: a BAM file's CRC32s and end-of-file marker checked
+int lsq::host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r) {
+	if (strcmp(read_format, "SAM_SINGLE") == 0) return lsq_sam_parse(path, E, skip_flags, min_mapq, n_threads, r);
+	if (strcmp(read_format, "BAM_SINGLE") == 0) return verify ? lsq_bam_parse_checked(path, E, skip_flags, min_mapq, n_threads, r) : lsq_bam_parse(path, E, skip_flags, min_mapq, n_threads, r);
+	return lsq_reads_parse(read_format, path, E, n_threads, r);
+}
+
+// ... under LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (the executables' --host)
+int lsq::cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r) {
+	unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
+	const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
+	for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
+		char *end = nullptr;
+		opt[k] = strtoul(e, &end, 0);
+		if (end == e || *end) return fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e);
+	}
+	return host_parse_reads(E, read_format, path, (unsigned)opt[0], (unsigned)opt[1], opt[2] != 0, 0, r);
+}
+
+void lsq::jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t) {
+	t.chrom_names = ix.E.chroms.names;
+	const size_t n = t.chrom.size();
+	// rows arrive ascending in (chromosome index, start, end)
+	const std::vector<size_t> from = rows_by_chrom_name(t.chrom_names, t.chrom);
 	auto permute = [&](auto &v) { auto w = v; for (size_t i = 0; i < n; ++i) w[i] = v[from[i]]; v.swap(w); };
 	permute(t.chrom); permute(t.start); permute(t.end); permute(t.ann); permute(t.reads); permute(t.plus); permute(t.minus); permute(t.max_overhang);
 }
@@ -114,14 +151,14 @@ int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY 
 	if (!a || !out) return fail(LSQ_E_ARG, "null argument");
 	std::unique_ptr<lsq_jn_index> ix(new lsq_jn_index);
 	lsq_events &E = ix->E;
-	E.strands.intern("+"); E.strands.intern("-");
+	int rc;
+	if ((rc = annotation_dictionaries(*a, E))) return rc;
 	struct Intron { uint32_t chrom; uint64_t key; uint8_t ann; };
 	std::vector<Intron> in;
 	std::vector<std::pair<int64_t, int64_t>> ex;
 	for (const auto &rp : a->recs) {
 		const IsoRec &r = *rp;
-		const int cid = E.chroms.intern(r.chrom);
-		if (cid >= (int)JN_NOCHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
+		const int cid = E.chroms.find(r.chrom);
 		// the union of the line's exons: its maximal intervals, and the gaps between them
 		ex.clear();
 		const size_t ne = std::min<size_t>({(size_t)r.exonCount, r.exonStarts.size(), r.exonEnds.size()});
@@ -140,8 +177,6 @@ int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY 
 			if (ix->in_ann.back() != i.ann) ix->in_ann.back() = '*';
 		} else { ix->in_chrom.push_back(i.chrom); ix->in_key.push_back(i.key); ix->in_ann.push_back(i.ann); }
 	}
-	E.covered.resize(E.chroms.names.size());
-	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
 	*out = ix.release();
 	return LSQ_OK;
 } LSQ_API_CATCH
@@ -170,10 +205,7 @@ int lsq_jn_host(lsq_jn_index *ix, const char *read_format, const char *path, uns
 	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
 	lsq_reads *r = nullptr;
-	int rc;
-	if (strcmp(read_format, "SAM_SINGLE") == 0) rc = lsq_sam_parse(path, &ix->E, skip_flags, min_mapq, n_threads, &r);
-	else if (strcmp(read_format, "BAM_SINGLE") == 0) rc = lsq_bam_parse(path, &ix->E, skip_flags, min_mapq, n_threads, &r);
-	else rc = lsq_reads_parse(read_format, path, &ix->E, n_threads, &r);
+	int rc = host_parse_reads(&ix->E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
 	if (rc) return rc;
 	rc = lsq_jn_host_reads(ix, r, min_overhang, n_threads, out);
 	lsq_reads_free(r);
@@ -260,19 +292,10 @@ int lsq::run_junctions(int argc, const char *const *argv, std::string &out) {
 	if (!st) st = lsq_jn_index_build(O.a, &O.ix);
 	if (st) return failed(st);
 	if (host) {
-		unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
-		const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
-		for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
-			char *end = nullptr;
-			opt[k] = strtoul(e, &end, 0);
-			if (end == e || *end) { fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e); return failed(LSQ_E_ARG); }
-		}
-		if (opt[2] && strcmp(pos[4], "BAM_SINGLE") == 0) {
-			lsq_reads *r = nullptr;
-			st = lsq_bam_parse_checked(pos[5], &O.ix->E, (unsigned)opt[0], (unsigned)opt[1], 0, &r);
-			if (!st) st = lsq_jn_host_reads(O.ix, r, (uint32_t)min_ov, 0, &O.t);
-			lsq_reads_free(r);
-		} else st = lsq_jn_host(O.ix, pos[4], pos[5], (unsigned)opt[0], (unsigned)opt[1], (uint32_t)min_ov, 0, &O.t);
+		lsq_reads *r = nullptr;
+		st = cli_host_parse(&O.ix->E, pos[4], pos[5], &r);
+		if (!st) st = lsq_jn_host_reads(O.ix, r, (uint32_t)min_ov, 0, &O.t);
+		lsq_reads_free(r);
 	} else {
 		st = lsq_ctx_create(cli_device(), &O.c);
 		if (!st) st = cli_env_options(O.c);

@@ -59,6 +59,11 @@ constexpr unsigned JN_OV_MASK = 0x3FFFFFFFu, JN_PLUS = 1u << 30, JN_MINUS = 1u <
 // lsq_junc.cpp: rows in (chromosome index, start, end) order -> the table's order (chromosome names bytewise), names attached
 void jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t);
 int jn_host_reads(const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t);
+std::vector<size_t> rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom);
+// what lsq_cov.cpp shares: the dictionaries of an index, a read file through its host parser, the same under the executables' environment
+int annotation_dictionaries(const lsq_annotation &a, lsq_events &E);
+int host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r);
+int cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r);
 int run_junctions(int argc, const char *const *argv, std::string &out);      // the junctions executable
 int cli_env_options(lsq_ctx *c);                                             // lsq_cli.cpp: LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ, LSQ_BAM_VERIFY, LSQ_OPTIONS
 // lsq_junc.hip: the device passes over device arrays; the table's rows come back in (chromosome index, start, end) order

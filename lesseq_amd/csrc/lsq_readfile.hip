@@ -11,6 +11,7 @@
 #include "lsq_sam_device.hpp"
 #include "lsq_bam_device.hpp"
 #include "lsq_junc.hpp"
+#include "lsq_cov.hpp"
 
 namespace {
 
@@ -318,6 +319,21 @@ int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &T, unsi
 	return LSQ_OK;
 }
 
+// A read file parsed as lsq_mrf_parse_device parses it, against dictionaries that are not the context's events' (lsq_jn_device,
+// lsq_cov_device: an index's chromosomes and strand table): for the length of the call E stands where the context's events do,
+// so every parser finds its chromosomes, its strand table and its library type (unstranded) where it always looks.  The text is
+// freed once it has been read (its room is the caller's sort's); the context's events, reads and counters are not touched.
+int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const char *path, DevParsed &P) {
+	HIP_TRY(hipSetDevice(c->device));
+	const ReadFormat *fmt;
+	lsq_text T;
+	int rc;
+	if ((rc = ensure_lanes(c)) || (rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
+	struct Stand { lsq_ctx *c; lsq_events *own; ~Stand() { c->E = own; } } stand{c, c->E};
+	c->E = &E;
+	return parse_staged_text(c, fmt, T, P);
+}
+
 } // namespace
 
 extern "C" {
@@ -453,27 +469,34 @@ int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
-// The splice junctions of a read file (include/lesseq_hip.h): the file parsed as lsq_mrf_parse_device parses it, against the
-// index's dictionaries instead of the events' -- for the length of the call the index's lsq_events stands where the context's
-// does, so every parser finds its chromosomes, its strand table and its library type (unstranded) where it always looks -- and the
-// device arrays handed to lsq_junc.hip.  The context's events, reads and counters are not touched.
+// The splice junctions of a read file (include/lesseq_hip.h): the file parsed against the index's dictionaries
+// (parse_file_against) and the device arrays handed to lsq_junc.hip.
 int lsq_jn_device(lsq_ctx *c, lsq_jn_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_jn_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
-	HIP_TRY(hipSetDevice(c->device));
-	const ReadFormat *fmt;
-	lsq_text T;
-	int rc;
-	if ((rc = ensure_lanes(c)) || (rc = stage_text_file(c, path, 0, ~0ull, T)) || (rc = read_format_named(read_format, fmt))) return rc;
-	struct Stand { lsq_ctx *c; lsq_events *own; ~Stand() { c->E = own; } } stand{c, c->E};
-	c->E = &ix->E;
 	DevParsed P;
-	if ((rc = parse_staged_text(c, fmt, T, P))) return rc;
-	T.d_text.alloc(0); T.d_tile_base.alloc(0);          // (the text has been read: its room is the sort's)
+	int rc;
+	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
 	std::unique_ptr<lsq_jn_table> t(new lsq_jn_table);
 	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
 	if ((rc = jn_device_reads(c, *ix, R, min_overhang, *t))) return rc;
 	jn_finish_table(*ix, *t);
+	*out = t.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+// The per-base depth of a read file (include/lesseq_hip.h): the same parse, the device arrays handed to lsq_cov.hip
+int lsq_cov_device(lsq_ctx *c, lsq_cov_index *ix, const char *read_format, const char *path, int strand, uint32_t min_depth, lsq_cov_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	if (!cov_strand_ok(strand)) return fail(LSQ_E_ARG, "strand must be 0, '+' or '-'");
+	DevParsed P;
+	int rc;
+	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
+	std::unique_ptr<lsq_cov_table> t(new lsq_cov_table);
+	t->min_depth = min_depth;
+	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
+	if ((rc = cov_device_reads(c, *ix, R, strand, min_depth, *t))) return rc;
+	cov_finish_table(*ix, *t);
 	*out = t.release();
 	return LSQ_OK;
 } LSQ_API_CATCH

@@ -1,6 +1,6 @@
 // Exclusive prefix sums on the device (included by the translation units that scan; not a public header).
 //
-//   out[i] = sum of f(in[0..i)),  out[n] = the total          (u32 in, u64 out)
+//   out[i] = sum of f(in[0..i)),  out[n] = the total          (u32 or u64 in, u64 out)
 //
 // f rounds every value up to a multiple of PAD (a power of two) -- the padded sizes of the pools' groups -- or, with
 // FLAG, turns it into 0 / 1.  Three launches over blocks of 4 096 values: block sums, one workgroup over the block sums
@@ -16,6 +16,12 @@ template <unsigned PAD, bool FLAG>
 __device__ inline unsigned scan_value(unsigned v) {
 	if (FLAG) return v ? 1u : 0u;
 	return (v + (PAD - 1u)) & ~(PAD - 1u);
+}
+// the 64-bit-input form (lsq_cov.hip: bases times depth a row): sums that 32 bits do not hold; the caller keeps the total below 2^64
+template <unsigned PAD, bool FLAG>
+__device__ inline unsigned long long scan_value(unsigned long long v) {
+	if (FLAG) return v ? 1ull : 0ull;
+	return (v + (PAD - 1ull)) & ~(unsigned long long)(PAD - 1u);
 }
 
 __device__ inline unsigned long long scan_wave_incl(unsigned long long v) {
@@ -56,8 +62,8 @@ __device__ inline unsigned scan_block_excl32(unsigned v, unsigned *lds4, unsigne
 	return base + inc - v;
 }
 
-template <unsigned PAD, bool FLAG>
-__global__ void __launch_bounds__(256) lsq_scan_sums_kernel(const unsigned *in, unsigned long long n, unsigned long long *block_sum) {
+template <unsigned PAD, bool FLAG, class T>
+__global__ void __launch_bounds__(256) lsq_scan_sums_kernel(const T *in, unsigned long long n, unsigned long long *block_sum) {
 	__shared__ unsigned long long lds16[16];
 	const unsigned long long b0 = (unsigned long long)blockIdx.x * SCAN_BLOCK;
 	unsigned long long acc = 0;
@@ -91,16 +97,16 @@ __global__ void __launch_bounds__(1024) lsq_scan_spine_kernel(unsigned long long
 	if (threadIdx.x == 0) block_sum[n_blocks] = carry_s;
 }
 
-template <unsigned PAD, bool FLAG>
-__global__ void __launch_bounds__(256) lsq_scan_apply_kernel(const unsigned *in, unsigned long long n, const unsigned long long *block_base, unsigned long long *out) {
+template <unsigned PAD, bool FLAG, class T>
+__global__ void __launch_bounds__(256) lsq_scan_apply_kernel(const T *in, unsigned long long n, const unsigned long long *block_base, unsigned long long *out) {
 	__shared__ unsigned long long lds16[16];
 	const unsigned long long b0 = (unsigned long long)blockIdx.x * SCAN_BLOCK;
 	// a lane takes 16 consecutive values
 	const unsigned long long i0 = b0 + threadIdx.x * 16ull;
-	unsigned v[16];
+	T v[16];
 	unsigned long long acc = 0;
 #pragma unroll
-	for (unsigned q = 0; q < 16; ++q) { v[q] = i0 + q < n ? scan_value<PAD, FLAG>(in[i0 + q]) : 0u; acc += v[q]; }
+	for (unsigned q = 0; q < 16; ++q) { v[q] = i0 + q < n ? scan_value<PAD, FLAG>(in[i0 + q]) : (T)0; acc += v[q]; }
 	unsigned long long total;
 	unsigned long long run = block_base[blockIdx.x] + scan_block_excl(acc, lds16, total);
 #pragma unroll
@@ -119,15 +125,15 @@ struct ScanScratch {
 };
 
 // out must hold n + 1 values.  The scratch must have been reserved for n (no allocation between launches: hipMalloc may wait for the device)
-template <unsigned PAD, bool FLAG = false>
-static int device_scan(ScanScratch &S, const unsigned *in, unsigned long long n, unsigned long long *out, hipStream_t st) {
+template <unsigned PAD, bool FLAG = false, class T = unsigned>
+static int device_scan(ScanScratch &S, const T *in, unsigned long long n, unsigned long long *out, hipStream_t st) {
 	if (n == 0) { HIP_TRY(hipMemsetAsync(out, 0, 8, st)); return LSQ_OK; }
 	const unsigned long long nb = (n + SCAN_BLOCK - 1) / SCAN_BLOCK;
 	if (nb > 0x7FFFFFFFull) return fail(LSQ_E_RANGE, "prefix sum over more than 2^43 values");
 	if (S.sums.n < nb + 1) return fail(LSQ_E_INTERNAL, "scan scratch not reserved");
-	hipLaunchKernelGGL((lsq_scan_sums_kernel<PAD, FLAG>), dim3((unsigned)nb), dim3(256), 0, st, in, n, S.sums.p);
+	hipLaunchKernelGGL((lsq_scan_sums_kernel<PAD, FLAG, T>), dim3((unsigned)nb), dim3(256), 0, st, in, n, S.sums.p);
 	hipLaunchKernelGGL(lsq_scan_spine_kernel, dim3(1), dim3(1024), 0, st, S.sums.p, nb);
-	hipLaunchKernelGGL((lsq_scan_apply_kernel<PAD, FLAG>), dim3((unsigned)nb), dim3(256), 0, st, in, n, (const unsigned long long *)S.sums.p, out);
+	hipLaunchKernelGGL((lsq_scan_apply_kernel<PAD, FLAG, T>), dim3((unsigned)nb), dim3(256), 0, st, in, n, (const unsigned long long *)S.sums.p, out);
 	HIP_TRY(hipGetLastError());
 	return LSQ_OK;
 }
