@@ -401,7 +401,9 @@ int lsq_host_evaluated(const lsq_ctx *c, uint64_t *n_genes, uint64_t *n_reads);
  * file run six ordinary EM iterations and finish in the closed form of their EM map -- the step of read.h:592-618 is then a
  * Moebius map of theta_0, theta after m more iterations one exponential away, and the iteration at which read.h:659 stops
  * is found by search: the same iteration counts, theta within 1e-13; pays where the slowest events take hundreds of
- * iterations and little else runs beside the EM, e.g. a rank of an event-sharded job).  LSQ_E_ARG for an unknown name.  The executables
+ * iterations and little else runs beside the EM, e.g. a rank of an event-sharded job), "bootstrap_chunk" (default 0: lsq_bootstrap
+ * resamples and solves as many replicates per launch as keep their count buffers below 256 MiB -- fewer where the device's free
+ * memory asks for it; n in 1 .. 4096: n replicates per launch; a replicate's numbers never depend on it).  LSQ_E_ARG for an unknown name.  The executables
  * pass LSQ_OPTIONS="name=value,..." from the environment through this call. */
 int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value);
 
@@ -459,6 +461,45 @@ int lsq_fim(lsq_ctx *c);
 int64_t lsq_results_fim_size(const lsq_ctx *c);
 int lsq_results_fim_offsets(const lsq_ctx *c, uint64_t *fim_off /* n_events+1 */);
 int lsq_results_fim(lsq_ctx *c, double *fim, double *var_by_diag, double *var_by_inverse);
+
+/* Optional (not in the reference): the read bootstrap of theta -- how far the library's depth lets one trust lsq_solve's number
+ * (DESIGN 4.14).  A replicate resamples the counted reads of each (read file m, event e) with replacement, keeping that pair's
+ * total: with cnt[m][e][c] the class counts (c = 1 .. 2^K - 1, the layout of lsq_results_counts) and n their sum, replicate b
+ * draws i = 0 .. n - 1.  Random numbers: Philox4x32-10 (multipliers 0xD2511F53 and 0xCD9E8D57, key increments 0x9E3779B9 and
+ * 0xBB67AE85, ten rounds, the key bumped before rounds 2 to 10) with key = (seed low word, seed high word) and counter =
+ * (j low word, j high word, e, (m << 24) | b), j = i >> 1, e the event's index in the output order of the compiled events (not
+ * of a shard), b < 2^24.  Of the block's words x0..x3 even i uses u = x0 | x1 << 32, odd i uses u = x2 | x3 << 32.  The draw is
+ * r = (u * n) >> 64 (a 64 x 64 -> high 64 multiply), the class drawn the smallest c whose inclusive cumulative count exceeds r;
+ * the replicate's counts are the histogram of the n draws, all zeros for n = 0.  All integer arithmetic: the result does not
+ * depend on how the draws are split over lanes, tiles, chunks or devices.  Matched bases are not resampled.
+ * Each replicate's counts are solved as lsq_solve solves counts given through lsq_results_set_counts with "em_regroup" 0 and
+ * no closed form: four lanes an event for the lean places, the general kernel for the others, the context's guard band, the
+ * same iteration cap; no host replay -- flag bit 0 may be set and the kernel's numbers stand.  Replicates carry theta only.
+ * Summaries per isoform over the replicates whose theta is finite: n_ok, the mean, sd (two-pass, denominator n_ok - 1, no
+ * number for n_ok < 2) and the quantiles 0.025, 0.5, 0.975 by linear interpolation on the sorted values v at h = (n_ok - 1) p:
+ * v[floor h] + (h - floor h)(v[floor h + 1] - v[floor h]) (R type 7, numpy's default).  Events evaluated on the host (beyond
+ * LSQ_MAX_ISOFORMS / LSQ_MAX_SEGMENTS / the LDS) are not resampled: n_ok 0 and no number -- a documented limit.
+ * lsq_bootstrap: n_replicates in 1 .. 4096, else LSQ_E_ARG; needs lsq_count (or counts set from outside) and lsq_solve first,
+ * else LSQ_E_STATE; runs on the result stream behind the latest solve, in chunks of replicates ("bootstrap_chunk") that never
+ * change a result, and leaves the point estimate's arrays as they were.  The theta of every replicate stays on the device
+ * until the next lsq_bootstrap, the next lsq_events_upload or lsq_ctx_destroy; if it and one chunk exceed the free device
+ * memory: LSQ_E_RANGE, the text names the bytes.  Blocks until the replicates are done.
+ * lsq_results_bootstrap: the six summaries, n_iso entries each in output order (theta's layout in lsq_results_solve).
+ * lsq_results_bootstrap_theta: every replicate's theta, [n_replicates][n_iso].
+ * lsq_bootstrap_replicate: replicate b alone through the same kernels (counts in the layout of lsq_results_counts, the rest as
+ * lsq_results_solve; iters and flags may be NULL); the stored replicates are left alone.
+ * lsq_bootstrap_tile: draws of one work item of the resampling kernel (tests place their cases around it). */
+int lsq_bootstrap(lsq_ctx *c, uint32_t n_replicates, uint64_t seed);
+int lsq_results_bootstrap(lsq_ctx *c, uint32_t *n_ok, double *mean, double *sd, double *q025, double *q500, double *q975);
+int lsq_results_bootstrap_theta(lsq_ctx *c, double *theta /* [n_replicates][n_iso] */);
+int lsq_bootstrap_replicate(lsq_ctx *c, uint64_t seed, uint32_t b, uint64_t *class_count, double *theta, double *logll, uint32_t *iters, uint8_t *flags);
+int lsq_bootstrap_tile(void);
+/* Host-only, no GPU: replicate b's counts of n_events events' class counts -- class_off (n_events + 1 values) and
+ * class_count[m * class_off[n_events] + slot] as lsq_results_class_offsets and lsq_results_counts give them, event e being
+ * the e-th of them -- into out, same layout, by the same code the device runs (csrc/lsq_philox.hpp).  One draw at a time on
+ * one thread: meant for checks and small inputs. */
+int lsq_bootstrap_resample_host(int n_methods, uint64_t n_events, const uint64_t *class_off, const uint64_t *class_count, uint64_t seed, uint32_t b,
+                                uint64_t *out);
 
 /* Copies the raw device-order results into caller-provided DEVICE buffers (e.g. tensors of a
  * framework that will run a collective on them), asynchronously on the context's RESULT stream (the

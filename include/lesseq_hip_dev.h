@@ -92,6 +92,16 @@ int lsq_debug_hip_versions(int *compiled, int *runtime);
  * argument.  The tests hold a stranded compile's regions against those of the two split compiles with it. */
 int64_t lsq_debug_events_covered(const lsq_events *e, const char *chrom, int minus, int64_t *starts, int64_t *ends, int64_t capacity);
 
+/* The read bootstrap's draws one by one (host only, no device; csrc/lsq_philox.hpp): the classes (1-based) that the draws
+ * first_draw .. first_draw + n_draws - 1 of replicate b take for read file m (< 256) and event e (the generator's event
+ * number) whose n_cls classes hold class_count reads -- so that a test can look at the first draws of an event of 2^40
+ * reads without making them all.  LSQ_E_RANGE when the draws run past the event's reads. */
+int lsq_debug_bootstrap_draws(uint32_t n_cls, const uint64_t *class_count, uint64_t seed, uint32_t m, uint32_t e, uint32_t b, uint64_t first_draw,
+                              uint64_t n_draws, uint32_t *cls);
+/* Device milliseconds of the latest lsq_bootstrap's three phases -- resampling, EM, summaries; the first two summed over
+ * its chunks -- when it ran with lsq_set_timing on (LSQ_E_STATE otherwise), and the replicates a chunk held (chunk may be NULL). */
+int lsq_debug_bootstrap_times(lsq_ctx *c, float ms[3], unsigned *chunk);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,7 +7,8 @@ no compute of its own and refuses to import without the built library.
 """
 from ._lib import lib, LsqError, check  # noqa: F401
 from .api import (Annotation, Events, Reads, Context, SynthSpec, cli_run, synth_write, synth_write_sam,  # noqa: F401
-                  format_count, format_solve, EVENT_TYPES, sam_to_mrf, bam_to_mrf, bam_check_host, SAM_DEFAULT_SKIP_FLAGS)
+                  format_count, format_solve, EVENT_TYPES, sam_to_mrf, bam_to_mrf, bam_check_host, SAM_DEFAULT_SKIP_FLAGS,
+                  bootstrap_resample_host, bootstrap_draws)
 from .diffsplice import fisher, lrt, wilcox, adjust  # noqa: F401
 from . import localevents  # noqa: F401
 from . import gencode  # noqa: F401
@@ -19,4 +20,4 @@ from .coverage import CoverageIndex  # noqa: F401
 
 __all__ = ["lib", "LsqError", "check", "Annotation", "Events", "Reads", "Context", "SynthSpec",
            "cli_run", "synth_write", "synth_write_sam", "sam_to_mrf", "bam_to_mrf", "bam_check_host", "SAM_DEFAULT_SKIP_FLAGS", "format_count", "format_solve", "EVENT_TYPES",
-           "fisher", "lrt", "wilcox", "adjust", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex"]
+           "fisher", "lrt", "wilcox", "adjust", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex", "bootstrap_resample_host", "bootstrap_draws"]

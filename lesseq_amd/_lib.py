@@ -168,6 +168,14 @@ _sig("lsq_fim", C.c_int, vp)
 _sig("lsq_results_fim_size", C.c_int64, vp)
 _sig("lsq_results_fim_offsets", C.c_int, vp, P(C.c_uint64))
 _sig("lsq_results_fim", C.c_int, vp, P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_bootstrap", C.c_int, vp, u32, u64)
+_sig("lsq_results_bootstrap", C.c_int, vp, P(u32), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_results_bootstrap_theta", C.c_int, vp, P(C.c_double))
+_sig("lsq_bootstrap_replicate", C.c_int, vp, u64, u32, P(u64), P(C.c_double), P(C.c_double), P(u32), P(u8))
+_sig("lsq_bootstrap_tile", C.c_int)
+_sig("lsq_bootstrap_resample_host", C.c_int, C.c_int, u64, P(u64), P(u64), u64, u32, P(u64))
+_sig("lsq_debug_bootstrap_draws", C.c_int, u32, P(u64), u64, u32, u32, u32, u64, u64, P(u32))
+_sig("lsq_debug_bootstrap_times", C.c_int, vp, P(C.c_float), P(C.c_uint))
 _sig("lsq_set_timing", C.c_int, vp, C.c_int)
 _sig("lsq_last_fast_kernel_ms", C.c_int, vp, P(C.c_float))
 _sig("lsq_last_timing", C.c_int, vp, P(C.c_float), P(C.c_float))

@@ -456,7 +456,7 @@ class Context:
 
     def set_option(self, name, value):
         """lsq_ctx_set_option: grid_multiplier, exception_capacity, recount_every_read, em_guard_band,
-        snap_shares, em_regroup, em_flat_min_events, compact_pools, sam_skip_flags, sam_min_mapq, bam_verify"""
+        snap_shares, em_regroup, em_flat_min_events, compact_pools, sam_skip_flags, sam_min_mapq, bam_verify, bootstrap_chunk"""
         check(lib.lsq_ctx_set_option(self.h, _b(name), float(value)))
 
     def count_status(self):
@@ -599,6 +599,65 @@ class Context:
         vi = np.zeros(max(M * ne, 1), np.float64)
         check(lib.lsq_results_fim(self.h, _ptr(f, C.c_double), _ptr(vd, C.c_double), _ptr(vi, C.c_double)))
         return off, f[:M * size].reshape(M, size), vd[:M * ne].reshape(M, ne), vi[:M * ne].reshape(M, ne)
+
+    def bootstrap(self, B, seed=0):
+        """after solve(): B read-bootstrap replicates of theta (lsq_bootstrap) and their summaries per isoform in
+        output order, a dict of arrays: n_ok (replicates with a finite theta), mean, sd, q025, q500, q975"""
+        check(lib.lsq_bootstrap(self.h, int(B), int(seed)))
+        ni = self.events.total_isoforms
+        n_ok = np.zeros(max(ni, 1), np.uint32)
+        out = {k: np.zeros(max(ni, 1), np.float64) for k in ("mean", "sd", "q025", "q500", "q975")}
+        check(lib.lsq_results_bootstrap(self.h, _ptr(n_ok, u32), *[_ptr(out[k], C.c_double) for k in ("mean", "sd", "q025", "q500", "q975")]))
+        res = {"n_ok": n_ok[:ni]}
+        res.update((k, v[:ni]) for k, v in out.items())
+        self._boot_B = int(B)
+        return res
+
+    def bootstrap_theta(self):
+        """theta of every replicate of the latest bootstrap(): float64 [B, n_isoforms], output order"""
+        B, ni = getattr(self, "_boot_B", 0), self.events.total_isoforms
+        t = np.zeros(max(B * ni, 1), np.float64)
+        check(lib.lsq_results_bootstrap_theta(self.h, _ptr(t, C.c_double)))
+        return t[:B * ni].reshape(B, ni)
+
+    def bootstrap_replicate(self, seed, b):
+        """replicate b of the bootstrap with that seed on its own, through the same kernels (lsq_bootstrap_replicate):
+        (class_count[n_methods, n_classes], theta, logll, iters, flags), output order"""
+        n = lib.lsq_results_num_classes(self.h)
+        M, ne, ni = self.events.n_methods, len(self.events), self.events.total_isoforms
+        cnt = np.zeros((max(M, 1), max(n, 1)), np.uint64)
+        theta = np.zeros(max(ni, 1), np.float64)
+        ll = np.zeros(max(ne, 1), np.float64)
+        it = np.zeros(max(ne, 1), np.uint32)
+        fl = np.zeros(max(ne, 1), np.uint8)
+        check(lib.lsq_bootstrap_replicate(self.h, int(seed), int(b), _ptr(cnt, u64), _ptr(theta, C.c_double), _ptr(ll, C.c_double), _ptr(it, u32), _ptr(fl, u8)))
+        return cnt[:M, :n], theta[:ni], ll[:ne], it[:ne], fl[:ne]
+
+    def bootstrap_times(self):
+        """device milliseconds of the latest bootstrap() under set_timing(): resample, em, summary, and the replicates per chunk"""
+        ms, chunk = (C.c_float * 3)(), C.c_uint()
+        check(lib.lsq_debug_bootstrap_times(self.h, ms, C.byref(chunk)))
+        return {"resample_ms": float(ms[0]), "em_ms": float(ms[1]), "summary_ms": float(ms[2]), "chunk": int(chunk.value)}
+
+
+def bootstrap_resample_host(class_off, class_count, seed, b):
+    """replicate b's counts on the CPU (lsq_bootstrap_resample_host): class_off[n_events + 1] and class_count[n_methods,
+    n_classes] in the layout of Events.class_offsets() / Context.counts(); event e is the e-th of them.  No GPU."""
+    off = np.ascontiguousarray(class_off, np.uint64)
+    cnt = np.ascontiguousarray(class_count, np.uint64)
+    assert cnt.ndim == 2 and len(off) >= 1 and cnt.shape[1] == int(off[-1])
+    out = np.zeros((cnt.shape[0], max(cnt.shape[1], 1)), np.uint64)[:, :cnt.shape[1]]
+    out = np.ascontiguousarray(out)
+    check(lib.lsq_bootstrap_resample_host(cnt.shape[0], len(off) - 1, _ptr(off, u64), _ptr(cnt, u64), int(seed), int(b), _ptr(out, u64)))
+    return out
+
+
+def bootstrap_draws(class_count, seed, m, e, b, first_draw, n_draws):
+    """the classes (1-based) of single draws of one (read file m, event e) of replicate b (lsq_debug_bootstrap_draws).  No GPU."""
+    cnt = np.ascontiguousarray(class_count, np.uint64)
+    out = np.zeros(max(int(n_draws), 1), np.uint32)
+    check(lib.lsq_debug_bootstrap_draws(len(cnt), _ptr(cnt, u64), int(seed), int(m), int(e), int(b), int(first_draw), int(n_draws), _ptr(out, u32)))
+    return out[:int(n_draws)]
 
 
 class SynthSpec:

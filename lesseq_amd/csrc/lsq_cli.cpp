@@ -530,6 +530,20 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	// appends, behind the table, one `#fim` line per event and read file with fim.h's two variance estimates and the
 	// expected Fisher information matrix (lsq_fim; parity unpinned).  The table itself does not change.
 	bool want_fim = false;
+	// ... and `solve ... [--fim] --bootstrap B [--seed S]` appends, behind the table and the `#fim` lines, one `#boot` line per
+	// event form with the summaries of B read-bootstrap replicates of theta (lsq_bootstrap); seed 0 unless given
+	unsigned long boot_B = 0, boot_seed = 0;
+	if (solve) {
+		int at = -1;
+		for (int i = 15; i < argc && at < 0; ++i) if (strcmp(argv[i], "--bootstrap") == 0) at = i;
+		if (at >= 0) {
+			const int rest = argc - at;
+			if (rest != 2 && rest != 4) return usage();
+			if (!cast_ulong(argv[at + 1], boot_B) || boot_B < 1 || boot_B > 4096) return usage();
+			if (rest == 4 && (strcmp(argv[at + 2], "--seed") != 0 || !cast_ulong(argv[at + 3], boot_seed))) return usage();
+			argc = at;
+		}
+	}
 	if (solve && argc > 15 && strcmp(argv[argc - 1], "--fim") == 0) { want_fim = true; --argc; }
 	if (argc < (solve ? 15 : 14)) return usage();
 	long lvl;
@@ -562,7 +576,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	// LSQ_DEVICE picks the GPU (cli_device); LSQ_GPUS=N runs the job over N of them (LSQ_DEVICES="a,b,..." names them, default 0..N-1)
 	int G = 1;
 	if (const char *e = getenv("LSQ_GPUS")) G = std::max(1, atoi(e));
-	if (want_fim) G = 1;
+	if (want_fim || boot_B) G = 1;
 	std::vector<int> devices;
 	if (const char *e = getenv("LSQ_DEVICES")) { const char *q = e; while (*q) { devices.push_back(atoi(q)); q = strchr(q, ','); if (!q) break; ++q; } }
 	if (G > 1 && devices.size() < (size_t)G) { devices.clear(); for (int r = 0; r < G; ++r) devices.push_back(r); }
@@ -571,7 +585,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 	// LSQ_SHARD=reads: the job's GPUs share the READS instead of the events (run_read_sharded_job): MRF_SINGLE files only
 	const char *const gather_mode = getenv("LSQ_GATHER");          // (set at all: the staged texts are kept for the event-sharded job below, its one-slice self-check included)
 	bool shard_reads = false;
-	if (const char *e = getenv("LSQ_SHARD")) shard_reads = strcmp(e, "reads") == 0 && G > 1 && !want_fim;
+	if (const char *e = getenv("LSQ_SHARD")) shard_reads = strcmp(e, "reads") == 0 && G > 1 && !want_fim && !boot_B;
 	for (const char *f : fmts) if (strcmp(f, "MRF_SINGLE") != 0) shard_reads = false;
 	if (shard_reads && library != LSQ_LIBRARY_UNSTRANDED) {
 		logf(1, "LSQ_SHARD=reads: a stranded job (LSQ_LIBRARY=%s) is sharded by events instead", getenv("LSQ_LIBRARY"));
@@ -703,7 +717,7 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 			     (unsigned long long)hg, LSQ_MAX_ISOFORMS, LSQ_MAX_SEGMENTS, (unsigned long long)hr);
 	}
 	// (LSQ_GPUS=1 with LSQ_GATHER=rccl spelled out takes the same path with one slice: a self-check of the gather on one GPU)
-	if ((G > 1 || (getenv("LSQ_GPUS") && gather_mode && strcmp(gather_mode, "rccl") == 0 && !want_fim)) && n_ev > 0) {
+	if ((G > 1 || (getenv("LSQ_GPUS") && gather_mode && strcmp(gather_mode, "rccl") == 0 && !want_fim && !boot_B)) && n_ev > 0) {
 		const int rc = run_sharded_job(J, F.c, F.e, texts, trb, out);
 		T.mark("sharded job");
 		return rc;
@@ -746,6 +760,27 @@ int run_count_solve(bool solve, int argc, const char *const *argv, std::string &
 				snprintf(buf, sizeof buf, "%d", m); out += buf; out += "\t";
 				num(vd[(size_t)m * (size_t)n_ev + (size_t)i]); out += "\t"; num(vi[(size_t)m * (size_t)n_ev + (size_t)i]);
 				for (uint64_t q = off[(size_t)i]; q < off[(size_t)i + 1]; ++q) { out += "\t"; num(fim[(size_t)m * total + (size_t)q]); }
+				out += "\n";
+			}
+	}
+	if (boot_B) {
+		if (lsq_bootstrap(F.c, (uint32_t)boot_B, (uint64_t)boot_seed)) { logf(0, "%s", lsq_last_error()); return 3; }
+		const size_t n_iso = std::max<size_t>((size_t)lsq_events_total_isoforms(F.e), 1);
+		std::vector<uint32_t> n_ok(n_iso);
+		std::vector<double> s[5];
+		for (auto &v : s) v.resize(n_iso);
+		if (lsq_results_bootstrap(F.c, n_ok.data(), s[0].data(), s[1].data(), s[2].data(), s[3].data(), s[4].data())) { logf(0, "%s", lsq_last_error()); return 3; }
+		char buf[64];
+		size_t io = 0;
+		for (int64_t i = 0; i < n_ev; ++i)
+			for (int j = 0; j < lsq_events_num_isoforms(F.e, i); ++j, ++io) {
+				out += "#boot\t"; out += lsq_events_gene_name(F.e, i); out += "\t"; out += lsq_events_isoform_name(F.e, i, j);
+				snprintf(buf, sizeof buf, "\t%u", n_ok[io]); out += buf;
+				for (const auto &v : s) {
+					out += "\t";
+					if (v[io] != v[io]) out += "NA";
+					else { snprintf(buf, sizeof buf, "%.17g", v[io]); out += buf; }
+				}
 				out += "\n";
 			}
 	}

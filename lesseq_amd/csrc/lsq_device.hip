@@ -200,6 +200,7 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 	if (E->max_lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables exceed the CU's LDS");
 	c->E = E;
 	c->counted = c->solved = false;
+	c->boot.done = false;
 	c->has_fast = c->has_generic = c->has_host = false;
 	for (const BucketDesc &bd : E->buckets) { if (bd.kind == 1) c->has_fast = true; else if (bd.kind == 0) c->has_generic = true; else c->has_host = true; }
 	std::vector<bool> host_event(E->dev2out.size(), false);
@@ -922,6 +923,9 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 	} else if (n == "em_quad_cap") {
 		if (value < 0 || value > 1e6) return fail(LSQ_E_ARG, "em_quad_cap out of range");
 		c->em.opt_quad_cap = (unsigned)value;
+	} else if (n == "bootstrap_chunk") {
+		if (!(value >= 0 && value <= 4096)) return fail(LSQ_E_ARG, "bootstrap_chunk must lie in 0..4096 (0 = automatic)");
+		c->boot.opt_chunk = (unsigned)value;
 	} else if (n == "em_regroup") {
 		c->em.opt_regroup = value != 0;
 		for (EmLane &l : c->em.lane) l.order_valid = false;

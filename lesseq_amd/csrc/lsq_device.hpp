@@ -225,6 +225,20 @@ struct EmState {                        // the EM of a context: placement, optio
 	}
 };
 
+// The read bootstrap of a context (lsq_boot.hip): the replicates' theta and their summaries, kept until the next
+// lsq_bootstrap, a new event set or the end of the context
+struct BootState {
+	lsq::DevBuf<double> theta;          // [B][n_iso], device isoform order
+	lsq::DevBuf<double> stats;          // [5][n_iso]: mean, sd, quantiles 0.025, 0.5, 0.975
+	lsq::DevBuf<uint32_t> n_ok;         // [n_iso]: replicates with a finite theta
+	unsigned B = 0;
+	bool done = false;
+	unsigned opt_chunk = 0;             // "bootstrap_chunk": replicates resampled and solved per launch (0: by BOOT_CHUNK_BYTES)
+	unsigned last_chunk = 0;            // ... and what the latest lsq_bootstrap took
+	float ms[3] = {0, 0, 0};            // resample, EM, summary of the latest lsq_bootstrap that ran with lsq_set_timing
+	bool timed = false;
+};
+
 struct lsq_ctx {
 	// lsq_ctx_create_with(LSQ_CTX_LANES_IN_BACKGROUND): the helper thread that makes the lanes' streams and events, and how it ended
 	std::thread lanes_thread;
@@ -274,6 +288,7 @@ struct lsq_ctx {
 	DevBuf<char> gene_names;                // device event order
 	DevBuf<uint32_t> pack_cls, pack_iso, pack_ev;      // lsq_results_pack_device: device index of every class / isoform / event of the shard, in output order
 	EmState em;
+	BootState boot;
 	DevBuf<double> G, theta2[2], logll2[2];
 	DevBuf<uint32_t> iters2[2];
 	DevBuf<uint8_t> flags2[2];
@@ -375,6 +390,7 @@ int upload_strand_ranks(lsq_ctx *c);                 // lsq_device.hip
 int run_count(lsq_ctx *c);                           // lsq_count.hip
 int run_solve(lsq_ctx *c);
 int run_fim(lsq_ctx *c);
+int run_boot_em(lsq_ctx *c, unsigned n_rep, const unsigned long long *cnt, double *theta, double *logll, unsigned *iters, unsigned char *flags);      // lsq_em.hip, for lsq_boot.hip
 int sync_all(lsq_ctx *c);                 // both streams
 int ensure_lanes(lsq_ctx *c);             // lsq_device.hip: joins a context's helper thread (lanes made in the background), once
 void note_overflow(lsq_ctx *c, const std::vector<unsigned> &exc_count);      // lsq_device.hip: the warning about an overflowed exception list, once per count

@@ -745,6 +745,19 @@ __global__ void __launch_bounds__(64) lsq_em_lean_quad_capped_kernel(EmArgs A, E
 // the other events: more than two isoforms or more than one (method, class) pair per lane
 __global__ void __launch_bounds__(256) lsq_em_kernel(EmArgs A) { em_quad_body<false>(A, blockIdx.x); }
 
+// The read bootstrap's batched EM (lsq_boot.hip): grid y is the replicate, whose counts and outputs lie `stride`
+// apart; the bodies are the two above, so a replicate's numbers are those of lsq_solve on its counts with em_regroup = 0.
+// (Here and not in lsq_boot.hip: without relocatable device code a kernel calls only the device functions of its own unit.)
+struct EmBatch { size_t cnt_stride, theta_stride, ev_stride; };
+__device__ inline EmArgs em_replicate(EmArgs A, const EmBatch &S) {
+	const size_t r = blockIdx.y;
+	A.cnt += r * S.cnt_stride; A.theta += r * S.theta_stride;
+	A.logll += r * S.ev_stride; A.iters += r * S.ev_stride; A.flags += r * S.ev_stride;
+	return A;
+}
+__global__ void __launch_bounds__(64) lsq_em_boot_lean_kernel(EmArgs A, EmBatch S) { em_quad_body<true>(em_replicate(A, S), blockIdx.x); }
+__global__ void __launch_bounds__(256) lsq_em_boot_general_kernel(EmArgs A, EmBatch S) { em_quad_body<false>(em_replicate(A, S), blockIdx.x); }
+
 // ---- expected Fisher information and the variance estimates made from it (fim.h, linalg.h) ------------
 // PARITY UNPINNED: no translation unit of the reference includes these headers.  fim.h:115-158 sums, over
 // every isoform k with theta_k != 0 and every accessible read start of it, theta_k G_k times the
@@ -991,6 +1004,39 @@ int run_solve(lsq_ctx *c) {
 	}
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev3, st));
 	c->solve_timed = c->time_events;
+	return LSQ_OK;
+}
+
+// The EM of n_rep bootstrap replicates in one launch per group (lsq_boot.hip): replicate r reads cnt + r * [method][n_cls] and writes
+// theta + r * n_iso, logll / iters / flags + r * n_events.  Four lanes an event for the lean places in the order of
+// lsq_events_upload, the general kernel for the others, the context's guard band and run_solve's iteration cap; none of
+// the bookkeeping of run_solve (em.last, the lanes' learnt orders) is read or written.
+int run_boot_em(lsq_ctx *c, unsigned n_rep, const unsigned long long *cnt, double *theta, double *logll, unsigned *iters, unsigned char *flags) {
+	const lsq_events &E = *c->E;
+	const unsigned n_ev = (unsigned)E.dev2out.size();
+	if (!n_ev || !n_rep) return LSQ_OK;
+	EmArgs A{};
+	A.n_events = n_ev; A.n_methods = (unsigned)E.n_methods; A.n_cls = E.n_cls_total; A.n_iso = E.n_iso_total;
+	A.K = c->dK.p; A.cls_base = c->cls_base.p; A.iso_base = c->iso_base.p;
+	A.order = c->em.order.p;
+	A.split = c->em.split.p + EM_SPLIT_NONE;
+	A.max_iters = 1000000u;
+	A.band = c->em_band;
+#ifdef LSQ_DEV
+	if (const char *e = getenv("LSQ_EM_CAP")) { const int v = atoi(e); if (v > 0) A.max_iters = (unsigned)v; }
+#endif
+	A.cnt = cnt; A.G = c->G.p; A.theta = theta; A.logll = logll; A.iters = iters; A.flags = flags;
+	const EmBatch S{(size_t)E.n_methods * E.n_cls_total, (size_t)E.n_iso_total, (size_t)n_ev};
+	const unsigned np = c->em.small_places;
+	if (np) {
+		A.place0 = 0; A.n_places = np;
+		hipLaunchKernelGGL(lsq_em_boot_lean_kernel, dim3((np * EM_LANES + 63) / 64, n_rep), dim3(64), 0, c->stream_em, A, S);
+	}
+	if (c->em.places > np) {
+		A.place0 = np; A.n_places = c->em.places;
+		hipLaunchKernelGGL(lsq_em_boot_general_kernel, dim3(((c->em.places - np) * EM_LANES + 255) / 256, n_rep), dim3(256), 0, c->stream_em, A, S);
+	}
+	HIP_TRY(hipGetLastError());
 	return LSQ_OK;
 }
 
