@@ -567,7 +567,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*) or "coverage" (lsq_cov_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*) or "exonbins" (lsq_xb_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -740,6 +740,68 @@ int lsq_cov_table_times(const lsq_cov_table *t, float ms[6]);
 int lsq_cov_format(const lsq_cov_table *t, uint32_t min_depth, char **out_text);
 int lsq_cov_format_regions(const lsq_cov_table *t, char **out_text);
 int lsq_cov_sort_tile(void);     /* records a workgroup of the device sort takes (tests place their cases around it) */
+
+/* ------------------------------------------------------------------------------------
+ * Reads per exon bin and per gene of a read file: the table dexseq_count / featureCounts -f -O print, in the
+ * four columns `test_as lrt --tables` reads
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition, on the arrays the parsers above give (blocks 0-based half-open, in file order, unmerged):
+ *   chromosomes    as for lsq_jn_index: the distinct chromosome strings of the annotation's isoform lines.  A block on another
+ *                  chromosome, or with a coordinate outside +-2^30, has no chromosome (the parsers' own rule).
+ *   genes          the groups of the gene->isoform file, every gene the annotation holds, in the loader's order (the order in which
+ *                  count prints them).  A gene whose isoform lines name more than one chromosome: LSQ_E_UNSUPPORTED, the message names
+ *                  the first such gene.  A gene's strand is its lines' strand string when they all agree, else ".".
+ *   bins           of a gene: every exon with end > start of every isoform line of the gene (the first exonCount of a line); the
+ *                  distinct exon starts and ends sorted; a stretch between two neighbouring boundaries is a bin when at least one of
+ *                  those exons covers it.  Numbered 1, 2, ... ascending; the id is <gene>:<k>, k unpadded.  The bins of one gene are
+ *                  disjoint, bins of different genes may overlap.
+ *   hit            a read hits a bin when some block of it with end > start lies on the bin's chromosome and has block_start <
+ *                  bin_end && block_end > bin_start; it hits a gene when it hits at least one of its bins.
+ *   counts         reads[bin]: the reads that hit the bin; total[gene]: the reads that hit the gene.  A read counts once per bin and
+ *                  once per gene, however many of its blocks hit and in whatever order they come; a read that hits several genes
+ *                  counts in each.  Strand plays no part.  Both are uint64.
+ *   report         reads in the file, blocks in the file, blocks without a chromosome or empty, reads that hit no gene, reads that hit
+ *                  more than one gene, the sum of all reads[bin].
+ *   table          a row per bin, genes in gene order, a gene's bins ascending, zeros included:
+ *                  gene TAB total[gene] TAB gene:k TAB reads[bin] NL -- a count table of `test_as lrt --tables`.
+ *   bins texts     the bins as an annotation: an LH_GENE_TXT line per bin -- gene:k chrom strand start end 1 start end, TABs between --
+ *                  and a gene->isoform line per bin, gene TAB gene:k.
+ * Limits: 2^32-1 bins, 2^32-1 entries of the lookup below (the sum over the bins of the cells a bin spans), 65 535 chromosomes; any
+ * number of exons and isoforms per gene (no event is compiled).  Beyond a limit: LSQ_E_RANGE. */
+typedef struct lsq_xb_index lsq_xb_index;       /* the dictionaries, the bins gene-major, per chromosome the cells between bin boundaries with their bins */
+typedef struct lsq_xb_table lsq_xb_table;
+int lsq_xb_index_build(const lsq_annotation *a, lsq_xb_index **out);
+void lsq_xb_index_free(lsq_xb_index *ix);
+int64_t lsq_xb_index_num_chroms(const lsq_xb_index *ix);
+int64_t lsq_xb_index_num_genes(const lsq_xb_index *ix);
+int64_t lsq_xb_index_num_bins(const lsq_xb_index *ix);
+const char *lsq_xb_index_chrom_name(const lsq_xb_index *ix, int64_t chrom);      /* NULL when out of range */
+const char *lsq_xb_index_gene_name(const lsq_xb_index *ix, int64_t gene);
+const char *lsq_xb_index_gene_strand(const lsq_xb_index *ix, int64_t gene);
+lsq_events *lsq_xb_index_dictionaries(lsq_xb_index *ix);                  /* as lsq_jn_index_dictionaries */
+/* The bins (the arrays live as long as the index; any pointer may be null): per bin start, end and gene; per gene its first bin
+ * (num_genes + 1 entries) and its chromosome (0xFFFFFFFF: a gene without an isoform line). */
+int lsq_xb_index_arrays(const lsq_xb_index *ix, const int64_t **bin_start, const int64_t **bin_end, const uint32_t **bin_gene,
+                        const uint32_t **gene_first_bin, const uint32_t **gene_chrom);
+/* Host-only, threaded: the table from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  lsq_xb_host_reads: from arrays parsed against the index. */
+int lsq_xb_host(lsq_xb_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_xb_table **out);
+int lsq_xb_host_reads(lsq_xb_index *ix, const lsq_reads *r, int n_threads, lsq_xb_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed exactly as lsq_jn_device parses it, then one count kernel
+ * over the device arrays; the counters alone come back.  The context needs no events, and its events, reads and counters are as
+ * they were afterwards.  LSQ_XB_GRID in the environment bounds the count's workgroups (tests). */
+int lsq_xb_device(lsq_ctx *c, lsq_xb_index *ix, const char *read_format, const char *path, lsq_xb_table **out);
+void lsq_xb_table_free(lsq_xb_table *t);
+/* reads[num_bins], total[num_genes] (they live as long as the table; either pointer may be null) */
+int lsq_xb_table_arrays(const lsq_xb_table *t, const uint64_t **reads, const uint64_t **total);
+int lsq_xb_table_report(const lsq_xb_table *t, uint64_t report[6]);
+/* Device milliseconds per phase of the lsq_xb_device call that made the table -- index upload, count, copy-back -- from HIP events
+ * on the library's stream (zeros from the host path); the parse ahead of them: lsq_last_mrf_timing. */
+int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]);
+/* The table's text; the two bins texts of an index; malloc'd, NUL-terminated (lsq_free). */
+int lsq_xb_format(const lsq_xb_table *t, char **out_text);
+int lsq_xb_format_bins(const lsq_xb_index *ix, char **interval_text, char **map_text);
 
 /* ------------------------------------------------------------------------------------
  * Local events: step 2 of the pipeline, bin/Events.r

@@ -265,6 +265,25 @@ _sig("lsq_cov_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_cov_format", C.c_int, vp, u32, P(vp))
 _sig("lsq_cov_format_regions", C.c_int, vp, P(vp))
 _sig("lsq_cov_sort_tile", C.c_int)
+_sig("lsq_xb_index_build", C.c_int, vp, P(vp))
+_sig("lsq_xb_index_free", None, vp)
+_sig("lsq_xb_index_num_chroms", i64, vp)
+_sig("lsq_xb_index_num_genes", i64, vp)
+_sig("lsq_xb_index_num_bins", i64, vp)
+_sig("lsq_xb_index_chrom_name", cs, vp, i64)
+_sig("lsq_xb_index_gene_name", cs, vp, i64)
+_sig("lsq_xb_index_gene_strand", cs, vp, i64)
+_sig("lsq_xb_index_dictionaries", vp, vp)
+_sig("lsq_xb_index_arrays", C.c_int, vp, P(P(i64)), P(P(i64)), P(P(u32)), P(P(u32)), P(P(u32)))
+_sig("lsq_xb_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, C.c_int, P(vp))
+_sig("lsq_xb_host_reads", C.c_int, vp, vp, C.c_int, P(vp))
+_sig("lsq_xb_device", C.c_int, vp, vp, cs, cs, P(vp))
+_sig("lsq_xb_table_free", None, vp)
+_sig("lsq_xb_table_arrays", C.c_int, vp, P(P(u64)), P(P(u64)))
+_sig("lsq_xb_table_report", C.c_int, vp, P(u64))
+_sig("lsq_xb_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_xb_format", C.c_int, vp, P(vp))
+_sig("lsq_xb_format_bins", C.c_int, vp, P(vp), P(vp))
 
 
 def _warn_on_runtime_mismatch():

@@ -1,0 +1,349 @@
+// Reads per exon bin and per gene of a read file (include/lesseq_hip.h, lsq_xb_*): the index made from an annotation,
+// the host path over the host parsers' arrays, the tables' text and the exonbins executable.  The device count is
+// lsq_exonbins.hip, the entry that opens a read file on the device is lsq_readfile.hip's lsq_xb_device.
+#include <algorithm>
+#include <cerrno>
+#include <cstdlib>
+#include <cstring>
+
+#include "lsq_exonbins.hpp"
+
+using namespace lsq;
+
+namespace {
+
+char *dup_text(const std::string &s) {
+	char *p = (char *)malloc(s.size() + 1);
+	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
+	return p;
+}
+
+inline int32_t clamped(int64_t x) { return (int32_t)std::max<int64_t>(-XB_LIM, std::min<int64_t>(XB_LIM, x)); }
+
+// The bins of one gene from its isoform lines' exons: the stretches between neighbouring boundaries that an exon covers.  The
+// union of the exons as maximal intervals decides "covered": a stretch between two neighbouring boundaries lies inside one
+// maximal interval or outside all of them.
+void gene_bins(const Gene &g, std::vector<std::pair<int64_t, int64_t>> &ex, std::vector<int64_t> &cut, std::vector<int64_t> &bs, std::vector<int64_t> &be) {
+	ex.clear(); cut.clear();
+	for (const IsoRec *r : g.isos) {
+		const size_t ne = std::min<size_t>({(size_t)r->exonCount, r->exonStarts.size(), r->exonEnds.size()});
+		for (size_t i = 0; i < ne; ++i) if (r->exonEnds[i] > r->exonStarts[i]) {
+			ex.emplace_back(r->exonStarts[i], r->exonEnds[i]);
+			cut.push_back(r->exonStarts[i]); cut.push_back(r->exonEnds[i]);
+		}
+	}
+	std::sort(ex.begin(), ex.end());
+	std::sort(cut.begin(), cut.end());
+	cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
+	size_t q = 0;                               // the boundary the next stretch begins at
+	for (size_t i = 0; i < ex.size();) {
+		int64_t s = ex[i].first, e = ex[i].second;
+		for (++i; i < ex.size() && ex[i].first <= e; ++i) e = std::max(e, ex[i].second);
+		while (cut[q] < s) ++q;                 // (s and e are boundaries themselves)
+		for (; cut[q] < e; ++q) { bs.push_back(cut[q]); be.push_back(cut[q + 1]); }
+	}
+}
+
+// the cells of the lookup from the clamped bins (lsq_xb_index): per chromosome the boundaries, the bins over every stretch
+// between two of them counted, the stretches with any compacted into cells, their lists filled bin by bin (so they ascend)
+int build_cells(lsq_xb_index &ix) {
+	const size_t nc = ix.E.covered.size(), nb = ix.bin_gene.size();
+	std::vector<std::vector<uint32_t>> of_chrom(nc);
+	for (size_t b = 0; b < nb; ++b) if (ix.c_bin_end[b] > ix.c_bin_start[b]) of_chrom[ix.gene_chrom[ix.bin_gene[b]]].push_back((uint32_t)b);
+	ix.chrom_first_cell.assign(nc + 1, 0);
+	ix.cell_off.assign(1, 0);
+	std::vector<int32_t> cut;
+	std::vector<uint64_t> cnt;
+	std::vector<uint32_t> cell_of;
+	uint64_t n_entries = 0;
+	for (size_t c = 0; c < nc; ++c) {
+		const std::vector<uint32_t> &bins = of_chrom[c];
+		cut.clear();
+		for (uint32_t b : bins) { cut.push_back(ix.c_bin_start[b]); cut.push_back(ix.c_bin_end[b]); }
+		std::sort(cut.begin(), cut.end());
+		cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
+		auto at = [&](int32_t x) { return (size_t)(std::lower_bound(cut.begin(), cut.end(), x) - cut.begin()); };
+		cnt.assign(cut.size(), 0);
+		for (uint32_t b : bins) for (size_t i = at(ix.c_bin_start[b]), e = at(ix.c_bin_end[b]); i < e; ++i) ++cnt[i];
+		cell_of.assign(cut.size(), XB_NONE);
+		for (size_t i = 0; i + 1 < cut.size(); ++i) if (cnt[i]) {
+			n_entries += cnt[i];
+			if (n_entries > 0xFFFFFFFFull || ix.cell_start.size() >= 0xFFFFFFFEull) return fail(LSQ_E_RANGE, "more than 2^32-1 entries in the bin lookup (overlapping genes)");
+			cell_of[i] = (uint32_t)ix.cell_start.size();
+			ix.cell_start.push_back(cut[i]); ix.cell_end.push_back(cut[i + 1]);
+			ix.cell_off.push_back((uint32_t)n_entries);
+		}
+		ix.chrom_first_cell[c + 1] = (uint32_t)ix.cell_start.size();
+		ix.cell_bins.resize((size_t)n_entries);
+		const uint32_t c0 = ix.chrom_first_cell[c];
+		std::vector<uint32_t> next(ix.cell_off.begin() + c0, ix.cell_off.begin() + ix.chrom_first_cell[c + 1]);      // every cell's next free place
+		for (uint32_t b : bins) for (size_t i = at(ix.c_bin_start[b]), e = at(ix.c_bin_end[b]); i < e; ++i) ix.cell_bins[next[cell_of[i] - c0]++] = b;
+	}
+	return LSQ_OK;
+}
+
+// the first cell of chromosome c that ends behind s (chrom_first_cell[c + 1]: none)
+inline uint32_t first_cell(const lsq_xb_index &ix, uint32_t c, int32_t s) {
+	uint32_t lo = ix.chrom_first_cell[c], hi = ix.chrom_first_cell[c + 1];
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (ix.cell_end[mid] <= s) lo = mid + 1; else hi = mid;
+	}
+	return lo;
+}
+
+bool write_file(const std::string &path, const char *text) {
+	FILE *fp = fopen(path.c_str(), "wb");
+	const size_t n = strlen(text);
+	const bool ok = fp && fwrite(text, 1, n, fp) == n;
+	if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", path.c_str()); return false; }
+	return true;
+}
+
+} // namespace
+
+void lsq::xb_start_table(const lsq_xb_index &ix, lsq_xb_table &t) {
+	t.gene_name = ix.gene_name; t.gene_first_bin = ix.gene_first_bin;
+	t.reads.assign(ix.bin_gene.size(), 0); t.total.assign(ix.gene_name.size(), 0);
+	for (uint64_t &v : t.report) v = 0;
+	for (float &m : t.ms) m = 0;
+}
+
+// A thread a stretch of reads, counters of its own: the bins of every cell a block's walk meets are listed per read, sorted and
+// made distinct (a read counts once a bin), the genes are the distinct bin_gene of that list (bins are gene-major: they ascend)
+int lsq::xb_host_reads(const lsq_xb_index &ix, const JnReads &R, int n_threads, lsq_xb_table &t) {
+	int T = host_threads(n_threads);
+	if (R.n_reads < (1u << 16)) T = 1;
+	const size_t nb = ix.bin_gene.size(), ng = ix.gene_name.size(), nc = ix.E.covered.size();
+	xb_start_table(ix, t);
+	std::vector<std::vector<uint64_t>> part((size_t)T);
+	std::vector<uint64_t> tally((size_t)T * 4, 0);       // blocks without chromosome or empty, reads on no gene, on several, bin hits
+	{
+		ThreadGroup th;
+		for (int k = 0; k < T; ++k) th.spawn([&, k] {
+			std::vector<uint64_t> &cnt = part[(size_t)k];
+			cnt.assign(nb + ng, 0);
+			uint64_t *n = &tally[(size_t)k * 4];
+			std::vector<uint32_t> hit;
+			const uint64_t r0 = R.n_reads * (uint64_t)k / (uint64_t)T, r1 = R.n_reads * (uint64_t)(k + 1) / (uint64_t)T;
+			for (uint64_t r = r0; r < r1; ++r) {
+				hit.clear();
+				for (uint64_t b = R.blk_off[r]; b < R.blk_off[r + 1]; ++b) {
+					const unsigned c = R.bc[b];
+					const int32_t s = R.bs[b], e = R.be[b];
+					if (c == JN_NOCHROM || c >= nc || e <= s) { ++n[0]; continue; }
+					for (uint32_t i = first_cell(ix, c, s); i < ix.chrom_first_cell[c + 1] && ix.cell_start[i] < e; ++i)
+						hit.insert(hit.end(), ix.cell_bins.begin() + ix.cell_off[i], ix.cell_bins.begin() + ix.cell_off[i + 1]);
+				}
+				std::sort(hit.begin(), hit.end());
+				hit.erase(std::unique(hit.begin(), hit.end()), hit.end());
+				uint32_t genes = 0, last = XB_NONE;
+				for (uint32_t b : hit) {
+					++cnt[b];
+					if (ix.bin_gene[b] != last) { last = ix.bin_gene[b]; ++cnt[nb + last]; ++genes; }
+				}
+				n[3] += hit.size();
+				if (genes == 0) ++n[1];
+				if (genes > 1) ++n[2];
+			}
+		});
+		th.join();
+		if (th.failed()) return fail(LSQ_E_INTERNAL, "%s", th.error().c_str());
+	}
+	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
+	for (int k = 0; k < T; ++k) {
+		for (size_t b = 0; b < nb; ++b) t.reads[b] += part[(size_t)k][b];
+		for (size_t g = 0; g < ng; ++g) t.total[g] += part[(size_t)k][nb + g];
+		for (int q = 0; q < 4; ++q) t.report[2 + q] += tally[(size_t)k * 4 + q];
+	}
+	return LSQ_OK;
+}
+
+extern "C" {
+
+int lsq_xb_index_build(const lsq_annotation *a, lsq_xb_index **out) LSQ_API_TRY {
+	if (!a || !out) return fail(LSQ_E_ARG, "null argument");
+	std::unique_ptr<lsq_xb_index> ix(new lsq_xb_index);
+	int rc;
+	if ((rc = annotation_dictionaries(*a, ix->E))) return rc;
+	std::vector<std::pair<int64_t, int64_t>> ex;
+	std::vector<int64_t> cut;
+	ix->gene_first_bin.push_back(0);
+	for (const Gene &g : a->selected) {
+		uint32_t chrom = XB_NONE;
+		std::string strand = g.isos.empty() ? "." : g.isos[0]->strand;
+		for (const IsoRec *r : g.isos) {
+			const uint32_t c = (uint32_t)ix->E.chroms.find(r->chrom);
+			if (chrom != XB_NONE && c != chrom)
+				return fail(LSQ_E_UNSUPPORTED, "gene %s has isoforms on more than one chromosome (%s and %s): it has no exon bins", g.name.c_str(), ix->E.chroms.names[chrom].c_str(), r->chrom.c_str());
+			chrom = c;
+			if (r->strand != strand) strand = ".";
+		}
+		gene_bins(g, ex, cut, ix->bin_start, ix->bin_end);
+		if (ix->bin_start.size() > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32-1 exon bins");
+		ix->bin_gene.resize(ix->bin_start.size(), (uint32_t)ix->gene_name.size());
+		ix->gene_name.push_back(g.name); ix->gene_strand.push_back(strand); ix->gene_chrom.push_back(chrom);
+		ix->gene_first_bin.push_back((uint32_t)ix->bin_start.size());
+	}
+	const size_t nb = ix->bin_start.size();
+	ix->c_bin_start.resize(nb); ix->c_bin_end.resize(nb);
+	for (size_t b = 0; b < nb; ++b) { ix->c_bin_start[b] = clamped(ix->bin_start[b]); ix->c_bin_end[b] = clamped(ix->bin_end[b]); }
+	if ((rc = build_cells(*ix))) return rc;
+	*out = ix.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+void lsq_xb_index_free(lsq_xb_index *ix) { delete ix; }
+int64_t lsq_xb_index_num_chroms(const lsq_xb_index *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
+int64_t lsq_xb_index_num_genes(const lsq_xb_index *ix) { return ix ? (int64_t)ix->gene_name.size() : 0; }
+int64_t lsq_xb_index_num_bins(const lsq_xb_index *ix) { return ix ? (int64_t)ix->bin_gene.size() : 0; }
+const char *lsq_xb_index_chrom_name(const lsq_xb_index *ix, int64_t chrom) {
+	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
+}
+const char *lsq_xb_index_gene_name(const lsq_xb_index *ix, int64_t gene) {
+	return ix && gene >= 0 && (size_t)gene < ix->gene_name.size() ? ix->gene_name[(size_t)gene].c_str() : nullptr;
+}
+const char *lsq_xb_index_gene_strand(const lsq_xb_index *ix, int64_t gene) {
+	return ix && gene >= 0 && (size_t)gene < ix->gene_strand.size() ? ix->gene_strand[(size_t)gene].c_str() : nullptr;
+}
+lsq_events *lsq_xb_index_dictionaries(lsq_xb_index *ix) { return ix ? &ix->E : nullptr; }
+int lsq_xb_index_arrays(const lsq_xb_index *ix, const int64_t **bin_start, const int64_t **bin_end, const uint32_t **bin_gene, const uint32_t **gene_first_bin, const uint32_t **gene_chrom) {
+	if (!ix) return fail(LSQ_E_ARG, "null argument");
+	if (bin_start) *bin_start = ix->bin_start.data();
+	if (bin_end) *bin_end = ix->bin_end.data();
+	if (bin_gene) *bin_gene = ix->bin_gene.data();
+	if (gene_first_bin) *gene_first_bin = ix->gene_first_bin.data();
+	if (gene_chrom) *gene_chrom = ix->gene_chrom.data();
+	return LSQ_OK;
+}
+
+int lsq_xb_host_reads(lsq_xb_index *ix, const lsq_reads *r, int n_threads, lsq_xb_table **out) LSQ_API_TRY {
+	if (!ix || !r || !out) return fail(LSQ_E_ARG, "null argument");
+	std::unique_ptr<lsq_xb_table> t(new lsq_xb_table);
+	const JnReads R{r->n_reads, r->n_blocks, (const unsigned long long *)r->blk_off, r->blk_start, r->blk_end, r->blk_chrom, r->blk_strand};
+	const int rc = xb_host_reads(*ix, R, n_threads, *t);
+	if (rc) return rc;
+	*out = t.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+int lsq_xb_host(lsq_xb_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_xb_table **out) LSQ_API_TRY {
+	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	lsq_reads *r = nullptr;
+	int rc = host_parse_reads(&ix->E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
+	if (rc) return rc;
+	rc = lsq_xb_host_reads(ix, r, n_threads, out);
+	lsq_reads_free(r);
+	return rc;
+} LSQ_API_CATCH
+
+void lsq_xb_table_free(lsq_xb_table *t) { delete t; }
+int lsq_xb_table_arrays(const lsq_xb_table *t, const uint64_t **reads, const uint64_t **total) {
+	if (!t) return fail(LSQ_E_ARG, "null argument");
+	if (reads) *reads = t->reads.data();
+	if (total) *total = t->total.data();
+	return LSQ_OK;
+}
+int lsq_xb_table_report(const lsq_xb_table *t, uint64_t report[6]) {
+	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
+	memcpy(report, t->report, sizeof(t->report));
+	return LSQ_OK;
+}
+int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]) {
+	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
+	memcpy(ms, t->ms, sizeof(t->ms));
+	return LSQ_OK;
+}
+
+int lsq_xb_format(const lsq_xb_table *t, char **out_text) LSQ_API_TRY {
+	if (!t || !out_text) return fail(LSQ_E_ARG, "null argument");
+	std::string o;
+	char buf[96];
+	for (size_t g = 0; g < t->gene_name.size(); ++g)
+		for (uint32_t b = t->gene_first_bin[g]; b < t->gene_first_bin[g + 1]; ++b) {
+			o += t->gene_name[g];
+			snprintf(buf, sizeof buf, "\t%llu\t", (unsigned long long)t->total[g]);
+			o += buf; o += t->gene_name[g];
+			snprintf(buf, sizeof buf, ":%u\t%llu\n", b - t->gene_first_bin[g] + 1u, (unsigned long long)t->reads[b]);
+			o += buf;
+		}
+	*out_text = dup_text(o);
+	return *out_text ? LSQ_OK : fail(LSQ_E_INTERNAL, "out of memory");
+} LSQ_API_CATCH
+
+int lsq_xb_format_bins(const lsq_xb_index *ix, char **interval_text, char **map_text) LSQ_API_TRY {
+	if (!ix || !interval_text || !map_text) return fail(LSQ_E_ARG, "null argument");
+	std::string iv, mp;
+	char buf[160];
+	for (size_t g = 0; g < ix->gene_name.size(); ++g)
+		for (uint32_t b = ix->gene_first_bin[g]; b < ix->gene_first_bin[g + 1]; ++b) {
+			snprintf(buf, sizeof buf, ":%u", b - ix->gene_first_bin[g] + 1u);
+			const std::string id = ix->gene_name[g] + buf;
+			const long long s = (long long)ix->bin_start[b], e = (long long)ix->bin_end[b];
+			iv += id; iv += '\t'; iv += ix->E.chroms.names[ix->gene_chrom[g]]; iv += '\t'; iv += ix->gene_strand[g];
+			snprintf(buf, sizeof buf, "\t%lld\t%lld\t1\t%lld\t%lld\n", s, e, s, e);
+			iv += buf;
+			mp += ix->gene_name[g]; mp += '\t'; mp += id; mp += '\n';
+		}
+	*interval_text = dup_text(iv);
+	*map_text = dup_text(mp);
+	if (!*interval_text || !*map_text) { free(*interval_text); free(*map_text); *interval_text = *map_text = nullptr; return fail(LSQ_E_INTERNAL, "out of memory"); }
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+} // extern "C"
+
+// exonbins [--host] [--bins <prefix>] <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
+// The table on standard output (or in <out>; "-": standard output), the bins as an annotation in <prefix>.interval and
+// <prefix>.map, the report in the log.  Exit status 1, nothing on standard output and no file, for a gene on two chromosomes
+// and for a file that does not open or parse.
+int lsq::run_exonbins(int argc, const char *const *argv, std::string &out) {
+	static const char *USAGE = "Usage:\nexonbins [--host] [--bins prefix] isoform_format isoforms_path g2i_format g2i_path read_format reads_path [out_path]";
+	bool host = false, bad = false;
+	const char *prefix = nullptr;
+	std::vector<const char *> pos;
+	for (int i = 1; i < argc && !bad; ++i) {
+		if (strcmp(argv[i], "--host") == 0) host = true;
+		else if (strcmp(argv[i], "--bins") == 0) {
+			if (i + 1 < argc) prefix = argv[++i]; else bad = true;
+		} else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
+		else pos.push_back(argv[i]);
+	}
+	if (bad || pos.size() < 6 || pos.size() > 7) { cli_log(0, USAGE); return 1; }
+	struct Owned {
+		lsq_annotation *a = nullptr; lsq_xb_index *ix = nullptr; lsq_xb_table *t = nullptr; lsq_ctx *c = nullptr; char *text = nullptr, *iv = nullptr, *mp = nullptr;
+		~Owned() { lsq_xb_table_free(t); if (c) lsq_ctx_destroy(c); lsq_xb_index_free(ix); lsq_annotation_free(a); lsq_free(text); lsq_free(iv); lsq_free(mp); }
+	} O;
+	auto failed = [&](int st) {
+		cli_log(0, lsq_last_error());
+		if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
+		return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
+	};
+	int st = lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &O.a);
+	if (!st) st = lsq_xb_index_build(O.a, &O.ix);
+	if (st) return failed(st);
+	if (host) {
+		lsq_reads *r = nullptr;
+		st = cli_host_parse(&O.ix->E, pos[4], pos[5], &r);
+		if (!st) st = lsq_xb_host_reads(O.ix, r, 0, &O.t);
+		lsq_reads_free(r);
+	} else {
+		st = lsq_ctx_create(cli_device(), &O.c);
+		if (!st) st = cli_env_options(O.c);
+		if (!st) st = lsq_xb_device(O.c, O.ix, pos[4], pos[5], &O.t);
+	}
+	if (!st) st = lsq_xb_format(O.t, &O.text);
+	if (!st && prefix) st = lsq_xb_format_bins(O.ix, &O.iv, &O.mp);
+	if (st) return failed(st);
+	const uint64_t *rep = O.t->report;
+	char msg[384];
+	snprintf(msg, sizeof msg, "exonbins: %llu read(s), %llu block(s), %llu without a chromosome of the annotation or empty; %lld bin(s) of %lld gene(s): %llu read(s) on no gene, %llu on more than one, %llu bin hit(s)",
+	         (unsigned long long)rep[0], (unsigned long long)rep[1], (unsigned long long)rep[2], (long long)lsq_xb_index_num_bins(O.ix), (long long)lsq_xb_index_num_genes(O.ix),
+	         (unsigned long long)rep[3], (unsigned long long)rep[4], (unsigned long long)rep[5]);
+	cli_log(2, msg);
+	if (prefix && (!write_file(std::string(prefix) + ".interval", O.iv) || !write_file(std::string(prefix) + ".map", O.mp))) return failed(LSQ_E_IO);
+	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) {
+		if (!write_file(pos[6], O.text)) return failed(LSQ_E_IO);
+	} else out = O.text;
+	return 0;
+}

@@ -12,6 +12,7 @@
 #include "lsq_bam_device.hpp"
 #include "lsq_junc.hpp"
 #include "lsq_cov.hpp"
+#include "lsq_exonbins.hpp"
 
 namespace {
 
@@ -497,6 +498,19 @@ int lsq_cov_device(lsq_ctx *c, lsq_cov_index *ix, const char *read_format, const
 	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
 	if ((rc = cov_device_reads(c, *ix, R, strand, min_depth, *t))) return rc;
 	cov_finish_table(*ix, *t);
+	*out = t.release();
+	return LSQ_OK;
+} LSQ_API_CATCH
+
+// The reads per exon bin and per gene of a read file (include/lesseq_hip.h): the same parse, the device arrays handed to lsq_exonbins.hip
+int lsq_xb_device(lsq_ctx *c, lsq_xb_index *ix, const char *read_format, const char *path, lsq_xb_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	DevParsed P;
+	int rc;
+	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
+	std::unique_ptr<lsq_xb_table> t(new lsq_xb_table);
+	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
+	if ((rc = xb_device_reads(c, *ix, R, *t))) return rc;
 	*out = t.release();
 	return LSQ_OK;
 } LSQ_API_CATCH
