@@ -4,7 +4,7 @@
 // DESIGN.md ("Differential splicing tests"); the host side (readers, formatter, the test_as executable) is lsq_as.cpp.
 //
 //   lsq_as_fisher_kernel   one wave per table: the hypergeometric pmf walked outward from its mode, 64 terms a step
-//   lsq_as_lrt_kernel      one lane per row: two IRLS fits (R's glm.fit), normal equations in registers, Cholesky
+//   lsq_as_lrt_kernel      one lane per row: two IRLS fits (R's glm.fit), normal equations in registers, Cholesky; the difference of their deviances
 //   lsq_as_wilcox_kernel   one lane per row: W and the tie groups by counting over the row; exact tables from the host
 //   correction             NA compaction (lsq_scan.hpp, flag mode), stable LSD radix sort of (p bits, index) (lsq_sort.hpp), reverse min-scan
 #include <cfloat>
@@ -174,9 +174,17 @@ __device__ inline bool cholesky_solve(const double *a, const double *b, double *
 	return true;
 }
 
+// One observation's share of the Poisson deviance, 2 (y log(y/mu) - (y - mu)), as 2 mu ((1 + r) log1p(r) - r) with
+// r = (y - mu)/mu: the first form subtracts two numbers of the size of y (an error of 1e-4 at y = 10^12), the second
+// works on r alone and keeps the share to a relative 1e-9 or better.  y >= 1 here, so r > -1.
+__device__ inline double poisson_dev(double y, double mu) {
+	const double r = (y - mu) / mu;
+	return 2.0 * mu * ((1.0 + r) * log1p(r) - r);
+}
+
 // R's glm.fit for family = poisson(log) with an offset: start at mu = y + 0.1, WLS by the normal equations, stop on the
-// relative deviance change or after GLM_MAXIT solves.  y and o lie sample-major (y[j * stride]).  Returns
-// sum(y log mu - mu) at the last iterate (the log-likelihood without its lgamma terms), NaN when a solve fails.
+// relative deviance change or after GLM_MAXIT solves.  y and o lie sample-major (y[j * stride]).  Returns the deviance
+// of the last iterate, NaN when a solve fails.
 template <int P, bool TISSUE>
 __device__ double glm_poisson(const double *y, const double *o, unsigned long long stride, int n1, int n) {
 	double a[P * (P + 1) / 2], b[P], beta[P], x[P];
@@ -184,11 +192,11 @@ __device__ double glm_poisson(const double *y, const double *o, unsigned long lo
 	for (int q = 0; q < P * (P + 1) / 2; ++q) a[q] = 0.0;
 #pragma unroll
 	for (int q = 0; q < P; ++q) b[q] = 0.0;
-	double dev_old = 0.0;
+	double dev_old = 0.0, dev = 0.0;
 	for (int j = 0; j < n; ++j) {
 		const double yj = y[(unsigned long long)j * stride], oj = o[(unsigned long long)j * stride];
 		const double eta = log(yj + 0.1), mu = fmax(exp(eta), DBL_EPSILON);
-		dev_old += 2.0 * (yj * log(yj / mu) - (yj - mu));
+		dev_old += poisson_dev(yj, mu);
 		design_row<P, TISSUE>(j < n1 ? 1.0 : 2.0, (double)(j < n1 ? j + 1 : j - n1 + 1), x);
 		const double z = (eta - oj) + (yj - mu) / mu;
 #pragma unroll
@@ -200,7 +208,7 @@ __device__ double glm_poisson(const double *y, const double *o, unsigned long lo
 	}
 	for (int it = 0; it < GLM_MAXIT; ++it) {
 		if (!cholesky_solve<P>(a, b, beta)) return NAN;
-		double dev = 0.0;
+		dev = 0.0;
 #pragma unroll
 		for (int q = 0; q < P * (P + 1) / 2; ++q) a[q] = 0.0;
 #pragma unroll
@@ -212,7 +220,7 @@ __device__ double glm_poisson(const double *y, const double *o, unsigned long lo
 #pragma unroll
 			for (int r = 0; r < P; ++r) lin += x[r] * beta[r];
 			const double eta = lin + oj, mu = fmax(exp(eta), DBL_EPSILON);
-			dev += 2.0 * (yj * log(yj / mu) - (yj - mu));
+			dev += poisson_dev(yj, mu);
 			const double z = (eta - oj) + (yj - mu) / mu;
 #pragma unroll
 			for (int r = 0; r < P; ++r) {
@@ -224,17 +232,7 @@ __device__ double glm_poisson(const double *y, const double *o, unsigned long lo
 		if (fabs(dev - dev_old) / (fabs(dev) + 0.1) < GLM_EPS) break;
 		dev_old = dev;
 	}
-	double ll = 0.0;
-	for (int j = 0; j < n; ++j) {
-		const double yj = y[(unsigned long long)j * stride], oj = o[(unsigned long long)j * stride];
-		design_row<P, TISSUE>(j < n1 ? 1.0 : 2.0, (double)(j < n1 ? j + 1 : j - n1 + 1), x);
-		double lin = 0.0;
-#pragma unroll
-		for (int r = 0; r < P; ++r) lin += x[r] * beta[r];
-		const double mu = fmax(exp(lin + oj), DBL_EPSILON);
-		ll += yj * log(mu) - mu;
-	}
-	return ll;
+	return dev;
 }
 
 // One lane per row.  count / total arrive sample-major ([sample][row]) and are turned in place into y = round(count) + 1
@@ -253,16 +251,18 @@ __global__ void __launch_bounds__(256) lsq_as_lrt_kernel(double *count, double *
 		}
 		if (na) { stat_out[r] = NAN; p_out[r] = NAN; continue; }
 		const double *y = count + r, *o = total + r;
-		double lf, lr;
+		double df, dr;
 		if (aliased) {
-			lf = glm_poisson<2, true>(y, o, n_rows, n1, n);
-			lr = glm_poisson<1, false>(y, o, n_rows, n1, n);
+			df = glm_poisson<2, true>(y, o, n_rows, n1, n);
+			dr = glm_poisson<1, false>(y, o, n_rows, n1, n);
 		} else {
-			lf = glm_poisson<3, true>(y, o, n_rows, n1, n);
-			lr = glm_poisson<2, false>(y, o, n_rows, n1, n);
+			df = glm_poisson<3, true>(y, o, n_rows, n1, n);
+			dr = glm_poisson<2, false>(y, o, n_rows, n1, n);
 		}
-		const double stat = 2.0 * fabs(lf - lr);
-		if (!isfinite(lf) || !isfinite(lr) || isnan(stat)) { stat_out[r] = 0.0; p_out[r] = 1.0; continue; }   // Test_AS.r:112-114
+		// the difference of the two deviances is 2 (l_full - l_reduced) exactly; the log-likelihoods themselves are 10^10
+		// times the statistic at totals of 10^8, and their difference kept five digits of it
+		const double stat = fabs(dr - df);
+		if (!isfinite(df) || !isfinite(dr) || isnan(stat)) { stat_out[r] = 0.0; p_out[r] = 1.0; continue; }   // Test_AS.r:112-114
 		stat_out[r] = stat;
 		p_out[r] = erfc(sqrt(stat / 2.0));      // upper chi-square tail, one degree of freedom
 	}
