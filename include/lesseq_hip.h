@@ -453,8 +453,12 @@ int lsq_set_em_guard_band(lsq_ctx *c, double band);
  * and the two variance estimates made from it -- common/fim.h:115-158,320-367 (bruteforce_fim / ofim:
  * the sum over every accessible read start of every isoform), :58-93 (estimate_mle_variance_by_diag,
  * _by_inv) with common/linalg.h:28-71's inverse.  PARITY UNPINNED: the reference never includes these
- * headers, no reference binary prints these numbers; the tests check the HIP path against the oracle's
- * restatement of the headers.  One matrix per event and read file, (K-1) x (K-1), row-major; events
+ * headers, no reference binary prints these numbers; the project's tests are the only pin: tests/fim_ref.py
+ * states the headers' definition in exact rational arithmetic (one accessible read start at a time, exact
+ * inverse, derived rounding bounds), tests/test_fim_reference_host.py holds it against the oracle's
+ * double-precision restatement, tests/test_fim_direct_gpu.py the HIP path against it on events and class
+ * counts chosen by hand, tests/test_parity_gpu.py the HIP path against the oracle on the golden inputs.
+ * One matrix per event and read file, (K-1) x (K-1), row-major; events
  * in output order at lsq_results_fim_offsets (n_events + 1 values; K = 1: empty matrix, variances 0).
  * Call after lsq_solve.  fim: [method][lsq_results_fim_size], variances: [method][n_events]. */
 int lsq_fim(lsq_ctx *c);

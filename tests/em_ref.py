@@ -352,14 +352,22 @@ def general_cases(M):
 
 def write_annotation(directory, stem, genes):
     """genes: [(gene name, [exon length per isoform])] -> (<stem>.interval, <stem>.map) paths: every isoform is one exon of
-    its own on chr1 +, no two overlap (a single-exon isoform of length L has ARS L - read length + 1, 0 when that is negative)"""
+    its own on chr1 +, no two overlap (a single-exon isoform of length L has ARS L - read length + 1, 0 when that is negative).
+    An isoform given as a list of (start, end) pairs instead of a length has those exons, counted from the first base of the
+    gene's own stretch of 16 000 bases (tests/fim_ref.py: isoforms that share segments)."""
     import os
     from golden_inputs import interval_line
     iv, mp = [], []
     for g, (name, lengths) in enumerate(genes):
         for j, length in enumerate(lengths):
-            start = 1000 + (g * 8 + j) * 2000
-            iv.append(interval_line("%s.i%d" % (name, j), "chr1", "+", [(start, start + length)]))
+            if isinstance(length, (list, tuple)):
+                base = 1000 + g * 16000
+                assert all(0 <= s < e <= 15000 for s, e in length), (name, length)
+                exons = [(base + s, base + e) for s, e in length]
+            else:
+                start = 1000 + (g * 8 + j) * 2000
+                exons = [(start, start + length)]
+            iv.append(interval_line("%s.i%d" % (name, j), "chr1", "+", exons))
             mp.append("%s\t%s.i%d\n" % (name, name, j))
     a, b = os.path.join(directory, stem + ".interval"), os.path.join(directory, stem + ".map")
     with open(a, "w") as f:

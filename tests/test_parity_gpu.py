@@ -951,7 +951,7 @@ def test_fisher_information_and_variances_vs_oracle(name, tmp_path, monkeypatch)
     monkeypatch.setenv("LSQO_FIM", "1")
     c, d = load_case(name, tmp_path)
     monkeypatch.chdir(d)
-    checked = 0
+    eligible = checked = other_theta = 0           # events
     for tool, r in runs(c):
         if tool != "solve" or r["exit"] != 0:
             continue
@@ -961,9 +961,12 @@ def test_fisher_information_and_variances_vs_oracle(name, tmp_path, monkeypatch)
         assert len(got) == len(exact)
         for g, e in zip(got, exact):
             assert g["gname"] == e["gname"] and g["K"] == e["K"]
-            if g["K"] > 6 or "fim" not in e:
+            if g["K"] > 6:
                 continue
+            assert "fim" in e
+            eligible += 1
             if any(abs(a - b) > 1e-9 * max(abs(a), abs(b)) for a, b in zip(g["theta"], e["theta"])):
+                other_theta += 1
                 continue                  # (an event whose EM was flagged: another theta, another matrix)
             for m in range(len(e["fim"])):
                 A, B = np.array(g["fim"][m], float).reshape(-1), np.array(e["fim"][m], float).reshape(-1)
@@ -975,8 +978,10 @@ def test_fisher_information_and_variances_vs_oracle(name, tmp_path, monkeypatch)
                         assert abs(a - b) <= 1e-7 * max(abs(b), 1e-300), (name, g["gname"], m, w, a, b)
                     else:
                         assert not np.isfinite(a) or abs(a) >= 1e11 or (not np.isfinite(b)), (name, g["gname"], m, w, a, b)
-                checked += 1
-    assert checked >= 1
+            checked += 1
+    # (the matrices at theta values chosen by hand, against an exact reference and with no event left out: tests/test_fim_direct_gpu.py)
+    print("%s: %d events with at most six isoforms, %d checked, %d left out for a theta that differs from the oracle's" % (name, eligible, checked, other_theta))
+    assert checked + other_theta == eligible and checked >= 1
 
 
 def test_solve_fim_extension_keeps_the_table_and_appends_the_matrices(tmp_path, monkeypatch):
