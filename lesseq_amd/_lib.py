@@ -318,3 +318,19 @@ def check_runtime_once():
 def check(status):
     if status != 0:
         raise LsqError(status, lib.lsq_last_error().decode("utf-8", "replace"))
+
+
+def _b(s):
+    return s.encode() if isinstance(s, str) else s
+
+
+def take_text(call, *args, n=1):
+    """call(*args, n output texts): the texts decoded and freed (lsq_free); one str, or a tuple of n"""
+    out = [vp() for _ in range(n)]
+    check(call(*args, *[C.byref(o) for o in out]))
+    try:
+        texts = tuple(C.string_at(o).decode() for o in out)
+    finally:
+        for o in out:
+            lib.lsq_free(o)
+    return texts[0] if n == 1 else texts

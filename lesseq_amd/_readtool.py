@@ -1,0 +1,75 @@
+"""What the tools that take an annotation and a read file share (junctions, coverage, exonbins): the handle of an index with its
+chromosome dictionary and host parse, the handle of a table with its report and phase times.  A subclass names its entry points'
+prefix (`lsq_jn`: lsq_jn_index_build, lsq_jn_table_report, ...) and keeps what is its own."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import lib, check, vp, u64
+
+
+def copied(ptr, n, dtype):
+    """n items behind a ctypes pointer as a numpy array of its own (n == 0: an empty one of `dtype`)"""
+    return np.ctypeslib.as_array(ptr, (n,)).copy() if n else np.zeros(0, dtype)
+
+
+class _Handle:
+    PREFIX = KIND = None      # the entry points are lsq_<PREFIX>_<KIND>_<name>
+
+    @classmethod
+    def _entry(cls, name):
+        return getattr(lib, "%s_%s_%s" % (cls.PREFIX, cls.KIND, name))
+
+    def __init_subclass__(cls):
+        if cls.PREFIX and cls.KIND:
+            cls._free = cls._entry("free")      # (bound now: the module's globals may be gone when the last handle is)
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            self._free(self.h)
+            self.h = None
+
+
+class Table(_Handle):
+    KIND = "table"
+
+    def __init__(self, h, index, report, phases):
+        self.h = h
+        self.index = index
+        rep = (u64 * len(report))()
+        check(self._entry("report")(h, rep))
+        self.report = dict(zip(report, (int(v) for v in rep)))
+        ms = (C.c_float * len(phases))()
+        check(self._entry("times")(h, ms))
+        self.times = dict(zip(phases, (float(v) for v in ms)))
+
+
+class Index(_Handle):
+    KIND = "index"
+
+    def __init__(self, annotation):
+        h = vp()
+        check(self._entry("build")(annotation.h, C.byref(h)))
+        self.h = h
+
+    @property
+    def num_chroms(self):
+        return self._entry("num_chroms")(self.h)
+
+    def chrom_names(self):
+        name = self._entry("chrom_name")
+        return [name(self.h, c).decode() for c in range(self.num_chroms)]
+
+    def parse_host(self, read_format, path, n_threads=0):
+        """lsq_reads_parse against the index's dictionaries: an api.Reads for host_reads"""
+        from .api import Reads
+
+        class _Dictionaries:
+            h = vp(self._entry("dictionaries")(self.h))
+        return Reads.from_mrf(path, _Dictionaries, n_threads, read_format)
+
+    def _table(self, cls, call, *args):
+        """call(*args, a new table): the table as a `cls`"""
+        t = vp()
+        check(call(*args, C.byref(t)))
+        return cls(t, self)

@@ -4,13 +4,9 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, check_runtime_once, SynthSpecStruct, BamReportStruct, u64, u32, i32, u16, u8, i64, vp, cs, P
+from ._lib import lib, check, check_runtime_once, SynthSpecStruct, BamReportStruct, u64, u32, i32, u16, u8, i64, vp, cs, P, _b
 
 EVENT_TYPES = ("SE", "RI", "A5SS", "A3SS", "MXE", "AFE", "ALE", "T3")
-
-
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
 
 
 def _take_text(ptr):

@@ -5,15 +5,12 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, vp, u64, u32, i32, P
+from ._lib import lib, check, u64, u32, i32, P, _b, take_text
+from ._readtool import Index, Table, copied
 
 SORT_TILE = lib.lsq_cov_sort_tile()     # records a workgroup of the device sort takes (two records per counted block)
 PHASES = ("extract", "sort", "reduce_scan", "emit", "regions", "copy_back")
 REPORT = ("reads", "blocks", "counted", "no_chromosome", "empty", "other_strand", "bases")
-
-
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
 
 
 def _strand(s):
@@ -24,45 +21,25 @@ def _strand(s):
     raise ValueError("strand must be None, '+' or '-'")
 
 
-def _text(call, *args):
-    out = vp()
-    check(call(*args, C.byref(out)))
-    try:
-        return C.string_at(out).decode()
-    finally:
-        lib.lsq_free(out)
-
-
-class Coverage:
+class Coverage(Table):
     """The tables of one read file: numpy arrays (copies) of the rows -- chrom, start, end, depth -- and of the regions -- region_chrom,
     bases, covered, depth_sum, with region_names and region_strands -- `report`, `times` (device ms per phase), text(), regions_text()."""
+    PREFIX = "lsq_cov"
 
     def __init__(self, h, index):
-        self.h = h
-        self.index = index
+        super().__init__(h, index, REPORT, PHASES)
         n = lib.lsq_cov_table_rows(h)
         ptrs = [P(u32)(), P(i32)(), P(i32)(), P(u32)()]
         check(lib.lsq_cov_table_arrays(h, *[C.byref(p) for p in ptrs]))
         for (k, dt), p in zip((("chrom", np.uint32), ("start", np.int32), ("end", np.int32), ("depth", np.uint32)), ptrs):
-            setattr(self, k, np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, dt))
+            setattr(self, k, copied(p, n, dt))
         m = lib.lsq_cov_table_regions(h)
         ptrs = [P(u32)(), P(u64)(), P(u64)(), P(u64)()]
         check(lib.lsq_cov_table_region_arrays(h, *[C.byref(p) for p in ptrs]))
         for (k, dt), p in zip((("region_chrom", np.uint32), ("bases", np.uint64), ("covered", np.uint64), ("depth_sum", np.uint64)), ptrs):
-            setattr(self, k, np.ctypeslib.as_array(p, (m,)).copy() if m else np.zeros(0, dt))
+            setattr(self, k, copied(p, m, dt))
         self.region_names = [lib.lsq_cov_table_region_name(h, r).decode() for r in range(m)]
         self.region_strands = [lib.lsq_cov_table_region_strand(h, r).decode() for r in range(m)]
-        rep = (u64 * 7)()
-        check(lib.lsq_cov_table_report(h, rep))
-        self.report = dict(zip(REPORT, (int(v) for v in rep)))
-        ms = (C.c_float * 6)()
-        check(lib.lsq_cov_table_times(h, ms))
-        self.times = dict(zip(PHASES, (float(v) for v in ms)))
-
-    def __del__(self, _free=lib.lsq_cov_table_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
 
     def __len__(self):
         return len(self.chrom)
@@ -80,61 +57,31 @@ class Coverage:
 
     def text(self, min_depth=0):
         """the bedGraph of the rows with depth >= min_depth"""
-        return _text(lib.lsq_cov_format, self.h, min_depth)
+        return take_text(lib.lsq_cov_format, self.h, min_depth)
 
     def regions_text(self):
-        return _text(lib.lsq_cov_format_regions, self.h)
+        return take_text(lib.lsq_cov_format_regions, self.h)
 
 
-class CoverageIndex:
+class CoverageIndex(Index):
     """lsq_cov_index_build: the annotation's chromosomes and the exon union of every isoform line"""
-
-    def __init__(self, annotation):
-        h = vp()
-        check(lib.lsq_cov_index_build(annotation.h, C.byref(h)))
-        self.h = h
-
-    def __del__(self, _free=lib.lsq_cov_index_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
-
-    @property
-    def num_chroms(self):
-        return lib.lsq_cov_index_num_chroms(self.h)
+    PREFIX = "lsq_cov"
 
     @property
     def num_regions(self):
         return lib.lsq_cov_index_num_regions(self.h)
 
-    def chrom_names(self):
-        return [lib.lsq_cov_index_chrom_name(self.h, c).decode() for c in range(self.num_chroms)]
-
     def host(self, read_format, path, strand=None, min_depth=1, skip_flags=0x904, min_mapq=0, n_threads=0):
         """lsq_cov_host: every read format lsq_reads_parse takes; no GPU touched"""
-        t = vp()
-        check(lib.lsq_cov_host(self.h, _b(read_format), _b(path), skip_flags, min_mapq, _strand(strand), min_depth, n_threads, C.byref(t)))
-        return Coverage(t, self)
-
-    def parse_host(self, read_format, path, n_threads=0):
-        """lsq_reads_parse against the index's dictionaries: an api.Reads for host_reads"""
-        from .api import Reads
-
-        class _Dictionaries:
-            h = vp(lib.lsq_cov_index_dictionaries(self.h))
-        return Reads.from_mrf(path, _Dictionaries, n_threads, read_format)
+        return self._table(Coverage, lib.lsq_cov_host, self.h, _b(read_format), _b(path), skip_flags, min_mapq, _strand(strand), min_depth, n_threads)
 
     def host_reads(self, reads, strand=None, min_depth=1, n_threads=0):
         """lsq_cov_host_reads: from arrays already parsed against this index (parse_host)"""
-        t = vp()
-        check(lib.lsq_cov_host_reads(self.h, reads.h, _strand(strand), min_depth, n_threads, C.byref(t)))
-        return Coverage(t, self)
+        return self._table(Coverage, lib.lsq_cov_host_reads, self.h, reads.h, _strand(strand), min_depth, n_threads)
 
     def device(self, ctx, read_format, path, strand=None, min_depth=1):
         """lsq_cov_device: MRF_SINGLE, SAM_SINGLE or BAM_SINGLE under the context's sam_skip_flags / sam_min_mapq / bam_verify"""
-        t = vp()
-        check(lib.lsq_cov_device(ctx.h, self.h, _b(read_format), _b(path), _strand(strand), min_depth, C.byref(t)))
-        return Coverage(t, self)
+        return self._table(Coverage, lib.lsq_cov_device, ctx.h, self.h, _b(read_format), _b(path), _strand(strand), min_depth)
 
 
 __all__ = ["CoverageIndex", "Coverage", "SORT_TILE", "PHASES", "REPORT"]

@@ -39,12 +39,6 @@ void put_g(std::string &o, double v) {
 	o.append(t, (size_t)n);
 }
 
-char *dup_text(const std::string &s) {
-	char *p = (char *)malloc(s.size() + 1);
-	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
-	return p;
-}
-
 // jsc/util/log.hpp:22-79: "[LOG YYYY-MM-DD hh:mm:ss LEVEL] text" on stderr when level <= reporting level
 int g_log_level = 2;
 void logf(int level, const char *fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -1,8 +1,8 @@
 // Per-base read depth of a read file (include/lesseq_hip.h, lsq_cov_*): the index made from an annotation, the host
 // path over the host parsers' arrays, the tables' text and the coverage executable.  The device passes are lsq_cov.hip, the
-// entry that opens a read file on the device is lsq_readfile.hip's lsq_cov_device.
+// entry that opens a read file on the device is lsq_readfile.hip's lsq_cov_device; what the tool shares with junctions and
+// exonbins is lsq_readtool.hpp.
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 
@@ -24,12 +24,6 @@ void fold_steps(std::vector<Step> &v) {
 		else v[o++] = v[i];
 	}
 	v.resize(o);
-}
-
-char *dup_text(const std::string &s) {
-	char *p = (char *)malloc(s.size() + 1);
-	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
-	return p;
 }
 
 // covered and depth_sum of every region from rows in (chromosome index, start) order: the rows an interval overlaps, one by one
@@ -62,45 +56,32 @@ void lsq::cov_finish_table(const lsq_cov_index &ix, lsq_cov_table &t) {
 	t.r_name = ix.name; t.r_strand = ix.strand; t.r_chrom = ix.chrom; t.r_bases = ix.bases;
 }
 
-int lsq::cov_host_reads(const lsq_cov_index &ix, const JnReads &R, int strand, uint32_t min_depth, int n_threads, lsq_cov_table &t) {
-	int T = host_threads(n_threads);
-	if (R.n_reads < (1u << 16)) T = 1;
+int lsq::cov_host_reads(const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, int n_threads, lsq_cov_table &t) {
+	const int T = read_slices(R.n_reads, n_threads);
 	const unsigned strand_id = strand == '+' ? 0u : strand == '-' ? 1u : 0xFFFFFFFFu;
 	std::vector<std::vector<Step>> part((size_t)T);
 	std::vector<uint64_t> tally((size_t)T * 5, 0);       // counted, without chromosome, empty or descending, other strand, bases
-	{
-		ThreadGroup th;
-		for (int k = 0; k < T; ++k) th.spawn([&, k] {
-			std::vector<Step> &v = part[(size_t)k];
-			uint64_t *n = &tally[(size_t)k * 5];
-			const uint64_t r0 = R.n_reads * (uint64_t)k / (uint64_t)T, r1 = R.n_reads * (uint64_t)(k + 1) / (uint64_t)T;
-			for (uint64_t b = R.blk_off[r0]; b < R.blk_off[r1]; ++b) {
-				const unsigned c = R.bc[b];
-				if (c == JN_NOCHROM) { ++n[1]; continue; }
-				if (R.be[b] <= R.bs[b]) { ++n[2]; continue; }
-				if (strand_id != 0xFFFFFFFFu && R.bst[b] != strand_id) { ++n[3]; continue; }
-				++n[0]; n[4] += (uint64_t)((int64_t)R.be[b] - R.bs[b]);
-				v.push_back(Step{((uint64_t)c << 32) | (uint64_t)((int64_t)R.bs[b] + COV_BIAS), 1});
-				v.push_back(Step{((uint64_t)c << 32) | (uint64_t)((int64_t)R.be[b] + COV_BIAS), -1});
-			}
-			std::sort(v.begin(), v.end(), step_less);
-			fold_steps(v);
-		});
-		th.join();
-		if (th.failed()) return fail(LSQ_E_INTERNAL, "%s", th.error().c_str());
-	}
+	const int rc = for_read_slices(R.n_reads, T, [&](int k, uint64_t r0, uint64_t r1) {
+		std::vector<Step> &v = part[(size_t)k];
+		uint64_t *n = &tally[(size_t)k * 5];
+		for (uint64_t b = R.blk_off[r0]; b < R.blk_off[r1]; ++b) {
+			const unsigned c = R.bc[b];
+			if (c == NO_CHROM) { ++n[1]; continue; }
+			if (R.be[b] <= R.bs[b]) { ++n[2]; continue; }
+			if (strand_id != 0xFFFFFFFFu && R.bst[b] != strand_id) { ++n[3]; continue; }
+			++n[0]; n[4] += (uint64_t)((int64_t)R.be[b] - R.bs[b]);
+			v.push_back(Step{((uint64_t)c << 32) | (uint64_t)((int64_t)R.bs[b] + COV_BIAS), 1});
+			v.push_back(Step{((uint64_t)c << 32) | (uint64_t)((int64_t)R.be[b] + COV_BIAS), -1});
+		}
+		std::sort(v.begin(), v.end(), step_less);
+		fold_steps(v);
+	});
+	if (rc) return rc;
 	for (uint64_t &v : t.report) v = 0;
 	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
 	for (int k = 0; k < T; ++k) for (int q = 0; q < 5; ++q) t.report[2 + q] += tally[(size_t)k * 5 + q];
 	if (t.report[2] > 0x7FFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32-1 sort records (two per counted block)");
-	std::vector<Step> all = std::move(part[0]);
-	for (int k = 1; k < T; ++k) {
-		std::vector<Step> m(all.size() + part[(size_t)k].size());
-		std::merge(all.begin(), all.end(), part[(size_t)k].begin(), part[(size_t)k].end(), m.begin(), step_less);
-		fold_steps(m);
-		all.swap(m);
-		std::vector<Step>().swap(part[(size_t)k]);
-	}
+	const std::vector<Step> all = merge_folded(part, step_less, fold_steps);
 	// the sweep: the depth behind every step; a stretch of positive depth joins the row before it when it abuts it at the same depth
 	t.resize(0);
 	int64_t depth = 0;
@@ -133,9 +114,7 @@ int lsq_cov_index_build(const lsq_annotation *a, lsq_cov_index **out) LSQ_API_TR
 		const IsoRec &r = *rp;
 		// the union of the line's exons as maximal intervals
 		ex.clear();
-		const size_t ne = std::min<size_t>({(size_t)r.exonCount, r.exonStarts.size(), r.exonEnds.size()});
-		for (size_t i = 0; i < ne; ++i) if (r.exonEnds[i] > r.exonStarts[i]) ex.emplace_back(r.exonStarts[i], r.exonEnds[i]);
-		std::sort(ex.begin(), ex.end());
+		exon_union(r, ex);
 		uint64_t bases = 0;
 		const size_t first = ix->iv_s.size();
 		for (const auto &x : ex) {
@@ -151,34 +130,22 @@ int lsq_cov_index_build(const lsq_annotation *a, lsq_cov_index **out) LSQ_API_TR
 } LSQ_API_CATCH
 
 void lsq_cov_index_free(lsq_cov_index *ix) { delete ix; }
-int64_t lsq_cov_index_num_chroms(const lsq_cov_index *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
-const char *lsq_cov_index_chrom_name(const lsq_cov_index *ix, int64_t chrom) {
-	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
-}
+int64_t lsq_cov_index_num_chroms(const lsq_cov_index *ix) { return index_num_chroms(ix); }
+const char *lsq_cov_index_chrom_name(const lsq_cov_index *ix, int64_t chrom) { return index_chrom_name(ix, chrom); }
 int64_t lsq_cov_index_num_regions(const lsq_cov_index *ix) { return ix ? (int64_t)ix->name.size() : 0; }
-lsq_events *lsq_cov_index_dictionaries(lsq_cov_index *ix) { return ix ? &ix->E : nullptr; }
+lsq_events *lsq_cov_index_dictionaries(lsq_cov_index *ix) { return index_dictionaries(ix); }
 
 int lsq_cov_host_reads(lsq_cov_index *ix, const lsq_reads *r, int strand, uint32_t min_depth, int n_threads, lsq_cov_table **out) LSQ_API_TRY {
 	if (!ix || !r || !out) return fail(LSQ_E_ARG, "null argument");
 	if (!cov_strand_ok(strand)) return fail(LSQ_E_ARG, "strand must be 0, '+' or '-'");
-	std::unique_ptr<lsq_cov_table> t(new lsq_cov_table);
-	const JnReads R{r->n_reads, r->n_blocks, (const unsigned long long *)r->blk_off, r->blk_start, r->blk_end, r->blk_chrom, r->blk_strand};
-	const int rc = cov_host_reads(*ix, R, strand, min_depth, n_threads, *t);
-	if (rc) return rc;
-	*out = t.release();
-	return LSQ_OK;
+	return new_table(out, [&](lsq_cov_table &t) { return cov_host_reads(*ix, host_view(*r), strand, min_depth, n_threads, t); });
 } LSQ_API_CATCH
 
 int lsq_cov_host(lsq_cov_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int strand, uint32_t min_depth, int n_threads,
                  lsq_cov_table **out) LSQ_API_TRY {
 	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (!cov_strand_ok(strand)) return fail(LSQ_E_ARG, "strand must be 0, '+' or '-'");
-	lsq_reads *r = nullptr;
-	int rc = host_parse_reads(&ix->E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
-	if (rc) return rc;
-	rc = lsq_cov_host_reads(ix, r, strand, min_depth, n_threads, out);
-	lsq_reads_free(r);
-	return rc;
+	return host_file(ix->E, read_format, path, skip_flags, min_mapq, n_threads, [&](const lsq_reads *r) { return lsq_cov_host_reads(ix, r, strand, min_depth, n_threads, out); });
 } LSQ_API_CATCH
 
 void lsq_cov_table_free(lsq_cov_table *t) { delete t; }
@@ -206,16 +173,8 @@ const char *lsq_cov_table_region_name(const lsq_cov_table *t, int64_t region) {
 const char *lsq_cov_table_region_strand(const lsq_cov_table *t, int64_t region) {
 	return t && region >= 0 && (size_t)region < t->r_strand.size() ? t->r_strand[(size_t)region].c_str() : nullptr;
 }
-int lsq_cov_table_report(const lsq_cov_table *t, uint64_t report[7]) {
-	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
-	memcpy(report, t->report, sizeof(t->report));
-	return LSQ_OK;
-}
-int lsq_cov_table_times(const lsq_cov_table *t, float ms[6]) {
-	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
-	memcpy(ms, t->ms, sizeof(t->ms));
-	return LSQ_OK;
-}
+int lsq_cov_table_report(const lsq_cov_table *t, uint64_t report[7]) { return table_report(t, report); }
+int lsq_cov_table_times(const lsq_cov_table *t, float ms[6]) { return table_times(t, ms); }
 
 int lsq_cov_format(const lsq_cov_table *t, uint32_t min_depth, char **out_text) LSQ_API_TRY {
 	if (!t || !out_text) return fail(LSQ_E_ARG, "null argument");
@@ -263,60 +222,33 @@ int lsq::run_coverage(int argc, const char *const *argv, std::string &out) {
 		if (strcmp(argv[i], "--host") == 0) host = true;
 		else if (strcmp(argv[i], "--strand") == 0) {
 			if (i + 1 < argc && (strcmp(argv[i + 1], "+") == 0 || strcmp(argv[i + 1], "-") == 0)) strand = argv[++i][0]; else bad = true;
-		} else if (strcmp(argv[i], "--min-depth") == 0) {
-			char *end = nullptr;
-			if (i + 1 >= argc) { bad = true; break; }
-			errno = 0;
-			min_depth = strtoul(argv[++i], &end, 10);
-			if (end == argv[i] || *end || errno || min_depth > 0xFFFFFFFFul || argv[i][0] == '-') bad = true;
-		} else if (strcmp(argv[i], "--regions") == 0) {
+		} else if (strcmp(argv[i], "--min-depth") == 0) bad = !cli_u32_option(argc, argv, i, min_depth);
+		else if (strcmp(argv[i], "--regions") == 0) {
 			if (i + 1 < argc) regions_path = argv[++i]; else bad = true;
 		} else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
 		else pos.push_back(argv[i]);
 	}
 	if (bad || pos.size() < 6 || pos.size() > 7) { cli_log(0, USAGE); return 1; }
-	struct Owned {
-		lsq_annotation *a = nullptr; lsq_cov_index *ix = nullptr; lsq_cov_table *t = nullptr; lsq_ctx *c = nullptr; char *text = nullptr, *regions = nullptr;
-		~Owned() { lsq_cov_table_free(t); if (c) lsq_ctx_destroy(c); lsq_cov_index_free(ix); lsq_annotation_free(a); lsq_free(text); lsq_free(regions); }
-	} O;
-	auto failed = [&](int st) {
-		cli_log(0, lsq_last_error());
-		if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
-		return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
-	};
-	int st = lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &O.a);
-	if (!st) st = lsq_cov_index_build(O.a, &O.ix);
-	if (st) return failed(st);
+	CliFrame F(pos);                                       // text[0] the bedGraph, text[1] the regions
+	CliOwned<lsq_cov_index, lsq_cov_index_free> ix;
+	CliOwned<lsq_cov_table, lsq_cov_table_free> t;
+	int st = F.load_annotation();
+	if (!st) st = lsq_cov_index_build(F.a, &ix.p);
+	if (st) return cli_failed(st);
 	if (host) {
-		lsq_reads *r = nullptr;
-		st = cli_host_parse(&O.ix->E, pos[4], pos[5], &r);
-		if (!st) st = lsq_cov_host_reads(O.ix, r, strand, (uint32_t)min_depth, 0, &O.t);
-		lsq_reads_free(r);
-	} else {
-		st = lsq_ctx_create(cli_device(), &O.c);
-		if (!st) st = cli_env_options(O.c);
-		if (!st) st = lsq_cov_device(O.c, O.ix, pos[4], pos[5], strand, (uint32_t)min_depth, &O.t);
-	}
-	if (!st) st = lsq_cov_format(O.t, (uint32_t)min_depth, &O.text);
-	if (!st && regions_path) st = lsq_cov_format_regions(O.t, &O.regions);
-	if (st) return failed(st);
-	const uint64_t *rep = O.t->report;
+		if (!(st = F.host_parse(&ix.p->E))) st = lsq_cov_host_reads(ix.p, F.reads, strand, (uint32_t)min_depth, 0, &t.p);
+		F.free_reads();
+	} else if (!(st = F.create_context())) st = lsq_cov_device(F.c, ix.p, pos[4], pos[5], strand, (uint32_t)min_depth, &t.p);
+	if (!st) st = lsq_cov_format(t.p, (uint32_t)min_depth, &F.text[0]);
+	if (!st && regions_path) st = lsq_cov_format_regions(t.p, &F.text[1]);
+	if (st) return cli_failed(st);
+	const uint64_t *rep = t.p->report;
 	char msg[384];
 	snprintf(msg, sizeof msg, "coverage: %llu read(s), %llu block(s), %llu counted in %lld row(s); %llu on no chromosome of the annotation, %llu empty or descending, %llu of the other strand; "
 	         "%llu base(s) in the counted blocks (solve's total_read_bases)",
-	         (unsigned long long)rep[0], (unsigned long long)rep[1], (unsigned long long)rep[2], (long long)lsq_cov_table_rows(O.t), (unsigned long long)rep[3], (unsigned long long)rep[4],
+	         (unsigned long long)rep[0], (unsigned long long)rep[1], (unsigned long long)rep[2], (long long)lsq_cov_table_rows(t.p), (unsigned long long)rep[3], (unsigned long long)rep[4],
 	         (unsigned long long)rep[5], (unsigned long long)rep[6]);
 	cli_log(1, msg);
-	auto write_file = [&](const char *path, const char *text) {
-		FILE *fp = fopen(path, "wb");
-		const size_t n = strlen(text);
-		const bool ok = fp && fwrite(text, 1, n, fp) == n;
-		if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", path); return false; }
-		return true;
-	};
-	if (regions_path && !write_file(regions_path, O.regions)) return failed(LSQ_E_IO);
-	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) {
-		if (!write_file(pos[6], O.text)) return failed(LSQ_E_IO);
-	} else out = O.text;
-	return 0;
+	if (regions_path && !write_file(regions_path, F.text[1])) return cli_failed(LSQ_E_IO);
+	return F.deliver(F.text[0], out);
 }

@@ -5,7 +5,7 @@
 // (neighbouring stretches of one depth joined into rows by a second compaction), regions (a lane an exon-union interval: two binary
 // searches in the rows, sums from cumulative 64-bit arrays), copy-back.  Every number is an integer and no result depends on the
 // order in which lanes arrive: sums only.
-#include "lsq_device.hpp"
+#include "lsq_wave.hpp"
 #include "lsq_scan.hpp"
 #include "lsq_sort.hpp"
 #include "lsq_cov.hpp"
@@ -15,22 +15,13 @@ namespace {
 // A record: w0 = position + 2^30; w1 = chromosome index << 32 | COV_START where a block begins
 struct CovAcc { unsigned long long nochrom, empty, other, bases, any0, any1, all0, all1; };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-	for (unsigned d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-	return v;
-}
-__device__ inline unsigned long long wave_or(unsigned long long v) {
-	for (unsigned d = 32; d; d >>= 1) v |= __shfl_xor(v, d);
-	return v;
-}
-
 // A lane a read, a fixed number of workgroups striding over the reads.  EMIT false: the read's counted blocks (cnt), the blocks
 // that are not counted and the counted bases for the report.  EMIT true: two records per counted block written at the read's place
 // (off counts blocks), the OR and the AND of all of them kept for the sort's choice of digits.  The tallies are kept per lane over
 // the stride, summed over the workgroup once, and added to `acc` by one lane (lsq_junc.hip's extract: what an atomic a wave costs).
 // strand_id: the strand a counted block must carry (0 "+", 1 "-"), or a value no block carries the other way round: 0xFFFFFFFF = any.
 template <bool EMIT>
-__global__ void __launch_bounds__(256) lsq_cov_extract_kernel(JnReads R, unsigned strand_id, unsigned *cnt, const unsigned long long *off,
+__global__ void __launch_bounds__(256) lsq_cov_extract_kernel(ParsedReads R, unsigned strand_id, unsigned *cnt, const unsigned long long *off,
                                                               unsigned long long *w0, unsigned long long *w1, CovAcc *acc) {
 	__shared__ unsigned long long part[4][4];
 	unsigned long long t0 = 0, t1 = 0, t2 = 0, t3 = 0;          // EMIT: any0, any1, ~all0, ~all1; else nochrom, empty, other, bases
@@ -41,7 +32,7 @@ __global__ void __launch_bounds__(256) lsq_cov_extract_kernel(JnReads R, unsigne
 		for (unsigned long long k = b0; k < b1; ++k) {
 			const int s = R.bs[k], e = R.be[k];
 			const unsigned ch = R.bc[k];
-			if (ch == JN_NOCHROM) { if (!EMIT) ++t0; continue; }
+			if (ch == NO_CHROM) { if (!EMIT) ++t0; continue; }
 			if (e <= s) { if (!EMIT) ++t1; continue; }
 			if (strand_id != 0xFFFFFFFFu && (unsigned)R.bst[k] != strand_id) { if (!EMIT) ++t2; continue; }
 			if (EMIT) {
@@ -54,14 +45,9 @@ __global__ void __launch_bounds__(256) lsq_cov_extract_kernel(JnReads R, unsigne
 		}
 		if (!EMIT) cnt[r] = m;
 	}
-	const unsigned wave = threadIdx.x >> 6;
-	if (EMIT) { t0 = wave_or(t0); t1 = wave_or(t1); t2 = wave_or(t2); t3 = wave_or(t3); }
-	else { t0 = wave_sum(t0); t1 = wave_sum(t1); t2 = wave_sum(t2); t3 = wave_sum(t3); }
-	if ((threadIdx.x & 63u) == 0) { part[wave][0] = t0; part[wave][1] = t1; part[wave][2] = t2; part[wave][3] = t3; }
-	__syncthreads();
+	unsigned long long v[4] = {t0, t1, t2, t3};
+	workgroup_tally<EMIT>(v, part);
 	if (threadIdx.x == 0) {
-		unsigned long long v[4] = {0, 0, 0, 0};
-		for (unsigned w = 0; w < 4; ++w) for (unsigned q = 0; q < 4; ++q) v[q] = EMIT ? (v[q] | part[w][q]) : (v[q] + part[w][q]);
 		if (EMIT) {
 			if (v[0]) atomicOr(&acc->any0, v[0]);
 			if (v[1]) atomicOr(&acc->any1, v[1]);
@@ -173,12 +159,6 @@ __global__ void __launch_bounds__(256) lsq_cov_regions_kernel(CovIntervals I, Co
 	if (sum) atomicAdd(&depth_sum[line], sum);
 }
 
-// workgroups of the extract: eight a compute unit at most (LSQ_COV_EXTRACT_GRID: another bound -- tests: the stride on a small file)
-inline unsigned extract_grid(const lsq_ctx *c, unsigned long long n_reads) {
-	if (const char *e = getenv("LSQ_COV_EXTRACT_GRID")) { const long long v = atoll(e); if (v >= 1 && v <= 1 << 20) return std::min(grid_for(n_reads, 256), (unsigned)v); }
-	return grid_for(c->n_cu, n_reads, 256, 8);
-}
-
 struct DevPieces {
 	DevBuf<unsigned> chrom, depth;
 	DevBuf<int> start, end;
@@ -188,7 +168,7 @@ struct DevPieces {
 
 } // namespace
 
-int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const JnReads &R, int strand, uint32_t min_depth, lsq_cov_table &t) {
+int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, lsq_cov_table &t) {
 	hipStream_t st = c->stream;
 	int rc;
 	PhaseClock<COV_PHASES> PC;
@@ -212,8 +192,9 @@ int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const JnReads &R,
 	const CovAcc acc0{0, 0, 0, 0, 0, 0, ~0ull, ~0ull};
 	CovAcc acc = acc0;
 	unsigned long long n_counted = 0;
+	const unsigned grid = stride_grid(c, "LSQ_COV_EXTRACT_GRID", R.n_reads);
 	if ((rc = d_cnt.alloc((size_t)R.n_reads)) || (rc = d_off.alloc((size_t)R.n_reads + 1)) || (rc = d_acc.upload(&acc0, 1, st)) || (rc = SS.reserve(R.n_reads))) return rc;
-	hipLaunchKernelGGL((lsq_cov_extract_kernel<false>), dim3(extract_grid(c, R.n_reads)), dim3(256), 0, st, R, strand_id, d_cnt.p, (const unsigned long long *)nullptr,
+	hipLaunchKernelGGL((lsq_cov_extract_kernel<false>), dim3(grid), dim3(256), 0, st, R, strand_id, d_cnt.p, (const unsigned long long *)nullptr,
 	                   (unsigned long long *)nullptr, (unsigned long long *)nullptr, d_acc.p);
 	HIP_TRY(hipGetLastError());
 	if ((rc = device_scan<1, false>(SS, d_cnt.p, R.n_reads, d_off.p, st))) return rc;
@@ -224,7 +205,7 @@ int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const JnReads &R,
 	SortBuf B;                                  // (allocations follow the counted blocks)
 	if ((rc = B.reserve(n))) return rc;
 	if (n) {
-		hipLaunchKernelGGL((lsq_cov_extract_kernel<true>), dim3(extract_grid(c, R.n_reads)), dim3(256), 0, st, R, strand_id, (unsigned *)nullptr, (const unsigned long long *)d_off.p,
+		hipLaunchKernelGGL((lsq_cov_extract_kernel<true>), dim3(grid), dim3(256), 0, st, R, strand_id, (unsigned *)nullptr, (const unsigned long long *)d_off.p,
 		                   B.w0[0].p, B.w1[0].p, d_acc.p);
 		HIP_TRY(hipGetLastError());
 	}

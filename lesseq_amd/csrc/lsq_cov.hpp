@@ -1,8 +1,9 @@
 // Per-base read depth of a read file (include/lesseq_hip.h, lsq_cov_*): what lsq_cov.cpp (index, host path, text, the
 // coverage executable), lsq_cov.hip (the device passes) and lsq_readfile.hip (the entry that opens the read file) share.
+// The parsed reads, the dictionaries and the executables' frame are lsq_readtool.hpp's.
 #pragma once
 
-#include "lsq_junc.hpp"
+#include "lsq_readtool.hpp"
 
 namespace lsq {
 constexpr int COV_PHASES = 6;                  // extract, sort, reduce and scan, emit, regions, copy-back
@@ -12,7 +13,7 @@ constexpr unsigned long long COV_START = 1ull; // a sort record's payload (w1, b
 }
 
 struct lsq_cov_index {
-	// the dictionaries the parsers intern against, as lsq_jn_index's: the annotation's chromosomes, "+" (0) and "-" (1), one
+	// the dictionaries the parsers intern against (annotation_dictionaries): the annotation's chromosomes, "+" (0) and "-" (1), one
 	// whole-line interval a chromosome
 	lsq_events E;
 	// a region per isoform line, in file order; its exon union as maximal intervals, ascending: iv_off[r] .. iv_off[r + 1]
@@ -45,9 +46,9 @@ inline bool cov_strand_ok(int strand) { return strand == 0 || strand == '+' || s
 // lsq_cov.cpp: rows in (chromosome index, start) order -> the table's order (chromosome names bytewise); the regions' names and
 // sizes attached (covered and depth_sum are the caller's)
 void cov_finish_table(const lsq_cov_index &ix, lsq_cov_table &t);
-int cov_host_reads(const lsq_cov_index &ix, const JnReads &R, int strand, uint32_t min_depth, int n_threads, lsq_cov_table &t);
+int cov_host_reads(const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, int n_threads, lsq_cov_table &t);
 int run_coverage(int argc, const char *const *argv, std::string &out);       // the coverage executable
 // lsq_cov.hip: the device passes over device arrays; rows come back in (chromosome index, start) order, r_covered and r_depth_sum filled
-int cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const JnReads &R, int strand, uint32_t min_depth, lsq_cov_table &t);
+int cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, lsq_cov_table &t);
 
 } // namespace lsq

@@ -1,8 +1,8 @@
 // Reads per exon bin and per gene of a read file (include/lesseq_hip.h, lsq_xb_*): the index made from an annotation,
 // the host path over the host parsers' arrays, the tables' text and the exonbins executable.  The device count is
-// lsq_exonbins.hip, the entry that opens a read file on the device is lsq_readfile.hip's lsq_xb_device.
+// lsq_exonbins.hip, the entry that opens a read file on the device is lsq_readfile.hip's lsq_xb_device; what the tool shares with
+// junctions and coverage is lsq_readtool.hpp.
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
 #include <cstring>
 
@@ -12,12 +12,6 @@ using namespace lsq;
 
 namespace {
 
-char *dup_text(const std::string &s) {
-	char *p = (char *)malloc(s.size() + 1);
-	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
-	return p;
-}
-
 inline int32_t clamped(int64_t x) { return (int32_t)std::max<int64_t>(-XB_LIM, std::min<int64_t>(XB_LIM, x)); }
 
 // The bins of one gene from its isoform lines' exons: the stretches between neighbouring boundaries that an exon covers.  The
@@ -25,14 +19,8 @@ inline int32_t clamped(int64_t x) { return (int32_t)std::max<int64_t>(-XB_LIM, s
 // maximal interval or outside all of them.
 void gene_bins(const Gene &g, std::vector<std::pair<int64_t, int64_t>> &ex, std::vector<int64_t> &cut, std::vector<int64_t> &bs, std::vector<int64_t> &be) {
 	ex.clear(); cut.clear();
-	for (const IsoRec *r : g.isos) {
-		const size_t ne = std::min<size_t>({(size_t)r->exonCount, r->exonStarts.size(), r->exonEnds.size()});
-		for (size_t i = 0; i < ne; ++i) if (r->exonEnds[i] > r->exonStarts[i]) {
-			ex.emplace_back(r->exonStarts[i], r->exonEnds[i]);
-			cut.push_back(r->exonStarts[i]); cut.push_back(r->exonEnds[i]);
-		}
-	}
-	std::sort(ex.begin(), ex.end());
+	for (const IsoRec *r : g.isos) exon_union(*r, ex);
+	for (const auto &x : ex) { cut.push_back(x.first); cut.push_back(x.second); }
 	std::sort(cut.begin(), cut.end());
 	cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
 	size_t q = 0;                               // the boundary the next stretch begins at
@@ -92,14 +80,6 @@ inline uint32_t first_cell(const lsq_xb_index &ix, uint32_t c, int32_t s) {
 	return lo;
 }
 
-bool write_file(const std::string &path, const char *text) {
-	FILE *fp = fopen(path.c_str(), "wb");
-	const size_t n = strlen(text);
-	const bool ok = fp && fwrite(text, 1, n, fp) == n;
-	if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", path.c_str()); return false; }
-	return true;
-}
-
 } // namespace
 
 void lsq::xb_start_table(const lsq_xb_index &ix, lsq_xb_table &t) {
@@ -111,45 +91,39 @@ void lsq::xb_start_table(const lsq_xb_index &ix, lsq_xb_table &t) {
 
 // A thread a stretch of reads, counters of its own: the bins of every cell a block's walk meets are listed per read, sorted and
 // made distinct (a read counts once a bin), the genes are the distinct bin_gene of that list (bins are gene-major: they ascend)
-int lsq::xb_host_reads(const lsq_xb_index &ix, const JnReads &R, int n_threads, lsq_xb_table &t) {
-	int T = host_threads(n_threads);
-	if (R.n_reads < (1u << 16)) T = 1;
+int lsq::xb_host_reads(const lsq_xb_index &ix, const ParsedReads &R, int n_threads, lsq_xb_table &t) {
+	const int T = read_slices(R.n_reads, n_threads);
 	const size_t nb = ix.bin_gene.size(), ng = ix.gene_name.size(), nc = ix.E.covered.size();
 	xb_start_table(ix, t);
 	std::vector<std::vector<uint64_t>> part((size_t)T);
 	std::vector<uint64_t> tally((size_t)T * 4, 0);       // blocks without chromosome or empty, reads on no gene, on several, bin hits
-	{
-		ThreadGroup th;
-		for (int k = 0; k < T; ++k) th.spawn([&, k] {
-			std::vector<uint64_t> &cnt = part[(size_t)k];
-			cnt.assign(nb + ng, 0);
-			uint64_t *n = &tally[(size_t)k * 4];
-			std::vector<uint32_t> hit;
-			const uint64_t r0 = R.n_reads * (uint64_t)k / (uint64_t)T, r1 = R.n_reads * (uint64_t)(k + 1) / (uint64_t)T;
-			for (uint64_t r = r0; r < r1; ++r) {
-				hit.clear();
-				for (uint64_t b = R.blk_off[r]; b < R.blk_off[r + 1]; ++b) {
-					const unsigned c = R.bc[b];
-					const int32_t s = R.bs[b], e = R.be[b];
-					if (c == JN_NOCHROM || c >= nc || e <= s) { ++n[0]; continue; }
-					for (uint32_t i = first_cell(ix, c, s); i < ix.chrom_first_cell[c + 1] && ix.cell_start[i] < e; ++i)
-						hit.insert(hit.end(), ix.cell_bins.begin() + ix.cell_off[i], ix.cell_bins.begin() + ix.cell_off[i + 1]);
-				}
-				std::sort(hit.begin(), hit.end());
-				hit.erase(std::unique(hit.begin(), hit.end()), hit.end());
-				uint32_t genes = 0, last = XB_NONE;
-				for (uint32_t b : hit) {
-					++cnt[b];
-					if (ix.bin_gene[b] != last) { last = ix.bin_gene[b]; ++cnt[nb + last]; ++genes; }
-				}
-				n[3] += hit.size();
-				if (genes == 0) ++n[1];
-				if (genes > 1) ++n[2];
+	const int rc = for_read_slices(R.n_reads, T, [&](int k, uint64_t r0, uint64_t r1) {
+		std::vector<uint64_t> &cnt = part[(size_t)k];
+		cnt.assign(nb + ng, 0);
+		uint64_t *n = &tally[(size_t)k * 4];
+		std::vector<uint32_t> hit;
+		for (uint64_t r = r0; r < r1; ++r) {
+			hit.clear();
+			for (uint64_t b = R.blk_off[r]; b < R.blk_off[r + 1]; ++b) {
+				const unsigned c = R.bc[b];
+				const int32_t s = R.bs[b], e = R.be[b];
+				if (c == NO_CHROM || c >= nc || e <= s) { ++n[0]; continue; }
+				for (uint32_t i = first_cell(ix, c, s); i < ix.chrom_first_cell[c + 1] && ix.cell_start[i] < e; ++i)
+					hit.insert(hit.end(), ix.cell_bins.begin() + ix.cell_off[i], ix.cell_bins.begin() + ix.cell_off[i + 1]);
 			}
-		});
-		th.join();
-		if (th.failed()) return fail(LSQ_E_INTERNAL, "%s", th.error().c_str());
-	}
+			std::sort(hit.begin(), hit.end());
+			hit.erase(std::unique(hit.begin(), hit.end()), hit.end());
+			uint32_t genes = 0, last = XB_NONE;
+			for (uint32_t b : hit) {
+				++cnt[b];
+				if (ix.bin_gene[b] != last) { last = ix.bin_gene[b]; ++cnt[nb + last]; ++genes; }
+			}
+			n[3] += hit.size();
+			if (genes == 0) ++n[1];
+			if (genes > 1) ++n[2];
+		}
+	});
+	if (rc) return rc;
 	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
 	for (int k = 0; k < T; ++k) {
 		for (size_t b = 0; b < nb; ++b) t.reads[b] += part[(size_t)k][b];
@@ -194,19 +168,17 @@ int lsq_xb_index_build(const lsq_annotation *a, lsq_xb_index **out) LSQ_API_TRY 
 } LSQ_API_CATCH
 
 void lsq_xb_index_free(lsq_xb_index *ix) { delete ix; }
-int64_t lsq_xb_index_num_chroms(const lsq_xb_index *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
+int64_t lsq_xb_index_num_chroms(const lsq_xb_index *ix) { return index_num_chroms(ix); }
 int64_t lsq_xb_index_num_genes(const lsq_xb_index *ix) { return ix ? (int64_t)ix->gene_name.size() : 0; }
 int64_t lsq_xb_index_num_bins(const lsq_xb_index *ix) { return ix ? (int64_t)ix->bin_gene.size() : 0; }
-const char *lsq_xb_index_chrom_name(const lsq_xb_index *ix, int64_t chrom) {
-	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
-}
+const char *lsq_xb_index_chrom_name(const lsq_xb_index *ix, int64_t chrom) { return index_chrom_name(ix, chrom); }
 const char *lsq_xb_index_gene_name(const lsq_xb_index *ix, int64_t gene) {
 	return ix && gene >= 0 && (size_t)gene < ix->gene_name.size() ? ix->gene_name[(size_t)gene].c_str() : nullptr;
 }
 const char *lsq_xb_index_gene_strand(const lsq_xb_index *ix, int64_t gene) {
 	return ix && gene >= 0 && (size_t)gene < ix->gene_strand.size() ? ix->gene_strand[(size_t)gene].c_str() : nullptr;
 }
-lsq_events *lsq_xb_index_dictionaries(lsq_xb_index *ix) { return ix ? &ix->E : nullptr; }
+lsq_events *lsq_xb_index_dictionaries(lsq_xb_index *ix) { return index_dictionaries(ix); }
 int lsq_xb_index_arrays(const lsq_xb_index *ix, const int64_t **bin_start, const int64_t **bin_end, const uint32_t **bin_gene, const uint32_t **gene_first_bin, const uint32_t **gene_chrom) {
 	if (!ix) return fail(LSQ_E_ARG, "null argument");
 	if (bin_start) *bin_start = ix->bin_start.data();
@@ -219,22 +191,12 @@ int lsq_xb_index_arrays(const lsq_xb_index *ix, const int64_t **bin_start, const
 
 int lsq_xb_host_reads(lsq_xb_index *ix, const lsq_reads *r, int n_threads, lsq_xb_table **out) LSQ_API_TRY {
 	if (!ix || !r || !out) return fail(LSQ_E_ARG, "null argument");
-	std::unique_ptr<lsq_xb_table> t(new lsq_xb_table);
-	const JnReads R{r->n_reads, r->n_blocks, (const unsigned long long *)r->blk_off, r->blk_start, r->blk_end, r->blk_chrom, r->blk_strand};
-	const int rc = xb_host_reads(*ix, R, n_threads, *t);
-	if (rc) return rc;
-	*out = t.release();
-	return LSQ_OK;
+	return new_table(out, [&](lsq_xb_table &t) { return xb_host_reads(*ix, host_view(*r), n_threads, t); });
 } LSQ_API_CATCH
 
 int lsq_xb_host(lsq_xb_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_xb_table **out) LSQ_API_TRY {
 	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
-	lsq_reads *r = nullptr;
-	int rc = host_parse_reads(&ix->E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
-	if (rc) return rc;
-	rc = lsq_xb_host_reads(ix, r, n_threads, out);
-	lsq_reads_free(r);
-	return rc;
+	return host_file(ix->E, read_format, path, skip_flags, min_mapq, n_threads, [&](const lsq_reads *r) { return lsq_xb_host_reads(ix, r, n_threads, out); });
 } LSQ_API_CATCH
 
 void lsq_xb_table_free(lsq_xb_table *t) { delete t; }
@@ -244,16 +206,8 @@ int lsq_xb_table_arrays(const lsq_xb_table *t, const uint64_t **reads, const uin
 	if (total) *total = t->total.data();
 	return LSQ_OK;
 }
-int lsq_xb_table_report(const lsq_xb_table *t, uint64_t report[6]) {
-	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
-	memcpy(report, t->report, sizeof(t->report));
-	return LSQ_OK;
-}
-int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]) {
-	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
-	memcpy(ms, t->ms, sizeof(t->ms));
-	return LSQ_OK;
-}
+int lsq_xb_table_report(const lsq_xb_table *t, uint64_t report[6]) { return table_report(t, report); }
+int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]) { return table_times(t, ms); }
 
 int lsq_xb_format(const lsq_xb_table *t, char **out_text) LSQ_API_TRY {
 	if (!t || !out_text) return fail(LSQ_E_ARG, "null argument");
@@ -310,40 +264,25 @@ int lsq::run_exonbins(int argc, const char *const *argv, std::string &out) {
 		else pos.push_back(argv[i]);
 	}
 	if (bad || pos.size() < 6 || pos.size() > 7) { cli_log(0, USAGE); return 1; }
-	struct Owned {
-		lsq_annotation *a = nullptr; lsq_xb_index *ix = nullptr; lsq_xb_table *t = nullptr; lsq_ctx *c = nullptr; char *text = nullptr, *iv = nullptr, *mp = nullptr;
-		~Owned() { lsq_xb_table_free(t); if (c) lsq_ctx_destroy(c); lsq_xb_index_free(ix); lsq_annotation_free(a); lsq_free(text); lsq_free(iv); lsq_free(mp); }
-	} O;
-	auto failed = [&](int st) {
-		cli_log(0, lsq_last_error());
-		if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
-		return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
-	};
-	int st = lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &O.a);
-	if (!st) st = lsq_xb_index_build(O.a, &O.ix);
-	if (st) return failed(st);
+	CliFrame F(pos);                                       // text[0] the table, text[1] and text[2] the bins' two files
+	CliOwned<lsq_xb_index, lsq_xb_index_free> ix;
+	CliOwned<lsq_xb_table, lsq_xb_table_free> t;
+	int st = F.load_annotation();
+	if (!st) st = lsq_xb_index_build(F.a, &ix.p);
+	if (st) return cli_failed(st);
 	if (host) {
-		lsq_reads *r = nullptr;
-		st = cli_host_parse(&O.ix->E, pos[4], pos[5], &r);
-		if (!st) st = lsq_xb_host_reads(O.ix, r, 0, &O.t);
-		lsq_reads_free(r);
-	} else {
-		st = lsq_ctx_create(cli_device(), &O.c);
-		if (!st) st = cli_env_options(O.c);
-		if (!st) st = lsq_xb_device(O.c, O.ix, pos[4], pos[5], &O.t);
-	}
-	if (!st) st = lsq_xb_format(O.t, &O.text);
-	if (!st && prefix) st = lsq_xb_format_bins(O.ix, &O.iv, &O.mp);
-	if (st) return failed(st);
-	const uint64_t *rep = O.t->report;
+		if (!(st = F.host_parse(&ix.p->E))) st = lsq_xb_host_reads(ix.p, F.reads, 0, &t.p);
+		F.free_reads();
+	} else if (!(st = F.create_context())) st = lsq_xb_device(F.c, ix.p, pos[4], pos[5], &t.p);
+	if (!st) st = lsq_xb_format(t.p, &F.text[0]);
+	if (!st && prefix) st = lsq_xb_format_bins(ix.p, &F.text[1], &F.text[2]);
+	if (st) return cli_failed(st);
+	const uint64_t *rep = t.p->report;
 	char msg[384];
 	snprintf(msg, sizeof msg, "exonbins: %llu read(s), %llu block(s), %llu without a chromosome of the annotation or empty; %lld bin(s) of %lld gene(s): %llu read(s) on no gene, %llu on more than one, %llu bin hit(s)",
-	         (unsigned long long)rep[0], (unsigned long long)rep[1], (unsigned long long)rep[2], (long long)lsq_xb_index_num_bins(O.ix), (long long)lsq_xb_index_num_genes(O.ix),
+	         (unsigned long long)rep[0], (unsigned long long)rep[1], (unsigned long long)rep[2], (long long)lsq_xb_index_num_bins(ix.p), (long long)lsq_xb_index_num_genes(ix.p),
 	         (unsigned long long)rep[3], (unsigned long long)rep[4], (unsigned long long)rep[5]);
 	cli_log(2, msg);
-	if (prefix && (!write_file(std::string(prefix) + ".interval", O.iv) || !write_file(std::string(prefix) + ".map", O.mp))) return failed(LSQ_E_IO);
-	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) {
-		if (!write_file(pos[6], O.text)) return failed(LSQ_E_IO);
-	} else out = O.text;
-	return 0;
+	if (prefix && (!write_file((std::string(prefix) + ".interval").c_str(), F.text[1]) || !write_file((std::string(prefix) + ".map").c_str(), F.text[2]))) return cli_failed(LSQ_E_IO);
+	return F.deliver(F.text[0], out);
 }

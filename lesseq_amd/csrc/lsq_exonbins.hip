@@ -3,7 +3,7 @@
 // walk over them; a read counts once a bin and once a gene by predicates alone, no per-lane list; equal ids are combined inside the
 // wave, then added to the workgroup's own counters in LDS, or to the global ones where the id has no slot there), copy-back (the
 // counters).  Every number is an integer and sums commute: no result depends on the order in which lanes arrive.
-#include "lsq_device.hpp"
+#include "lsq_wave.hpp"
 #include "lsq_exonbins.hpp"
 
 namespace {
@@ -17,11 +17,6 @@ struct XbIndex {
 	unsigned n_chroms;
 };
 struct XbAcc { unsigned long long bad_blocks, no_gene, multi_gene, bin_hits; };
-
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-	for (unsigned d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-	return v;
-}
 
 // Whether block [s, e) overlaps any bin of a gene: its bins first .. last ascend and are disjoint, so the first that ends behind s decides
 __device__ inline bool xb_gene_overlaps(const XbIndex &I, unsigned first, unsigned last, int s, int e) {
@@ -83,7 +78,7 @@ __device__ inline void xb_wave_add(XbLocal<SLOTS> &local, unsigned long long *co
 //   counts has a bin that counts: an earlier block on the bin is an earlier block on the gene.
 // The report's tallies are kept per lane over the stride, summed over the workgroup once and added by one lane.  The LDS counters
 // (36 KiB: four workgroups a compute unit) are added to the global ones behind the same barrier.
-__global__ void __launch_bounds__(256) lsq_xb_count_kernel(JnReads R, XbIndex I, unsigned long long *reads, unsigned long long *total, XbAcc *acc) {
+__global__ void __launch_bounds__(256) lsq_xb_count_kernel(ParsedReads R, XbIndex I, unsigned long long *reads, unsigned long long *total, XbAcc *acc) {
 	__shared__ unsigned long long part[4][4];
 	__shared__ XbLocal<2048> local_bins;
 	__shared__ XbLocal<1024> local_genes;
@@ -130,7 +125,7 @@ __global__ void __launch_bounds__(256) lsq_xb_count_kernel(JnReads R, XbIndex I,
 					s = R.bs[k]; e = R.be[k];
 					const unsigned ch = R.bc[k];
 					++k;
-					if (ch == JN_NOCHROM || ch >= I.n_chroms || e <= s) { ++bad; continue; }
+					if (ch == NO_CHROM || ch >= I.n_chroms || e <= s) { ++bad; continue; }
 					unsigned lo = I.chrom_first_cell[ch];
 					cell_hi = I.chrom_first_cell[ch + 1u];
 					unsigned hi = cell_hi;
@@ -150,14 +145,10 @@ __global__ void __launch_bounds__(256) lsq_xb_count_kernel(JnReads R, XbIndex I,
 		if (have && genes == 0) ++none;
 		if (genes > 1) ++multi;
 	}
-	const unsigned wave = threadIdx.x >> 6;
-	bad = wave_sum(bad); none = wave_sum(none); multi = wave_sum(multi); hits = wave_sum(hits);
-	if (lane == 0) { part[wave][0] = bad; part[wave][1] = none; part[wave][2] = multi; part[wave][3] = hits; }
-	__syncthreads();
+	unsigned long long v[4] = {bad, none, multi, hits};
+	workgroup_tally<false>(v, part);                 // (its barrier is the one the LDS counters wait behind)
 	local_bins.flush(reads); local_genes.flush(total);
 	if (threadIdx.x == 0) {
-		unsigned long long v[4] = {0, 0, 0, 0};
-		for (unsigned w = 0; w < 4; ++w) for (unsigned q = 0; q < 4; ++q) v[q] += part[w][q];
 		if (v[0]) atomicAdd(&acc->bad_blocks, v[0]);
 		if (v[1]) atomicAdd(&acc->no_gene, v[1]);
 		if (v[2]) atomicAdd(&acc->multi_gene, v[2]);
@@ -165,15 +156,9 @@ __global__ void __launch_bounds__(256) lsq_xb_count_kernel(JnReads R, XbIndex I,
 	}
 }
 
-// workgroups of the count: eight a compute unit at most (LSQ_XB_GRID: another bound -- tests: the stride on a small file)
-inline unsigned count_grid(const lsq_ctx *c, unsigned long long n_reads) {
-	if (const char *e = getenv("LSQ_XB_GRID")) { const long long v = atoll(e); if (v >= 1 && v <= 1 << 20) return std::min(grid_for(n_reads, 256), (unsigned)v); }
-	return grid_for(c->n_cu, n_reads, 256, 8);
-}
-
 } // namespace
 
-int lsq::xb_device_reads(lsq_ctx *c, const lsq_xb_index &ix, const JnReads &R, lsq_xb_table &t) {
+int lsq::xb_device_reads(lsq_ctx *c, const lsq_xb_index &ix, const ParsedReads &R, lsq_xb_table &t) {
 	hipStream_t st = c->stream;
 	int rc;
 	PhaseClock<XB_PHASES> PC;
@@ -202,7 +187,7 @@ int lsq::xb_device_reads(lsq_ctx *c, const lsq_xb_index &ix, const JnReads &R, l
 	HIP_TRY(PC.mark(1, st));
 	if (R.n_reads) {
 		const XbIndex I{d_bs.p, d_be.p, d_bg.p, d_gf.p, d_cf.p, d_cs.p, d_ce.p, d_co.p, d_cb.p, (unsigned)nc};
-		hipLaunchKernelGGL(lsq_xb_count_kernel, dim3(count_grid(c, R.n_reads)), dim3(256), 0, st, R, I, d_reads.p, d_total.p, d_acc.p);
+		hipLaunchKernelGGL(lsq_xb_count_kernel, dim3(stride_grid(c, "LSQ_XB_GRID", R.n_reads)), dim3(256), 0, st, R, I, d_reads.p, d_total.p, d_acc.p);
 		HIP_TRY(hipGetLastError());
 	}
 

@@ -1,9 +1,10 @@
 // Reads per exon bin and per gene of a read file (include/lesseq_hip.h, lsq_xb_*): what lsq_exonbins.cpp (index, host
 // path, text, the exonbins executable), lsq_exonbins.hip (the device count) and lsq_readfile.hip (the entry that opens the read
 // file) share.
+// The parsed reads, the dictionaries and the executables' frame are lsq_readtool.hpp's.
 #pragma once
 
-#include "lsq_junc.hpp"
+#include "lsq_readtool.hpp"
 
 namespace lsq {
 constexpr int XB_PHASES = 3;                   // index upload, count, copy-back
@@ -13,7 +14,7 @@ constexpr uint32_t XB_NONE = 0xFFFFFFFFu;
 }
 
 struct lsq_xb_index {
-	// the dictionaries the parsers intern against, as lsq_jn_index's: the annotation's chromosomes, "+" (0) and "-" (1), one
+	// the dictionaries the parsers intern against (annotation_dictionaries): the annotation's chromosomes, "+" (0) and "-" (1), one
 	// whole-line interval a chromosome
 	lsq_events E;
 	// genes in the loader's order (count's); gene g's bins are gene_first_bin[g] .. gene_first_bin[g + 1], ascending and disjoint
@@ -44,9 +45,9 @@ namespace lsq {
 
 // lsq_exonbins.cpp: the table's names and sizes from the index, every count zero
 void xb_start_table(const lsq_xb_index &ix, lsq_xb_table &t);
-int xb_host_reads(const lsq_xb_index &ix, const JnReads &R, int n_threads, lsq_xb_table &t);
+int xb_host_reads(const lsq_xb_index &ix, const ParsedReads &R, int n_threads, lsq_xb_table &t);
 int run_exonbins(int argc, const char *const *argv, std::string &out);       // the exonbins executable
 // lsq_exonbins.hip: the count over device arrays
-int xb_device_reads(lsq_ctx *c, const lsq_xb_index &ix, const JnReads &R, lsq_xb_table &t);
+int xb_device_reads(lsq_ctx *c, const lsq_xb_index &ix, const ParsedReads &R, lsq_xb_table &t);
 
 } // namespace lsq

@@ -47,12 +47,6 @@ void put_int(std::string &o, long long v) {
 	o.append(b, (size_t)n);
 }
 
-char *dup_text(const std::string &s) {
-	char *p = (char *)malloc(s.size() + 1);
-	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
-	return p;
-}
-
 } // namespace
 
 // Runs of one name in file order -> transcripts ordered by gene id, then transcript id.  A stable sort keeps the runs of

@@ -1,11 +1,10 @@
 // Splice junctions of a read file (include/lesseq_hip.h, lsq_jn_*): the index made from an annotation, the host
 // path over the host parsers' arrays, the table's text and the junctions executable.  The device passes are lsq_junc.hip, the
-// entry that opens a read file on the device is lsq_readfile.hip's lsq_jn_device.
+// entry that opens a read file on the device is lsq_readfile.hip's lsq_jn_device; what the tool shares with coverage and
+// exonbins is lsq_readtool.hpp.
 #include <algorithm>
-#include <cerrno>
 #include <cstdlib>
 #include <cstring>
-#include <numeric>
 
 #include "lsq_junc.hpp"
 
@@ -28,58 +27,7 @@ void fold_rows(std::vector<Row> &v) {
 	v.resize(o);
 }
 
-char *dup_text(const std::string &s) {
-	char *p = (char *)malloc(s.size() + 1);
-	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
-	return p;
-}
-
 } // namespace
-
-// rows ascending in chromosome index -> where each row of the tables' order (chromosome names bytewise) comes from: the
-// chromosomes' groups reordered, every group as it is
-std::vector<size_t> lsq::rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom) {
-	const size_t n = chrom.size(), nc = names.size();
-	std::vector<size_t> first(nc + 1, 0);
-	for (size_t i = 0; i < n; ++i) ++first[chrom[i] + 1];
-	for (size_t c = 0; c < nc; ++c) first[c + 1] += first[c];
-	std::vector<uint32_t> order(nc);
-	std::iota(order.begin(), order.end(), 0u);
-	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
-	std::vector<size_t> from;
-	from.reserve(n);
-	for (uint32_t c : order) for (size_t i = first[c]; i < first[c + 1]; ++i) from.push_back(i);
-	return from;
-}
-
-// The dictionaries a read file is parsed against without events (lsq_jn_index, lsq_cov_index): "+" and "-" as strands 0 and 1, the
-// distinct chromosome strings of the annotation's isoform lines in file order, one whole-line interval a chromosome
-int lsq::annotation_dictionaries(const lsq_annotation &a, lsq_events &E) {
-	E.strands.intern("+"); E.strands.intern("-");
-	for (const auto &rp : a.recs) if (E.chroms.intern(rp->chrom) >= (int)JN_NOCHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
-	E.covered.resize(E.chroms.names.size());
-	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
-	return LSQ_OK;
-}
-
-// A read file through the host parser of its format, against dictionaries E; verify: a BAM file's CRC32s and end-of-file marker checked
-int lsq::host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r) {
-	if (strcmp(read_format, "SAM_SINGLE") == 0) return lsq_sam_parse(path, E, skip_flags, min_mapq, n_threads, r);
-	if (strcmp(read_format, "BAM_SINGLE") == 0) return verify ? lsq_bam_parse_checked(path, E, skip_flags, min_mapq, n_threads, r) : lsq_bam_parse(path, E, skip_flags, min_mapq, n_threads, r);
-	return lsq_reads_parse(read_format, path, E, n_threads, r);
-}
-
-// ... under LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (the executables' --host)
-int lsq::cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r) {
-	unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
-	const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
-	for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
-		char *end = nullptr;
-		opt[k] = strtoul(e, &end, 0);
-		if (end == e || *end) return fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e);
-	}
-	return host_parse_reads(E, read_format, path, (unsigned)opt[0], (unsigned)opt[1], opt[2] != 0, 0, r);
-}
 
 void lsq::jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t) {
 	t.chrom_names = ix.E.chroms.names;
@@ -90,42 +38,30 @@ void lsq::jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t) {
 	permute(t.chrom); permute(t.start); permute(t.end); permute(t.ann); permute(t.reads); permute(t.plus); permute(t.minus); permute(t.max_overhang);
 }
 
-int lsq::jn_host_reads(const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t) {
-	int T = host_threads(n_threads);
-	if (R.n_reads < (1u << 16)) T = 1;
+int lsq::jn_host_reads(const lsq_jn_index &ix, const ParsedReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t) {
+	const int T = read_slices(R.n_reads, n_threads);
 	std::vector<std::vector<Row>> part((size_t)T);
 	std::vector<uint64_t> dropped((size_t)T, 0), nochrom((size_t)T, 0), occ((size_t)T, 0);
-	{
-		ThreadGroup th;
-		for (int k = 0; k < T; ++k) th.spawn([&, k] {
-			std::vector<Row> &v = part[(size_t)k];
-			const uint64_t r0 = R.n_reads * (uint64_t)k / (uint64_t)T, r1 = R.n_reads * (uint64_t)(k + 1) / (uint64_t)T;
-			for (uint64_t r = r0; r < r1; ++r)
-				for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
-					const unsigned c0 = R.bc[b], c1 = R.bc[b + 1];
-					if (c0 == JN_NOCHROM || c1 == JN_NOCHROM) { ++nochrom[(size_t)k]; continue; }
-					if (c0 != c1 || R.bs[b + 1] <= R.be[b]) continue;
-					const int64_t ov = std::min((int64_t)R.be[b] - R.bs[b], (int64_t)R.be[b + 1] - R.bs[b + 1]);
-					if (ov < (int64_t)min_overhang) { ++dropped[(size_t)k]; continue; }
-					v.push_back(Row{c0, jn_key(R.be[b], R.bs[b + 1]), 1u, R.bst[b] == 0 ? 1u : 0u, R.bst[b] == 1 ? 1u : 0u, (uint32_t)ov});
-				}
-			occ[(size_t)k] = v.size();
-			std::sort(v.begin(), v.end(), row_less);
-			fold_rows(v);
-		});
-		th.join();
-		if (th.failed()) return fail(LSQ_E_INTERNAL, "%s", th.error().c_str());
-	}
+	const int rc = for_read_slices(R.n_reads, T, [&](int k, uint64_t r0, uint64_t r1) {
+		std::vector<Row> &v = part[(size_t)k];
+		for (uint64_t r = r0; r < r1; ++r)
+			for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
+				const unsigned c0 = R.bc[b], c1 = R.bc[b + 1];
+				if (c0 == NO_CHROM || c1 == NO_CHROM) { ++nochrom[(size_t)k]; continue; }
+				if (c0 != c1 || R.bs[b + 1] <= R.be[b]) continue;
+				const int64_t ov = std::min((int64_t)R.be[b] - R.bs[b], (int64_t)R.be[b + 1] - R.bs[b + 1]);
+				if (ov < (int64_t)min_overhang) { ++dropped[(size_t)k]; continue; }
+				v.push_back(Row{c0, jn_key(R.be[b], R.bs[b + 1]), 1u, R.bst[b] == 0 ? 1u : 0u, R.bst[b] == 1 ? 1u : 0u, (uint32_t)ov});
+			}
+		occ[(size_t)k] = v.size();
+		std::sort(v.begin(), v.end(), row_less);
+		fold_rows(v);
+	});
+	if (rc) return rc;
 	uint64_t n_occ = 0;
 	for (uint64_t o : occ) n_occ += o;
 	if (n_occ > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32-1 junction occurrences");
-	std::vector<Row> all = std::move(part[0]);
-	for (int k = 1; k < T; ++k) {
-		std::vector<Row> m(all.size() + part[(size_t)k].size());
-		std::merge(all.begin(), all.end(), part[(size_t)k].begin(), part[(size_t)k].end(), m.begin(), row_less);
-		fold_rows(m);
-		all.swap(m);
-	}
+	const std::vector<Row> all = merge_folded(part, row_less, fold_rows);
 	t.resize(all.size());
 	for (size_t i = 0; i < all.size(); ++i) {
 		const Row &r = all[i];
@@ -161,9 +97,7 @@ int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY 
 		const int cid = E.chroms.find(r.chrom);
 		// the union of the line's exons: its maximal intervals, and the gaps between them
 		ex.clear();
-		const size_t ne = std::min<size_t>({(size_t)r.exonCount, r.exonStarts.size(), r.exonEnds.size()});
-		for (size_t i = 0; i < ne; ++i) if (r.exonEnds[i] > r.exonStarts[i]) ex.emplace_back(r.exonStarts[i], r.exonEnds[i]);
-		std::sort(ex.begin(), ex.end());
+		exon_union(r, ex);
 		const uint8_t ann = r.strand == "+" ? '+' : r.strand == "-" ? '-' : '*';
 		int64_t reach = 0;
 		for (size_t i = 0; i < ex.size(); ++i) {
@@ -182,34 +116,22 @@ int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY 
 } LSQ_API_CATCH
 
 void lsq_jn_index_free(lsq_jn_index *ix) { delete ix; }
-int64_t lsq_jn_index_num_chroms(const lsq_jn_index *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
-const char *lsq_jn_index_chrom_name(const lsq_jn_index *ix, int64_t chrom) {
-	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
-}
-lsq_events *lsq_jn_index_dictionaries(lsq_jn_index *ix) { return ix ? &ix->E : nullptr; }
+int64_t lsq_jn_index_num_chroms(const lsq_jn_index *ix) { return index_num_chroms(ix); }
+const char *lsq_jn_index_chrom_name(const lsq_jn_index *ix, int64_t chrom) { return index_chrom_name(ix, chrom); }
+lsq_events *lsq_jn_index_dictionaries(lsq_jn_index *ix) { return index_dictionaries(ix); }
 int64_t lsq_jn_index_num_introns(const lsq_jn_index *ix) { return ix ? (int64_t)ix->in_key.size() : 0; }
 
 int lsq_jn_host_reads(lsq_jn_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_jn_table **out) LSQ_API_TRY {
 	if (!ix || !r || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
-	std::unique_ptr<lsq_jn_table> t(new lsq_jn_table);
-	const JnReads R{r->n_reads, r->n_blocks, (const unsigned long long *)r->blk_off, r->blk_start, r->blk_end, r->blk_chrom, r->blk_strand};
-	const int rc = jn_host_reads(*ix, R, min_overhang, n_threads, *t);
-	if (rc) return rc;
-	*out = t.release();
-	return LSQ_OK;
+	return new_table(out, [&](lsq_jn_table &t) { return jn_host_reads(*ix, host_view(*r), min_overhang, n_threads, t); });
 } LSQ_API_CATCH
 
 int lsq_jn_host(lsq_jn_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, int n_threads,
                 lsq_jn_table **out) LSQ_API_TRY {
 	if (!ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
-	lsq_reads *r = nullptr;
-	int rc = host_parse_reads(&ix->E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
-	if (rc) return rc;
-	rc = lsq_jn_host_reads(ix, r, min_overhang, n_threads, out);
-	lsq_reads_free(r);
-	return rc;
+	return host_file(ix->E, read_format, path, skip_flags, min_mapq, n_threads, [&](const lsq_reads *r) { return lsq_jn_host_reads(ix, r, min_overhang, n_threads, out); });
 } LSQ_API_CATCH
 
 void lsq_jn_table_free(lsq_jn_table *t) { delete t; }
@@ -227,16 +149,8 @@ int lsq_jn_table_arrays(const lsq_jn_table *t, const uint32_t **chrom, const int
 	if (max_overhang) *max_overhang = t->max_overhang.data();
 	return LSQ_OK;
 }
-int lsq_jn_table_report(const lsq_jn_table *t, uint64_t report[5]) {
-	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
-	memcpy(report, t->report, sizeof(t->report));
-	return LSQ_OK;
-}
-int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]) {
-	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
-	memcpy(ms, t->ms, sizeof(t->ms));
-	return LSQ_OK;
-}
+int lsq_jn_table_report(const lsq_jn_table *t, uint64_t report[5]) { return table_report(t, report); }
+int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]) { return table_times(t, ms); }
 
 int lsq_jn_format(const lsq_jn_table *t, uint32_t min_reads, int novel_only, char **out_text) LSQ_API_TRY {
 	if (!t || !out_text) return fail(LSQ_E_ARG, "null argument");
@@ -263,56 +177,31 @@ int lsq::run_junctions(int argc, const char *const *argv, std::string &out) {
 	bool host = false, novel = false, bad = false;
 	unsigned long min_ov = 1, min_reads = 0;
 	std::vector<const char *> pos;
-	auto number = [&](int &i, unsigned long &v) {
-		char *end = nullptr;
-		if (i + 1 >= argc) { bad = true; return; }
-		errno = 0;
-		v = strtoul(argv[++i], &end, 10);
-		if (end == argv[i] || *end || errno || v > 0xFFFFFFFFul || argv[i][0] == '-') bad = true;
-	};
 	for (int i = 1; i < argc && !bad; ++i) {
 		if (strcmp(argv[i], "--host") == 0) host = true;
 		else if (strcmp(argv[i], "--novel") == 0) novel = true;
-		else if (strcmp(argv[i], "--min-overhang") == 0) number(i, min_ov);
-		else if (strcmp(argv[i], "--min-reads") == 0) number(i, min_reads);
+		else if (strcmp(argv[i], "--min-overhang") == 0) bad = !cli_u32_option(argc, argv, i, min_ov);
+		else if (strcmp(argv[i], "--min-reads") == 0) bad = !cli_u32_option(argc, argv, i, min_reads);
 		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
 		else pos.push_back(argv[i]);
 	}
 	if (bad || pos.size() < 6 || pos.size() > 7 || min_ov < 1) { cli_log(0, USAGE); return 1; }
-	struct Owned {
-		lsq_annotation *a = nullptr; lsq_jn_index *ix = nullptr; lsq_jn_table *t = nullptr; lsq_ctx *c = nullptr; char *text = nullptr;
-		~Owned() { lsq_jn_table_free(t); if (c) lsq_ctx_destroy(c); lsq_jn_index_free(ix); lsq_annotation_free(a); lsq_free(text); }
-	} O;
-	auto failed = [&](int st) {
-		cli_log(0, lsq_last_error());
-		if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
-		return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
-	};
-	int st = lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &O.a);
-	if (!st) st = lsq_jn_index_build(O.a, &O.ix);
-	if (st) return failed(st);
+	CliFrame F(pos);
+	CliOwned<lsq_jn_index, lsq_jn_index_free> ix;
+	CliOwned<lsq_jn_table, lsq_jn_table_free> t;
+	int st = F.load_annotation();
+	if (!st) st = lsq_jn_index_build(F.a, &ix.p);
+	if (st) return cli_failed(st);
 	if (host) {
-		lsq_reads *r = nullptr;
-		st = cli_host_parse(&O.ix->E, pos[4], pos[5], &r);
-		if (!st) st = lsq_jn_host_reads(O.ix, r, (uint32_t)min_ov, 0, &O.t);
-		lsq_reads_free(r);
-	} else {
-		st = lsq_ctx_create(cli_device(), &O.c);
-		if (!st) st = cli_env_options(O.c);
-		if (!st) st = lsq_jn_device(O.c, O.ix, pos[4], pos[5], (uint32_t)min_ov, &O.t);
-	}
-	if (!st) st = lsq_jn_format(O.t, (uint32_t)min_reads, novel ? 1 : 0, &O.text);
-	if (st) return failed(st);
+		if (!(st = F.host_parse(&ix.p->E))) st = lsq_jn_host_reads(ix.p, F.reads, (uint32_t)min_ov, 0, &t.p);
+		F.free_reads();
+	} else if (!(st = F.create_context())) st = lsq_jn_device(F.c, ix.p, pos[4], pos[5], (uint32_t)min_ov, &t.p);
+	if (!st) st = lsq_jn_format(t.p, (uint32_t)min_reads, novel ? 1 : 0, &F.text[0]);
+	if (st) return cli_failed(st);
 	char msg[256];
 	snprintf(msg, sizeof msg, "junctions: %llu read(s), %llu block(s), %llu occurrence(s) of %lld junction(s); %llu block pair(s) below the overhang, %llu with a block on no chromosome of the annotation",
-	         (unsigned long long)O.t->report[0], (unsigned long long)O.t->report[1], (unsigned long long)O.t->report[2], (long long)lsq_jn_table_rows(O.t),
-	         (unsigned long long)O.t->report[3], (unsigned long long)O.t->report[4]);
+	         (unsigned long long)t.p->report[0], (unsigned long long)t.p->report[1], (unsigned long long)t.p->report[2], (long long)lsq_jn_table_rows(t.p),
+	         (unsigned long long)t.p->report[3], (unsigned long long)t.p->report[4]);
 	cli_log(1, msg);
-	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) {
-		FILE *fp = fopen(pos[6], "wb");
-		const size_t n = strlen(O.text);
-		const bool ok = fp && fwrite(O.text, 1, n, fp) == n;
-		if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", pos[6]); return failed(LSQ_E_IO); }
-	} else out = O.text;
-	return 0;
+	return F.deliver(F.text[0], out);
 }

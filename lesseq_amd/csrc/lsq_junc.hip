@@ -3,7 +3,7 @@
 // sort by chromosome, start, end), reduce (run heads, then sums and maxima per run), annotate (a lane a distinct junction: binary
 // search in the index's introns), copy-back (the distinct rows alone).  Every number is an integer and no result depends on the
 // order in which lanes arrive: sums and maxima only.
-#include "lsq_device.hpp"
+#include "lsq_wave.hpp"
 #include "lsq_scan.hpp"
 #include "lsq_sort.hpp"
 #include "lsq_junc.hpp"
@@ -13,21 +13,12 @@ namespace {
 // A record: w0 = jn_key(start, end); w1 = chromosome index << 32 | payload (overhang, JN_PLUS, JN_MINUS)
 struct JnAcc { unsigned long long dropped, nochrom, any0, any1, all0, all1; };
 
-__device__ inline unsigned long long wave_sum(unsigned long long v) {
-	for (unsigned d = 32; d; d >>= 1) v += __shfl_xor(v, d);
-	return v;
-}
-__device__ inline unsigned long long wave_or(unsigned long long v) {
-	for (unsigned d = 32; d; d >>= 1) v |= __shfl_xor(v, d);
-	return v;
-}
-
 // A lane a read, a fixed number of workgroups striding over the reads.  EMIT false: the read's occurrences counted (cnt), the
 // pairs that make none for the report.  EMIT true: the records written at the read's place (off), the OR and the AND of all of
 // them kept for the sort's choice of digits.  The tallies are kept per lane over the stride, summed over the workgroup once, and
 // added to `acc` by one lane: a few thousand atomics a launch (one a wave of reads was 6e6 on four addresses, and most of the pass).
 template <bool EMIT>
-__global__ void __launch_bounds__(256) lsq_jn_extract_kernel(JnReads R, unsigned min_overhang, unsigned *cnt, const unsigned long long *off,
+__global__ void __launch_bounds__(256) lsq_jn_extract_kernel(ParsedReads R, unsigned min_overhang, unsigned *cnt, const unsigned long long *off,
                                                              unsigned long long *w0, unsigned long long *w1, JnAcc *acc) {
 	__shared__ unsigned long long part[4][4];
 	unsigned long long dropped = 0, nochrom = 0, any0 = 0, any1 = 0, all0 = ~0ull, all1 = ~0ull;
@@ -41,7 +32,7 @@ __global__ void __launch_bounds__(256) lsq_jn_extract_kernel(JnReads R, unsigned
 			for (unsigned long long k = b0 + 1; k < b1; ++k) {
 				const int s1 = R.bs[k], e1 = R.be[k];
 				const unsigned c1 = R.bc[k], st1 = R.bst[k];
-				if (c0 == JN_NOCHROM || c1 == JN_NOCHROM) ++nochrom;
+				if (c0 == NO_CHROM || c1 == NO_CHROM) ++nochrom;
 				else if (c0 == c1 && s1 > e0) {
 					const long long ov = min((long long)e0 - s0, (long long)e1 - s1);
 					if (ov < (long long)min_overhang) ++dropped;
@@ -60,14 +51,9 @@ __global__ void __launch_bounds__(256) lsq_jn_extract_kernel(JnReads R, unsigned
 		}
 		if (!EMIT) cnt[r] = m;
 	}
-	const unsigned wave = threadIdx.x >> 6;
-	if (EMIT) { any0 = wave_or(any0); any1 = wave_or(any1); all0 = wave_or(~all0); all1 = wave_or(~all1); }      // (the ANDs as the OR of the complements)
-	else { any0 = wave_sum(dropped); any1 = wave_sum(nochrom); all0 = all1 = 0; }
-	if ((threadIdx.x & 63u) == 0) { part[wave][0] = any0; part[wave][1] = any1; part[wave][2] = all0; part[wave][3] = all1; }
-	__syncthreads();
+	unsigned long long v[4] = {EMIT ? any0 : dropped, EMIT ? any1 : nochrom, EMIT ? ~all0 : 0ull, EMIT ? ~all1 : 0ull};      // (the ANDs as the OR of the complements)
+	workgroup_tally<EMIT>(v, part);
 	if (threadIdx.x == 0) {
-		unsigned long long v[4] = {0, 0, 0, 0};
-		for (unsigned w = 0; w < 4; ++w) for (unsigned q = 0; q < 4; ++q) v[q] = EMIT ? (v[q] | part[w][q]) : (v[q] + part[w][q]);
 		if (EMIT) {
 			if (v[0]) atomicOr(&acc->any0, v[0]);
 			if (v[1]) atomicOr(&acc->any1, v[1]);
@@ -139,15 +125,9 @@ __global__ void __launch_bounds__(256) lsq_jn_annotate_kernel(const unsigned lon
 	O.reads[r] = (unsigned)(i1 - i0);
 }
 
-// workgroups of the extract: eight a compute unit at most (LSQ_JN_EXTRACT_GRID: another bound -- tests: the stride on a small file)
-inline unsigned extract_grid(const lsq_ctx *c, unsigned long long n_reads) {
-	if (const char *e = getenv("LSQ_JN_EXTRACT_GRID")) { const long long v = atoll(e); if (v >= 1 && v <= 1 << 20) return std::min(grid_for(n_reads, 256), (unsigned)v); }
-	return grid_for(c->n_cu, n_reads, 256, 8);
-}
-
 } // namespace
 
-int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, lsq_jn_table &t) {
+int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const ParsedReads &R, uint32_t min_overhang, lsq_jn_table &t) {
 	hipStream_t st = c->stream;
 	int rc;
 	PhaseClock<JN_PHASES> PC;
@@ -167,8 +147,9 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 	const JnAcc acc0{0, 0, 0, 0, ~0ull, ~0ull};
 	JnAcc acc = acc0;
 	unsigned long long n_occ = 0;
+	const unsigned grid = stride_grid(c, "LSQ_JN_EXTRACT_GRID", R.n_reads);
 	if ((rc = d_cnt.alloc((size_t)R.n_reads)) || (rc = d_off.alloc((size_t)R.n_reads + 1)) || (rc = d_acc.upload(&acc0, 1, st)) || (rc = SS.reserve(R.n_reads))) return rc;
-	hipLaunchKernelGGL((lsq_jn_extract_kernel<false>), dim3(extract_grid(c, R.n_reads)), dim3(256), 0, st, R, min_overhang, d_cnt.p, (const unsigned long long *)nullptr,
+	hipLaunchKernelGGL((lsq_jn_extract_kernel<false>), dim3(grid), dim3(256), 0, st, R, min_overhang, d_cnt.p, (const unsigned long long *)nullptr,
 	                   (unsigned long long *)nullptr, (unsigned long long *)nullptr, d_acc.p);
 	HIP_TRY(hipGetLastError());
 	if ((rc = device_scan<1, false>(SS, d_cnt.p, R.n_reads, d_off.p, st))) return rc;
@@ -178,7 +159,7 @@ int lsq::jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, u
 	SortBuf B;                                  // (allocations follow the counted occurrences)
 	if ((rc = B.reserve(n_occ))) return rc;
 	if (n_occ) {
-		hipLaunchKernelGGL((lsq_jn_extract_kernel<true>), dim3(extract_grid(c, R.n_reads)), dim3(256), 0, st, R, min_overhang, (unsigned *)nullptr, (const unsigned long long *)d_off.p,
+		hipLaunchKernelGGL((lsq_jn_extract_kernel<true>), dim3(grid), dim3(256), 0, st, R, min_overhang, (unsigned *)nullptr, (const unsigned long long *)d_off.p,
 		                   B.w0[0].p, B.w1[0].p, d_acc.p);
 		HIP_TRY(hipGetLastError());
 	}

@@ -1,8 +1,9 @@
 // Splice junctions of a read file (include/lesseq_hip.h, lsq_jn_*): what lsq_junc.cpp (index, host path, text, the
 // junctions executable), lsq_junc.hip (the device passes) and lsq_readfile.hip (the entry that opens the read file) share.
+// The parsed reads, the dictionaries and the executables' frame are lsq_readtool.hpp's.
 #pragma once
 
-#include "lsq_internal.hpp"
+#include "lsq_readtool.hpp"
 
 // The key of a junction: the chromosome's index, and start and end biased by 2^30 (coordinates lie in (-2^30, 2^30)) in one word
 namespace lsq {
@@ -23,7 +24,7 @@ constexpr int JN_PHASES = 5;                   // extract, sort, reduce, annotat
 }
 
 struct lsq_jn_index {
-	// the dictionaries the parsers intern against: `chroms` the annotation's chromosomes, `strands` seeded with "+" (0) and "-" (1),
+	// the dictionaries the parsers intern against (annotation_dictionaries): `chroms` the annotation's chromosomes, `strands` seeded with "+" (0) and "-" (1),
 	// `covered` one whole-line interval a chromosome (the name-keyed formats of lsq_reads_parse keep every line of a known chromosome)
 	lsq_events E;
 	// the distinct introns, ascending in (chromosome index, key)
@@ -45,28 +46,13 @@ struct lsq_jn_table {
 
 namespace lsq {
 
-// parsed reads in file order (lsq_reads' arrays), on the host or on the device
-struct JnReads {
-	uint64_t n_reads, n_blocks;
-	const unsigned long long *blk_off;
-	const int32_t *bs, *be;
-	const uint16_t *bc;
-	const uint8_t *bst;
-};
-constexpr unsigned JN_NOCHROM = 0xFFFFu;
 constexpr unsigned JN_OV_MASK = 0x3FFFFFFFu, JN_PLUS = 1u << 30, JN_MINUS = 1u << 31;      // an occurrence's payload: overhang (< 2^30), strand flags
 
 // lsq_junc.cpp: rows in (chromosome index, start, end) order -> the table's order (chromosome names bytewise), names attached
 void jn_finish_table(const lsq_jn_index &ix, lsq_jn_table &t);
-int jn_host_reads(const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t);
-std::vector<size_t> rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom);
-// what lsq_cov.cpp shares: the dictionaries of an index, a read file through its host parser, the same under the executables' environment
-int annotation_dictionaries(const lsq_annotation &a, lsq_events &E);
-int host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r);
-int cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r);
+int jn_host_reads(const lsq_jn_index &ix, const ParsedReads &R, uint32_t min_overhang, int n_threads, lsq_jn_table &t);
 int run_junctions(int argc, const char *const *argv, std::string &out);      // the junctions executable
-int cli_env_options(lsq_ctx *c);                                             // lsq_cli.cpp: LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ, LSQ_BAM_VERIFY, LSQ_OPTIONS
 // lsq_junc.hip: the device passes over device arrays; the table's rows come back in (chromosome index, start, end) order
-int jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const JnReads &R, uint32_t min_overhang, lsq_jn_table &t);
+int jn_device_reads(lsq_ctx *c, const lsq_jn_index &ix, const ParsedReads &R, uint32_t min_overhang, lsq_jn_table &t);
 
 } // namespace lsq

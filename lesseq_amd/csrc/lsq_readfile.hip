@@ -1,8 +1,9 @@
 // The read files of the loader: the formats the device parses from a file's own bytes (READ_FORMATS), a file of one of them opened
 // (ReadSource), and the entry points that take one -- through the chain (lsq_ingest.hip) for count and solve, into the arrays of
 // lsq_mrf_parse for tests and tools, or over its records alone (lsq_bam_check).  The parsers themselves are lsq_mrf_device.hpp,
-// lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only, this unit and the
-// junction passes (lsq_junc.hip) through lsq_junc.hpp.
+// lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only.  The tools that take a
+// read file against an index's dictionaries (junctions, coverage, exonbins) enter through table_of_file: their passes
+// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -77,6 +78,7 @@ struct DevParsed {
 	DevBuf<int> bs, be;
 	DevBuf<unsigned short> bc;
 	DevBuf<unsigned char> bst;
+	ParsedReads view() const { return ParsedReads{n_reads, n_blocks, blk_off.p, bs.p, be.p, bc.p, bst.p}; }
 };
 
 // ---- the read formats: the one place that names them.  Per format: whether a whole file's first line is a header (MRF; every
@@ -320,8 +322,8 @@ int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &T, unsi
 	return LSQ_OK;
 }
 
-// A read file parsed as lsq_mrf_parse_device parses it, against dictionaries that are not the context's events' (lsq_jn_device,
-// lsq_cov_device: an index's chromosomes and strand table): for the length of the call E stands where the context's events do,
+// A read file parsed as lsq_mrf_parse_device parses it, against dictionaries that are not the context's events' (table_of_file:
+// an index's chromosomes and strand table): for the length of the call E stands where the context's events do,
 // so every parser finds its chromosomes, its strand table and its library type (unstranded) where it always looks.  The text is
 // freed once it has been read (its room is the caller's sort's); the context's events, reads and counters are not touched.
 int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const char *path, DevParsed &P) {
@@ -333,6 +335,15 @@ int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const
 	struct Stand { lsq_ctx *c; lsq_events *own; ~Stand() { c->E = own; } } stand{c, c->E};
 	c->E = &E;
 	return parse_staged_text(c, fmt, T, P);
+}
+
+// lsq_jn_device, lsq_cov_device, lsq_xb_device behind their argument checks: the file parsed against the index's dictionaries, a
+// new table filled from the device arrays by the tool's passes (fill(reads, table)) and handed out
+template <class IX, class T, class F>
+int table_of_file(lsq_ctx *c, IX *ix, const char *read_format, const char *path, T **out, F fill) {
+	DevParsed P;
+	const int rc = parse_file_against(c, ix->E, read_format, path, P);
+	return rc ? rc : new_table(out, [&](T &t) { return fill(P.view(), t); });
 }
 
 } // namespace
@@ -470,49 +481,33 @@ int lsq_bam_check(lsq_ctx *c, const char *path, lsq_bam_report *r) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
-// The splice junctions of a read file (include/lesseq_hip.h): the file parsed against the index's dictionaries
-// (parse_file_against) and the device arrays handed to lsq_junc.hip.
+// The splice junctions of a read file (include/lesseq_hip.h): the device arrays handed to lsq_junc.hip
 int lsq_jn_device(lsq_ctx *c, lsq_jn_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_jn_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
-	DevParsed P;
-	int rc;
-	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
-	std::unique_ptr<lsq_jn_table> t(new lsq_jn_table);
-	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
-	if ((rc = jn_device_reads(c, *ix, R, min_overhang, *t))) return rc;
-	jn_finish_table(*ix, *t);
-	*out = t.release();
-	return LSQ_OK;
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_jn_table &t) {
+		const int rc = jn_device_reads(c, *ix, R, min_overhang, t);
+		if (!rc) jn_finish_table(*ix, t);
+		return rc;
+	});
 } LSQ_API_CATCH
 
-// The per-base depth of a read file (include/lesseq_hip.h): the same parse, the device arrays handed to lsq_cov.hip
+// The per-base depth of a read file (include/lesseq_hip.h): the device arrays handed to lsq_cov.hip
 int lsq_cov_device(lsq_ctx *c, lsq_cov_index *ix, const char *read_format, const char *path, int strand, uint32_t min_depth, lsq_cov_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (!cov_strand_ok(strand)) return fail(LSQ_E_ARG, "strand must be 0, '+' or '-'");
-	DevParsed P;
-	int rc;
-	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
-	std::unique_ptr<lsq_cov_table> t(new lsq_cov_table);
-	t->min_depth = min_depth;
-	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
-	if ((rc = cov_device_reads(c, *ix, R, strand, min_depth, *t))) return rc;
-	cov_finish_table(*ix, *t);
-	*out = t.release();
-	return LSQ_OK;
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_cov_table &t) {
+		t.min_depth = min_depth;
+		const int rc = cov_device_reads(c, *ix, R, strand, min_depth, t);
+		if (!rc) cov_finish_table(*ix, t);
+		return rc;
+	});
 } LSQ_API_CATCH
 
-// The reads per exon bin and per gene of a read file (include/lesseq_hip.h): the same parse, the device arrays handed to lsq_exonbins.hip
+// The reads per exon bin and per gene of a read file (include/lesseq_hip.h): the device arrays handed to lsq_exonbins.hip
 int lsq_xb_device(lsq_ctx *c, lsq_xb_index *ix, const char *read_format, const char *path, lsq_xb_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
-	DevParsed P;
-	int rc;
-	if ((rc = parse_file_against(c, ix->E, read_format, path, P))) return rc;
-	std::unique_ptr<lsq_xb_table> t(new lsq_xb_table);
-	const JnReads R{P.n_reads, P.n_blocks, P.blk_off.p, P.bs.p, P.be.p, P.bc.p, P.bst.p};
-	if ((rc = xb_device_reads(c, *ix, R, *t))) return rc;
-	*out = t.release();
-	return LSQ_OK;
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_xb_table &t) { return xb_device_reads(c, *ix, R, t); });
 } LSQ_API_CATCH
 
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {

@@ -1,0 +1,104 @@
+// What the tools that take an annotation and a read file share on the host (lsq_readtool.hpp): the dictionaries of an index, a
+// read file through its host parser, a line's exon union, the tables' row order, and the frame of the junctions, coverage and
+// exonbins executables -- arguments, owned handles, the log on failure, the output file.
+#include <cerrno>
+#include <cstdlib>
+#include <numeric>
+
+#include "lsq_readtool.hpp"
+
+using namespace lsq;
+
+char *lsq::dup_text(const std::string &s) {
+	char *p = (char *)malloc(s.size() + 1);
+	if (p) { memcpy(p, s.data(), s.size()); p[s.size()] = 0; }
+	return p;
+}
+
+bool lsq::write_file(const char *path, const char *text) {
+	FILE *fp = fopen(path, "wb");
+	const size_t n = strlen(text);
+	const bool ok = fp && fwrite(text, 1, n, fp) == n;
+	if ((fp && fclose(fp) != 0) || !ok) { fail(LSQ_E_IO, "cannot write %s", path); return false; }
+	return true;
+}
+
+// the chromosomes' groups reordered, every group as it is
+std::vector<size_t> lsq::rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom) {
+	const size_t n = chrom.size(), nc = names.size();
+	std::vector<size_t> first(nc + 1, 0);
+	for (size_t i = 0; i < n; ++i) ++first[chrom[i] + 1];
+	for (size_t c = 0; c < nc; ++c) first[c + 1] += first[c];
+	std::vector<uint32_t> order(nc);
+	std::iota(order.begin(), order.end(), 0u);
+	std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return names[a] < names[b]; });
+	std::vector<size_t> from;
+	from.reserve(n);
+	for (uint32_t c : order) for (size_t i = first[c]; i < first[c + 1]; ++i) from.push_back(i);
+	return from;
+}
+
+int lsq::annotation_dictionaries(const lsq_annotation &a, lsq_events &E) {
+	E.strands.intern("+"); E.strands.intern("-");
+	for (const auto &rp : a.recs) if (E.chroms.intern(rp->chrom) >= (int)NO_CHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
+	E.covered.resize(E.chroms.names.size());
+	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
+	return LSQ_OK;
+}
+
+int lsq::host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r) {
+	if (strcmp(read_format, "SAM_SINGLE") == 0) return lsq_sam_parse(path, E, skip_flags, min_mapq, n_threads, r);
+	if (strcmp(read_format, "BAM_SINGLE") == 0) return verify ? lsq_bam_parse_checked(path, E, skip_flags, min_mapq, n_threads, r) : lsq_bam_parse(path, E, skip_flags, min_mapq, n_threads, r);
+	return lsq_reads_parse(read_format, path, E, n_threads, r);
+}
+
+int lsq::cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r) {
+	unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
+	const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
+	for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
+		char *end = nullptr;
+		opt[k] = strtoul(e, &end, 0);
+		if (end == e || *end) return fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e);
+	}
+	return host_parse_reads(E, read_format, path, (unsigned)opt[0], (unsigned)opt[1], opt[2] != 0, 0, r);
+}
+
+void lsq::exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &sorted_exons) {
+	const size_t ne = std::min<size_t>({(size_t)r.exonCount, r.exonStarts.size(), r.exonEnds.size()}), held = sorted_exons.size();
+	for (size_t i = 0; i < ne; ++i) if (r.exonEnds[i] > r.exonStarts[i]) sorted_exons.emplace_back(r.exonStarts[i], r.exonEnds[i]);
+	std::sort(sorted_exons.begin() + held, sorted_exons.end());
+	std::inplace_merge(sorted_exons.begin(), sorted_exons.begin() + held, sorted_exons.end());
+}
+
+bool lsq::cli_u32_option(int argc, const char *const *argv, int &i, unsigned long &v) {
+	char *end = nullptr;
+	if (i + 1 >= argc) return false;
+	errno = 0;
+	v = strtoul(argv[++i], &end, 10);
+	return !(end == argv[i] || *end || errno || v > 0xFFFFFFFFul || argv[i][0] == '-');
+}
+
+int lsq::cli_failed(int st) {
+	cli_log(0, lsq_last_error());
+	if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
+	return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
+}
+
+CliFrame::~CliFrame() {
+	free_reads();
+	if (c) lsq_ctx_destroy(c);
+	lsq_annotation_free(a);
+	for (char *t : text) lsq_free(t);
+}
+int CliFrame::load_annotation() { return lsq_annotation_load(pos[0], pos[1], pos[2], pos[3], 0, (uint64_t)1 << 62, &a); }
+int CliFrame::host_parse(lsq_events *E) { return cli_host_parse(E, pos[4], pos[5], &reads); }
+void CliFrame::free_reads() { lsq_reads_free(reads); reads = nullptr; }
+int CliFrame::create_context() {
+	const int st = lsq_ctx_create(cli_device(), &c);
+	return st ? st : cli_env_options(c);
+}
+int CliFrame::deliver(const char *t, std::string &out) const {
+	if (pos.size() == 7 && strcmp(pos[6], "-") != 0) return write_file(pos[6], t) ? 0 : cli_failed(LSQ_E_IO);
+	out = t;
+	return 0;
+}

@@ -1,0 +1,129 @@
+// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins):
+// the view of parsed reads their passes take, the dictionaries a read file is parsed against without events, a line's exon
+// union, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
+// the frame of the three executables.  lsq_readtool.cpp defines what is no template.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+#include <utility>
+
+#include "lsq_internal.hpp"
+
+namespace lsq {
+
+// parsed reads in file order (lsq_reads' arrays), on the host or on the device
+struct ParsedReads {
+	uint64_t n_reads, n_blocks;
+	const unsigned long long *blk_off;
+	const int32_t *bs, *be;
+	const uint16_t *bc;
+	const uint8_t *bst;
+};
+constexpr unsigned NO_CHROM = 0xFFFFu;         // bc of a block on no chromosome of the dictionaries
+inline ParsedReads host_view(const lsq_reads &r) {
+	return ParsedReads{r.n_reads, r.n_blocks, (const unsigned long long *)r.blk_off, r.blk_start, r.blk_end, r.blk_chrom, r.blk_strand};
+}
+
+// The dictionaries a read file is parsed against without events (an index's `lsq_events E`): "+" and "-" as strands 0 and 1, the
+// distinct chromosome strings of the annotation's isoform lines in file order, one whole-line interval a chromosome
+int annotation_dictionaries(const lsq_annotation &a, lsq_events &E);
+// A read file through the host parser of its format, against dictionaries E; verify: a BAM file's CRC32s and end-of-file marker checked
+int host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r);
+// ... under LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (the executables' --host)
+int cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r);
+int cli_env_options(lsq_ctx *c);               // lsq_cli.cpp: LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ, LSQ_BAM_VERIFY, LSQ_OPTIONS
+// rows ascending in chromosome index -> where each row of the tables' order (chromosome names bytewise) comes from
+std::vector<size_t> rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom);
+// The exons of a line that are not empty (no more than exonCount of them) merged into `sorted_exons` (empty, or other lines'
+// exons in order): the exon union is what a walk with a running maximum of the ends makes of the list
+void exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &sorted_exons);
+bool write_file(const char *path, const char *text);       // false: the status and text of the failure are set (LSQ_E_IO)
+
+// ---- the reads over host threads: T slices of whole reads, one slice below 2^16 reads; f(k, r0, r1) on a thread of its own
+inline int read_slices(uint64_t n_reads, int n_threads) { return n_reads < (1u << 16) ? 1 : host_threads(n_threads); }
+template <class F>
+int for_read_slices(uint64_t n_reads, int T, F f) {
+	ThreadGroup th;
+	for (int k = 0; k < T; ++k) th.spawn([=] { f(k, n_reads * (uint64_t)k / (uint64_t)T, n_reads * (uint64_t)(k + 1) / (uint64_t)T); });
+	th.join();
+	return th.failed() ? fail(LSQ_E_INTERNAL, "%s", th.error().c_str()) : LSQ_OK;
+}
+// the slices' parts, each sorted and folded (fold: sorted items with equal keys -> one each), merged into one such list
+template <class X, class Less, class Fold>
+std::vector<X> merge_folded(std::vector<std::vector<X>> &parts, Less less, Fold fold) {
+	std::vector<X> all = std::move(parts[0]);
+	for (size_t k = 1; k < parts.size(); ++k) {
+		std::vector<X> m(all.size() + parts[k].size());
+		std::merge(all.begin(), all.end(), parts[k].begin(), parts[k].end(), m.begin(), less);
+		fold(m);
+		all.swap(m);
+		std::vector<X>().swap(parts[k]);
+	}
+	return all;
+}
+
+// ---- the bodies of the entry points that differ by the type alone (every index begins with `lsq_events E`)
+template <class IX> int64_t index_num_chroms(const IX *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
+template <class IX> const char *index_chrom_name(const IX *ix, int64_t chrom) {
+	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
+}
+template <class IX> lsq_events *index_dictionaries(IX *ix) { return ix ? &ix->E : nullptr; }
+template <class T> int table_report(const T *t, uint64_t *report) {
+	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
+	memcpy(report, t->report, sizeof(t->report));
+	return LSQ_OK;
+}
+template <class T> int table_times(const T *t, float *ms) {
+	if (!t || !ms) return fail(LSQ_E_ARG, "null argument");
+	memcpy(ms, t->ms, sizeof(t->ms));
+	return LSQ_OK;
+}
+// a new table filled by fill(table), handed out when that succeeds
+template <class T, class F> int new_table(T **out, F fill) {
+	std::unique_ptr<T> t(new T);
+	const int rc = fill(*t);
+	if (rc) return rc;
+	*out = t.release();
+	return LSQ_OK;
+}
+// lsq_*_host: the file parsed on the host, the arrays through the tool's lsq_*_host_reads, the arrays freed
+template <class F> int host_file(lsq_events &E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int n_threads, F host_reads) {
+	lsq_reads *r = nullptr;
+	int rc = host_parse_reads(&E, read_format, path, skip_flags, min_mapq, false, n_threads, &r);
+	if (rc) return rc;
+	rc = host_reads(r);
+	lsq_reads_free(r);
+	return rc;
+}
+
+// ---- the frame of the executables: <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
+// The value behind a number option argv[i]: decimal, at most 2^32-1, nothing before or behind it; i moves on to it
+bool cli_u32_option(int argc, const char *const *argv, int &i, unsigned long &v);
+// the last error to the log; the exit status of a failure: 2 for LSQ_E_DEVICE and LSQ_E_INTERNAL, else 1
+int cli_failed(int st);
+template <class T, void (*FREE)(T *)> struct CliOwned {
+	T *p = nullptr;
+	CliOwned() = default;
+	CliOwned(const CliOwned &) = delete;
+	CliOwned &operator=(const CliOwned &) = delete;
+	~CliOwned() { FREE(p); }
+};
+struct CliFrame {
+	const std::vector<const char *> &pos;      // the positional arguments: six or seven
+	lsq_annotation *a = nullptr;
+	lsq_ctx *c = nullptr;
+	lsq_reads *reads = nullptr;
+	char *text[3] = {nullptr, nullptr, nullptr};       // the tool's output texts
+	explicit CliFrame(const std::vector<const char *> &p) : pos(p) {}
+	CliFrame(const CliFrame &) = delete;
+	CliFrame &operator=(const CliFrame &) = delete;
+	~CliFrame();
+	int load_annotation();                     // pos[0..3] -> a
+	int host_parse(lsq_events *E);             // --host: pos[4], pos[5] -> reads (cli_host_parse)
+	void free_reads();
+	int create_context();                      // c on cli_device(), under cli_env_options
+	int deliver(const char *t, std::string &out) const;       // t into pos[6], or into `out` without one or with "-"; the exit status
+};
+
+} // namespace lsq

@@ -5,39 +5,24 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, vp, u64, u32, i64, P
+from ._lib import lib, check, u64, u32, i64, P, _b, take_text
+from ._readtool import Index, Table, copied
 
 PHASES = ("index_upload", "count", "copy_back")
 REPORT = ("reads", "blocks", "no_chromosome_or_empty", "no_gene", "several_genes", "bin_hits")
 
 
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
-
-
-class ExonBins:
+class ExonBins(Table):
     """The table of one read file: numpy arrays (copies) `reads` per bin and `total` per gene, `report`, `times` (device ms per
     phase), rows(), text(), bins_text()."""
+    PREFIX = "lsq_xb"
 
     def __init__(self, h, index):
-        self.h = h
-        self.index = index
-        nb, ng = index.num_bins, index.num_genes
+        super().__init__(h, index, REPORT, PHASES)
         reads, total = P(u64)(), P(u64)()
         check(lib.lsq_xb_table_arrays(h, C.byref(reads), C.byref(total)))
-        self.reads = np.ctypeslib.as_array(reads, (nb,)).copy() if nb else np.zeros(0, np.uint64)
-        self.total = np.ctypeslib.as_array(total, (ng,)).copy() if ng else np.zeros(0, np.uint64)
-        rep = (u64 * 6)()
-        check(lib.lsq_xb_table_report(h, rep))
-        self.report = dict(zip(REPORT, (int(v) for v in rep)))
-        ms = (C.c_float * 3)()
-        check(lib.lsq_xb_table_times(h, ms))
-        self.times = dict(zip(PHASES, (float(v) for v in ms)))
-
-    def __del__(self, _free=lib.lsq_xb_table_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
+        self.reads = copied(reads, index.num_bins, np.uint64)
+        self.total = copied(total, index.num_genes, np.uint64)
 
     def __len__(self):
         return len(self.reads)
@@ -49,39 +34,24 @@ class ExonBins:
                 for g in range(len(names)) for b in range(int(first[g]), int(first[g + 1]))]
 
     def text(self):
-        out = vp()
-        check(lib.lsq_xb_format(self.h, C.byref(out)))
-        try:
-            return C.string_at(out).decode()
-        finally:
-            lib.lsq_free(out)
+        return take_text(lib.lsq_xb_format, self.h)
 
     def bins_text(self):
         return self.index.bins_text()
 
 
-class ExonBinIndex:
+class ExonBinIndex(Index):
     """lsq_xb_index_build: the annotation's chromosomes, every gene's bins, the lookup of the bins that overlap a block"""
+    PREFIX = "lsq_xb"
 
     def __init__(self, annotation):
-        h = vp()
-        check(lib.lsq_xb_index_build(annotation.h, C.byref(h)))
-        self.h = h
+        super().__init__(annotation)
         nb, ng = self.num_bins, self.num_genes
         ptrs = [P(i64)(), P(i64)(), P(u32)(), P(u32)(), P(u32)()]
-        check(lib.lsq_xb_index_arrays(h, *[C.byref(p) for p in ptrs]))
+        check(lib.lsq_xb_index_arrays(self.h, *[C.byref(p) for p in ptrs]))
         for (k, dt, n), p in zip((("bin_start", np.int64, nb), ("bin_end", np.int64, nb), ("bin_gene", np.uint32, nb), ("gene_first_bin", np.uint32, ng + 1),
                                   ("gene_chrom", np.uint32, ng)), ptrs):
-            setattr(self, k, np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, dt))
-
-    def __del__(self, _free=lib.lsq_xb_index_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
-
-    @property
-    def num_chroms(self):
-        return lib.lsq_xb_index_num_chroms(self.h)
+            setattr(self, k, copied(p, n, dt))
 
     @property
     def num_genes(self):
@@ -90,9 +60,6 @@ class ExonBinIndex:
     @property
     def num_bins(self):
         return lib.lsq_xb_index_num_bins(self.h)
-
-    def chrom_names(self):
-        return [lib.lsq_xb_index_chrom_name(self.h, c).decode() for c in range(self.num_chroms)]
 
     def gene_names(self):
         return [lib.lsq_xb_index_gene_name(self.h, g).decode() for g in range(self.num_genes)]
@@ -108,39 +75,19 @@ class ExonBinIndex:
 
     def bins_text(self):
         """(the LH_GENE_TXT text with a line per bin, the gene->isoform text): the bins as an annotation"""
-        iv, mp = vp(), vp()
-        check(lib.lsq_xb_format_bins(self.h, C.byref(iv), C.byref(mp)))
-        try:
-            return C.string_at(iv).decode(), C.string_at(mp).decode()
-        finally:
-            lib.lsq_free(iv)
-            lib.lsq_free(mp)
+        return take_text(lib.lsq_xb_format_bins, self.h, n=2)
 
     def host(self, read_format, path, skip_flags=0x904, min_mapq=0, n_threads=0):
         """lsq_xb_host: every read format lsq_reads_parse takes; no GPU touched"""
-        t = vp()
-        check(lib.lsq_xb_host(self.h, _b(read_format), _b(path), skip_flags, min_mapq, n_threads, C.byref(t)))
-        return ExonBins(t, self)
-
-    def parse_host(self, read_format, path, n_threads=0):
-        """lsq_reads_parse against the index's dictionaries: an api.Reads for host_reads"""
-        from .api import Reads
-
-        class _Dictionaries:
-            h = vp(lib.lsq_xb_index_dictionaries(self.h))
-        return Reads.from_mrf(path, _Dictionaries, n_threads, read_format)
+        return self._table(ExonBins, lib.lsq_xb_host, self.h, _b(read_format), _b(path), skip_flags, min_mapq, n_threads)
 
     def host_reads(self, reads, n_threads=0):
         """lsq_xb_host_reads: from arrays already parsed against this index (parse_host)"""
-        t = vp()
-        check(lib.lsq_xb_host_reads(self.h, reads.h, n_threads, C.byref(t)))
-        return ExonBins(t, self)
+        return self._table(ExonBins, lib.lsq_xb_host_reads, self.h, reads.h, n_threads)
 
     def device(self, ctx, read_format, path):
         """lsq_xb_device: MRF_SINGLE, SAM_SINGLE or BAM_SINGLE under the context's sam_skip_flags / sam_min_mapq / bam_verify"""
-        t = vp()
-        check(lib.lsq_xb_device(ctx.h, self.h, _b(read_format), _b(path), C.byref(t)))
-        return ExonBins(t, self)
+        return self._table(ExonBins, lib.lsq_xb_device, ctx.h, self.h, _b(read_format), _b(path))
 
 
 __all__ = ["ExonBinIndex", "ExonBins", "PHASES", "REPORT"]

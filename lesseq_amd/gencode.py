@@ -5,11 +5,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, vp
-
-
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
+from ._lib import lib, check, vp, _b
 
 
 class Gtf:

@@ -5,41 +5,27 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, vp, u64, u32, i32, u8, P
+from ._lib import lib, check, u32, i32, u8, P, _b, take_text
+from ._readtool import Index, Table, copied
 
 SORT_TILE = lib.lsq_jn_sort_tile()      # records a workgroup of the device sort takes
 PHASES = ("extract", "sort", "reduce", "annotate", "copy_back")
 REPORT = ("reads", "blocks", "occurrences", "dropped_overhang", "no_chromosome")
 
 
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
-
-
-class Junctions:
+class Junctions(Table):
     """A junction table: numpy arrays (copies) in row order, `report`, `times` (device ms per phase), text()."""
+    PREFIX = "lsq_jn"
 
     def __init__(self, h, index):
-        self.h = h
-        self.index = index
+        super().__init__(h, index, REPORT, PHASES)
         n = lib.lsq_jn_table_rows(h)
         ptrs = [P(u32)(), P(i32)(), P(i32)(), P(u8)(), P(u32)(), P(u32)(), P(u32)(), P(u32)()]
         check(lib.lsq_jn_table_arrays(h, *[C.byref(p) for p in ptrs]))
         names = (("chrom", np.uint32), ("start", np.int32), ("end", np.int32), ("ann", np.uint8), ("reads", np.uint32), ("plus", np.uint32),
                  ("minus", np.uint32), ("max_overhang", np.uint32))
         for (k, dt), p in zip(names, ptrs):
-            setattr(self, k, np.ctypeslib.as_array(p, (n,)).copy() if n else np.zeros(0, dt))
-        rep = (u64 * 5)()
-        check(lib.lsq_jn_table_report(h, rep))
-        self.report = dict(zip(REPORT, (int(v) for v in rep)))
-        ms = (C.c_float * 5)()
-        check(lib.lsq_jn_table_times(h, ms))
-        self.times = dict(zip(PHASES, (float(v) for v in ms)))
-
-    def __del__(self, _free=lib.lsq_jn_table_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
+            setattr(self, k, copied(p, n, dt))
 
     def __len__(self):
         return len(self.chrom)
@@ -51,63 +37,28 @@ class Junctions:
                 zip(self.chrom, self.start, self.end, self.ann, self.reads, self.plus, self.minus, self.max_overhang)]
 
     def text(self, min_reads=0, novel_only=False):
-        out = vp()
-        check(lib.lsq_jn_format(self.h, min_reads, int(bool(novel_only)), C.byref(out)))
-        try:
-            return C.string_at(out).decode()
-        finally:
-            lib.lsq_free(out)
+        return take_text(lib.lsq_jn_format, self.h, min_reads, int(bool(novel_only)))
 
 
-class JunctionIndex:
+class JunctionIndex(Index):
     """lsq_jn_index_build: the annotation's chromosomes and its distinct introns"""
-
-    def __init__(self, annotation):
-        h = vp()
-        check(lib.lsq_jn_index_build(annotation.h, C.byref(h)))
-        self.h = h
-
-    def __del__(self, _free=lib.lsq_jn_index_free):
-        if getattr(self, "h", None):
-            _free(self.h)
-            self.h = None
-
-    @property
-    def num_chroms(self):
-        return lib.lsq_jn_index_num_chroms(self.h)
+    PREFIX = "lsq_jn"
 
     @property
     def num_introns(self):
         return lib.lsq_jn_index_num_introns(self.h)
 
-    def chrom_names(self):
-        return [lib.lsq_jn_index_chrom_name(self.h, c).decode() for c in range(self.num_chroms)]
-
     def host(self, read_format, path, min_overhang=1, skip_flags=0x904, min_mapq=0, n_threads=0):
         """lsq_jn_host: every read format lsq_reads_parse takes; no GPU touched"""
-        t = vp()
-        check(lib.lsq_jn_host(self.h, _b(read_format), _b(path), skip_flags, min_mapq, min_overhang, n_threads, C.byref(t)))
-        return Junctions(t, self)
-
-    def parse_host(self, read_format, path, n_threads=0):
-        """lsq_reads_parse against the index's dictionaries: an api.Reads for host_reads"""
-        from .api import Reads
-
-        class _Dictionaries:
-            h = vp(lib.lsq_jn_index_dictionaries(self.h))
-        return Reads.from_mrf(path, _Dictionaries, n_threads, read_format)
+        return self._table(Junctions, lib.lsq_jn_host, self.h, _b(read_format), _b(path), skip_flags, min_mapq, min_overhang, n_threads)
 
     def host_reads(self, reads, min_overhang=1, n_threads=0):
         """lsq_jn_host_reads: from arrays already parsed against this index (parse_host)"""
-        t = vp()
-        check(lib.lsq_jn_host_reads(self.h, reads.h, min_overhang, n_threads, C.byref(t)))
-        return Junctions(t, self)
+        return self._table(Junctions, lib.lsq_jn_host_reads, self.h, reads.h, min_overhang, n_threads)
 
     def device(self, ctx, read_format, path, min_overhang=1):
         """lsq_jn_device: MRF_SINGLE, SAM_SINGLE or BAM_SINGLE under the context's sam_skip_flags / sam_min_mapq / bam_verify"""
-        t = vp()
-        check(lib.lsq_jn_device(ctx.h, self.h, _b(read_format), _b(path), min_overhang, C.byref(t)))
-        return Junctions(t, self)
+        return self._table(Junctions, lib.lsq_jn_device, ctx.h, self.h, _b(read_format), _b(path), min_overhang)
 
 
 __all__ = ["JunctionIndex", "Junctions", "SORT_TILE", "PHASES", "REPORT"]

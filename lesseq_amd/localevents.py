@@ -4,13 +4,9 @@ directory of .matrix files plus the gene list, or from an annotation with classi
 Graphs.from_gtf starts from the GTF itself, which is parsed on the device."""
 import ctypes as C
 
-from ._lib import lib, check, vp
+from ._lib import lib, check, vp, _b
 
 TYPES = ("ES", "RI", "A5SS", "A3SS", "MXE", "AFE", "ALE", "T3")
-
-
-def _b(s):
-    return s.encode() if isinstance(s, str) else s
 
 
 class Record:

@@ -8,11 +8,13 @@ import pytest
 import lesseq_amd as L
 import bam_writer
 import coverage_ref as V
-from test_junctions_host import sam_of, spliced_reads
+from test_junctions_host import sam_of, spliced_reads, log_messages
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BIN = os.path.join(os.path.dirname(HERE), "lesseq_amd", "bin")
 LSQ_E_PARSE = -4
+USAGE = ("Usage:\ncoverage [--host] [--strand +|-] [--min-depth N] [--regions regions_path] isoform_format isoforms_path g2i_format g2i_path read_format reads_path "
+         "[out_path]")
 
 
 def index_of(paths):
@@ -193,11 +195,24 @@ def test_the_tool_logs_the_report_and_takes_an_output_path(base, tmp_path):
     p = subprocess.run(argv + [out], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout == "" and open(out).read() == V.text(rows)
     assert "%d counted in %d row(s)" % (report["counted"], len(rows)) in p.stderr and "%d base(s) in the counted blocks (solve's total_read_bases)" % report["bases"] in p.stderr
+    line = ("coverage: %d read(s), %d block(s), %d counted in %d row(s); %d on no chromosome of the annotation, %d empty or descending, %d of the other strand; "
+            "%d base(s) in the counted blocks (solve's total_read_bases)"
+            % (report["reads"], report["blocks"], report["counted"], len(rows), report["no_chromosome"], report["empty"], report["other_strand"], report["bases"]))
+    assert log_messages(p.stderr) == [("WARNING", line)]
     p = subprocess.run(argv + ["-"], capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout == V.text(rows)
-    for bad in (["--strand", "x"], ["--strand"], ["--min-depth", "-1"], ["--min-depth"], ["--regions"], ["--nonsense"]):
+    for bad in (["--strand", "x"], ["--strand"], ["--min-depth", "-1"], ["--min-depth", "4294967296"], ["--min-depth", "1x"], ["--min-depth"], ["--regions"], ["--nonsense"]):
         p = tool(paths, paths["mrf"], opts=bad)
-        assert p.returncode == 1 and p.stdout == "" and "Usage" in p.stderr, bad
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], bad
+    # an option that ends the line has no value; five and eight positional arguments
+    for bad in (argv[2:] + ["--min-depth"], argv[2:] + ["--regions"], argv[2:] + ["--strand"], argv[2:7], argv[2:] + ["-", "-"]):
+        p = subprocess.run(argv[:2] + bad, capture_output=True, text=True)
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], bad
+    # the regions file is written before the output file: an output path that cannot be written leaves the regions behind
+    regions, lost = str(tmp_path / "r.tsv"), str(tmp_path / "no_such_directory" / "t.bedgraph")
+    p = subprocess.run(argv[:2] + ["--regions", regions] + argv[2:] + [lost], capture_output=True, text=True)
+    assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr)[-1] == ("ERROR", "cannot write " + lost)
+    assert open(regions).read() == V.regions_text(V.table(interval, mrf)[1]) and not os.path.exists(lost)
 
 
 def test_a_malformed_record_gives_counts_status_and_message(base, tmp_path):

@@ -10,12 +10,13 @@ import lesseq_amd as L
 import bam_writer
 import exonbins_ref as V
 from lesseq_amd import diffsplice as ds
-from test_junctions_host import sam_of
+from test_junctions_host import sam_of, log_messages
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 BIN = os.path.join(os.path.dirname(HERE), "lesseq_amd", "bin")
 TOY = os.path.join(HERE, "golden", "toy")
 LSQ_E_PARSE = -4
+USAGE = "Usage:\nexonbins [--host] [--bins prefix] isoform_format isoforms_path g2i_format g2i_path read_format reads_path [out_path]"
 TOY_TABLE = "RI1\t4\tRI1:1\t3\nRI1\t4\tRI1:2\t1\nRI1\t4\tRI1:3\t2\nSE1\t8\tSE1:1\t5\nSE1\t8\tSE1:2\t3\nSE1\t8\tSE1:3\t3\n"
 TOY_REPORT = {"reads": 13, "blocks": 17, "no_chromosome_or_empty": 1, "no_gene": 1, "several_genes": 0, "bin_hits": 17}
 
@@ -250,12 +251,23 @@ def test_two_samples_make_an_lrt_input(base, tmp_path):
 
 def test_the_tool_takes_an_output_path_and_refuses_nonsense(base, tmp_path):
     interval, gmap, mrf, paths = base
-    rows, _ = V.table(interval, gmap, mrf)
+    rows, report = V.table(interval, gmap, mrf)
     p = tool(paths, paths["mrf"], out="-")
     assert p.returncode == 0 and p.stdout == V.text(rows)
+    assert log_messages(p.stderr) == [("INFO", V.report_line(report, len(rows), index_of(paths).num_genes))]
     for bad in (["--bins"], ["--nonsense"], ["--strand", "+"]):
         p = tool(paths, paths["mrf"], opts=bad)
-        assert p.returncode == 1 and p.stdout == "" and "Usage" in p.stderr, bad
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], bad
+    positional = ["LH_GENE_TXT", paths["interval"], "UCSC_GENE2ISOFORM", paths["map"], "MRF_SINGLE", paths["mrf"]]
+    # --bins at the end of the line has no value; five and eight positional arguments
+    for argv in (positional + ["--bins"], positional[:5], positional + ["-", "-"]):
+        p = subprocess.run([os.path.join(BIN, "exonbins"), "--host"] + argv, capture_output=True, text=True)
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], argv
+    # everything is formatted before anything is written, and the bins' files come first: a prefix that cannot be written leaves no file
+    prefix, out = str(tmp_path / "no_such_directory" / "bins"), str(tmp_path / "t.tab")
+    p = tool(paths, paths["mrf"], opts=["--bins", prefix], out=out)
+    assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr)[-1] == ("ERROR", "cannot write " + prefix + ".interval")
+    assert not os.path.exists(out) and os.listdir(str(tmp_path)) == []
 
 
 def test_a_malformed_record_gives_counts_status_and_message(base, tmp_path):

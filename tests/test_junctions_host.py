@@ -1,6 +1,7 @@
 """Splice junctions without a GPU (include/lesseq_hip.h, lsq_jn_*): lsq_jn_host and `junctions --host` against the definition as
 tests/junction_ref.py restates it."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -12,6 +13,16 @@ import junction_ref as J
 HERE = os.path.dirname(os.path.abspath(__file__))
 BIN = os.path.join(os.path.dirname(HERE), "lesseq_amd", "bin")
 LSQ_E_PARSE = -4
+USAGE = ("Usage:\njunctions [--host] [--min-overhang N] [--min-reads N] [--novel] isoform_format isoforms_path g2i_format g2i_path read_format reads_path "
+         "[out_path]")
+LOG_PREFIX = re.compile(r"^\[LOG \d{4}-\d\d-\d\d \d\d:\d\d:\d\d (ERROR|WARNING|INFO|DEBUG)\] ", re.M)
+
+
+def log_messages(stderr):
+    """[(level, text)] of an executable's log: every message behind its "[LOG <date> <time> <level>] ", nothing between them"""
+    parts = LOG_PREFIX.split(stderr)
+    assert parts[0] == "" and all(t.endswith("\n") for t in parts[2::2]), stderr
+    return [(lv, t[:-1]) for lv, t in zip(parts[1::2], parts[2::2])]
 
 
 def index_of(paths):
@@ -68,12 +79,21 @@ def test_the_tool_writes_the_report_to_the_log_and_takes_an_output_path(base, tm
                        capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout == "" and open(out).read() == J.text(rows)
     assert "%d occurrence(s) of %d junction(s)" % (report["occurrences"], len(rows)) in p.stderr
+    line = ("junctions: %d read(s), %d block(s), %d occurrence(s) of %d junction(s); %d block pair(s) below the overhang, %d with a block on no chromosome of the annotation"
+            % (report["reads"], report["blocks"], report["occurrences"], len(rows), report["dropped_overhang"], report["no_chromosome"]))
+    assert log_messages(p.stderr) == [("WARNING", line)]
     p = subprocess.run([os.path.join(BIN, "junctions"), "--host", "LH_GENE_TXT", paths["interval"], "UCSC_GENE2ISOFORM", paths["map"], "MRF_SINGLE", paths["mrf"], "-"],
                        capture_output=True, text=True)
     assert p.returncode == 0 and p.stdout == J.text(rows)      # "-": standard output
-    for bad in (["--min-overhang", "0"], ["--min-reads"], ["--nonsense"]):
+    numbers = [[opt] + v for opt in ("--min-overhang", "--min-reads") for v in ([], ["-1"], ["4294967296"], ["1x"])]
+    for bad in [["--min-overhang", "0"], ["--nonsense"]] + numbers:
         p = tool(paths, paths["mrf"], opts=bad)
-        assert p.returncode == 1 and p.stdout == "" and "Usage" in p.stderr
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], bad
+    positional = ["LH_GENE_TXT", paths["interval"], "UCSC_GENE2ISOFORM", paths["map"], "MRF_SINGLE", paths["mrf"]]
+    # a number option that ends the line has no value; five and eight positional arguments
+    for argv in (positional + ["--min-overhang"], positional + ["--min-reads"], positional[:5], positional + ["-", "-"]):
+        p = subprocess.run([os.path.join(BIN, "junctions"), "--host"] + argv, capture_output=True, text=True)
+        assert p.returncode == 1 and p.stdout == "" and log_messages(p.stderr) == [("ERROR", USAGE)], argv
 
 
 def test_formatter_options(base):
