@@ -391,6 +391,10 @@ int lsq_host_evaluated(const lsq_ctx *c, uint64_t *n_genes, uint64_t *n_reads);
  * re-sorts the placement by the iteration counts of one of its own earlier solves, refreshed every
  * sixteenth solve, so that events of similar cost share a wavefront), "count_streams" (1: every lsq_count on one
  * stream; default 2: a stream per step lane, so that a count may begin while the tail of the one before still runs),
+ * "counter_sets" (default 3: consecutive counts take three sets of counters and exception lists in turn, so that a count waits for
+ * the readers of the step three back and two counts are in flight at a time; 2: the rotation of two, where a count waits for the
+ * result chain of the step before last, and the default of a context made with LSQ_CTX_LANES_IN_BACKGROUND, whose step streams share
+ * hardware queues; LSQ_E_STATE unless every stream of the context has drained, lsq_ctx_synchronize),
  * "reads_per_look" (0 = automatic: eight one-block reads per lane and table look where the count kernel is held to five
  * workgroups a compute unit and the pools are compact, else four; 4; 8), "workgroups_per_cu" (resident workgroups of the count kernel per compute unit: 0 = as many as fit, default -1 = five
  * when the EM runs its one-lane-per-event kernel beside it and the read set is evenly deep, else as many as fit), "em_flat_min_events" (default 16 384: with at

@@ -452,7 +452,8 @@ class Context:
 
     def set_option(self, name, value):
         """lsq_ctx_set_option: grid_multiplier, exception_capacity, recount_every_read, em_guard_band,
-        snap_shares, em_regroup, em_flat_min_events, compact_pools, sam_skip_flags, sam_min_mapq, bam_verify, bootstrap_chunk"""
+        snap_shares, em_regroup, em_flat_min_events, compact_pools, sam_skip_flags, sam_min_mapq, bam_verify, bootstrap_chunk,
+        counter_sets (2 or 3; only while nothing is in flight)"""
         check(lib.lsq_ctx_set_option(self.h, _b(name), float(value)))
 
     def count_status(self):

@@ -1581,18 +1581,20 @@ int run_count(lsq_ctx *c) {
 	const size_t n_cls = E.n_cls_total;
 	const int M = E.n_methods;
 	hipStream_t st_em = nullptr;
-	// This count writes the counter set the solve before last read; the previous count had it
-	// zeroed on the result stream, behind those readers, and recorded ev_mark after that.  Now the
-	// same for the next count: zero the set the latest solve reads, behind it.
-	// (Lanes: this count takes lane `set`; the lane of the count before -- its result stream carries that step's EM and
-	// hand-off -- gets the zeroing of its counters and its mark queued behind them now.)
-	const int set = c->flip ^ 1, other = c->flip;
-	hipStream_t st = c->opt_two_count_streams ? c->stream_count2[set] : c->stream;      // (lsq_device.hpp: a count stream per lane)
+	// Count k takes the lanes in turn (two) and the counter sets in turn (`opt_counter_sets`: three, or two).  The set of the count
+	// before is zeroed now, on that count's lane -- its result stream carries that step's exception pass, EM and hand-off, and by now
+	// every call that can ever read that set has been queued there, whether a solve came or not -- and its mark recorded behind the
+	// zeroing.  This count waits for the mark of its own set: with three sets that one was zeroed when count k-2 was submitted, behind
+	// the readers of step k-3, so nothing of step k-1's or k-2's result chain stands in front of this count; with two it
+	// was zeroed when count k-1 was submitted, behind the readers of step k-2.
+	const int prev_lane = c->lane, prev_set = c->set;
+	const int lane = prev_lane ^ 1, set = (prev_set + 1) % c->opt_counter_sets;
+	hipStream_t st = c->opt_two_count_streams ? c->stream_count2[lane] : c->stream;      // (lsq_device.hpp: a count stream per lane)
 	if (c->mark_recorded2[set]) HIP_TRY(hipStreamWaitEvent(st, c->ev_mark2[set], 0));
-	HIP_TRY(hipMemsetAsync(c->counters.p + (size_t)other * c->counters_per_set, 0, c->counters_per_set * sizeof(unsigned long long), c->stream_em2[other]));
-	HIP_TRY(hipEventRecord(c->ev_mark2[other], c->stream_em2[other]));
-	c->mark_recorded2[other] = true;
-	select_counter_set(c, set);
+	HIP_TRY(hipMemsetAsync(c->counters.p + (size_t)prev_set * c->counters_per_set, 0, c->counters_per_set * sizeof(unsigned long long), c->stream_em2[prev_lane]));
+	HIP_TRY(hipEventRecord(c->ev_mark2[prev_set], c->stream_em2[prev_lane]));
+	c->mark_recorded2[prev_set] = true;
+	select_counter_set(c, lane, set);
 	st_em = c->stream_em;
 	c->fast_launched = 0;
 	struct Cleanup { CountArgs A; unsigned long long n_pn; int m; };
@@ -1652,6 +1654,8 @@ int run_count(lsq_ctx *c) {
 		// 0.151 ms per step; the skewed c5s 3 -> 0.179, 4 -> 0.176, 6 -> 0.178, 8 -> 0.183; C2 1 -> 0.046, 2 -> 0.044, 3 -> 0.044.
 		// The five-wave kernel's steps are twice as long, and its shares pay for being smaller: C3 1.6 -> 0.137, 2 -> 0.133,
 		// 2.4 -> 0.1335, 3 -> 0.129, 3.5 -> 0.132, 4 -> 0.133, 5 -> 0.137, 6 -> 0.1355.
+		// With three counter sets two counts are co-resident throughout; same box, one process: C3 2 -> 0.0985, 3 -> 0.0992, 4 -> 0.1040
+		// (share_taper 0.25 / 0.5 / 1: 0.0991 / 0.0986 / 0.1004; six workgroups a compute unit 0.1131 against 0.0995 with five): the rules stay.
 		// lsq_ctx_set_option "grid_multiplier" overrides
 		const double mult = c->opt_grid_mult > 0 ? c->opt_grid_mult : (mr.skew >= 32.0 ? 4.0 : (mr.skew >= 4.0 || p1w == 4 ? 3.0 : 2.0));
 		unsigned long long grid = (unsigned long long)((double)c->n_cu * per_cu * mult);
@@ -1759,7 +1763,7 @@ int run_count(lsq_ctx *c) {
 			}
 #endif
 			void *kargs[] = {(void *)&A};
-			HIP_TRY(hipExtLaunchKernel(mr.compact ? fn_compact : fn_wide, fgrid, dim3(COUNT_BLOCK), kargs, lds_bytes, st, nullptr, last_streaming ? c->ev_counted2[set] : nullptr, 0));
+			HIP_TRY(hipExtLaunchKernel(mr.compact ? fn_compact : fn_wide, fgrid, dim3(COUNT_BLOCK), kargs, lds_bytes, st, nullptr, last_streaming ? c->ev_counted2[lane] : nullptr, 0));
 			if (last_streaming) counted_signalled = true;
 			if (c->time_events) HIP_TRY(hipEventRecord(c->evf1[m], st));
 			c->fast_launched |= 1 << m;
@@ -1774,16 +1778,16 @@ int run_count(lsq_ctx *c) {
 	c->count_timed = c->time_events;
 	// the exception pass, and everything that reads the counts, on the result stream behind the streaming kernels;
 	// (it turns into the recount where the exception list overflowed)
-	if (!counted_signalled) HIP_TRY(hipEventRecord(c->ev_counted2[set], st));
-	HIP_TRY(hipStreamWaitEvent(st_em, c->ev_counted2[set], 0));
+	if (!counted_signalled) HIP_TRY(hipEventRecord(c->ev_counted2[lane], st));
+	HIP_TRY(hipStreamWaitEvent(st_em, c->ev_counted2[lane], 0));
 	// One workgroup a compute unit: the launch normally finds a handful of pairs to settle beside the next count's kernel (C3: a step
 	// takes 0.107-0.109 ms with 16, 64, 128 or 256 of them, profiles/r04_recount_c3.json), and when the list has overflowed the same
 	// workgroups count every read again -- 14 ms per C3 step on 256, 37 on 64, 90-108 on the 16 of round 3.  No workgroup waits for another.
 	const unsigned rgrid = std::max(16u, (unsigned)c->n_cu);
-	if (c->recount_args.n < 2 * (size_t)LSQ_MAX_METHODS * sizeof(CountArgs)) {
-		int rc = c->recount_args.alloc(2 * (size_t)LSQ_MAX_METHODS * sizeof(CountArgs));
+	if (c->recount_args.n < (size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs)) {
+		int rc = c->recount_args.alloc((size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs));
 		if (rc) return rc;
-		c->recount_args_host.assign(2 * (size_t)LSQ_MAX_METHODS * sizeof(CountArgs), 0);
+		c->recount_args_host.assign((size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs), 0);
 	}
 	for (const Cleanup &u : cleanups) {
 		// the arguments of these two kernels live in device memory, one record per (counter set, read file); rewritten only when they change

@@ -48,15 +48,16 @@ int sync_all(lsq_ctx *c) {
 	return LSQ_OK;
 }
 
-void select_counter_set(lsq_ctx *c, int set) {
+void select_counter_set(lsq_ctx *c, int lane, int set) {
 	unsigned long long *base = c->counters.p + (size_t)set * c->counters_per_set;
 	const size_t per = c->cnt.n;
-	c->flip = set;
-	c->stream_em = c->stream_em2[set];
-	c->theta.p = c->theta2[set].p; c->theta.n = c->theta2[set].n;
-	c->logll.p = c->logll2[set].p; c->logll.n = c->logll2[set].n;
-	c->iters.p = c->iters2[set].p; c->iters.n = c->iters2[set].n;
-	c->flags.p = c->flags2[set].p; c->flags.n = c->flags2[set].n;
+	c->lane = lane;
+	c->set = set;
+	c->stream_em = c->stream_em2[lane];
+	c->theta.p = c->theta2[lane].p; c->theta.n = c->theta2[lane].n;
+	c->logll.p = c->logll2[lane].p; c->logll.n = c->logll2[lane].n;
+	c->iters.p = c->iters2[lane].p; c->iters.n = c->iters2[lane].n;
+	c->flags.p = c->flags2[lane].p; c->flags.n = c->flags2[lane].n;
 	c->cnt.p = base;
 	c->bases.p = base + per;
 	c->exc_count.p = reinterpret_cast<unsigned *>(base + 2 * per);
@@ -107,12 +108,9 @@ int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TR
 	std::unique_ptr<lsq_ctx> c(new lsq_ctx);
 	c->device = device_id;
 	c->n_cu = prop.multiProcessorCount;
-	HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-	HIP_TRY(hipEventCreate(&c->evt0)); HIP_TRY(hipEventCreate(&c->evt1));
-	mark("context: upload stream");
-	// The rest -- the two lanes' streams and events, 0.04 s of the runtime's time -- is not needed by what an executable does first with
-	// its context (copying the MRF text to HBM, lsq_text_stage): with LSQ_CTX_LANES_IN_BACKGROUND a helper thread makes it meanwhile,
-	// and the first call that wants a lane (lsq_events_upload is ahead of every one of them) joins it.
+	// The two lanes' streams and events -- 0.04 s of the runtime's time -- are not needed by what an executable does first with its
+	// context (copying the MRF text to HBM, lsq_text_stage): with LSQ_CTX_LANES_IN_BACKGROUND a helper thread makes them while the upload
+	// stream is already at work, and the first call that wants a lane (lsq_events_upload is ahead of every one of them) joins it.
 	lsq_ctx *cp = c.get();
 	auto make_lanes = [cp]() -> int {
 		HIP_TRY(hipSetDevice(cp->device));
@@ -120,20 +118,38 @@ int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TR
 			HIP_TRY(hipStreamCreateWithFlags(&cp->stream_em2[l], hipStreamNonBlocking));      // (a higher stream priority changed nothing measurable)
 			HIP_TRY(hipStreamCreateWithFlags(&cp->stream_count2[l], hipStreamNonBlocking));
 			HIP_TRY(hipEventCreateWithFlags(&cp->ev_counted2[l], hipEventDisableTiming));
-			HIP_TRY(hipEventCreateWithFlags(&cp->ev_mark2[l], hipEventDisableTiming));
 		}
+		for (hipEvent_t &e : cp->ev_mark2) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
 		cp->stream_em = cp->stream_em2[0];
 		HIP_TRY(hipEventCreate(&cp->ev0)); HIP_TRY(hipEventCreate(&cp->ev1));
 		HIP_TRY(hipEventCreate(&cp->ev2)); HIP_TRY(hipEventCreate(&cp->ev3));
 		for (int m = 0; m < LSQ_MAX_METHODS; ++m) { HIP_TRY(hipEventCreate(&cp->evf0[m])); HIP_TRY(hipEventCreate(&cp->evf1[m])); }
 		return LSQ_OK;
 	};
+	// Otherwise the lanes come FIRST.  The runtime hands a process's hardware queues (four by default) to its streams in the order in
+	// which they are made and pairs further streams up with those; packets of one queue run one after the other.  Made behind the
+	// upload stream, the four step streams took three queues: the kernel trace of the pipelined step showed lane 1's count stream and
+	// lane 1's result stream on one (profiles/counter_sets_summary.md), so that lane's next count stood behind its result chain whatever
+	// the events said.  Made first, each step stream has a queue of its own and the upload stream, idle during steps, shares one.
+	bool lanes_first = !(flags & LSQ_CTX_LANES_IN_BACKGROUND);
+#ifdef LSQ_DEV
+	if (getenv("LSQ_UPLOAD_STREAM_FIRST")) lanes_first = false;          // timing experiments: the order of the rounds before
+#endif
+	if (lanes_first) {
+		const int rc = make_lanes();
+		if (rc) return rc;
+		mark("context: lanes");
+	} else
+		c->opt_counter_sets = 2;          // (on shared queues three sets are slower than two, 0.153 against 0.119 ms per C3 step; "counter_sets" still asks for them)
+	HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+	HIP_TRY(hipEventCreate(&c->evt0)); HIP_TRY(hipEventCreate(&c->evt1));
+	mark("context: upload stream");
 	if (flags & LSQ_CTX_LANES_IN_BACKGROUND) {
 		c->lanes_thread = std::thread([cp, make_lanes]() noexcept {
 			try { cp->lanes_status = make_lanes(); if (cp->lanes_status) cp->lanes_error = lsq_last_error(); }
 			catch (...) { cp->lanes_status = LSQ_E_INTERNAL; try { cp->lanes_error = "the lanes' helper thread failed"; } catch (...) {} }
 		});
-	} else {
+	} else if (!lanes_first) {
 		const int rc = make_lanes();
 		if (rc) return rc;
 		mark("context: lanes");
@@ -151,8 +167,8 @@ void lsq_ctx_destroy(lsq_ctx *c) {
 		if (c->stream_em2[l]) (void)hipStreamSynchronize(c->stream_em2[l]);
 		if (c->stream_count2[l]) (void)hipStreamSynchronize(c->stream_count2[l]);
 		if (c->ev_counted2[l]) (void)hipEventDestroy(c->ev_counted2[l]);
-		if (c->ev_mark2[l]) (void)hipEventDestroy(c->ev_mark2[l]);
 	}
+	for (hipEvent_t e : c->ev_mark2) if (e) (void)hipEventDestroy(e);
 	if (c->ev0) (void)hipEventDestroy(c->ev0);
 	if (c->ev1) (void)hipEventDestroy(c->ev1);
 	if (c->ev2) (void)hipEventDestroy(c->ev2);
@@ -292,18 +308,18 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 	{
 		const size_t per = std::max<size_t>(M, 1) * n_cls;
 		c->counters_per_set = 2 * per + LSQ_MAX_METHODS + 16 + LSQ_MAX_METHODS;          // cnt | bases | exc_count (two words a read file) | dbg | one barrier word a read file (lsq_count_cleanup_kernel)
-		if ((rc = c->counters.alloc(2 * c->counters_per_set))) return rc;
+		if ((rc = c->counters.alloc(LSQ_COUNTER_SETS * c->counters_per_set))) return rc;
 		c->cnt.n = per; c->bases.n = per; c->exc_count.n = 2 * LSQ_MAX_METHODS; c->dbg.n = 16;
-		c->mark_recorded2[0] = c->mark_recorded2[1] = false;
+		for (bool &r : c->mark_recorded2) r = false;
 		c->fim_uploaded = false; c->fim_done = false;
-		select_counter_set(c, 0);
-		HIP_TRY(hipMemsetAsync(c->counters.p, 0, c->counters.n * sizeof(unsigned long long), c->stream));      // both sets start out zero
+		select_counter_set(c, 0, 0);
+		HIP_TRY(hipMemsetAsync(c->counters.p, 0, c->counters.n * sizeof(unsigned long long), c->stream));      // every set starts out zero
 	}
 	for (int l = 0; l < 2; ++l) {
 		if ((rc = c->theta2[l].alloc(n_iso)) || (rc = c->logll2[l].alloc(n_ev)) || (rc = c->iters2[l].alloc(n_ev)) || (rc = c->flags2[l].alloc(n_ev))) return rc;
 		HIP_TRY(hipMemsetAsync(c->flags2[l].p, 0, std::max<size_t>(n_ev, 1), c->stream));
 	}
-	select_counter_set(c, 0);
+	select_counter_set(c, 0, 0);
 	mark("events: G, counters, EM outputs");
 	{
 		// ingest tables (lsq_device.hpp: RouteChrom): per chromosome id the covered regions (count/count.cpp:244) as (start, end)
@@ -609,6 +625,7 @@ int lsq_counts_export_device(lsq_ctx *c, void *d_words) LSQ_API_TRY {
 	if (!c || !d_words) return fail(LSQ_E_ARG, "null argument");
 	if (!c->counted) return fail(LSQ_E_STATE, "lsq_count must come first");
 	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = ensure_lanes(c); if (rc) return rc; }
 	const size_t per = (size_t)c->E->n_methods * c->E->n_cls_total;
 	if (per) {         // on the result stream, behind the count's exception pass
 		HIP_TRY(hipMemcpyAsync(d_words, c->cnt.p, per * sizeof(unsigned long long), hipMemcpyDeviceToDevice, c->stream_em));
@@ -687,6 +704,7 @@ int lsq_results_copy_device(lsq_ctx *c, void *d_class_count, void *d_theta, void
 	if (!c->counted) return fail(LSQ_E_STATE, "lsq_count must come first");
 	if ((d_theta || d_logll) && !c->solved) return fail(LSQ_E_STATE, "lsq_solve must come first");
 	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = ensure_lanes(c); if (rc) return rc; }
 	const lsq_events &E = *c->E;
 	const size_t n_cls = E.n_cls_total, M = (size_t)E.n_methods;
 	const size_t n0 = d_class_count ? M * n_cls : 0, n1 = d_theta ? (size_t)E.n_iso_total : 0, n2 = d_logll ? E.dev2out.size() : 0;
@@ -723,6 +741,7 @@ int lsq_results_pack_device(lsq_ctx *c, void *d_block) LSQ_API_TRY {
 	if (!c || !d_block) return fail(LSQ_E_ARG, "null argument");
 	if (!c->solved) return fail(LSQ_E_STATE, "lsq_solve must come first");
 	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = ensure_lanes(c); if (rc) return rc; }
 	const lsq_events &E = *c->E;
 	const size_t M = (size_t)E.n_methods, C = c->pack_cls.n, I = c->pack_iso.n, N = c->pack_ev.n;
 	const size_t total = 2 * M * C + I + N;
@@ -736,12 +755,13 @@ int lsq_results_pack_device(lsq_ctx *c, void *d_block) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
-void *lsq_ctx_result_stream(lsq_ctx *c) { return c ? (void *)c->stream_em : nullptr; }
+void *lsq_ctx_result_stream(lsq_ctx *c) { return (c && ensure_lanes(c) == LSQ_OK) ? (void *)c->stream_em : nullptr; }
 
 // device buffers for a C host that has no HIP of its own (the executables hold the packed / gathered records in them)
 int lsq_device_alloc(lsq_ctx *c, uint64_t bytes, void **out) LSQ_API_TRY {
 	if (!c || !out) return fail(LSQ_E_ARG, "null argument");
 	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = ensure_lanes(c); if (rc) return rc; }
 	HIP_TRY(hipMalloc(out, (size_t)std::max<uint64_t>(bytes, 8)));
 	// zeroed on the result stream, i.e. ahead of any hand-off into the buffer (a plain hipMemset runs on the null stream,
 	// which the context's non-blocking streams do not wait for: it could land behind the pack and wipe it)
@@ -914,6 +934,18 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 	} else if (n == "count_streams") {
 		{ int rc = sync_all(c); if (rc) return rc; }
 		c->opt_two_count_streams = value >= 2;
+	} else if (n == "counter_sets") {
+		// (the rotation of run_count; every set but the latest count's is zero at any time, so either number may follow the other --
+		// but only between steps: a count in flight has its successor's set and mark chosen by the number it was submitted under)
+		if (!(value == 2 || value == LSQ_COUNTER_SETS)) return fail(LSQ_E_ARG, "counter_sets must be 2 or %d", LSQ_COUNTER_SETS);
+		{ int rc = ensure_lanes(c); if (rc) return rc; }
+		HIP_TRY(hipSetDevice(c->device));
+		for (const hipStream_t q : {c->stream_count2[0], c->stream_count2[1], c->stream_em2[0], c->stream_em2[1], c->stream}) {
+			const hipError_t e = hipStreamQuery(q);
+			if (e == hipErrorNotReady) return fail(LSQ_E_STATE, "counter_sets may only be set while nothing is in flight (lsq_ctx_synchronize first)");
+			if (e != hipSuccess) return fail(LSQ_E_DEVICE, "hipStreamQuery: %s", hipGetErrorString(e));
+		}
+		c->opt_counter_sets = (int)value;
 	} else if (n == "em_flat_min_events") {
 		if (!(value >= 0 && value <= 4e9)) return fail(LSQ_E_ARG, "em_flat_min_events must lie in 0..4e9");
 		c->em.opt_flat_min = (unsigned)value;

@@ -37,6 +37,7 @@ constexpr unsigned P2_GROUP_PAD = LSQ_P2_PAD;      // ... and a junction group o
 constexpr unsigned P1_GROUP_PAD = LSQ_P1_PAD;      // records a cell's group of the one-block pool is padded to: what a lane of the count kernel takes per look
 constexpr int LSQ_INGEST_STAGES = 7;     // newline count, route, partition count, partition scatter, group classify, group offsets, group place
 constexpr int LSQ_INGEST_PASS_MAX = 16;  // ... and room for the passes a read file clocks ahead of its route (a BAM file: inflate, CRC32s, record starts)
+constexpr int LSQ_COUNTER_SETS = 3;  // counter sets a context holds (lsq_ctx::set)
 constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
 
 namespace lsq {
@@ -141,7 +142,7 @@ struct IngestPass {
 };
 
 struct MethodReads {
-	DevBuf<ExcEntry> exc;                  // exception lists: two halves of exc_cap entries, one per counter set
+	DevBuf<ExcEntry> exc;                  // exception lists: LSQ_COUNTER_SETS stretches of exc_cap entries, one per counter set
 	size_t exc_cap = 0;
 	bool present = false;
 	uint64_t n_retained = 0, n_retained_blocks = 0, total_slots = 0;
@@ -250,15 +251,15 @@ struct lsq_ctx {
 	// The EM and the hand-off of results run on a stream of their own: the EM ends in a long tail
 	// of a few slow events on an otherwise idle device, and the next lsq_count may run beside it.
 	// So do the zeroing of the counters and the exception pass of a count (lsq_count_cleanup_kernel).
-	// For that the counters and the exception lists exist twice (a count writes the set the solve
-	// before last read); ev_counted: end of the latest count's streaming kernels; ev_mark: recorded
-	// on the result stream when a count is submitted, behind the zeroing of the set the NEXT count
-	// writes -- that count waits for it, i.e. for the readers of its set and not for the EM in between.
-	// ... and all of that exists twice, as two LANES that consecutive counts take in turn: a counter set, exception
-	// lists, a result stream, the EM's output arrays and the two events.  The EM of step k (a chain of dependent passes on a
+	// For that the counters and the exception lists exist more than once (counter sets, below: a count writes a set
+	// whose readers are steps back); ev_counted: end of the latest count's streaming kernels; ev_mark: recorded
+	// on the result stream when a count is submitted, behind the zeroing of the set of the count before -- the count
+	// that takes that set next waits for it, i.e. for the readers of its set and not for the EMs in between.
+	// ... and the streams exist twice, as two LANES that consecutive counts take in turn: a count stream, a result
+	// stream, the EM's output arrays and ev_counted.  The EM of step k (a chain of dependent passes on a
 	// handful of waves) then runs beside the exception pass and the EM of step k+1 instead of ahead of them: with small
 	// shards (a rank of an event-sharded job) the result stream's chain, not the count kernel, bounded the step.
-	hipStream_t stream_em = nullptr;        // the latest count's lane (= stream_em2[flip])
+	hipStream_t stream_em = nullptr;        // the latest count's lane (= stream_em2[lane])
 	hipStream_t stream_em2[2] = {nullptr, nullptr};
 	// A lane's counts run on a stream of the lane's own: consecutive counts write different counter sets and share only
 	// what they read, so the next count's workgroups may fill the compute units the tail of this one leaves idle, and no
@@ -266,9 +267,16 @@ struct lsq_ctx {
 	hipStream_t stream_count2[2] = {nullptr, nullptr};
 	bool opt_two_count_streams = true;
 	int opt_wg_per_cu = -1;                 // "workgroups_per_cu": resident workgroups of the count kernel per compute unit (lsq_count.hip)
-	hipEvent_t ev_counted2[2] = {nullptr, nullptr}, ev_mark2[2] = {nullptr, nullptr};
-	bool mark_recorded2[2] = {false, false};
-	int flip = 0;                           // counter set of the latest count
+	// LANE and COUNTER SET are two things.  The lanes stay two -- streams, ev_counted2, the EM's outputs -- and consecutive
+	// counts take them in turn.  The counter sets (counters, exception lists, the exception pass's argument records, ev_mark2) are
+	// LSQ_COUNTER_SETS, of which counts take the first `opt_counter_sets` in turn: with three, count k+1 waits for the readers of step k-2
+	// and not for those of step k-1, whose chain (exception pass, EM, hand-off, zeroing) otherwise stands between two counts of a lane.
+	// Every set but the latest count's is zero or has its zeroing queued, its mark recorded behind that: whichever comes next may be taken.
+	hipEvent_t ev_counted2[2] = {nullptr, nullptr}, ev_mark2[LSQ_COUNTER_SETS] = {};
+	bool mark_recorded2[LSQ_COUNTER_SETS] = {};
+	int lane = 0;                           // lane of the latest count
+	int set = 0;                            // counter set of the latest count
+	int opt_counter_sets = LSQ_COUNTER_SETS;      // "counter_sets": 2 or 3 (set only while nothing is in flight)
 	size_t counters_per_set = 0;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	hipEvent_t evt0 = nullptr, evt1 = nullptr;      // around a text copy (lsq_text_stage may run beside other host work)
@@ -301,7 +309,7 @@ struct lsq_ctx {
 	DevBuf<double> fim, fim_var;
 	size_t fim_starts_total = 0, fim_mat_total = 0;
 	bool fim_uploaded = false, fim_done = false;
-	DevBuf<unsigned long long> counters;   // two sets of cnt | bases | exc_count | dbg (one memset per count); the views below are the latest count's
+	DevBuf<unsigned long long> counters;   // LSQ_COUNTER_SETS sets of cnt | bases | exc_count | dbg (one memset per count); the views below are the latest count's
 	DevView<unsigned long long> cnt, bases, dbg;
 	DevBuf<unsigned long long> wg_trace;   // developer build (LSQ_ABLATE 4194304): lsq_debug_wg_trace
 	unsigned long long wg_trace_n = 0, wg_trace_workers = 0;
@@ -397,5 +405,5 @@ void note_overflow(lsq_ctx *c, const std::vector<unsigned> &exc_count);      // 
 int host_count(lsq_ctx *c);                          // lsq_replay.hip: host buckets (genes beyond the kernels' limits)
 int host_solve(lsq_ctx *c);
 int replay_flagged(lsq_ctx *c, unsigned *n_done);    // lsq_replay.hip: the EM of guard-band events in the reference's per-read order
-void select_counter_set(lsq_ctx *c, int set);                           // lsq_em.hip
+void select_counter_set(lsq_ctx *c, int lane, int set);                 // lsq_device.hip: the views of the latest count's lane and counter set
 } // namespace lsq

@@ -932,7 +932,7 @@ static int launch_lean(lsq_ctx *c, EmArgs A) {
 	const lsq_events &E = *c->E;
 	EmState &S = c->em;
 	hipStream_t st = c->stream_em;
-	const int lane = c->flip;
+	const int lane = c->lane;
 	// one wave per workgroup: beside a streaming kernel that fills the device, a wave that is done gives its
 	// registers back without waiting for three others (measured 0.259 -> 0.254 ms per pipelined step)
 	const unsigned blk = 64, np = S.small_places, n_lane_wg = (np + blk - 1) / blk;
@@ -986,7 +986,7 @@ int run_solve(lsq_ctx *c) {
 	if (c->time_events) HIP_TRY(hipEventRecord(c->ev2, st));
 	const unsigned n_ev = (unsigned)E.dev2out.size();
 	c->em.last = {};
-	c->em.last.lane = (unsigned)c->flip;
+	c->em.last.lane = (unsigned)c->lane;
 	if (n_ev) {
 		EmArgs A{};
 		A.n_events = n_ev; A.n_methods = (unsigned)E.n_methods; A.n_cls = E.n_cls_total; A.n_iso = E.n_iso_total;

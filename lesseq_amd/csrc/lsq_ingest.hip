@@ -698,7 +698,7 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 		size_t want = std::max<size_t>(65536, (n1 + n2) / 4);
 		if (c->opt_exc_cap) want = c->opt_exc_cap;           // lsq_ctx_set_option "exception_capacity" (the tests provoke the overflow path with it)
 		if (mr.exc_cap != want) {
-			if ((rc = mr.exc.alloc(2 * want))) return rc;
+			if ((rc = mr.exc.alloc(LSQ_COUNTER_SETS * want))) return rc;          // one list a counter set
 			mr.exc_cap = want;
 		}
 	}
