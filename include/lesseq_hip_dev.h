@@ -1,7 +1,7 @@
 /* lesseq_hip_dev.h -- developer entry points of liblesseq_hip.so, beside the product ABI of
  * lesseq_hip.h.  Nothing here replaces anything in the reference; the tools under tools/ and a
  * few tests use them to look inside a run (tools/kbench.py, tools/step_bench.py,
- * tests/test_parity_gpu.py, tests/test_em_direct_gpu.py).  They may change without notice. */
+ * tests/test_parity_gpu.py, tests/test_em_direct_gpu.py, tests/test_prims_direct_gpu.py).  They may change without notice. */
 #ifndef LESSEQ_HIP_DEV_H
 #define LESSEQ_HIP_DEV_H
 
@@ -81,6 +81,21 @@ int lsq_debug_bgzf_inflate(lsq_ctx *c, const void *bytes, uint64_t len, void *ou
  * device COMPUTED for every block's inflated bytes, in file order, into crc (cap entries; *n = the number of blocks, also when
  * cap is too small: LSQ_E_RANGE then).  The stored values are not looked at; a test holds the result against zlib. */
 int lsq_debug_bgzf_crc32(lsq_ctx *c, const void *bytes, uint64_t len, uint32_t *crc, uint64_t cap, uint64_t *n);
+
+/* The device prefix sum alone (csrc/lsq_scan.hpp, device_scan): in (n values) uploaded, scanned on the context's stream, and
+ * out[i] = the sum of f(in[0 .. i)) copied back, out[n] the total (n + 1 values; n == 0 gives out[0] == 0).  form names the
+ * instantiations the library uses -- 0: 32-bit values as they are, 1: 32-bit values as 0 / 1 flags, 2: 64-bit values as they
+ * are, 3 / 4: 32-bit values rounded up to a multiple of the two-block / one-block pool's group padding (P2_GROUP_PAD /
+ * P1_GROUP_PAD of csrc/lsq_device.hpp); in holds uint64_t for form 2 and uint32_t otherwise.  Another form: LSQ_E_ARG. */
+int lsq_debug_scan(lsq_ctx *c, int form, const void *in, uint64_t n, uint64_t *out /* n + 1 */);
+
+/* The device radix sort alone (csrc/lsq_sort.hpp, device_radix_sort): the n records (w0[i], w1[i]) sorted in place, stably, by
+ * the 8-bit digits that begin at the bit positions bits[0 .. n_bits) of the 128 bits w1:w0 (bit 64 + k = bit k of w1), least
+ * significant first as listed; bits that no digit names ride along.  With drop_constant_digits the digits on which all
+ * records agree are left out first (sort_digits), as the library's callers do.  *n_passes = the digits sorted by (0 for fewer
+ * than two records, which take no pass).  A position above 120 or more than 16 digits: LSQ_E_ARG. */
+int lsq_debug_sort(lsq_ctx *c, uint64_t *w0, uint64_t *w1, uint64_t n, const unsigned *bits, unsigned n_bits,
+                   int drop_constant_digits, unsigned *n_passes);
 
 /* HIP_VERSION the library was compiled against and hipRuntimeGetVersion() of the runtime it found in the process (0
  * when that call fails, e.g. without a driver): a binding that loads another runtime first (PyTorch's) can compare. */

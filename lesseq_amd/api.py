@@ -387,6 +387,31 @@ class Context:
             check(st)
             return [int(v) for v in out[:n.value]]
 
+    SCAN_FORMS = ("u32", "flag", "u64", "pad_p2", "pad_p1")
+
+    def debug_scan(self, form, values):
+        """the device prefix sum alone (lsq_debug_scan): len(values) + 1 uint64, the last the total.  form: an index into, or a
+        name of, SCAN_FORMS -- 32-bit values, 32-bit values as 0 / 1 flags, 64-bit values, 32-bit values rounded up to the
+        two-block / one-block pool's group padding"""
+        form = self.SCAN_FORMS.index(form) if isinstance(form, str) else int(form)
+        v = np.ascontiguousarray(values, dtype=np.uint64 if form == 2 else np.uint32)
+        out = np.empty(len(v) + 1, dtype=np.uint64)
+        check(lib.lsq_debug_scan(self.h, form, v.ctypes.data_as(vp), len(v), _ptr(out, u64)))
+        return out
+
+    def debug_sort(self, w0, w1, bits, drop_constant=False):
+        """the device radix sort alone (lsq_debug_sort): the records (w0[i], w1[i]) in stable order by the 8-bit digits at `bits`
+        (positions in the 128 bits w1:w0, least significant first as listed) as two new uint64 arrays, and the passes made"""
+        a = np.array(w0, dtype=np.uint64)           # (copies: the call sorts in place)
+        b = np.array(w1, dtype=np.uint64)
+        if a.ndim != 1 or a.shape != b.shape:
+            raise ValueError("w0 and w1 are two one-dimensional arrays of one length")
+        bits = [int(x) for x in bits]
+        cb = (C.c_uint * max(len(bits), 1))(*bits)
+        n_passes = C.c_uint()
+        check(lib.lsq_debug_sort(self.h, _ptr(a, u64), _ptr(b, u64), len(a), cb, len(bits), int(bool(drop_constant)), C.byref(n_passes)))
+        return a, b, n_passes.value
+
     def bam_check(self, path):
         """a whole BAM file checked on the device chain, CRC32s and end-of-file marker included; the context needs no events
         (lsq_bam_check): the report's fields as a dict"""

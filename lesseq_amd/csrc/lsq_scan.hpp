@@ -6,6 +6,12 @@
 // FLAG, turns it into 0 / 1.  Three launches over blocks of 4 096 values: block sums, one workgroup over the block sums
 // (a wave scan per 64, then over the waves), the blocks again with their bases.  A million values take ~15 us; the
 // one-workgroup form this replaces took 0.6-2.4 ms of a C3 ingest each, seven times.
+//
+// Domain.  The 32-bit forms with PAD > 1 round up in 32 bits: a value above 2^32 - PAD wraps to 0.  Their values are the
+// records of a group -- far below that -- and no caller has others.  The sums themselves are 64 bits in every form.
+// Paths.  More than SCAN_BLOCK values: a second block.  More than 1 024 * SCAN_BLOCK = 4 194 304: a second round of the
+// spine, which carries its running total on.  tests/test_prims_direct_gpu.py holds every form on both sides of both
+// (lsq_prims.hip: lsq_debug_scan).
 #pragma once
 
 namespace {

@@ -11,6 +11,7 @@
 //   scatter     the tile again: a wave takes a quarter of the tile, in order; its records' ranks among equals come from wave
 //               ballots (no atomics: the order of equals is the input's, so the sort is stable and the same from run to run).
 // The digit table is 1 KiB a tile against 64 KiB of records.
+// tests/test_prims_direct_gpu.py holds the whole permutation against the definition (lsq_prims.hip: lsq_debug_sort).
 #pragma once
 
 namespace {
