@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*) or "exonbins" (lsq_xb_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*) or "psi" (lsq_ps_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -810,6 +810,73 @@ int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]);
 /* The table's text; the two bins texts of an index; malloc'd, NUL-terminated (lsq_free). */
 int lsq_xb_format(const lsq_xb_table *t, char **out_text);
 int lsq_xb_format_bins(const lsq_xb_index *ix, char **interval_text, char **map_text);
+
+/* ------------------------------------------------------------------------------------
+ * Junction reads per event form of a read file: the junction counts of rMATS, the junction-read PSI of MISO and
+ * SUPPA, in count's four columns -- a count table of `test_as fisher --tables` and `test_as lrt --tables`
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition, on the arrays the parsers above give (blocks 0-based half-open, in file order, unmerged):
+ *   annotation     any isoform file with its gene->isoform file, normally the pair `events` writes.  An event is a gene of the map,
+ *                  its forms are its isoform lines; events in the loader's order, an event's forms in the order of its lines in the
+ *                  map: the order in which count prints them.  No event is compiled: any number of forms and exons.  An event the
+ *                  map gives no isoform (WORMBASE_GENE2ISOFORMS allows it) has no form and no row; an isoform the map names that
+ *                  has no line is the loader's error, as for every tool.
+ *   chromosomes    as for lsq_jn_index: the distinct chromosome strings of the annotation's isoform lines.  A block on another
+ *                  chromosome, or with a coordinate outside +-2^30, has no chromosome (the parsers' own rule).
+ *   introns        of a form: the gaps between the maximal intervals of the union of the line's exons with end > start (the first
+ *                  exonCount of them), exactly lsq_jn_index_build's; keyed (chromosome, end of the left interval, start of the right
+ *                  one).  An intron with an end outside (-2^30, 2^30) matches nothing and is none.
+ *   informative    D(f): the introns of form f that are not introns of every form of its event.  An event of one form has none.
+ *   junctions      of a read, S(r): exactly lsq_jn's rule -- blocks b and b + 1 in file order, both on a chromosome and on the same one,
+ *                  start[b + 1] > end[b], min(length of b, length of b + 1) >= min_overhang (at least 1, else LSQ_E_ARG); the
+ *                  junction is (chromosome, end[b], start[b + 1]).  Strand plays no part.
+ *   counts         reads[form]: the reads r whose S(r) meets D(f), each once however many of its junctions do; total[event]: the
+ *                  reads whose S(r) meets the union of the event's D(f), each once.  An intron may be informative in many forms
+ *                  and many events: the read counts in each.  Both are uint64.
+ *   report         reads in the file, blocks in the file, junction occurrences that pass the rule, block pairs below the overhang,
+ *                  block pairs with a block on no chromosome, occurrences found among the informative introns, reads counted for at
+ *                  least one event, reads counted for more than one.
+ *   table          a row per form, events in order, zeros included: event TAB total[event] TAB form TAB reads[form] NL.
+ *   psi            with_psi appends TAB introns TAB psi, introns = |D(f)|.  On the host, in double, from the integers, in this order:
+ *                  x_f = reads_f / introns_f; den = the sum of x_g over the event's forms in row order; psi_f = x_f / den, printed
+ *                  %.6f.  Every form of an event prints NA when any of its forms has introns 0 or when den is 0: retained-intron and
+ *                  tandem-UTR events, whose one form has no intron of its own, always do.
+ * Limits: 2^32-2 forms, 2^32-2 (form, informative intron) pairs, 65 535 chromosomes.  Beyond a limit: LSQ_E_RANGE. */
+typedef struct lsq_ps_index lsq_ps_index;       /* the dictionaries, the forms event-major, per chromosome the informative introns with their forms */
+typedef struct lsq_ps_table lsq_ps_table;
+int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out);
+void lsq_ps_index_free(lsq_ps_index *ix);
+int64_t lsq_ps_index_num_chroms(const lsq_ps_index *ix);
+int64_t lsq_ps_index_num_events(const lsq_ps_index *ix);
+int64_t lsq_ps_index_num_forms(const lsq_ps_index *ix);
+int64_t lsq_ps_index_num_introns(const lsq_ps_index *ix);                 /* the distinct informative introns */
+const char *lsq_ps_index_chrom_name(const lsq_ps_index *ix, int64_t chrom);      /* NULL when out of range */
+const char *lsq_ps_index_event_name(const lsq_ps_index *ix, int64_t event);
+const char *lsq_ps_index_form_name(const lsq_ps_index *ix, int64_t form);
+lsq_events *lsq_ps_index_dictionaries(lsq_ps_index *ix);                  /* as lsq_jn_index_dictionaries */
+/* Per event its first form (num_events + 1 entries), per form |D(f)| (the arrays live as long as the index; either pointer may be null) */
+int lsq_ps_index_arrays(const lsq_ps_index *ix, const uint32_t **event_first_form, const uint32_t **form_introns);
+/* Host-only, threaded: the table from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  lsq_ps_host_reads: from arrays parsed against the index. */
+int lsq_ps_host(lsq_ps_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, int n_threads,
+                lsq_ps_table **out);
+int lsq_ps_host_reads(lsq_ps_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_ps_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed exactly as lsq_jn_device parses it, then one count kernel
+ * over the device arrays; the counters alone come back.  The context needs no events, and its events, reads and counters are as
+ * they were afterwards.  LSQ_PS_GRID in the environment bounds the count's workgroups (tests). */
+int lsq_ps_device(lsq_ctx *c, lsq_ps_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ps_table **out);
+void lsq_ps_table_free(lsq_ps_table *t);
+/* reads[num_forms], total[num_events] (they live as long as the table; either pointer may be null) */
+int lsq_ps_table_arrays(const lsq_ps_table *t, const uint64_t **reads, const uint64_t **total);
+int lsq_ps_table_report(const lsq_ps_table *t, uint64_t report[8]);
+/* Device milliseconds per phase of the lsq_ps_device call that made the table -- index upload, count, copy-back -- from HIP events
+ * on the library's stream (zeros from the host path); the parse ahead of them: lsq_last_mrf_timing. */
+int lsq_ps_table_times(const lsq_ps_table *t, float ms[3]);
+/* psi[num_forms] as the text prints it before rounding, NaN where it prints NA */
+int lsq_ps_table_psi(const lsq_ps_table *t, double *psi);
+/* The table's text, four columns or (with_psi) six; malloc'd, NUL-terminated (lsq_free). */
+int lsq_ps_format(const lsq_ps_table *t, int with_psi, char **out_text);
 
 /* ------------------------------------------------------------------------------------
  * Local events: step 2 of the pipeline, bin/Events.r

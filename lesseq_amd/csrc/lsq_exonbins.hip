@@ -1,7 +1,7 @@
 // The reads per exon bin and per gene of a parsed read file on the device (include/lesseq_hip.h, lsq_xb_device): three
 // phases over device arrays -- index upload, count (a lane a read: every block a binary search in its chromosome's cells and a
 // walk over them; a read counts once a bin and once a gene by predicates alone, no per-lane list; equal ids are combined inside the
-// wave, then added to the workgroup's own counters in LDS, or to the global ones where the id has no slot there), copy-back (the
+// wave, then added to the workgroup's own counters in LDS, or to the global ones where the id has no slot there: lsq_wave.hpp), copy-back (the
 // counters).  Every number is an integer and sums commute: no result depends on the order in which lanes arrive.
 #include "lsq_wave.hpp"
 #include "lsq_exonbins.hpp"
@@ -28,48 +28,8 @@ __device__ inline bool xb_gene_overlaps(const XbIndex &I, unsigned first, unsign
 	return lo < last && I.bin_start[lo] < e;
 }
 
-// A workgroup's own counters in LDS, for the ids it meets first: SLOTS keys (XB_NONE: free) and 64-bit counts.  A key is set once
-// and never changes.  An id whose slot another id holds goes to the global counter at once; the slots are added to the global
-// counters when the workgroup has done all its reads.  With every hit a global atomic, a shuffled 100 M-read library -- whose
-// largest gene takes 12 M hits -- spent 65 of the count's 77 ms on them: a wave's lanes mostly differ there, and the atomics of
-// all waves on a hot id queue at one address.  A hot id is met early, so it finds a slot: one global atomic a workgroup.
-template <unsigned SLOTS>
-struct XbLocal {
-	unsigned key[SLOTS];
-	unsigned long long cnt[SLOTS];
-	__device__ void clear() {
-		for (unsigned i = threadIdx.x; i < SLOTS; i += 256u) { key[i] = XB_NONE; cnt[i] = 0ull; }
-	}
-	__device__ void add(unsigned long long *counter, unsigned id, unsigned long long n) {
-		const unsigned slot = (id * 2654435761u) >> 16 & (SLOTS - 1u);
-		const unsigned was = atomicCAS(&key[slot], XB_NONE, id);
-		if (was == XB_NONE || was == id) atomicAdd(&cnt[slot], n);
-		else atomicAdd(&counter[id], n);
-	}
-	__device__ void flush(unsigned long long *counter) const {
-		for (unsigned i = threadIdx.x; i < SLOTS; i += 256u) if (key[i] != XB_NONE && cnt[i]) atomicAdd(&counter[key[i]], cnt[i]);
-	}
-};
-
-// Every lane of the wave arrives (the callers' loops are uniform): the lanes that hold an id, equal ids found by a ballot on the
-// first such lane's id; that lane keeps their number.  When every id has its lane, those lanes add, all in one instruction.  In
-// a coordinate-sorted file the 64 reads of a wave mostly hold one id: one round and one add where there were 64 on one address.
-template <unsigned SLOTS>
-__device__ inline void xb_wave_add(XbLocal<SLOTS> &local, unsigned long long *counter, unsigned id, unsigned lane) {
-	unsigned long long todo = __ballot(id != XB_NONE);
-	unsigned mine = 0;
-	while (todo) {
-		const unsigned leader = (unsigned)__ffsll((long long)todo) - 1u;
-		const unsigned id0 = (unsigned)__shfl((int)id, (int)leader);
-		const unsigned long long same = __ballot(id == id0);      // (id0 is not XB_NONE: lanes without an id never match)
-		if (lane == leader) mine = (unsigned)__popcll(same);
-		todo &= ~same;
-	}
-	if (mine) local.add(counter, id, mine);
-}
-
 // A lane a read, a fixed number of workgroups striding over the reads.  A lane walks its read's (block, cell, bin) triples up to
-// the next one that counts, then the whole wave combines what its lanes found (xb_wave_add) and goes on: as many rounds as the
+// the next one that counts, then the whole wave combines what its lanes found (lsq_wave.hpp's wave_add_ids) and goes on: as many rounds as the
 // wave's busiest read has hits.  What counts:
 //   a (block k, bin) pair is looked at in the bin's first cell of block k's walk: the walk's first cell, or the cell the bin begins at;
 //   the bin counts unless an earlier block j < k of the read overlaps it too (the blocks come in any order: every j is tried);
@@ -80,8 +40,8 @@ __device__ inline void xb_wave_add(XbLocal<SLOTS> &local, unsigned long long *co
 // (36 KiB: four workgroups a compute unit) are added to the global ones behind the same barrier.
 __global__ void __launch_bounds__(256) lsq_xb_count_kernel(ParsedReads R, XbIndex I, unsigned long long *reads, unsigned long long *total, XbAcc *acc) {
 	__shared__ unsigned long long part[4][4];
-	__shared__ XbLocal<2048> local_bins;
-	__shared__ XbLocal<1024> local_genes;
+	__shared__ WgCounters<2048> local_bins;
+	__shared__ WgCounters<1024> local_genes;
 	local_bins.clear(); local_genes.clear();
 	__syncthreads();
 	const unsigned lane = threadIdx.x & 63u;
@@ -139,8 +99,8 @@ __global__ void __launch_bounds__(256) lsq_xb_count_kernel(ParsedReads R, XbInde
 			if (!__any(hit_bin != XB_NONE)) break;
 			if (hit_bin != XB_NONE) ++hits;
 			if (hit_gene != XB_NONE) ++genes;
-			xb_wave_add(local_bins, reads, hit_bin, lane);
-			xb_wave_add(local_genes, total, hit_gene, lane);
+			wave_add_ids(local_bins, reads, hit_bin, lane);
+			wave_add_ids(local_genes, total, hit_gene, lane);
 		}
 		if (have && genes == 0) ++none;
 		if (genes > 1) ++multi;

@@ -91,19 +91,15 @@ int lsq_jn_index_build(const lsq_annotation *a, lsq_jn_index **out) LSQ_API_TRY 
 	if ((rc = annotation_dictionaries(*a, E))) return rc;
 	struct Intron { uint32_t chrom; uint64_t key; uint8_t ann; };
 	std::vector<Intron> in;
-	std::vector<std::pair<int64_t, int64_t>> ex;
+	std::vector<std::pair<int64_t, int64_t>> ex, gaps;
 	for (const auto &rp : a->recs) {
 		const IsoRec &r = *rp;
 		const int cid = E.chroms.find(r.chrom);
 		// the union of the line's exons: its maximal intervals, and the gaps between them
-		ex.clear();
-		exon_union(r, ex);
+		gaps.clear();
+		line_introns(r, ex, gaps);
 		const uint8_t ann = r.strand == "+" ? '+' : r.strand == "-" ? '-' : '*';
-		int64_t reach = 0;
-		for (size_t i = 0; i < ex.size(); ++i) {
-			if (i && ex[i].first > reach && reach > -JN_BIAS && ex[i].first < JN_BIAS) in.push_back(Intron{(uint32_t)cid, jn_key(reach, ex[i].first), ann});
-			reach = i ? std::max(reach, ex[i].second) : ex[i].second;
-		}
+		for (const auto &g : gaps) in.push_back(Intron{(uint32_t)cid, jn_key(g.first, g.second), ann});
 	}
 	std::sort(in.begin(), in.end(), [](const Intron &x, const Intron &y) { return x.chrom != y.chrom ? x.chrom < y.chrom : x.key < y.key; });
 	for (const Intron &i : in) {

@@ -2,8 +2,8 @@
 // (ReadSource), and the entry points that take one -- through the chain (lsq_ingest.hip) for count and solve, into the arrays of
 // lsq_mrf_parse for tests and tools, or over its records alone (lsq_bam_check).  The parsers themselves are lsq_mrf_device.hpp,
 // lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only.  The tools that take a
-// read file against an index's dictionaries (junctions, coverage, exonbins) enter through table_of_file: their passes
-// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
+// read file against an index's dictionaries (junctions, coverage, exonbins, psi) enter through table_of_file: their passes
+// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -14,6 +14,7 @@
 #include "lsq_junc.hpp"
 #include "lsq_cov.hpp"
 #include "lsq_exonbins.hpp"
+#include "lsq_psi.hpp"
 
 namespace {
 
@@ -337,7 +338,7 @@ int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const
 	return parse_staged_text(c, fmt, T, P);
 }
 
-// lsq_jn_device, lsq_cov_device, lsq_xb_device behind their argument checks: the file parsed against the index's dictionaries, a
+// lsq_jn_device, lsq_cov_device, lsq_xb_device, lsq_ps_device behind their argument checks: the file parsed against the index's dictionaries, a
 // new table filled from the device arrays by the tool's passes (fill(reads, table)) and handed out
 template <class IX, class T, class F>
 int table_of_file(lsq_ctx *c, IX *ix, const char *read_format, const char *path, T **out, F fill) {
@@ -508,6 +509,13 @@ int lsq_cov_device(lsq_ctx *c, lsq_cov_index *ix, const char *read_format, const
 int lsq_xb_device(lsq_ctx *c, lsq_xb_index *ix, const char *read_format, const char *path, lsq_xb_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_xb_table &t) { return xb_device_reads(c, *ix, R, t); });
+} LSQ_API_CATCH
+
+// The junction reads per event form of a read file (include/lesseq_hip.h): the device arrays handed to lsq_psi.hip
+int lsq_ps_device(lsq_ctx *c, lsq_ps_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ps_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_ps_table &t) { return ps_device_reads(c, *ix, R, min_overhang, t); });
 } LSQ_API_CATCH
 
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {

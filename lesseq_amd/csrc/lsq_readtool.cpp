@@ -1,6 +1,6 @@
 // What the tools that take an annotation and a read file share on the host (lsq_readtool.hpp): the dictionaries of an index, a
-// read file through its host parser, a line's exon union, the tables' row order, and the frame of the junctions, coverage and
-// exonbins executables -- arguments, owned handles, the log on failure, the output file.
+// read file through its host parser, a line's exon union and introns, the tables' row order, and the frame of the junctions,
+// coverage, exonbins and psi executables -- arguments, owned handles, the log on failure, the output file.
 #include <cerrno>
 #include <cstdlib>
 #include <numeric>
@@ -68,6 +68,17 @@ void lsq::exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &
 	for (size_t i = 0; i < ne; ++i) if (r.exonEnds[i] > r.exonStarts[i]) sorted_exons.emplace_back(r.exonStarts[i], r.exonEnds[i]);
 	std::sort(sorted_exons.begin() + held, sorted_exons.end());
 	std::inplace_merge(sorted_exons.begin(), sorted_exons.begin() + held, sorted_exons.end());
+}
+
+void lsq::line_introns(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &ex, std::vector<std::pair<int64_t, int64_t>> &introns) {
+	constexpr int64_t LIM = (int64_t)1 << 30;
+	ex.clear();
+	exon_union(r, ex);
+	int64_t reach = 0;
+	for (size_t i = 0; i < ex.size(); ++i) {
+		if (i && ex[i].first > reach && reach > -LIM && ex[i].first < LIM) introns.emplace_back(reach, ex[i].first);
+		reach = i ? std::max(reach, ex[i].second) : ex[i].second;
+	}
 }
 
 bool lsq::cli_u32_option(int argc, const char *const *argv, int &i, unsigned long &v) {

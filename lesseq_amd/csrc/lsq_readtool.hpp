@@ -1,7 +1,7 @@
-// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins):
+// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi):
 // the view of parsed reads their passes take, the dictionaries a read file is parsed against without events, a line's exon
-// union, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
-// the frame of the three executables.  lsq_readtool.cpp defines what is no template.
+// union and its introns, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
+// the frame of the four executables.  lsq_readtool.cpp defines what is no template.
 #pragma once
 
 #include <algorithm>
@@ -38,6 +38,10 @@ std::vector<size_t> rows_by_chrom_name(const std::vector<std::string> &names, co
 // The exons of a line that are not empty (no more than exonCount of them) merged into `sorted_exons` (empty, or other lines'
 // exons in order): the exon union is what a walk with a running maximum of the ends makes of the list
 void exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &sorted_exons);
+// The introns of a line appended to `introns`, ascending: the gaps between the maximal intervals of its exon union (`ex`: the
+// union, scratch), each as (end of the left interval, start of the right one); a gap with an end outside (-2^30, 2^30) -- where no
+// block with a chromosome reaches -- is left out
+void line_introns(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &ex, std::vector<std::pair<int64_t, int64_t>> &introns);
 bool write_file(const char *path, const char *text);       // false: the status and text of the failure are set (LSQ_E_IO)
 
 // ---- the reads over host threads: T slices of whole reads, one slice below 2^16 reads; f(k, r0, r1) on a thread of its own
