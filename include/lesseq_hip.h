@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*) or "psi" (lsq_ps_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*) or "evidence" (lsq_fe_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -877,6 +877,82 @@ int lsq_ps_table_times(const lsq_ps_table *t, float ms[3]);
 int lsq_ps_table_psi(const lsq_ps_table *t, double *psi);
 /* The table's text, four columns or (with_psi) six; malloc'd, NUL-terminated (lsq_free). */
 int lsq_ps_format(const lsq_ps_table *t, int with_psi, char **out_text);
+
+/* ------------------------------------------------------------------------------------
+ * Form evidence: junction and exon-body reads per event form of a read file -- the junction counts plus exon counts
+ * (JCEC) of rMATS, in count's four columns: a count table of `test_as fisher --tables` and `test_as lrt --tables`.  Beside lsq_ps_*,
+ * which stays as it is: a retained-intron event, whose retaining form has no intron of its own, gets its evidence here.
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition.  Annotation, chromosomes, events, forms and their order, a form's exon union U(f), its introns, the informative
+ * introns D(f) and the junctions S(r) of a read under min_overhang are lsq_ps_*'s above, to the letter.  New:
+ *   common bases   C(e): the bases that lie in U(g) of every form g of event e (none where two forms lie on different chromosomes).
+ *   body           B(f) = U(f) \ C(e) as maximal intervals, the form's regions.  An event of one form has none.  The regions of one
+ *                  form are disjoint and never abut.  Coordinates are clamped to [-2^30, 2^30], as the exon-bin index clamps; a
+ *                  region that is empty after clamping is none.
+ *   body hit       block b of a read hits region [a, z) of form f when the block is on the form's chromosome (a chromosome of the
+ *                  dictionaries: coordinates inside (-2^30, 2^30)), start < end, and min(end_b, z) - max(start_b, a) >= min_body
+ *                  (at least 1, else LSQ_E_ARG).  Strand plays no part.
+ *   counts         reads[form]: the reads r with a junction of S(r) in D(f) or a block that hits a region of f, each once however
+ *                  much of either; total[event]: the reads that count for any form of the event, each once.  A region or intron
+ *                  that is informative in several forms or events counts the read in each.  Both are uint64.
+ *   report         eleven: reads, blocks, junction occurrences that pass the rule, block pairs below the overhang, block pairs with a
+ *                  block on no chromosome, occurrences found among the informative introns (lsq_ps_*'s first six); skipped blocks
+ *                  (on no chromosome, out of range or empty); body hits, the (block, region) couples that pass the rule; reads
+ *                  counted for at least one event; for more than one; reads counted for an event none of whose junctions is an
+ *                  informative intron (counted by body alone).
+ *   table          a row per form, events in order, zeros included: event TAB total[event] TAB form TAB reads[form] NL.
+ *   positions      of form f under a read length L (1 <= L < 2^18): take every start s of an ungapped L-base read laid along the
+ *                  form's own concatenated exon union; its blocks are the pieces of the union's intervals it covers; positions(f)
+ *                  is the number of starts at which the counts' rule counts the read for f, 0 when the form is shorter than L.
+ *                  Equally: the size of the union, clipped to [0, T - L] (T the form's length), of the windows
+ *                  [t - L + min_overhang, t - min_overhang] for each informative intron at transcript offset t whose two neighbouring
+ *                  union intervals are both at least min_overhang long, and [a - L + min_body, z - min_body] for each region [a, z) in
+ *                  transcript coordinates with z - a >= min_body (none when L < min_body).  A form with an exon beyond +-2^30 is
+ *                  enumerated, a piece that leaves the range being a block on no chromosome.
+ *   psi            with_psi appends TAB introns TAB body TAB positions TAB psi: |D(f)|, the bases of B(f), positions(f) under the
+ *                  table's own min_overhang and min_body.  On the host, in double, from the integers, in this order:
+ *                  x_f = reads_f / positions_f; den = the sum of x_g over the event's forms in row order; psi_f = x_f / den, printed
+ *                  %.6f.  Every form of an event prints NA when any of its forms has positions 0 or when den is 0.  A tandem-UTR
+ *                  event still does: its short form is a subset of the long one, no single read can show it.
+ * Limits: lsq_ps_*'s, and 2^32-2 regions.  Beyond a limit: LSQ_E_RANGE. */
+typedef struct lsq_fe_index lsq_fe_index;       /* an lsq_ps_index, the regions form-major, per chromosome the cells with the regions that cover them */
+typedef struct lsq_fe_table lsq_fe_table;
+int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out);
+void lsq_fe_index_free(lsq_fe_index *ix);
+int64_t lsq_fe_index_num_chroms(const lsq_fe_index *ix);
+int64_t lsq_fe_index_num_events(const lsq_fe_index *ix);
+int64_t lsq_fe_index_num_forms(const lsq_fe_index *ix);
+int64_t lsq_fe_index_num_introns(const lsq_fe_index *ix);                 /* the distinct informative introns */
+int64_t lsq_fe_index_num_regions(const lsq_fe_index *ix);                 /* the regions over all forms */
+const char *lsq_fe_index_chrom_name(const lsq_fe_index *ix, int64_t chrom);      /* NULL when out of range */
+const char *lsq_fe_index_event_name(const lsq_fe_index *ix, int64_t event);
+const char *lsq_fe_index_form_name(const lsq_fe_index *ix, int64_t form);
+lsq_events *lsq_fe_index_dictionaries(lsq_fe_index *ix);                  /* as lsq_jn_index_dictionaries */
+/* Per event its first form (num_events + 1 entries), per form |D(f)| and the bases of B(f) (the arrays live as long as the index; any pointer may be null) */
+int lsq_fe_index_arrays(const lsq_fe_index *ix, const uint32_t **event_first_form, const uint32_t **form_introns, const uint64_t **form_body);
+/* positions[num_forms] under a read length and the two thresholds */
+int lsq_fe_index_positions(const lsq_fe_index *ix, uint32_t read_length, uint32_t min_overhang, uint32_t min_body, uint64_t *positions);
+/* Host-only, threaded: the table from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  lsq_fe_host_reads: from arrays parsed against the index. */
+int lsq_fe_host(lsq_fe_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, uint32_t min_body, int n_threads,
+                lsq_fe_table **out);
+int lsq_fe_host_reads(lsq_fe_index *ix, const lsq_reads *r, uint32_t min_overhang, uint32_t min_body, int n_threads, lsq_fe_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed exactly as lsq_jn_device parses it, then one count kernel
+ * over the device arrays; the counters alone come back.  The context needs no events, and its events, reads and counters are as
+ * they were afterwards.  LSQ_FE_GRID in the environment bounds the count's workgroups (tests). */
+int lsq_fe_device(lsq_ctx *c, lsq_fe_index *ix, const char *read_format, const char *path, uint32_t min_overhang, uint32_t min_body, lsq_fe_table **out);
+void lsq_fe_table_free(lsq_fe_table *t);
+/* reads[num_forms], total[num_events] (they live as long as the table; either pointer may be null) */
+int lsq_fe_table_arrays(const lsq_fe_table *t, const uint64_t **reads, const uint64_t **total);
+int lsq_fe_table_report(const lsq_fe_table *t, uint64_t report[11]);
+/* Device milliseconds per phase of the lsq_fe_device call that made the table -- index upload, count, copy-back -- from HIP events
+ * on the library's stream (zeros from the host path); the parse ahead of them: lsq_last_mrf_timing. */
+int lsq_fe_table_times(const lsq_fe_table *t, float ms[3]);
+/* psi[num_forms] under read_length as the text prints it before rounding, NaN where it prints NA */
+int lsq_fe_table_psi(const lsq_fe_table *t, uint32_t read_length, double *psi);
+/* The table's text, four columns or (with_psi, under read_length) eight; malloc'd, NUL-terminated (lsq_free). */
+int lsq_fe_format(const lsq_fe_table *t, int with_psi, uint32_t read_length, char **out_text);
 
 /* ------------------------------------------------------------------------------------
  * Local events: step 2 of the pipeline, bin/Events.r

@@ -306,6 +306,28 @@ _sig("lsq_ps_table_report", C.c_int, vp, P(u64))
 _sig("lsq_ps_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_ps_table_psi", C.c_int, vp, P(C.c_double))
 _sig("lsq_ps_format", C.c_int, vp, C.c_int, P(vp))
+_sig("lsq_fe_index_build", C.c_int, vp, P(vp))
+_sig("lsq_fe_index_free", None, vp)
+_sig("lsq_fe_index_num_chroms", i64, vp)
+_sig("lsq_fe_index_num_events", i64, vp)
+_sig("lsq_fe_index_num_forms", i64, vp)
+_sig("lsq_fe_index_num_introns", i64, vp)
+_sig("lsq_fe_index_num_regions", i64, vp)
+_sig("lsq_fe_index_chrom_name", cs, vp, i64)
+_sig("lsq_fe_index_event_name", cs, vp, i64)
+_sig("lsq_fe_index_form_name", cs, vp, i64)
+_sig("lsq_fe_index_dictionaries", vp, vp)
+_sig("lsq_fe_index_arrays", C.c_int, vp, P(P(u32)), P(P(u32)), P(P(u64)))
+_sig("lsq_fe_index_positions", C.c_int, vp, u32, u32, u32, P(u64))
+_sig("lsq_fe_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, u32, u32, C.c_int, P(vp))
+_sig("lsq_fe_host_reads", C.c_int, vp, vp, u32, u32, C.c_int, P(vp))
+_sig("lsq_fe_device", C.c_int, vp, vp, cs, cs, u32, u32, P(vp))
+_sig("lsq_fe_table_free", None, vp)
+_sig("lsq_fe_table_arrays", C.c_int, vp, P(P(u64)), P(P(u64)))
+_sig("lsq_fe_table_report", C.c_int, vp, P(u64))
+_sig("lsq_fe_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_fe_table_psi", C.c_int, vp, u32, P(C.c_double))
+_sig("lsq_fe_format", C.c_int, vp, C.c_int, u32, P(vp))
 
 
 def _warn_on_runtime_mismatch():

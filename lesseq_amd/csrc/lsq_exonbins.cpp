@@ -32,44 +32,6 @@ void gene_bins(const Gene &g, std::vector<std::pair<int64_t, int64_t>> &ex, std:
 	}
 }
 
-// the cells of the lookup from the clamped bins (lsq_xb_index): per chromosome the boundaries, the bins over every stretch
-// between two of them counted, the stretches with any compacted into cells, their lists filled bin by bin (so they ascend)
-int build_cells(lsq_xb_index &ix) {
-	const size_t nc = ix.E.covered.size(), nb = ix.bin_gene.size();
-	std::vector<std::vector<uint32_t>> of_chrom(nc);
-	for (size_t b = 0; b < nb; ++b) if (ix.c_bin_end[b] > ix.c_bin_start[b]) of_chrom[ix.gene_chrom[ix.bin_gene[b]]].push_back((uint32_t)b);
-	ix.chrom_first_cell.assign(nc + 1, 0);
-	ix.cell_off.assign(1, 0);
-	std::vector<int32_t> cut;
-	std::vector<uint64_t> cnt;
-	std::vector<uint32_t> cell_of;
-	uint64_t n_entries = 0;
-	for (size_t c = 0; c < nc; ++c) {
-		const std::vector<uint32_t> &bins = of_chrom[c];
-		cut.clear();
-		for (uint32_t b : bins) { cut.push_back(ix.c_bin_start[b]); cut.push_back(ix.c_bin_end[b]); }
-		std::sort(cut.begin(), cut.end());
-		cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
-		auto at = [&](int32_t x) { return (size_t)(std::lower_bound(cut.begin(), cut.end(), x) - cut.begin()); };
-		cnt.assign(cut.size(), 0);
-		for (uint32_t b : bins) for (size_t i = at(ix.c_bin_start[b]), e = at(ix.c_bin_end[b]); i < e; ++i) ++cnt[i];
-		cell_of.assign(cut.size(), XB_NONE);
-		for (size_t i = 0; i + 1 < cut.size(); ++i) if (cnt[i]) {
-			n_entries += cnt[i];
-			if (n_entries > 0xFFFFFFFFull || ix.cell_start.size() >= 0xFFFFFFFEull) return fail(LSQ_E_RANGE, "more than 2^32-1 entries in the bin lookup (overlapping genes)");
-			cell_of[i] = (uint32_t)ix.cell_start.size();
-			ix.cell_start.push_back(cut[i]); ix.cell_end.push_back(cut[i + 1]);
-			ix.cell_off.push_back((uint32_t)n_entries);
-		}
-		ix.chrom_first_cell[c + 1] = (uint32_t)ix.cell_start.size();
-		ix.cell_bins.resize((size_t)n_entries);
-		const uint32_t c0 = ix.chrom_first_cell[c];
-		std::vector<uint32_t> next(ix.cell_off.begin() + c0, ix.cell_off.begin() + ix.chrom_first_cell[c + 1]);      // every cell's next free place
-		for (uint32_t b : bins) for (size_t i = at(ix.c_bin_start[b]), e = at(ix.c_bin_end[b]); i < e; ++i) ix.cell_bins[next[cell_of[i] - c0]++] = b;
-	}
-	return LSQ_OK;
-}
-
 // the first cell of chromosome c that ends behind s (chrom_first_cell[c + 1]: none)
 inline uint32_t first_cell(const lsq_xb_index &ix, uint32_t c, int32_t s) {
 	uint32_t lo = ix.chrom_first_cell[c], hi = ix.chrom_first_cell[c + 1];
@@ -162,7 +124,10 @@ int lsq_xb_index_build(const lsq_annotation *a, lsq_xb_index **out) LSQ_API_TRY 
 	const size_t nb = ix->bin_start.size();
 	ix->c_bin_start.resize(nb); ix->c_bin_end.resize(nb);
 	for (size_t b = 0; b < nb; ++b) { ix->c_bin_start[b] = clamped(ix->bin_start[b]); ix->c_bin_end[b] = clamped(ix->bin_end[b]); }
-	if ((rc = build_cells(*ix))) return rc;
+	std::vector<uint32_t> bin_chrom(nb);
+	for (size_t b = 0; b < nb; ++b) bin_chrom[b] = ix->gene_chrom[ix->bin_gene[b]];
+	if ((rc = build_cells(ix->E.covered.size(), bin_chrom, ix->c_bin_start, ix->c_bin_end, ix->chrom_first_cell, ix->cell_start, ix->cell_end, ix->cell_off, ix->cell_bins,
+	                      "more than 2^32-1 entries in the bin lookup (overlapping genes)"))) return rc;
 	*out = ix.release();
 	return LSQ_OK;
 } LSQ_API_CATCH

@@ -16,17 +16,6 @@ namespace {
 
 typedef std::pair<uint32_t, uint64_t> Intron;        // (chromosome index, jn_key): pairs compare as the lookup is ordered
 
-// the informative intron of chromosome c with key `key` (PS_NONE: none)
-inline uint32_t find_intron(const lsq_ps_index &ix, uint32_t c, uint64_t key) {
-	uint32_t lo = ix.chrom_first_intron[c], hi = ix.chrom_first_intron[c + 1];
-	const uint32_t end = hi;
-	while (lo < hi) {
-		const uint32_t mid = lo + ((hi - lo) >> 1);
-		if (ix.intron_key[mid] < key) lo = mid + 1; else hi = mid;
-	}
-	return lo < end && ix.intron_key[lo] == key ? lo : PS_NONE;
-}
-
 // psi per form from the integers, NaN for NA: x_f = reads_f / introns_f, den the sum of x_g over the event's forms in row order,
 // psi_f = x_f / den; NA for every form of an event that has a form without an informative intron or whose den is 0
 void psi_of(const lsq_ps_table &t, std::vector<double> &psi) {
@@ -58,7 +47,7 @@ void lsq::ps_start_table(const lsq_ps_index &ix, lsq_ps_table &t) {
 // event-major: they ascend)
 int lsq::ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t min_overhang, int n_threads, lsq_ps_table &t) {
 	const int T = read_slices(R.n_reads, n_threads);
-	const size_t nf = ix.form_name.size(), ne = ix.event_name.size(), nc = ix.E.covered.size();
+	const size_t nf = ix.form_name.size(), ne = ix.event_name.size();
 	ps_start_table(ix, t);
 	std::vector<std::vector<uint64_t>> part((size_t)T);
 	std::vector<uint64_t> tally((size_t)T * 6, 0);       // occurrences, below the overhang, no chromosome, found, reads on an event, on several
@@ -70,13 +59,7 @@ int lsq::ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t mi
 		for (uint64_t r = r0; r < r1; ++r) {
 			hit.clear();
 			for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
-				const unsigned c0 = R.bc[b], c1 = R.bc[b + 1];
-				if (c0 == NO_CHROM || c1 == NO_CHROM || c0 >= nc || c1 >= nc) { ++n[2]; continue; }
-				if (c0 != c1 || R.bs[b + 1] <= R.be[b]) continue;
-				const int64_t ov = std::min((int64_t)R.be[b] - R.bs[b], (int64_t)R.be[b + 1] - R.bs[b + 1]);
-				if (ov < (int64_t)min_overhang) { ++n[1]; continue; }
-				++n[0];
-				const uint32_t i = find_intron(ix, c0, jn_key(R.be[b], R.bs[b + 1]));
+				const uint32_t i = ps_host_pair(ix, R, b, min_overhang, n);
 				if (i == PS_NONE) continue;
 				++n[3];
 				hit.insert(hit.end(), ix.intron_forms.begin() + ix.intron_off[i], ix.intron_forms.begin() + ix.intron_off[i + 1]);

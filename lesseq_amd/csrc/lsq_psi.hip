@@ -3,66 +3,14 @@
 // search among its chromosome's informative introns, then a walk over the intron's forms; a read counts once a form and once an
 // event by predicates over its earlier pairs alone, no per-lane list; equal ids are combined inside the wave, then added to the
 // workgroup's own counters in LDS, or to the global ones where the id has no slot there: lsq_wave.hpp), copy-back (the counters).
-// Every number is an integer and sums commute: no result depends on the order in which lanes arrive.
+// Every number is an integer and sums commute: no result depends on the order in which lanes arrive.  The pair rule, the intron
+// search and the once-per-form predicates are lsq_psi_dev.hpp's, which the evidence count (lsq_evidence.hip) shares.
 #include "lsq_wave.hpp"
-#include "lsq_psi.hpp"
+#include "lsq_psi_dev.hpp"
 
 namespace {
 
-struct PsIndex {
-	const unsigned *chrom_first_intron;                  // n_chroms + 1
-	const unsigned long long *intron_key;                // n_introns = chrom_first_intron[n_chroms]
-	const unsigned *intron_off, *intron_forms;           // n_introns + 1; intron_off[n_introns]
-	const unsigned *form_event, *event_first_form;       // n_forms; n_events + 1
-	unsigned n_chroms;
-};
 struct PsAcc { unsigned long long occurrences, dropped, nochrom, found, counted, multi_event; };
-
-enum : unsigned { PS_PAIR_NO_JUNCTION, PS_PAIR_NO_CHROM, PS_PAIR_BELOW, PS_PAIR_PASSES };
-
-// Blocks j and j + 1 of one read (the caller holds j + 1 < blk_off[r + 1] <= n_blocks: both block loads are in bounds): what the
-// junction rule says of the pair and, where it passes, the informative intron it is (PS_NONE: none of them)
-__device__ inline unsigned ps_pair_intron(const ParsedReads &R, const PsIndex &I, unsigned long long j, unsigned min_overhang, unsigned &what) {
-	const unsigned c0 = R.bc[j], c1 = R.bc[j + 1];
-	// no table is read for a block on no chromosome, or on one beyond the index's
-	if (c0 == NO_CHROM || c1 == NO_CHROM || c0 >= I.n_chroms || c1 >= I.n_chroms) { what = PS_PAIR_NO_CHROM; return PS_NONE; }
-	const int s0 = R.bs[j], e0 = R.be[j], s1 = R.bs[j + 1], e1 = R.be[j + 1];
-	if (c0 != c1 || s1 <= e0) { what = PS_PAIR_NO_JUNCTION; return PS_NONE; }
-	if (min((long long)e0 - s0, (long long)e1 - s1) < (long long)min_overhang) { what = PS_PAIR_BELOW; return PS_NONE; }
-	what = PS_PAIR_PASSES;
-	const unsigned long long key = jn_key(e0, s1);
-	// c0 < n_chroms: chrom_first_intron[c0] and [c0 + 1] are entries of its n_chroms + 1; they ascend and end at n_introns, so
-	// lo <= mid < hi <= n_introns in the search, and the last load is guarded by lo < end
-	unsigned lo = I.chrom_first_intron[c0], hi = I.chrom_first_intron[c0 + 1u];
-	const unsigned end = hi;
-	while (lo < hi) {
-		const unsigned mid = lo + ((hi - lo) >> 1);
-		if (I.intron_key[mid] < key) lo = mid + 1u; else hi = mid;
-	}
-	return lo < end && I.intron_key[lo] == key ? lo : PS_NONE;
-}
-
-// Whether intron i's form list holds a form in [f_lo, f_hi): the list ascends, so the first entry at or behind f_lo decides.
-// i < n_introns: intron_off[i] and [i + 1] are entries of its n_introns + 1, they ascend and end at the list's size
-__device__ inline bool ps_list_holds(const PsIndex &I, unsigned i, unsigned f_lo, unsigned f_hi) {
-	unsigned lo = I.intron_off[i], hi = I.intron_off[i + 1u];
-	const unsigned end = hi;
-	while (lo < hi) {
-		const unsigned mid = lo + ((hi - lo) >> 1);
-		if (I.intron_forms[mid] < f_lo) lo = mid + 1u; else hi = mid;
-	}
-	return lo < end && I.intron_forms[lo] < f_hi;
-}
-
-// whether a pair of the read ahead of pair k that passes the rule is an informative intron with a form in [f_lo, f_hi)
-__device__ inline bool ps_met_before(const ParsedReads &R, const PsIndex &I, unsigned long long b0, unsigned long long k, unsigned min_overhang, unsigned f_lo, unsigned f_hi) {
-	for (unsigned long long j = b0; j < k; ++j) {      // (j + 1 <= k, and k + 1 < the read's last offset)
-		unsigned what;
-		const unsigned i = ps_pair_intron(R, I, j, min_overhang, what);
-		if (i != PS_NONE && ps_list_holds(I, i, f_lo, f_hi)) return true;
-	}
-	return false;
-}
 
 // A lane a read, a fixed number of workgroups striding over the reads.  A lane walks its read's (pair, form) couples up to the next
 // one that counts, then the whole wave combines what its lanes found (wave_add_ids) and goes on: as many rounds as the wave's
@@ -147,26 +95,23 @@ int lsq::ps_device_reads(lsq_ctx *c, const lsq_ps_index &ix, const ParsedReads &
 	if ((rc = PC.make())) return rc;
 	ps_start_table(ix, t);
 	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
-	const size_t nf = ix.form_name.size(), ne = ix.event_name.size(), nc = ix.E.covered.size(), ni = ix.intron_key.size();
+	const size_t nf = ix.form_name.size(), ne = ix.event_name.size();
 
 	// ---- index upload
 	HIP_TRY(PC.mark(0, st));
-	DevBuf<unsigned> d_cf, d_io, d_if, d_fe, d_ef;
-	DevBuf<unsigned long long> d_key, d_reads, d_total;
+	PsDeviceIndex d_ix;
+	DevBuf<unsigned long long> d_reads, d_total;
 	DevBuf<PsAcc> d_acc;
 	const PsAcc acc0{0, 0, 0, 0, 0, 0};
 	PsAcc acc = acc0;
-	if ((rc = d_cf.upload(ix.chrom_first_intron.data(), nc + 1, st)) || (rc = d_key.upload((const unsigned long long *)ix.intron_key.data(), ni, st)) ||
-	    (rc = d_io.upload(ix.intron_off.data(), ni + 1, st)) || (rc = d_if.upload(ix.intron_forms.data(), ix.intron_forms.size(), st)) ||
-	    (rc = d_fe.upload(ix.form_event.data(), nf, st)) || (rc = d_ef.upload(ix.event_first_form.data(), ne + 1, st)) ||
-	    (rc = d_reads.alloc(nf)) || (rc = d_total.alloc(ne)) || (rc = d_acc.upload(&acc0, 1, st))) return rc;
+	if ((rc = d_ix.upload(ix, st)) || (rc = d_reads.alloc(nf)) || (rc = d_total.alloc(ne)) || (rc = d_acc.upload(&acc0, 1, st))) return rc;
 	if (nf) HIP_TRY(hipMemsetAsync(d_reads.p, 0, nf * 8, st));
 	if (ne) HIP_TRY(hipMemsetAsync(d_total.p, 0, ne * 8, st));
 
 	// ---- count
 	HIP_TRY(PC.mark(1, st));
 	if (R.n_reads) {
-		const PsIndex I{d_cf.p, d_key.p, d_io.p, d_if.p, d_fe.p, d_ef.p, (unsigned)nc};
+		const PsIndex I = d_ix.view(ix);
 		hipLaunchKernelGGL(lsq_ps_count_kernel, dim3(stride_grid(c, "LSQ_PS_GRID", R.n_reads)), dim3(256), 0, st, R, I, (unsigned)min_overhang, d_reads.p, d_total.p, d_acc.p);
 		HIP_TRY(hipGetLastError());
 	}

@@ -40,6 +40,30 @@ struct lsq_ps_table {
 
 namespace lsq {
 
+// the informative intron of chromosome c with key `key` (PS_NONE: none)
+inline uint32_t ps_find_intron(const lsq_ps_index &ix, uint32_t c, uint64_t key) {
+	uint32_t lo = ix.chrom_first_intron[c], hi = ix.chrom_first_intron[c + 1];
+	const uint32_t end = hi;
+	while (lo < hi) {
+		const uint32_t mid = lo + ((hi - lo) >> 1);
+		if (ix.intron_key[mid] < key) lo = mid + 1; else hi = mid;
+	}
+	return lo < end && ix.intron_key[lo] == key ? lo : PS_NONE;
+}
+// The junction rule on blocks b and b + 1 of one read on the host (psi's and evidence's host paths): the verdict is tallied in
+// n -- [0] passes, [1] below the overhang, [2] a block on no chromosome -- and the informative intron the pair is comes back
+// (PS_NONE: no junction, or none of them)
+inline uint32_t ps_host_pair(const lsq_ps_index &ix, const ParsedReads &R, uint64_t b, uint32_t min_overhang, uint64_t *n) {
+	const size_t nc = ix.E.covered.size();
+	const unsigned c0 = R.bc[b], c1 = R.bc[b + 1];
+	if (c0 == NO_CHROM || c1 == NO_CHROM || c0 >= nc || c1 >= nc) { ++n[2]; return PS_NONE; }
+	if (c0 != c1 || R.bs[b + 1] <= R.be[b]) return PS_NONE;
+	const int64_t ov = std::min((int64_t)R.be[b] - R.bs[b], (int64_t)R.be[b + 1] - R.bs[b + 1]);
+	if (ov < (int64_t)min_overhang) { ++n[1]; return PS_NONE; }
+	++n[0];
+	return ps_find_intron(ix, c0, jn_key(R.be[b], R.bs[b + 1]));
+}
+
 // lsq_psi.cpp: the table's names and sizes from the index, every count zero
 void ps_start_table(const lsq_ps_index &ix, lsq_ps_table &t);
 int ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t min_overhang, int n_threads, lsq_ps_table &t);

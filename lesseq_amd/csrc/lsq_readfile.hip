@@ -2,8 +2,8 @@
 // (ReadSource), and the entry points that take one -- through the chain (lsq_ingest.hip) for count and solve, into the arrays of
 // lsq_mrf_parse for tests and tools, or over its records alone (lsq_bam_check).  The parsers themselves are lsq_mrf_device.hpp,
 // lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only.  The tools that take a
-// read file against an index's dictionaries (junctions, coverage, exonbins, psi) enter through table_of_file: their passes
-// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
+// read file against an index's dictionaries (junctions, coverage, exonbins, psi, evidence) enter through table_of_file: their passes
+// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip, lsq_evidence.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -15,6 +15,7 @@
 #include "lsq_cov.hpp"
 #include "lsq_exonbins.hpp"
 #include "lsq_psi.hpp"
+#include "lsq_evidence.hpp"
 
 namespace {
 
@@ -338,7 +339,7 @@ int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const
 	return parse_staged_text(c, fmt, T, P);
 }
 
-// lsq_jn_device, lsq_cov_device, lsq_xb_device, lsq_ps_device behind their argument checks: the file parsed against the index's dictionaries, a
+// lsq_jn_device, lsq_cov_device, lsq_xb_device, lsq_ps_device, lsq_fe_device behind their argument checks: the file parsed against the index's dictionaries, a
 // new table filled from the device arrays by the tool's passes (fill(reads, table)) and handed out
 template <class IX, class T, class F>
 int table_of_file(lsq_ctx *c, IX *ix, const char *read_format, const char *path, T **out, F fill) {
@@ -516,6 +517,14 @@ int lsq_ps_device(lsq_ctx *c, lsq_ps_index *ix, const char *read_format, const c
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
 	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_ps_table &t) { return ps_device_reads(c, *ix, R, min_overhang, t); });
+} LSQ_API_CATCH
+
+// The junction and exon-body reads per event form of a read file (include/lesseq_hip.h): the device arrays handed to lsq_evidence.hip
+int lsq_fe_device(lsq_ctx *c, lsq_fe_index *ix, const char *read_format, const char *path, uint32_t min_overhang, uint32_t min_body, lsq_fe_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
+	if (min_body < 1) return fail(LSQ_E_ARG, "min_body must be at least 1");
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_fe_table &t) { return fe_device_reads(c, *ix, R, min_overhang, min_body, t); });
 } LSQ_API_CATCH
 
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {

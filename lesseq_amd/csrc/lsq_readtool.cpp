@@ -1,6 +1,6 @@
 // What the tools that take an annotation and a read file share on the host (lsq_readtool.hpp): the dictionaries of an index, a
-// read file through its host parser, a line's exon union and introns, the tables' row order, and the frame of the junctions,
-// coverage, exonbins and psi executables -- arguments, owned handles, the log on failure, the output file.
+// read file through its host parser, a line's exon union and introns, the cells of an interval lookup, the tables' row order,
+// and the frame of the junctions, coverage, exonbins, psi and evidence executables -- arguments, owned handles, the log on failure, the output file.
 #include <cerrno>
 #include <cstdlib>
 #include <numeric>
@@ -79,6 +79,46 @@ void lsq::line_introns(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>>
 		if (i && ex[i].first > reach && reach > -LIM && ex[i].first < LIM) introns.emplace_back(reach, ex[i].first);
 		reach = i ? std::max(reach, ex[i].second) : ex[i].second;
 	}
+}
+
+// The cells of a lookup over intervals clamped to [-2^30, 2^30] (the exon bins' and the evidence regions'; lsq_readtool.hpp): per
+// chromosome the boundaries, the items over every stretch between two of them counted, the stretches with any compacted into
+// cells, their lists filled item by item (so they ascend)
+int lsq::build_cells(size_t nc, const std::vector<uint32_t> &item_chrom, const std::vector<int32_t> &start, const std::vector<int32_t> &end, std::vector<uint32_t> &chrom_first_cell,
+                     std::vector<int32_t> &cell_start, std::vector<int32_t> &cell_end, std::vector<uint32_t> &cell_off, std::vector<uint32_t> &cell_items, const char *too_many) {
+	const size_t nb = item_chrom.size();
+	std::vector<std::vector<uint32_t>> of_chrom(nc);
+	for (size_t b = 0; b < nb; ++b) if (end[b] > start[b]) of_chrom[item_chrom[b]].push_back((uint32_t)b);
+	chrom_first_cell.assign(nc + 1, 0);
+	cell_off.assign(1, 0);
+	std::vector<int32_t> cut;
+	std::vector<uint64_t> cnt;
+	std::vector<uint32_t> cell_of;
+	uint64_t n_entries = 0;
+	for (size_t c = 0; c < nc; ++c) {
+		const std::vector<uint32_t> &items = of_chrom[c];
+		cut.clear();
+		for (uint32_t b : items) { cut.push_back(start[b]); cut.push_back(end[b]); }
+		std::sort(cut.begin(), cut.end());
+		cut.erase(std::unique(cut.begin(), cut.end()), cut.end());
+		auto at = [&](int32_t x) { return (size_t)(std::lower_bound(cut.begin(), cut.end(), x) - cut.begin()); };
+		cnt.assign(cut.size(), 0);
+		for (uint32_t b : items) for (size_t i = at(start[b]), e = at(end[b]); i < e; ++i) ++cnt[i];
+		cell_of.assign(cut.size(), 0xFFFFFFFFu);
+		for (size_t i = 0; i + 1 < cut.size(); ++i) if (cnt[i]) {
+			n_entries += cnt[i];
+			if (n_entries > 0xFFFFFFFFull || cell_start.size() >= 0xFFFFFFFEull) return fail(LSQ_E_RANGE, "%s", too_many);
+			cell_of[i] = (uint32_t)cell_start.size();
+			cell_start.push_back(cut[i]); cell_end.push_back(cut[i + 1]);
+			cell_off.push_back((uint32_t)n_entries);
+		}
+		chrom_first_cell[c + 1] = (uint32_t)cell_start.size();
+		cell_items.resize((size_t)n_entries);
+		const uint32_t c0 = chrom_first_cell[c];
+		std::vector<uint32_t> next(cell_off.begin() + c0, cell_off.begin() + chrom_first_cell[c + 1]);      // every cell's next free place
+		for (uint32_t b : items) for (size_t i = at(start[b]), e = at(end[b]); i < e; ++i) cell_items[next[cell_of[i] - c0]++] = b;
+	}
+	return LSQ_OK;
 }
 
 bool lsq::cli_u32_option(int argc, const char *const *argv, int &i, unsigned long &v) {

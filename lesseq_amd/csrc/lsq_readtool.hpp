@@ -1,7 +1,7 @@
-// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi):
+// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi, evidence):
 // the view of parsed reads their passes take, the dictionaries a read file is parsed against without events, a line's exon
 // union and its introns, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
-// the frame of the four executables.  lsq_readtool.cpp defines what is no template.
+// the frame of the five executables.  lsq_readtool.cpp defines what is no template.
 #pragma once
 
 #include <algorithm>
@@ -42,6 +42,13 @@ void exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &sorte
 // union, scratch), each as (end of the left interval, start of the right one); a gap with an end outside (-2^30, 2^30) -- where no
 // block with a chromosome reaches -- is left out
 void line_introns(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &ex, std::vector<std::pair<int64_t, int64_t>> &introns);
+// The cells of a lookup over items with an interval each, clamped to [-2^30, 2^30], item b on chromosome item_chrom[b] (an item with
+// end <= start is in no cell): every chromosome cut at every item boundary, the stretches that at least one item covers as cells,
+// ascending and disjoint -- chromosome c's are chrom_first_cell[c] .. chrom_first_cell[c + 1] -- and the items that cover cell i,
+// ascending, as cell_items[cell_off[i] .. cell_off[i + 1]].  An item covers every cell between its start and its end.
+// LSQ_E_RANGE with the text `too_many` beyond 2^32-1 list entries.
+int build_cells(size_t n_chroms, const std::vector<uint32_t> &item_chrom, const std::vector<int32_t> &start, const std::vector<int32_t> &end, std::vector<uint32_t> &chrom_first_cell,
+                std::vector<int32_t> &cell_start, std::vector<int32_t> &cell_end, std::vector<uint32_t> &cell_off, std::vector<uint32_t> &cell_items, const char *too_many);
 bool write_file(const char *path, const char *text);       // false: the status and text of the failure are set (LSQ_E_IO)
 
 // ---- the reads over host threads: T slices of whole reads, one slice below 2^16 reads; f(k, r0, r1) on a thread of its own
