@@ -1,7 +1,10 @@
 /* lesseq_hip_dev.h -- developer entry points of liblesseq_hip.so, beside the product ABI of
  * lesseq_hip.h.  Nothing here replaces anything in the reference; the tools under tools/ and a
  * few tests use them to look inside a run (tools/kbench.py, tools/step_bench.py,
- * tests/test_parity_gpu.py, tests/test_em_direct_gpu.py, tests/test_prims_direct_gpu.py).  They may change without notice. */
+ * tests/test_parity_gpu.py, tests/test_em_direct_gpu.py, tests/test_prims_direct_gpu.py).  They may change without notice.
+ * The entries that need the developer build (liblesseq_hip_dev.so, -DLSQ_DEV: lsq_debug_counters, lsq_debug_wg_trace and the
+ * LSQ_ABLATE / LSQ_GRID_WGS environment switches) are loaded by tools/*.py and, in child processes of their own, by
+ * tests/test_count_paths_gpu.py (tests/count_paths_child.py); the release library answers them with zeros. */
 #ifndef LESSEQ_HIP_DEV_H
 #define LESSEQ_HIP_DEV_H
 
@@ -15,7 +18,13 @@ extern "C" {
 /* Counters the count kernels fill when LSQ_ABLATE has bit 256 set: [0] parked one-block reads,
  * [1] parked two-block reads, [2] walk steps, [3] walk lanes, [4] exception-list entries,
  * [5..7] reasons for parking one-block reads, [8..10], [13], [14] reasons for parking two-block reads, [11] / [12]
- * one-block steps of a wave with a parked read / all of them.  out16 holds 16 values. */
+ * one-block steps of a wave with a parked read / all of them.  out16 holds 16 values.
+ * By name, in order (Context.debug_counters() of lesseq_amd/api.py returns them so): parked1, parked2, walk_steps, walk_lanes,
+ * exceptions, park1_no_cell (the read starts outside the lane's cell, or in no cell), park1_one_owner (past e2 of a one-owner
+ * cell), park1_two_owner (a two-owner cell: past an end), park2_no_owner (block 1 of a looked-at record starts in no one-owner
+ * cell), park2_one_owner (... in one), unused10, steps1_parking, steps1, park2_follower_plain (compact pools: a record behind a
+ * first record that crosses no junction), park2_follower_past (compact pools: block 2 runs past the junction's segments), unused15.
+ * The wide two-block loop counts its second records in parked2 only.  The release library leaves all but `exceptions` zero. */
 int lsq_debug_counters(lsq_ctx *c, unsigned long long *out16);
 /* (start, end, steps of the general walk, reads those looked at) of each workgroup of the last count launch, times in 100 MHz
  * ticks (developer library with LSQ_ABLATE bit 4194304; otherwise *n = 0): out holds 4 * cap values; the first *n_workers
@@ -106,6 +115,20 @@ int lsq_debug_hip_versions(int *compiled, int *runtime);
  * (stranded events, lsq_events_compile_library).  Returns their number and writes at most `capacity` of them; -1 for a bad
  * argument.  The tests hold a stranded compile's regions against those of the two split compiles with it. */
 int64_t lsq_debug_events_covered(const lsq_events *e, const char *chrom, int minus, int64_t *starts, int64_t *ends, int64_t capacity);
+
+/* The shortcut table of a packed bucket as the count kernels' streaming loops read it (host only, no device; csrc/lsq_internal.hpp
+ * "Shortcut table of a packed bucket"): the Cell and CellX records of bucket `bucket`, copied out of its compiled image in start
+ * order -- lo / hi: the cell, e1 / e2: its two thresholds, info: owner event (index in the bucket) << 8 | segment << 2 | "lo is the
+ * segment's start", or CELL_INFO_SHARED / CELL_INFO_EMPTY, flags: CELLX_BOTH, the two no-abut flags and, in the low 16 bits, the
+ * event of the owner that ends last.  Returns the number of cells and writes at most `capacity` of them; 0 for a bucket without
+ * cells (generic records, or evaluated on the host); -1 for a bad argument.  tests/test_count_cells_host.py holds them against a
+ * plain model over every base of the bucket (tests/count_cells_ref.py). */
+int64_t lsq_debug_bucket_cells(const lsq_events *e, int64_t bucket, int32_t *lo, int32_t *hi, int32_t *e1, int32_t *e2, uint32_t *info, uint32_t *flags,
+                               int64_t capacity);
+/* The events of a bucket in the bucket's own order (span start, span end, output index), as output indices -- what the event
+ * numbers of the cells refer to -- and the bucket's kind (0 generic records, 1 packed, 2 evaluated on the host; kind may be NULL).
+ * Returns their number and writes at most `capacity`; -1 for a bad argument. */
+int64_t lsq_debug_bucket_events(const lsq_events *e, int64_t bucket, int *kind, int64_t *events, int64_t capacity);
 
 /* The read bootstrap's draws one by one (host only, no device; csrc/lsq_philox.hpp): the classes (1-based) that the draws
  * first_draw .. first_draw + n_draws - 1 of replicate b take for read file m (< 256) and event e (the generator's event

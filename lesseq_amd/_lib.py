@@ -66,6 +66,9 @@ _sig("lsq_events_compile_library", C.c_int, vp, C.c_int, P(cs), P(u64), C.c_int,
 _sig("lsq_events_library", C.c_int, vp)
 _sig("lsq_library_from_name", C.c_int, cs)
 _sig("lsq_debug_events_covered", C.c_int64, vp, cs, C.c_int, P(C.c_int64), P(C.c_int64), C.c_int64)
+_sig("lsq_debug_bucket_cells", C.c_int64, vp, C.c_int64, P(i32), P(i32), P(i32), P(i32), P(u32), P(u32), C.c_int64)
+_sig("lsq_debug_bucket_events", C.c_int64, vp, C.c_int64, P(C.c_int), P(C.c_int64), C.c_int64)
+_sig("lsq_debug_counters", C.c_int, vp, P(C.c_ulonglong))
 _sig("lsq_events_free", None, vp)
 _sig("lsq_events_count", i64, vp)
 _sig("lsq_events_total_isoforms", i64, vp)

@@ -69,6 +69,27 @@ class Events:
         lib.lsq_debug_events_covered(self.h, _b(chrom), int(minus), s, e, n)
         return [(s[q], e[q]) for q in range(n)]
 
+    def bucket_events(self, bucket):
+        """(kind, the bucket's events as output indices in the bucket's own order) -- kind 0: generic records, 1: packed,
+        2: evaluated on the host (a developer entry: lsq_debug_bucket_events).  No GPU."""
+        kind = C.c_int(0)
+        n = lib.lsq_debug_bucket_events(self.h, bucket, C.byref(kind), None, 0)
+        if n < 0:
+            raise ValueError("bad argument")
+        out = (C.c_int64 * max(n, 1))()
+        lib.lsq_debug_bucket_events(self.h, bucket, None, out, n)
+        return kind.value, [int(out[q]) for q in range(n)]
+
+    def bucket_cells(self, bucket):
+        """the shortcut table of a packed bucket as compiled: a list of (lo, hi, e1, e2, info, flags) per cell, in start
+        order (a developer entry: lsq_debug_bucket_cells; csrc/lsq_internal.hpp says what the fields hold).  No GPU."""
+        n = lib.lsq_debug_bucket_cells(self.h, bucket, None, None, None, None, None, None, 0)
+        if n < 0:
+            raise ValueError("bad argument")
+        a = [np.zeros(max(n, 1), np.int32) for _ in range(4)] + [np.zeros(max(n, 1), np.uint32) for _ in range(2)]
+        lib.lsq_debug_bucket_cells(self.h, bucket, *[_ptr(x, i32) for x in a[:4]], *[_ptr(x, u32) for x in a[4:]], n)
+        return [tuple(int(x[q]) for x in a) for q in range(n)]
+
     def __del__(self):
         if getattr(self, "h", None):
             lib.lsq_events_free(self.h)
@@ -498,6 +519,17 @@ class Context:
     def import_counts_device(self, d_ptr):
         """such a buffer (e.g. summed over the ranks of a read-sharded job) becomes the counts solve() works on"""
         check(lib.lsq_counts_import_device(self.h, vp(d_ptr)))
+
+    DEBUG_COUNTERS = ("parked1", "parked2", "walk_steps", "walk_lanes", "exceptions", "park1_no_cell", "park1_one_owner", "park1_two_owner",
+                      "park2_no_owner", "park2_one_owner", "unused10", "steps1_parking", "steps1", "park2_follower_plain", "park2_follower_past", "unused15")
+
+    def debug_counters(self):
+        """the path counters of the latest count()'s streaming loops, by the names include/lesseq_hip_dev.h gives them
+        (lsq_debug_counters).  Filled by the developer library (LSQ_LIB=.../liblesseq_hip_dev.so) under LSQ_ABLATE bit 256; the
+        release library leaves all but `exceptions` zero."""
+        out = (C.c_ulonglong * 16)()
+        check(lib.lsq_debug_counters(self.h, out))
+        return {k: int(out[i]) for i, k in enumerate(self.DEBUG_COUNTERS)}
 
     def launch_info(self):
         """(one-block reads a lane settles per table look, resident workgroups per compute unit) of the latest count()"""

@@ -1015,6 +1015,31 @@ int64_t lsq_debug_events_covered(const lsq_events *e, const char *chrom, int min
 	for (size_t q = 0; q < il.size() && (int64_t)q < capacity; ++q) { starts[q] = il.s[q]; ends[q] = il.e[q]; }
 	return (int64_t)il.size();
 } LSQ_API_CATCH
+// developer aid (include/lesseq_hip_dev.h): the events of a bucket, in the bucket's own order, as output indices
+int64_t lsq_debug_bucket_events(const lsq_events *e, int64_t bucket, int *kind, int64_t *events, int64_t capacity) LSQ_API_TRY {
+	if (!e || bucket < 0 || (size_t)bucket >= e->buckets.size() || capacity < 0 || (capacity && !events)) return -1;
+	const lsq::BucketDesc &d = e->buckets[(size_t)bucket];
+	if (kind) *kind = (int)d.kind;
+	for (uint32_t q = 0; q < d.n_events && (int64_t)q < capacity; ++q) events[q] = e->dev2out[(size_t)d.ev_base + q];
+	return (int64_t)d.n_events;
+} LSQ_API_CATCH
+// developer aid (include/lesseq_hip_dev.h): the Cell / CellX records of a packed bucket, copied out of its compiled image
+int64_t lsq_debug_bucket_cells(const lsq_events *e, int64_t bucket, int32_t *lo, int32_t *hi, int32_t *e1, int32_t *e2, uint32_t *info, uint32_t *flags,
+                               int64_t capacity) LSQ_API_TRY {
+	if (!e || bucket < 0 || (size_t)bucket >= e->buckets.size() || capacity < 0 || (capacity && (!lo || !hi || !e1 || !e2 || !info || !flags))) return -1;
+	const lsq::BucketDesc &d = e->buckets[(size_t)bucket];
+	if (d.kind != 1u) return 0;                                 // generic and host-evaluated buckets have no cells
+	const size_t n_main = d.iso_off & 0xFFFFu, n_all = d.iso_off >> 16;
+	const uint8_t *img = e->images.data() + d.img_off;
+	if ((size_t)d.seg_off + n_all * (sizeof(lsq::Cell) + sizeof(lsq::CellX)) > d.img_bytes) return -1;
+	for (size_t q = 0; q < n_main && (int64_t)q < capacity; ++q) {
+		lsq::Cell c; lsq::CellX x;
+		memcpy(&c, img + d.seg_off + q * sizeof c, sizeof c);
+		memcpy(&x, img + d.seg_off + n_all * sizeof c + q * sizeof x, sizeof x);
+		lo[q] = c.lo; hi[q] = c.hi; e1[q] = c.e1; e2[q] = c.e2; info[q] = x.info; flags[q] = x.flags;
+	}
+	return (int64_t)n_main;
+} LSQ_API_CATCH
 void lsq_events_free(lsq_events *e) { delete e; }
 
 int64_t lsq_events_count(const lsq_events *e) { return e ? (int64_t)e->ev.size() : 0; }

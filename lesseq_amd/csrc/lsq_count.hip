@@ -971,8 +971,10 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 // ending inside it: the two-segment class, matched == total), S (block 2 cannot continue the match: block 1's segment
 // alone, if that is more than 98 % of the read) or parked.  When it crosses a junction, the other records of the quadruple
 // cross the same one (layout): each only shows that block 2 ends inside that segment -- gap + length against one
-// threshold -- and adds its bases; one that runs on, and every follower of a first record that crosses no junction, is
-// parked for the general walk.
+// threshold -- and adds its bases; one that runs on is parked for the general walk.  Behind a first record that crosses no
+// junction a record gets no look of its own: it is settled only as "nothing" (block 1 alone cannot carry it: `nothing`
+// below, which the first record is put through as well) and parked otherwise -- also where it would be S or a start
+// cell's drop as a first record (tests/test_count_paths_gpu.py holds the parked counts of both places).
 template <int NR>
 __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const uint4 *cells, const uint4 *cellx, const unsigned n_cells, const BucketDesc &d,
                                             const CountArgs &A, uint4 *queue, const void *pool, const unsigned long long g0, const unsigned long long g1) {

@@ -1196,32 +1196,12 @@ def test_reads_on_every_threshold_of_the_streaming_loops_vs_oracle(tmp_path):
           + gi.interval_line("B.i", c, "+", [(2000, 2100), (2300, 2360), (2600, 2700)]) + gi.interval_line("B.k", c, "+", [(2000, 2100), (2600, 2700)])
           + gi.interval_line("C.l", c, "-", [(1450, 1600), (2050, 2130)]) + gi.interval_line("C.s", c, "-", [(1450, 1520), (2050, 2130)]))
     mp = "A\tA.l\nA\tA.s\nB\tB.i\nB\tB.k\nC\tC.l\nC\tC.s\n"
-    ends = sorted({1100, 1160, 1500, 1520, 1600, 2100, 2130, 2360, 2700})
-    starts = sorted({1000, 1100, 1400, 1450, 1520, 2000, 2050, 2300, 2600})
-    reads = []
-    # one-block reads: every start region x every end -1 / 0 / +1 / +2 / +30, several lengths
-    for s0 in (1001, 1040, 1099, 1101, 1130, 1401, 1449, 1451, 1470, 1499, 1501, 1530, 2001, 2049, 2051, 2080, 2099, 2101, 2120, 2301, 2601):
-        for e in ends:
-            for d in (-1, 0, 1, 2, 30):
-                if e + d > s0 and e + d - s0 < 900:
-                    reads.append(gi.mrf_line(c, "+" if (s0 + e) % 3 else "-", [(s0, e + d)]))
-    # two-block reads: block 1 ends on / beside every segment end, block 2 starts on / beside every later segment start or
-    # touches block 1; block 2 lengths put 50 |block 1| against 49 total on and around equality
-    for s0 in (1005, 1030, 1060, 1099, 1105, 1140, 1405, 1455, 1470, 1490, 1525, 1560, 2005, 2030, 2055, 2070, 2090, 2105, 2305, 2340):
-        for e in ends:
-            for d1 in (-1, 0, 1):
-                y = e + d1
-                if not (0 < y - s0 < 300):
-                    continue
-                l1 = y - s0
-                for z0 in starts:
-                    for dz in (0, 1):
-                        z = z0 + dz
-                        if z < y:
-                            continue
-                        for l2 in sorted({1, 2, max(1, l1 // 49), l1 // 49 + 1, 20, 60, 100, 131}):
-                            reads.append(gi.mrf_line(c, "+" if (s0 + z + l2) % 5 else "-", [(s0, y), (z, z + l2)]))
-                reads.append(gi.mrf_line(c, "+", [(s0, y), (y, y + 7)]))          # touching blocks
+    # (the reads: count_paths_inputs.threshold_reads, which tests/test_count_paths_gpu.py runs through each streaming kernel alone.
+    # Its "touching blocks" are listed in ascending order, so the loader merges each pair into one block and none of them
+    # reaches the exception list: touching blocks proper are held by
+    # test_count_paths_gpu.py::test_touching_blocks_and_span_start_ties_reach_the_exception_list)
+    import count_paths_inputs as ci
+    reads = [gi.mrf_line(c, strand, [(r[0], r[1])] if len(r) == 2 else [(r[0], r[1]), (r[2], r[3])]) for r, strand in ci.threshold_reads(with_strands=True)]
     _write(tmp_path / "t.interval", iv)
     _write(tmp_path / "t.map", mp)
     _write(tmp_path / "t.mrf", "AlignmentBlocks\n" + "".join(reads))
