@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*) or "evidence" (lsq_fe_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*) or "sites" (lsq_ss_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -689,6 +689,64 @@ int lsq_jn_table_times(const lsq_jn_table *t, float ms[5]);
 /* The text of the rows with reads >= min_reads and, with novel_only, ann '.'; malloc'd, NUL-terminated (lsq_free). */
 int lsq_jn_format(const lsq_jn_table *t, uint32_t min_reads, int novel_only, char **out_text);
 int lsq_jn_sort_tile(void);      /* records a workgroup of the device sort takes (tests place their cases around it) */
+
+/* ------------------------------------------------------------------------------------
+ * Splice-site usage and read-through per junction of a read file: of the blocks that reach a splice site, how
+ * many are spliced there, to which partner, and how many run straight through it -- the integers behind psi5 / psi3 and the
+ * completeness-of-splicing index (Pervouchine et al. 2013, bam2ssj) and behind the boundary-spanning reads of IRFinder
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition; inputs, coordinates, chromosomes, the occurrence rule and `ann` are the junction table's above.
+ *   rows           the distinct junctions of the file -- lsq_jn_*'s rows under the same min_overhang, with the same ann -- united
+ *                  with every intron of the annotation (lsq_jn_index_build's distinct introns): an annotated intron that no read
+ *                  supports is a row with reads 0.  Ascending in chromosome name (bytewise), start, end.  min_overhang may be 0
+ *                  here: the occurrence rule then asks nothing of the flanks.
+ *   boundaries     (chromosome, p): the place between base p-1 and base p.  A row has the left boundary p = start and the right
+ *                  boundary p = end; the distinct boundaries of all rows form one set a chromosome, and the start of one row and
+ *                  the end of another may be one boundary and then share its count.
+ *   through[p]     the blocks [s, e) on p's chromosome (with a chromosome, not empty) with s + m <= p <= e - m, m = max(min_overhang, 1):
+ *                  m bases on either side.  Every block counts on its own, whatever read it belongs to and in whatever order: for
+ *                  aligner output -- a read's blocks are disjoint -- that is reads, for a name-keyed format with overlapping lines
+ *                  it is blocks.  Nothing overflows for m up to 2^32-1.
+ *   spliced        left_spliced / right_spliced of a row: the sum of reads over all rows with the same (chromosome, start) /
+ *                  (chromosome, end).
+ *   text           chrom TAB start+1 TAB end TAB ann TAB reads TAB left_spliced TAB left_through TAB right_spliced TAB right_through
+ *                  NL, the first three as lsq_jn_format prints them; no header.  With ratios four more columns: psi_left =
+ *                  reads / left_spliced, psi_right = reads / right_spliced, cosi_left = left_spliced / (left_spliced + left_through),
+ *                  cosi_right likewise -- on the host in double from the integers, %.6f, NA where the denominator is 0.  left and
+ *                  right are genomic: which is donor and which acceptor follows from ann where it is '+' or '-'.
+ *   report         eight: lsq_jn_table_report's five, then the distinct boundaries, the sum of all boundary counts, the rows with reads 0.
+ * Limits: lsq_jn_*'s, and 2^32-2 boundaries.  Beyond a limit: LSQ_E_RANGE. */
+typedef struct lsq_ss_index lsq_ss_index;       /* an lsq_jn_index: the dictionaries and the sorted distinct introns */
+typedef struct lsq_ss_table lsq_ss_table;
+int lsq_ss_index_build(const lsq_annotation *a, lsq_ss_index **out);
+void lsq_ss_index_free(lsq_ss_index *ix);
+int64_t lsq_ss_index_num_chroms(const lsq_ss_index *ix);
+const char *lsq_ss_index_chrom_name(const lsq_ss_index *ix, int64_t chrom);      /* NULL when out of range */
+int64_t lsq_ss_index_num_introns(const lsq_ss_index *ix);
+lsq_events *lsq_ss_index_dictionaries(lsq_ss_index *ix);                  /* as lsq_jn_index_dictionaries */
+/* Host-only, threaded: the table from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  lsq_ss_host_reads: from arrays parsed against the index. */
+int lsq_ss_host(lsq_ss_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, int n_threads,
+                lsq_ss_table **out);
+int lsq_ss_host_reads(lsq_ss_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_ss_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed exactly as lsq_jn_device parses it; the junction rows by
+ * lsq_jn_device's passes, the rows and boundaries put together on the host and uploaded, one count kernel over the device arrays;
+ * the boundaries' counters alone come back.  The context needs no events, and its events, reads and counters are as they were
+ * afterwards.  LSQ_SS_GRID in the environment bounds the count's workgroups (tests). */
+int lsq_ss_device(lsq_ctx *c, lsq_ss_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ss_table **out);
+void lsq_ss_table_free(lsq_ss_table *t);
+int64_t lsq_ss_table_rows(const lsq_ss_table *t);
+/* The rows' arrays (they live as long as the table; any pointer may be null): chrom indexes lsq_ss_index_chrom_name. */
+int lsq_ss_table_arrays(const lsq_ss_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint8_t **ann, const uint64_t **reads,
+                        const uint64_t **left_spliced, const uint64_t **left_through, const uint64_t **right_spliced, const uint64_t **right_through);
+int lsq_ss_table_report(const lsq_ss_table *t, uint64_t report[8]);
+/* Device milliseconds per phase of the lsq_ss_device call that made the table -- junctions (the sum of lsq_jn_table_times' five),
+ * index (host work and upload), through, copy-back -- from HIP events on the library's stream (zeros from the host path). */
+int lsq_ss_table_times(const lsq_ss_table *t, float ms[4]);
+/* The text of the rows with reads >= min_reads and, with novel_only, ann '.'; malloc'd, NUL-terminated (lsq_free). */
+int lsq_ss_format(const lsq_ss_table *t, uint32_t min_reads, int novel_only, int ratios, char **out_text);
+int lsq_ss_lds_slots(void);      /* boundary ids a workgroup of the device count keeps in LDS (tests place their cases around it) */
 
 /* ------------------------------------------------------------------------------------
  * Per-base read depth of a read file: what `bedtools genomecov -bg -split` prints, and the depth of every

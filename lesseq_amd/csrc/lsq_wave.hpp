@@ -1,6 +1,6 @@
-// What the kernels that stride over parsed reads share (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip, lsq_evidence.hip): 64-bit
+// What the kernels that stride over parsed reads share (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip, lsq_evidence.hip, lsq_sites.hip): 64-bit
 // reductions over a wave, the tail that combines a workgroup's four tally words, the counters a workgroup keeps in LDS for the ids
-// it meets with the wave's combining add into them (the exon-bin, the psi and the evidence count), and the grid of such a kernel.
+// it meets with the wave's combining add into them (the exon-bin, the psi, the evidence and the sites count), and the grid of such a kernel.
 #pragma once
 
 #include "lsq_device.hpp"
