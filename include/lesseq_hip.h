@@ -600,6 +600,15 @@ int lsq_as_fisher(lsq_ctx *c, uint64_t n_tables, const double *cells /* [n][4]: 
  * non-finite log-likelihood stat = 0, p = 1.  count / total: [n][n1+n2], condition 1 first.  1 <= n1, n2 <= 4096. */
 int lsq_as_lrt(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count, const double *total /* [n][n1+n2] each */,
                double *stat, double *p);
+/* No counterpart in Test_AS.r: the replicate-aware test.  Per row y_j ~ BetaBinomial(n_j, mu_g, rho) with y = round(count),
+ * n = round(total) (no +1), one mean per condition in the full model, one in the reduced, and one dispersion rho shared by the
+ * samples of the row, both maximised over mu in [0, 1], rho in [0, 0.999] (DESIGN.md 4.6 has the likelihood); stat =
+ * max(0, 2 (l_full - l_reduced)), p its chi-square tail (one degree of freedom), mu1 / mu2 / rho the full model's maximum
+ * (rho = 0: the samples agree as well as binomial draws; where a maximum is attained on a set, one point of it).  A sample
+ * with n = 0 is left out.  NA in all five outputs: a rounded cell that is NA, negative, infinite or above 2^40, y > n in a
+ * sample, a condition without a sample of n > 0, fewer than 3 such samples in the row.  1 <= n1, n2 <= 4096, n1 + n2 >= 3. */
+int lsq_as_betabin(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count, const double *total /* [n][n1+n2] each */,
+                   double *mu1, double *mu2, double *rho, double *stat, double *p);
 /* Replaces Test_AS.r:162-175: diff = mean(condition 1) - mean(condition 2), p = wilcox.test(x, y)'s (two-sided,
  * correct = TRUE; non-finite values dropped; an empty group gives NA, the script's try-error).  value: [n][n1+n2]. */
 int lsq_as_wilcox(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *value /* [n][n1+n2] */, double *diff, double *p);
@@ -607,7 +616,8 @@ int lsq_as_wilcox(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *val
  * with at most one non-NA value p comes back unchanged).  LSQ_E_ARG for a negative p-value. */
 int lsq_as_adjust(lsq_ctx *c, uint64_t n, const double *p, double *p_bonferroni, double *p_bh);
 
-/* Host-only: the inputs of one test ("fisher", "lrt", "wilcox"), read and checked (no GPU touched).
+/* Host-only: the inputs of one test ("fisher", "lrt", "wilcox", "betabin"), read and checked (no GPU touched).  "betabin"
+ * reads what "lrt" reads, by the same rules, and wants n1+n2 >= 3 (LSQ_E_ARG otherwise).
  * lsq_as_read_matrix reads the script's own files -- a header line, then an ID and the same number of values per line;
  * a value is a number, NA / NaN / nan / -nan or Inf / -Inf / inf / -inf: "fisher" one file of 2 value columns, rows
  * taken in pairs (the ID is the second row's, an odd last row is ignored); "lrt" the count_one and count_all files of
@@ -626,7 +636,7 @@ uint64_t lsq_as_input_rows(const lsq_as_input *in);
 int lsq_as_input_columns(const lsq_as_input *in);                 /* 4 for "fisher", n1+n2 otherwise */
 const char *lsq_as_input_id(const lsq_as_input *in, uint64_t row);
 const double *lsq_as_input_values(const lsq_as_input *in);        /* [rows][columns]: cells, counts or values */
-const double *lsq_as_input_totals(const lsq_as_input *in);        /* "lrt": [rows][columns] totals; NULL otherwise */
+const double *lsq_as_input_totals(const lsq_as_input *in);        /* "lrt", "betabin": [rows][columns] totals; NULL otherwise */
 uint64_t lsq_as_input_left_out(const lsq_as_input *in);
 /* R's as.character(v): 15 significant digits, trailing zeros dropped, fixed unless scientific is strictly shorter
  * ("1e-04", "0.001", "1e+05", "123456"), NaN as "NA".  32 bytes always suffice. */

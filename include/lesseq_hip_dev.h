@@ -106,6 +106,13 @@ int lsq_debug_scan(lsq_ctx *c, int form, const void *in, uint64_t n, uint64_t *o
 int lsq_debug_sort(lsq_ctx *c, uint64_t *w0, uint64_t *w1, uint64_t n, const unsigned *bits, unsigned n_bits,
                    int drop_constant_digits, unsigned *n_passes);
 
+/* The log-likelihood lsq_as_betabin maximises, alone (csrc/lsq_as.hip, bb_loglik -- the device function the fit itself calls): per
+ * row r the sum over its n_samples samples of l_j(mu[r], rho[r]), y and n [n_rows][n_samples] whole numbers with
+ * 0 <= y <= n, 0 <= mu <= 1, 0 <= rho < 1; -inf where a sample has y > 0 at mu = 0 or y < n at mu = 1.  1 <= n_samples <= 8192.
+ * tests/test_betabin_gpu.py holds it against mpmath's loggamma. */
+int lsq_debug_as_bb_loglik(lsq_ctx *c, uint64_t n_rows, int n_samples, const double *y, const double *n, const double *mu, const double *rho,
+                           double *out);
+
 /* HIP_VERSION the library was compiled against and hipRuntimeGetVersion() of the runtime it found in the process (0
  * when that call fails, e.g. without a driver): a binding that loads another runtime first (PyTorch's) can compare. */
 int lsq_debug_hip_versions(int *compiled, int *runtime);

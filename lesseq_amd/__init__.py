@@ -9,7 +9,7 @@ from ._lib import lib, LsqError, check  # noqa: F401
 from .api import (Annotation, Events, Reads, Context, SynthSpec, cli_run, synth_write, synth_write_sam,  # noqa: F401
                   format_count, format_solve, EVENT_TYPES, sam_to_mrf, bam_to_mrf, bam_check_host, SAM_DEFAULT_SKIP_FLAGS,
                   bootstrap_resample_host, bootstrap_draws)
-from .diffsplice import fisher, lrt, wilcox, adjust  # noqa: F401
+from .diffsplice import fisher, lrt, wilcox, adjust, betabin  # noqa: F401
 from . import localevents  # noqa: F401
 from . import gencode  # noqa: F401
 from .gencode import parse_gtf, isoform_map  # noqa: F401
@@ -28,4 +28,4 @@ from .sites import SiteIndex, Sites  # noqa: F401
 
 __all__ = ["lib", "LsqError", "check", "Annotation", "Events", "Reads", "Context", "SynthSpec",
            "cli_run", "synth_write", "synth_write_sam", "sam_to_mrf", "bam_to_mrf", "bam_check_host", "SAM_DEFAULT_SKIP_FLAGS", "format_count", "format_solve", "EVENT_TYPES",
-           "fisher", "lrt", "wilcox", "adjust", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex", "exonbins", "ExonBinIndex", "ExonBins", "psi", "PsiIndex", "Psi", "evidence", "EvidenceIndex", "Evidence", "sites", "SiteIndex", "Sites", "bootstrap_resample_host", "bootstrap_draws"]
+           "fisher", "lrt", "wilcox", "adjust", "betabin", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex", "exonbins", "ExonBinIndex", "ExonBins", "psi", "PsiIndex", "Psi", "evidence", "EvidenceIndex", "Evidence", "sites", "SiteIndex", "Sites", "bootstrap_resample_host", "bootstrap_draws"]

@@ -192,6 +192,8 @@ _sig("lsq_synth_write_sam", C.c_int, P(SynthSpecStruct), cs, cs)
 _sig("lsq_as_fisher", C.c_int, vp, u64, P(C.c_double), P(C.c_double))
 _sig("lsq_as_lrt", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
 _sig("lsq_as_wilcox", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_as_betabin", C.c_int, vp, u64, C.c_int, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
+_sig("lsq_debug_as_bb_loglik", C.c_int, vp, u64, C.c_int, P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double), P(C.c_double))
 _sig("lsq_as_adjust", C.c_int, vp, u64, P(C.c_double), P(C.c_double), P(C.c_double))
 _sig("lsq_as_read_matrix", C.c_int, cs, C.c_int, P(cs), C.c_int, C.c_int, P(vp))
 _sig("lsq_as_read_tables", C.c_int, cs, C.c_int, P(cs), C.c_int, C.c_int, P(vp))

@@ -1,6 +1,6 @@
-// Host side of the differential splicing tests (step 4 of the pipeline, bin/Test_AS.r): the readers of the script's
-// matrices and of this project's count / solve tables, R's as.character formatting, and the test_as executable.  The
-// kernels and the four compute entry points are lsq_as.hip.  Every input is read and checked before the first HIP call.
+// Host side of the differential splicing tests (step 4 of the pipeline, bin/Test_AS.r, and the beta-binomial test beside
+// them): the readers of the script's matrices and of this project's count / solve tables, R's as.character formatting, and
+// the test_as executable.  The kernels and the five compute entry points are lsq_as.hip.  Every input is read and checked before the first HIP call.
 #include <algorithm>
 #include <cerrno>
 #include <cmath>
@@ -24,13 +24,17 @@ struct lsq_as_input {
 
 namespace {
 
-enum Test { T_FISHER, T_LRT, T_WILCOX, T_NONE };
+enum Test { T_FISHER, T_LRT, T_WILCOX, T_BETABIN, T_NONE };
+
+// the tests that read a count and a total per sample
+bool has_totals(Test t) { return t == T_LRT || t == T_BETABIN; }
 
 Test test_of(const char *s) {
 	if (!s) return T_NONE;
 	if (strcmp(s, "fisher") == 0) return T_FISHER;
 	if (strcmp(s, "lrt") == 0) return T_LRT;
 	if (strcmp(s, "wilcox") == 0) return T_WILCOX;
+	if (strcmp(s, "betabin") == 0) return T_BETABIN;
 	return T_NONE;
 }
 
@@ -112,6 +116,10 @@ int no_duplicates(const Lines &L, size_t id_col) {
 	return LSQ_OK;
 }
 
+int too_few_for_betabin(int n1, int n2) {
+	return fail(LSQ_E_ARG, "betabin needs at least 3 samples (n1 + n2 = %d): a mean per condition and one shared dispersion", n1 + n2);
+}
+
 int negative(const Lines &L, size_t row, double v) {
 	return fail(LSQ_E_ARG, "%s:%llu: negative count %g", L.path.c_str(), (unsigned long long)L.line_no[row], v);
 }
@@ -134,10 +142,11 @@ int read_matrix(const char *path, int cols, bool counts, Lines &L, std::vector<d
 }
 
 int read_matrix_input(Test t, int n_paths, const char *const *paths, int n1, int n2, lsq_as_input &in) {
-	const int want_paths = t == T_LRT ? 2 : 1;
+	const int want_paths = has_totals(t) ? 2 : 1;
 	if (n_paths != want_paths || !paths) return fail(LSQ_E_ARG, "%d matrix file(s) expected, %d given", want_paths, n_paths);
 	for (int q = 0; q < n_paths; ++q) if (!paths[q]) return fail(LSQ_E_ARG, "null path");
 	if (t != T_FISHER && (n1 < 1 || n2 < 1)) return fail(LSQ_E_ARG, "replicates per condition must be at least 1 (n1 = %d, n2 = %d)", n1, n2);
+	if (t == T_BETABIN && n1 + n2 < 3) return too_few_for_betabin(n1, n2);
 	const int cols = t == T_FISHER ? 2 : n1 + n2;
 	Lines L;
 	std::vector<double> v;
@@ -161,7 +170,7 @@ int read_matrix_input(Test t, int n_paths, const char *const *paths, int n1, int
 	in.values = std::move(v);
 	in.ids.resize(L.fields.size());
 	for (size_t r = 0; r < L.fields.size(); ++r) in.ids[r] = L.field(r, 0);
-	if (t == T_LRT) {
+	if (has_totals(t)) {
 		Lines L2;
 		if ((rc = read_matrix(paths[1], cols, true, L2, in.totals))) return rc;
 		for (size_t r = 0; r < std::max(L.fields.size(), L2.fields.size()); ++r) {
@@ -181,6 +190,7 @@ int read_tables_input(Test t, int n_paths, const char *const *paths, int n1, int
 	if (!paths) return fail(LSQ_E_ARG, "null argument");
 	if (t == T_FISHER) { n1 = 1; n2 = 1; }
 	if (n1 < 1 || n2 < 1) return fail(LSQ_E_ARG, "replicates per condition must be at least 1 (n1 = %d, n2 = %d)", n1, n2);
+	if (t == T_BETABIN && n1 + n2 < 3) return too_few_for_betabin(n1, n2);
 	if (n_paths != n1 + n2) return fail(LSQ_E_ARG, "n1 + n2 = %d tables expected, %d given", n1 + n2, n_paths);
 	const int extra = t == T_WILCOX ? 5 : 3;
 	std::vector<Lines> T((size_t)n_paths);
@@ -249,7 +259,7 @@ int read_tables_input(Test t, int n_paths, const char *const *paths, int n1, int
 	}
 	in.columns = N;
 	in.values = std::move(val);
-	if (t == T_LRT) in.totals = std::move(tot);
+	if (has_totals(t)) in.totals = std::move(tot);
 	in.ids.resize(rows);
 	for (size_t r = 0; r < rows; ++r) in.ids[r] = F.field(r, (size_t)M + 1);
 	return LSQ_OK;
@@ -277,8 +287,11 @@ void put_r(std::string &o, double v) {
 	o += b;
 }
 
-// The output table (Test_AS.r:45-47, :129-131, :173-175): header, then ID [stat] rawP bonP bhP per row.
-std::string format_output(Test t, const lsq_as_input &in, const std::vector<double> &stat, const std::vector<double> &p,
+// The fitted full model of "betabin", printed between the ID and the statistic
+struct BetabinFit { std::vector<double> mu1, mu2, rho; };
+
+// The output table (Test_AS.r:45-47, :129-131, :173-175): header, then ID [psi1 psi2 rho] [stat] rawP bonP bhP per row.
+std::string format_output(Test t, const lsq_as_input &in, const BetabinFit &fit, const std::vector<double> &stat, const std::vector<double> &p,
                           const std::vector<double> &bon, const std::vector<double> &bh) {
 	const size_t n = in.ids.size();
 	const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
@@ -288,6 +301,7 @@ std::string format_output(Test t, const lsq_as_input &in, const std::vector<doub
 		std::string &o = parts[k];
 		for (size_t i = n * k / T; i < n * (k + 1) / T; ++i) {
 			o += in.ids[i]; o += '\t';
+			if (t == T_BETABIN) { put_r(o, fit.mu1[i]); o += '\t'; put_r(o, fit.mu2[i]); o += '\t'; put_r(o, fit.rho[i]); o += '\t'; }
 			if (t != T_FISHER) { put_r(o, stat[i]); o += '\t'; }
 			put_r(o, p[i]); o += '\t'; put_r(o, bon[i]); o += '\t'; put_r(o, bh[i]); o += '\n';
 		}
@@ -299,7 +313,8 @@ std::string format_output(Test t, const lsq_as_input &in, const std::vector<doub
 		th.join();
 		if (th.failed()) throw std::runtime_error("formatting the rows: " + th.error());
 	}
-	std::string o = t == T_FISHER ? "ID\trawP\tbonP\tbhP\n" : (t == T_LRT ? "ID\tLRT_statistics\trawP\tbonP\tbhP\n" : "ID\tDiff\trawP\tbonP\tbhP\n");
+	std::string o = t == T_FISHER ? "ID\trawP\tbonP\tbhP\n" : (t == T_LRT ? "ID\tLRT_statistics\trawP\tbonP\tbhP\n" :
+	                (t == T_BETABIN ? "ID\tpsi1\tpsi2\trho\tLRT_statistics\trawP\tbonP\tbhP\n" : "ID\tDiff\trawP\tbonP\tbhP\n"));
 	for (const auto &s : parts) o += s;
 	return o;
 }
@@ -319,9 +334,11 @@ const char *USAGE =
 	"test_as fisher <count_matrix> <out>\n"
 	"test_as lrt    <count_one_matrix> <count_all_matrix> <n1> <n2> <out>\n"
 	"test_as wilcox <value_matrix> <n1> <n2> <out>\n"
+	"test_as betabin <count_one_matrix> <count_all_matrix> <n1> <n2> <out>\n"
 	"test_as fisher --tables <out> <count_table_a> <count_table_b>\n"
 	"test_as lrt    --tables <n1> <n2> <out> <count_table_1> ... <count_table_{n1+n2}>\n"
 	"test_as wilcox --tables <n1> <n2> <out> <solve_table_1> ... <solve_table_{n1+n2}>\n"
+	"test_as betabin --tables <n1> <n2> <out> <count_table_1> ... <count_table_{n1+n2}>\n"
 	"(<out> '-': standard output)";
 
 } // namespace
@@ -349,16 +366,17 @@ int run_test_as(int argc, const char *const *argv, std::string &out) {
 			inputs.assign(argv + a + 3, argv + argc);
 		}
 	} else {
-		const int want = t == T_FISHER ? 2 : (t == T_LRT ? 5 : 4);
+		const int want = t == T_FISHER ? 2 : (has_totals(t) ? 5 : 4);
 		if (argc != a + want) { cli_log(0, USAGE); return 1; }
 		if (t == T_FISHER) { inputs.push_back(argv[a]); out_path = argv[a + 1]; }
 		else {
-			const int k = t == T_LRT ? 2 : 1;
+			const int k = has_totals(t) ? 2 : 1;
 			inputs.assign(argv + a, argv + a + k);
 			if (!positive_int(argv[a + k], n1) || !positive_int(argv[a + k + 1], n2)) { cli_log(0, "n1 and n2 must be whole numbers in [1, 4096]"); return 1; }
 			out_path = argv[a + k + 2];
 		}
 	}
+	if (t == T_BETABIN && n1 + n2 < 3) { cli_log(0, USAGE); return 1; }
 	lsq_as_input *raw = nullptr;
 	int st = tables ? lsq_as_read_tables(argv[1], (int)inputs.size(), inputs.data(), n1, n2, &raw)
 	                : lsq_as_read_matrix(argv[1], (int)inputs.size(), inputs.data(), n1, n2, &raw);
@@ -383,16 +401,19 @@ int run_test_as(int argc, const char *const *argv, std::string &out) {
 	std::unique_ptr<FILE, int (*)(FILE *)> close_of(of, [](FILE *f) { return f ? fclose(f) : 0; });
 	lsq_ctx *c = nullptr;
 	std::vector<double> stat(n, 0.0), p(n), bon(n), bh(n);
+	BetabinFit fit;
+	if (t == T_BETABIN) { fit.mu1.resize(n); fit.mu2.resize(n); fit.rho.resize(n); }
 	st = lsq_ctx_create(cli_device(), &c);
 	std::unique_ptr<lsq_ctx, void (*)(lsq_ctx *)> ctx(c, lsq_ctx_destroy);
 	if (!st) {
 		if (t == T_FISHER) st = lsq_as_fisher(c, n, in->values.data(), p.data());
 		else if (t == T_LRT) st = lsq_as_lrt(c, n, n1, n2, in->values.data(), in->totals.data(), stat.data(), p.data());
+		else if (t == T_BETABIN) st = lsq_as_betabin(c, n, n1, n2, in->values.data(), in->totals.data(), fit.mu1.data(), fit.mu2.data(), fit.rho.data(), stat.data(), p.data());
 		else st = lsq_as_wilcox(c, n, n1, n2, in->values.data(), stat.data(), p.data());
 	}
 	if (!st) st = lsq_as_adjust(c, n, p.data(), bon.data(), bh.data());
 	if (st) { cli_log(0, lsq_last_error()); return 2; }
-	std::string text = format_output(t, *in, stat, p, bon, bh);
+	std::string text = format_output(t, *in, fit, stat, p, bon, bh);
 	if (!of) { out = std::move(text); return 0; }
 	if (fwrite(text.data(), 1, text.size(), of) != text.size() || fflush(of) != 0) {
 		std::string msg = std::string(out_path) + ": write error: " + strerror(errno);
@@ -410,7 +431,7 @@ int lsq_as_read_matrix(const char *test, int n_paths, const char *const *paths, 
 	if (!out) return fail(LSQ_E_ARG, "null argument");
 	*out = nullptr;
 	const Test t = test_of(test);
-	if (t == T_NONE) return fail(LSQ_E_ARG, "unknown test '%s' (fisher, lrt, wilcox)", test ? test : "(null)");
+	if (t == T_NONE) return fail(LSQ_E_ARG, "unknown test '%s' (fisher, lrt, wilcox, betabin)", test ? test : "(null)");
 	std::unique_ptr<lsq_as_input> in(new lsq_as_input);
 	const int rc = read_matrix_input(t, n_paths, paths, n1, n2, *in);
 	if (rc) return rc;
@@ -422,7 +443,7 @@ int lsq_as_read_tables(const char *test, int n_paths, const char *const *paths, 
 	if (!out) return fail(LSQ_E_ARG, "null argument");
 	*out = nullptr;
 	const Test t = test_of(test);
-	if (t == T_NONE) return fail(LSQ_E_ARG, "unknown test '%s' (fisher, lrt, wilcox)", test ? test : "(null)");
+	if (t == T_NONE) return fail(LSQ_E_ARG, "unknown test '%s' (fisher, lrt, wilcox, betabin)", test ? test : "(null)");
 	std::unique_ptr<lsq_as_input> in(new lsq_as_input);
 	const int rc = read_tables_input(t, n_paths, paths, n1, n2, *in);
 	if (rc) return rc;

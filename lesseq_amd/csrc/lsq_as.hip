@@ -1,10 +1,12 @@
 // Differential splicing tests (step 4 of the pipeline, bin/Test_AS.r) on the device: Fisher's exact test per 2x2 table, the
 // Poisson log-linear model + likelihood-ratio test per form, the Wilcoxon rank-sum test per form, and the Bonferroni / BH
-// corrections (R's p.adjust).  FP64 throughout; NaN stands for R's NA.  The rules each kernel follows are spelled out in
+// corrections (R's p.adjust); beside them this project's own replicate-aware test, a beta-binomial model with one dispersion per row.  FP64 throughout; NaN stands for R's NA.  The rules each kernel follows are spelled out in
 // DESIGN.md ("Differential splicing tests"); the host side (readers, formatter, the test_as executable) is lsq_as.cpp.
 //
 //   lsq_as_fisher_kernel   one wave per table: the hypergeometric pmf walked outward from its mode, 64 terms a step
 //   lsq_as_lrt_kernel      one lane per row: two IRLS fits (R's glm.fit), normal equations in registers, Cholesky; the difference of their deviances
+//   lsq_as_betabin_kernel  one lane per row: per model a grid in rho and Brent's minimiser over a profile whose inner maxima in mu are safeguarded Newton
+//                          solves; log-gamma and digamma differences as a few direct terms plus a difference of two Stirling forms
 //   lsq_as_wilcox_kernel   one lane per row: W and the tie groups by counting over the row; exact tables from the host
 //   correction             NA compaction (lsq_scan.hpp, flag mode), stable LSD radix sort of (p bits, index) (lsq_sort.hpp), reverse min-scan
 #include <cfloat>
@@ -268,6 +270,272 @@ __global__ void __launch_bounds__(256) lsq_as_lrt_kernel(double *count, double *
 	}
 }
 
+// ---- beta-binomial model + LRT ------------------------------------------------------------------------------------------
+
+// y_j ~ BetaBinomial(n_j, a, b), a = mu (1 - rho)/rho, b = (1 - mu)(1 - rho)/rho, the binomial coefficient dropped:
+//   l_j(mu, rho) = E(mu (1 - rho), rho, y) + E((1 - mu)(1 - rho), rho, n - y) - E(1 - rho, rho, n),   E(c, rho, k) = sum_{i<k} ln(c + i rho).
+// For rho > 0, E = k ln rho + L(c / rho, k) with L(x, k) = sum_{i<k} ln(x + i) = lgamma(x + k) - lgamma(x); the three k ln rho of a
+// sample cancel (y + (n - y) - n = 0) and are never formed.  At rho = 0 the sample is binomial.
+constexpr double BB_RHO_MAX = 0.999;
+constexpr double BB_SHIFT_TO = 8.0;       // the Stirling series start at x >= 8: the first term left out of each is below 5e-13 there
+constexpr int BB_GRID = 18;               // grid in rho: 0, then BB_GRID points, two a decade, the last BB_RHO_MAX (the first 3.2e-9)
+constexpr int BB_NEWTON_MAXIT = 40;       // solves for one mu at one rho
+constexpr int BB_BRENT_MAXIT = 48;        // profile evaluations after the grid
+constexpr double BB_MU_TOL = 1e-6;        // Newton stops at a step below this times min(mu, 1 - mu): quadratic, so mu is then good to ~1e-12 of itself and l to ~1e-24 of the row's reads
+constexpr double BB_RHO_RTOL = 1.5e-8;    // sqrt(DBL_EPSILON): closer than this two profile values do not differ
+constexpr double BB_RHO_ATOL = 1e-5;      // times the bracket's width: what an optimum at rho = 0 is approached to
+
+// lgamma(z) - ((z - 1/2) ln z - z + ln(2 pi)/2) as a series in w = 1/z (through B_12)
+__device__ inline double bb_stirling(double w) {
+	const double w2 = w * w;
+	return w * (1.0 / 12.0 + w2 * (-1.0 / 360.0 + w2 * (1.0 / 1260.0 + w2 * (-1.0 / 1680.0 + w2 * (1.0 / 1188.0 + w2 * (-691.0 / 360360.0))))));
+}
+// ln z - digamma(z), w = 1/z (through B_10)
+__device__ inline double bb_digamma_tail(double w) {
+	const double w2 = w * w;
+	return 0.5 * w + w2 * (1.0 / 12.0 + w2 * (-1.0 / 120.0 + w2 * (1.0 / 252.0 + w2 * (-1.0 / 240.0 + w2 * (1.0 / 132.0)))));
+}
+// trigamma(z) - 1/z, w = 1/z (through B_10)
+__device__ inline double bb_trigamma_tail(double w) {
+	const double w2 = w * w;
+	return w2 * (0.5 + w * (1.0 / 6.0 + w2 * (-1.0 / 30.0 + w2 * (1.0 / 42.0 + w2 * (-1.0 / 30.0 + w2 * (5.0 / 66.0))))));
+}
+
+// the terms taken directly before the series: enough to lift x to BB_SHIFT_TO, at most 8 and at most k
+__device__ inline double bb_shift(double x, double k) {
+	const double m = x >= BB_SHIFT_TO ? 0.0 : ceil(BB_SHIFT_TO - x);
+	return fmin(m, k);
+}
+
+// L(x, k) = sum_{i<k} ln(x + i), x >= 0, k a whole number: m direct terms (their product, one log; ln 0 = -inf at x = 0), then with
+// z = x + m and q = k - m the difference of two Stirling forms, (z - 1/2) log1p(q/z) + q ln(z + q) - q + S(z + q) - S(z).  A bounded
+// number of operations whatever k is; k <= m leaves q = 0 and the direct terms alone.
+__device__ inline double bb_logsum(double x, double k) {
+	if (!(k > 0.0)) return 0.0;
+	const double m = bb_shift(x, k), z = x + m, q = k - m;
+	double g = 0.0;
+	if (m > 0.0) {
+		double prod = 1.0;
+		for (double i = 0.0; i < m; i += 1.0) prod *= x + i;
+		g = log(prod);
+	}
+	if (q > 0.0) {
+		const double zq = z + q;
+		g += (z - 0.5) * log1p(q / z) + q * log(zq) - q + (bb_stirling(1.0 / zq) - bb_stirling(1.0 / z));
+	}
+	return g;
+}
+
+// The same shape for the derivatives the Newton step needs: d = sum_{i<k} 1/(x + i) = digamma(x + k) - digamma(x) and
+// t = sum_{i<k} 1/(x + i)^2 = trigamma(x) - trigamma(x + k).  The leading term of t is q/(z (z + q)), not 1/z - 1/(z + q).
+__device__ inline void bb_dsum(double x, double k, double &d, double &t) {
+	d = 0.0; t = 0.0;
+	if (!(k > 0.0)) return;
+	const double m = bb_shift(x, k), z = x + m, q = k - m;
+	for (double i = 0.0; i < m; i += 1.0) { const double r = 1.0 / (x + i); d += r; t += r * r; }
+	if (q > 0.0) {
+		const double w0 = 1.0 / z, w1 = 1.0 / (z + q);
+		d += log1p(q * w0) - (bb_digamma_tail(w1) - bb_digamma_tail(w0));
+		t += q * w0 * w1 + (bb_trigamma_tail(w0) - bb_trigamma_tail(w1));
+	}
+}
+
+__device__ inline double bb_xlogy(double x, double y) { return x == 0.0 ? 0.0 : x * log(y); }     // 0 ln 0 = 0
+
+// sum over the samples j0 <= j < j1 of l_j(mu, rho); y and n lie sample-major (y[j * stride]).  -inf where a sample has y > 0 at mu = 0
+// or y < n at mu = 1.  The fit and lsq_debug_as_bb_loglik both call this.
+__device__ double bb_loglik(const double *y, const double *n, unsigned long long stride, int j0, int j1, double mu, double rho) {
+	if (rho == 0.0) {
+		double sy = 0.0, sm = 0.0;
+		for (int j = j0; j < j1; ++j) { const double yj = y[(unsigned long long)j * stride]; sy += yj; sm += n[(unsigned long long)j * stride] - yj; }
+		return bb_xlogy(sy, mu) + bb_xlogy(sm, 1.0 - mu);
+	}
+	const double s = (1.0 - rho) / rho, a = mu * s, b = (1.0 - mu) * s;
+	double l = 0.0;
+	for (int j = j0; j < j1; ++j) {
+		const double yj = y[(unsigned long long)j * stride], nj = n[(unsigned long long)j * stride];
+		l += (bb_logsum(a, yj) + bb_logsum(b, nj - yj)) - bb_logsum(s, nj);
+	}
+	return l;
+}
+
+// One row of the fit: its samples, and per condition the sums of y and of n - y.
+struct BbRow {
+	const double *y, *n;
+	unsigned long long stride;
+	int n1, n_all;
+	double sy[2], sm[2];
+};
+
+// argmax over mu in [0, 1] of the samples j0 <= j < j1 at one rho > 0 (s = (1 - rho)/rho), from the start `mu` in (0, 1).  l is
+// concave in mu, so its derivative s sum(d_a - d_b) falls: Newton on it inside a bracket that each evaluation tightens, the
+// midpoint where a step leaves the bracket or is no number.  No y at all puts the maximum at mu = 0, no n - y at mu = 1.
+__device__ double bb_solve_mu(const BbRow &r, int j0, int j1, double sy, double sm, double s, double mu) {
+	if (sy == 0.0) return 0.0;
+	if (sm == 0.0) return 1.0;
+	double lo = 0.0, hi = 1.0;
+	for (int it = 0; it < BB_NEWTON_MAXIT; ++it) {
+		const double a = mu * s, b = (1.0 - mu) * s;
+		double g = 0.0, h = 0.0;
+		for (int j = j0; j < j1; ++j) {
+			const double yj = r.y[(unsigned long long)j * r.stride], nj = r.n[(unsigned long long)j * r.stride];
+			double d, t;
+			bb_dsum(a, yj, d, t); g += d; h += t;
+			bb_dsum(b, nj - yj, d, t); g -= d; h += t;
+		}
+		if (g > 0.0) lo = mu; else if (g < 0.0) hi = mu; else break;
+		double next = mu + g / (s * h);
+		if (!(next > lo && next < hi)) next = 0.5 * (lo + hi);
+		const double step = fabs(next - mu);
+		mu = next;
+		if (step <= BB_MU_TOL * fmin(mu, 1.0 - mu)) break;
+	}
+	return mu;
+}
+
+// max over the mu of l at one rho, and where: FULL one mu per condition (they separate), else one for all samples (in mu1).
+// mu1 / mu2 come in as the starts (the maxima at a rho nearby).
+template <bool FULL>
+__device__ double bb_profile(const BbRow &r, double rho, double &mu1, double &mu2) {
+	const double sy = r.sy[0] + r.sy[1], sm = r.sm[0] + r.sm[1];
+	if (rho == 0.0) {
+		if (FULL) {
+			mu1 = r.sy[0] / (r.sy[0] + r.sm[0]); mu2 = r.sy[1] / (r.sy[1] + r.sm[1]);
+			return (bb_xlogy(r.sy[0], mu1) + bb_xlogy(r.sm[0], 1.0 - mu1)) + (bb_xlogy(r.sy[1], mu2) + bb_xlogy(r.sm[1], 1.0 - mu2));
+		}
+		mu1 = sy / (sy + sm);
+		return bb_xlogy(sy, mu1) + bb_xlogy(sm, 1.0 - mu1);
+	}
+	const double s = (1.0 - rho) / rho;
+	if (FULL) {
+		mu1 = bb_solve_mu(r, 0, r.n1, r.sy[0], r.sm[0], s, mu1);
+		mu2 = bb_solve_mu(r, r.n1, r.n_all, r.sy[1], r.sm[1], s, mu2);
+		return bb_loglik(r.y, r.n, r.stride, 0, r.n1, mu1, rho) + bb_loglik(r.y, r.n, r.stride, r.n1, r.n_all, mu2, rho);
+	}
+	mu1 = bb_solve_mu(r, 0, r.n_all, sy, sm, s, mu1);
+	return bb_loglik(r.y, r.n, r.stride, 0, r.n_all, mu1, rho);
+}
+
+// dl/drho at rho = 0 of the samples j0 <= j < j1 (d/drho ln(c (1 - rho) + i rho) = (i - c)/c there), at their binomial maximum mu: the
+// slope of the profile at its left end, since there the mu-derivative is 0, or mu sits at 0 or 1 and the samples' terms are 0.
+__device__ double bb_slope_at_zero(const BbRow &r, int j0, int j1, double mu) {
+	double s = 0.0;
+	for (int j = j0; j < j1; ++j) {
+		const double yj = r.y[(unsigned long long)j * r.stride], nj = r.n[(unsigned long long)j * r.stride], mj = nj - yj;
+		double t = nj - 0.5 * nj * (nj - 1.0);
+		if (yj > 0.0) t += (0.5 * yj * (yj - 1.0) - yj * mu) / mu;
+		if (mj > 0.0) t += (0.5 * mj * (mj - 1.0) - mj * (1.0 - mu)) / (1.0 - mu);
+		s += t;
+	}
+	return s;
+}
+
+__device__ inline double bb_grid_rho(int i) {      // 0, then two a decade up to BB_RHO_MAX
+	return i == 0 ? 0.0 : BB_RHO_MAX * exp(-1.151292546497023 * (double)(BB_GRID - i));     // ln(10)/2
+}
+
+// The maximum of the profile over rho in [0, BB_RHO_MAX]: the grid, then Brent's minimiser (parabolic steps, golden-section
+// steps where those fail) on -profile between the two neighbours of the grid's best point, started at that point.  Every loop
+// is capped; the best point evaluated is what comes back, the grid's own points included, so a maximum at either end of the
+// domain is returned exactly.  The profile is not proved unimodal: between the neighbours of the best grid
+// point this finds a local maximum no lower than that point.
+template <bool FULL>
+__device__ void bb_fit(const BbRow &r, double &l_out, double &rho_out, double &mu1_out, double &mu2_out) {
+	double mu1 = 0.5, mu2 = 0.5;
+	double fx = INFINITY, x = 0.0, xm1 = 0.5, xm2 = 0.5;      // f = -profile
+	int ib = 0;
+	for (int i = 0; i <= BB_GRID; ++i) {
+		const double rho = bb_grid_rho(i), f = -bb_profile<FULL>(r, rho, mu1, mu2);
+		if (f < fx) { fx = f; x = rho; xm1 = mu1; xm2 = mu2; ib = i; }
+	}
+	if (ib == 0) {
+		// the binomial fit is the grid's best and the profile falls away from it: replicates that agree as well as binomial draws,
+		// the commonest row there is.  rho = 0 is then a local maximum, and the search that would only close in on it is left out.
+		const double slope = FULL ? bb_slope_at_zero(r, 0, r.n1, xm1) + bb_slope_at_zero(r, r.n1, r.n_all, xm2) : bb_slope_at_zero(r, 0, r.n_all, xm1);
+		if (slope <= 0.0) { l_out = -fx; rho_out = 0.0; mu1_out = xm1; mu2_out = xm2; return; }
+	}
+	double a = bb_grid_rho(ib > 0 ? ib - 1 : 0), b = bb_grid_rho(ib < BB_GRID ? ib + 1 : BB_GRID);
+	const double atol = BB_RHO_ATOL * (b - a);
+	double w = x, v = x, fw = fx, fv = fx, d = 0.0, e = 0.0;
+	for (int it = 0; it < BB_BRENT_MAXIT; ++it) {
+		const double mid = 0.5 * (a + b), tol1 = BB_RHO_RTOL * fabs(x) + atol, tol2 = 2.0 * tol1;
+		if (fabs(x - mid) <= tol2 - 0.5 * (b - a)) break;
+		bool golden = true;
+		if (fabs(e) > tol1) {
+			const double rr = (x - w) * (fx - fv);
+			double q = (x - v) * (fx - fw), p = (x - v) * q - (x - w) * rr;
+			q = 2.0 * (q - rr);
+			if (q > 0.0) p = -p;
+			q = fabs(q);
+			const double e_old = e;
+			e = d;
+			if (fabs(p) < fabs(0.5 * q * e_old) && p > q * (a - x) && p < q * (b - x)) {
+				d = p / q;
+				const double u = x + d;
+				if (u - a < tol2 || b - u < tol2) d = copysign(tol1, mid - x);
+				golden = false;
+			}
+		}
+		if (golden) { e = x >= mid ? a - x : b - x; d = 0.3819660112501051 * e; }
+		const double u = fabs(d) >= tol1 ? x + d : x + copysign(tol1, d);
+		mu1 = xm1; mu2 = xm2;
+		const double fu = -bb_profile<FULL>(r, u, mu1, mu2);
+		if (fu <= fx) {
+			if (u >= x) a = x; else b = x;
+			v = w; fv = fw; w = x; fw = fx; x = u; fx = fu; xm1 = mu1; xm2 = mu2;
+		} else {
+			if (u < x) a = u; else b = u;
+			if (fu <= fw || w == x) { v = w; fv = fw; w = u; fw = fu; }
+			else if (fu <= fv || v == x || v == w) { v = u; fv = fu; }
+		}
+	}
+	l_out = -fx; rho_out = x; mu1_out = xm1; mu2_out = xm2;
+}
+
+// One lane per row (DESIGN.md 4.6 says why).  count / total arrive sample-major and are rounded in place to y and n -- each
+// lane rewrites its own column only.  A sample with n = 0 adds nothing to any sum, so it needs no skipping, only counting.
+__global__ void __launch_bounds__(64) lsq_as_betabin_kernel(double *count, double *total, unsigned long long n_rows, int n1, int n2,
+                                                              double *mu1_out, double *mu2_out, double *rho_out, double *stat_out, double *p_out) {
+	const int n = n1 + n2;
+	for (unsigned long long row = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += (unsigned long long)gridDim.x * blockDim.x) {
+		BbRow r;
+		r.y = count + row; r.n = total + row; r.stride = n_rows; r.n1 = n1; r.n_all = n;
+		bool na = false;
+		int inf1 = 0, inf2 = 0;                   // informative samples (n > 0) per condition
+		double sy1 = 0.0, sm1 = 0.0, sy2 = 0.0, sm2 = 0.0;
+		for (int j = 0; j < n; ++j) {
+			const double c = rint(count[(unsigned long long)j * n_rows + row]), tt = rint(total[(unsigned long long)j * n_rows + row]);
+			if (!(c >= 0.0 && c <= AS_MAX_CELL) || !(tt >= 0.0 && tt <= AS_MAX_CELL) || c > tt) na = true;
+			count[(unsigned long long)j * n_rows + row] = c;
+			total[(unsigned long long)j * n_rows + row] = tt;
+			if (j < n1) { inf1 += tt > 0.0; sy1 += c; sm1 += tt - c; }
+			else { inf2 += tt > 0.0; sy2 += c; sm2 += tt - c; }
+		}
+		r.sy[0] = sy1; r.sy[1] = sy2; r.sm[0] = sm1; r.sm[1] = sm2;
+		double mu1 = NAN, mu2 = NAN, rho = NAN, stat = NAN, p = NAN;
+		if (!na && inf1 > 0 && inf2 > 0 && inf1 + inf2 >= 3) {
+			if (r.sy[0] + r.sy[1] == 0.0 || r.sm[0] + r.sm[1] == 0.0) {
+				// all y = 0 or all y = n: both profiles are 0 at every rho, the maximum is attained on the whole interval
+				mu1 = mu2 = r.sy[0] + r.sy[1] == 0.0 ? 0.0 : 1.0; rho = 0.0; stat = 0.0; p = 1.0;
+			} else {
+				double lf, lr, rho_r, m1_r, m2_r;
+				bb_fit<true>(r, lf, rho, mu1, mu2);
+				bb_fit<false>(r, lr, rho_r, m1_r, m2_r);
+				stat = fmax(0.0, 2.0 * (lf - lr));
+				p = erfc(sqrt(stat / 2.0));      // upper chi-square tail, one degree of freedom
+			}
+		}
+		mu1_out[row] = mu1; mu2_out[row] = mu2; rho_out[row] = rho; stat_out[row] = stat; p_out[row] = p;
+	}
+}
+
+// lsq_debug_as_bb_loglik: one lane per row, y and n sample-major as the fit reads them
+__global__ void __launch_bounds__(256) lsq_as_bb_loglik_kernel(const double *y, const double *n, unsigned long long n_rows, int n_samples,
+                                                                const double *mu, const double *rho, double *out) {
+	for (unsigned long long row = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; row < n_rows; row += (unsigned long long)gridDim.x * blockDim.x)
+		out[row] = bb_loglik(y + row, n + row, n_rows, 0, n_samples, mu[row], rho[row]);
+}
+
 // ---- Wilcoxon rank-sum --------------------------------------------------------------------------------------------------
 
 // mean() of R: the sum over n, then the mean of the residuals added (in double here; R sums in long double)
@@ -488,6 +756,48 @@ int lsq_as_lrt(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count,
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(stat, d_stat.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipMemcpyAsync(p, d_p.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	return finish(c);
+} LSQ_API_CATCH
+
+// No counterpart in Test_AS.r: the replicate-aware test (beta-binomial model + LRT per row)
+int lsq_as_betabin(lsq_ctx *c, uint64_t n_rows, int n1, int n2, const double *count, const double *total,
+                   double *mu1, double *mu2, double *rho, double *stat, double *p) LSQ_API_TRY {
+	if (!c || (n_rows && (!count || !total || !mu1 || !mu2 || !rho || !stat || !p))) return fail(LSQ_E_ARG, "null argument");
+	if (n1 < 1 || n2 < 1 || n1 > 4096 || n2 > 4096) return fail(LSQ_E_ARG, "replicates per condition must lie in [1, 4096] (n1 = %d, n2 = %d)", n1, n2);
+	if (n1 + n2 < 3) return fail(LSQ_E_ARG, "the beta-binomial test needs at least 3 samples (n1 + n2 = %d): one shared dispersion and a mean per condition", n1 + n2);
+	if (n_rows == 0) return LSQ_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	const int n = n1 + n2;
+	DevBuf<double> d_count, d_total, d_out;
+	int rc;
+	const std::vector<double> hc = sample_major(count, n_rows, n), ht = sample_major(total, n_rows, n);
+	if ((rc = d_count.upload(hc.data(), hc.size(), c->stream)) || (rc = d_total.upload(ht.data(), ht.size(), c->stream)) ||
+	    (rc = d_out.alloc((size_t)n_rows * 5))) return rc;
+	double *o = d_out.p;
+	// the fit's iteration counts differ from row to row: blocks of one wave, so that a long row holds up 63 others and no more
+	hipLaunchKernelGGL(lsq_as_betabin_kernel, dim3(grid_for(c->n_cu, n_rows, 64, 32)), dim3(64), 0, c->stream, d_count.p, d_total.p, (unsigned long long)n_rows, n1, n2,
+	                   o, o + n_rows, o + 2 * n_rows, o + 3 * n_rows, o + 4 * n_rows);
+	HIP_TRY(hipGetLastError());
+	double *const host[5] = {mu1, mu2, rho, stat, p};
+	for (int q = 0; q < 5; ++q) HIP_TRY(hipMemcpyAsync(host[q], o + (size_t)q * n_rows, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+	return finish(c);
+} LSQ_API_CATCH
+
+// developer entry (lesseq_hip_dev.h): sum_j l_j(mu_r, rho_r) per row through the fit's own device function
+int lsq_debug_as_bb_loglik(lsq_ctx *c, uint64_t n_rows, int n_samples, const double *y, const double *n, const double *mu, const double *rho, double *out) LSQ_API_TRY {
+	if (!c || (n_rows && (!y || !n || !mu || !rho || !out))) return fail(LSQ_E_ARG, "null argument");
+	if (n_samples < 1 || n_samples > 8192) return fail(LSQ_E_ARG, "samples per row must lie in [1, 8192] (%d)", n_samples);
+	if (n_rows == 0) return LSQ_OK;
+	HIP_TRY(hipSetDevice(c->device));
+	DevBuf<double> d_y, d_n, d_mu, d_rho, d_out;
+	int rc;
+	const std::vector<double> hy = sample_major(y, n_rows, n_samples), hn = sample_major(n, n_rows, n_samples);
+	if ((rc = d_y.upload(hy.data(), hy.size(), c->stream)) || (rc = d_n.upload(hn.data(), hn.size(), c->stream)) ||
+	    (rc = d_mu.upload(mu, (size_t)n_rows, c->stream)) || (rc = d_rho.upload(rho, (size_t)n_rows, c->stream)) || (rc = d_out.alloc((size_t)n_rows))) return rc;
+	hipLaunchKernelGGL(lsq_as_bb_loglik_kernel, dim3(grid_for(c->n_cu, n_rows, 256, 8)), dim3(256), 0, c->stream, (const double *)d_y.p, (const double *)d_n.p,
+	                   (unsigned long long)n_rows, n_samples, (const double *)d_mu.p, (const double *)d_rho.p, d_out.p);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(out, d_out.p, (size_t)n_rows * sizeof(double), hipMemcpyDeviceToHost, c->stream));
 	return finish(c);
 } LSQ_API_CATCH
 

@@ -39,6 +39,31 @@ def lrt(ctx, count, total, n1, n2):
     return stat, p
 
 
+def betabin(ctx, count, total, n1, n2):
+    """Beta-binomial model with one dispersion per row + likelihood-ratio test; count, total [n, n1+n2], n1+n2 >= 3
+    (DESIGN 4.6).  Returns (mu1, mu2, rho, stat, p): the full model's fit, the statistic and its chi-square p."""
+    a, b = _f64(count, n1 + n2), _f64(total, n1 + n2)
+    if a.shape != b.shape:
+        raise ValueError("count and total differ in shape: %s, %s" % (a.shape, b.shape))
+    out = [np.empty(len(a)) for _ in range(5)]
+    check(lib.lsq_as_betabin(ctx.h, len(a), n1, n2, _ptr(a), _ptr(b), *[_ptr(o) for o in out]))
+    return tuple(out)
+
+
+def bb_loglik(ctx, y, n, mu, rho):
+    """The beta-binomial log-likelihood alone (a developer entry: lsq_debug_as_bb_loglik): y, n [rows, samples]; mu, rho [rows].
+    Returns per row the sum over its samples."""
+    y, n = np.ascontiguousarray(y, dtype=np.float64), np.ascontiguousarray(n, dtype=np.float64)
+    if y.ndim != 2 or y.shape != n.shape:
+        raise ValueError("y and n must be [rows, samples] of one shape: %s, %s" % (y.shape, n.shape))
+    mu, rho = _f64(mu), _f64(rho)
+    if len(mu) != len(y) or len(rho) != len(y):
+        raise ValueError("one mu and one rho per row")
+    out = np.empty(len(y))
+    check(lib.lsq_debug_as_bb_loglik(ctx.h, len(y), y.shape[1], _ptr(y), _ptr(n), _ptr(mu), _ptr(rho), _ptr(out)))
+    return out
+
+
 def wilcox(ctx, value, n1, n2):
     """Mean difference and Wilcoxon rank-sum test per row; value [n, n1+n2] (Test_AS.r:162-175).  Returns (diff, p)."""
     v = _f64(value, n1 + n2)
@@ -89,11 +114,11 @@ def _read(fn, test, paths, n1, n2):
 
 
 def read_matrix(test, paths, n1=1, n2=1):
-    """The script's own input files (a header, then ID + values per line): fisher [count_matrix], lrt [count_one,
-    count_all], wilcox [value_matrix]."""
+    """The script's own input files (a header, then ID + values per line): fisher [count_matrix], lrt and betabin
+    [count_one, count_all], wilcox [value_matrix]."""
     return _read(lib.lsq_as_read_matrix, test, paths, n1, n2)
 
 
 def read_tables(test, paths, n1=1, n2=1):
-    """This project's count tables (fisher: two, lrt: n1+n2) or solve tables (wilcox: n1+n2), one per sample."""
+    """This project's count tables (fisher: two, lrt and betabin: n1+n2) or solve tables (wilcox: n1+n2), one per sample."""
     return _read(lib.lsq_as_read_tables, test, paths, n1, n2)

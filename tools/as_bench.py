@@ -1,5 +1,6 @@
 """Wall-clock seconds of the differential splicing tests (lsq_as_*, test_as) on synthetic inputs of configs[4]'s shape:
-200 k Fisher tables with Zipf-like depths up to 10^7, 400 k LRT and Wilcoxon rows x 16 samples (8 + 8).  Each entry
+200 k Fisher tables with Zipf-like depths up to 10^7, 400 k LRT, beta-binomial and Wilcoxon rows x 16 samples (8 + 8; the
+beta-binomial test on the LRT's own rows).  Each entry
 point returns after its results are on the host (it ends in a synchronise); a CLI run is test_as in-process, matrix
 files in, output file out.  Prints one JSON line.
 
@@ -59,13 +60,15 @@ def main():
     p_f = ds.fisher(ctx, cells)
     _, p_l = ds.lrt(ctx, count, total, 8, 8)
     _, p_w = ds.wilcox(ctx, value, 8, 8)
+    p_b = ds.betabin(ctx, count, total, 8, 8)[4]
     res = {"tables": len(cells), "rows": len(count), "samples": 16}
     res["fisher_s"] = best(lambda: ds.fisher(ctx, cells), a.repeat)
     res["lrt_s"] = best(lambda: ds.lrt(ctx, count, total, 8, 8), a.repeat)
+    res["betabin_s"] = best(lambda: ds.betabin(ctx, count, total, 8, 8), a.repeat)
     res["wilcox_s"] = best(lambda: ds.wilcox(ctx, value, 8, 8), a.repeat)
     res["adjust_200k_s"] = best(lambda: ds.adjust(ctx, p_f), a.repeat)
     res["adjust_400k_s"] = best(lambda: ds.adjust(ctx, p_l), a.repeat)
-    res["na_p"] = {"fisher": int(np.isnan(p_f).sum()), "lrt": int(np.isnan(p_l).sum()), "wilcox": int(np.isnan(p_w).sum())}
+    res["na_p"] = {"fisher": int(np.isnan(p_f).sum()), "lrt": int(np.isnan(p_l).sum()), "betabin": int(np.isnan(p_b).sum()), "wilcox": int(np.isnan(p_w).sum())}
     if not a.no_cli:
         with tempfile.TemporaryDirectory() as d:
             fm, one, al, rel, out = (os.path.join(d, n) for n in ("fisher.txt", "one.txt", "all.txt", "rel.txt", "out.txt"))
@@ -73,7 +76,8 @@ def main():
             write_matrix(one, count, "r")
             write_matrix(al, total, "r")
             write_matrix(rel, value, "r")
-            runs = {"cli_fisher_s": ["fisher", fm, out], "cli_lrt_s": ["lrt", one, al, "8", "8", out], "cli_wilcox_s": ["wilcox", rel, "8", "8", out]}
+            runs = {"cli_fisher_s": ["fisher", fm, out], "cli_lrt_s": ["lrt", one, al, "8", "8", out],
+                    "cli_betabin_s": ["betabin", one, al, "8", "8", out], "cli_wilcox_s": ["wilcox", rel, "8", "8", out]}
             for k, argv in runs.items():
                 def run():
                     rc, _ = L.cli_run("test_as", argv)
