@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*) or "sites" (lsq_ss_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*), "sites" (lsq_ss_*) or "libtype" (lsq_lt_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -848,6 +848,19 @@ int lsq_cov_sort_tile(void);     /* records a workgroup of the device sort takes
 typedef struct lsq_xb_index lsq_xb_index;       /* the dictionaries, the bins gene-major, per chromosome the cells between bin boundaries with their bins */
 typedef struct lsq_xb_table lsq_xb_table;
 int lsq_xb_index_build(const lsq_annotation *a, lsq_xb_index **out);
+/* Stranded counting: the library type (LSQ_LIBRARY_*) belongs to the index; LSQ_LIBRARY_UNSTRANDED is exactly
+ * lsq_xb_index_build.  A read has the transcript strand t = s XOR (library == reverse) XOR mate2 of its first block (lsq_events_compile_library's
+ * rule; a read whose first block's strand string is neither "+" nor "-" has none, counts for nothing and is tallied), and the table is,
+ * row by row, the unstranded table of the plus genes alone on the reads with t = + and that of the minus genes alone on the reads
+ * with t = -, in the rows' usual order.  The bins and the bins texts do not change.  Every gene needs a strand of its own ("+" or
+ * "-" on all of its isoform lines): LSQ_E_UNSUPPORTED otherwise, the message names the first such gene and says how many there are.
+ * The report keeps its six entries: reads, blocks and blocks without a chromosome or empty are those of the unstranded run on the
+ * whole annotation; no gene / several genes / bin hits count hits of the read's own strand, and a read without t is in none of them.
+ * lsq_xb_table_library_report: reads with t = +, with t = -, without t, and of the first two those that hit a gene (+, then -);
+ * all zeros and LSQ_E_STATE for the table of an unstranded index. */
+int lsq_xb_index_build_library(const lsq_annotation *a, int library, lsq_xb_index **out);
+int lsq_xb_index_library(const lsq_xb_index *ix);
+int lsq_xb_table_library_report(const lsq_xb_table *t, uint64_t report[5]);
 void lsq_xb_index_free(lsq_xb_index *ix);
 int64_t lsq_xb_index_num_chroms(const lsq_xb_index *ix);
 int64_t lsq_xb_index_num_genes(const lsq_xb_index *ix);
@@ -878,6 +891,44 @@ int lsq_xb_table_times(const lsq_xb_table *t, float ms[3]);
 /* The table's text; the two bins texts of an index; malloc'd, NUL-terminated (lsq_free). */
 int lsq_xb_format(const lsq_xb_table *t, char **out_text);
 int lsq_xb_format_bins(const lsq_xb_index *ix, char **interval_text, char **map_text);
+
+/* ------------------------------------------------------------------------------------
+ * Which library type is this read file?: what an infer_experiment-style check reports, for --library above
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition:
+ *   index     per chromosome of the annotation and strand, the union of all exons of that strand's genes there (the first
+ *             exonCount exons of every isoform line, end > start), as sorted disjoint intervals clamped to +-2^30.  A gene has a
+ *             strand when all its isoform lines carry the same one of "+" / "-"; genes without one are left out and counted.
+ *   reads     parsed as under a stranded index: every read with a first-mate strand r = s XOR mate2 (lsq_xb_index_build_library's
+ *             s and mate2) of its first block.  P: some block of the read with end > start on a chromosome of the annotation shares
+ *             at least one base with the plus union of that chromosome; M: the same for the minus union.
+ *   counts    [0] reads; [1] reads without r; [2..5] r = +: neither, P only, M only, both; [6..9] r = -: the same; [10] genes left out.
+ *   derived   sense = (+, P only) + (-, M only); antisense = (+, M only) + (-, P only); ambiguous: both; no_gene: neither;
+ *             forward_fraction = sense / (sense + antisense) in double (has_fraction 0 when the denominator is 0).
+ *   library   sense + antisense < 100: "undetermined"; fraction >= 0.9: "forward"; <= 0.1: "reverse"; 0.4 <= fraction <= 0.6:
+ *             "unstranded"; anything else "undetermined" (a static string).
+ *   text      key TAB value lines: reads, no_strand, plus_none, plus_plus, plus_minus, plus_both, minus_none, minus_plus,
+ *             minus_minus, minus_both, sense, antisense, ambiguous, no_gene, unplaced_genes, forward_fraction (%.6f or NA), library.
+ * Host, device, formats, options, statuses and messages as for lsq_xb_host / lsq_xb_host_reads / lsq_xb_device; LSQ_LT_GRID in the
+ * environment bounds the count's workgroups (tests).  Times: index upload, count, copy-back. */
+typedef struct lsq_lt_index lsq_lt_index;
+typedef struct lsq_lt_table lsq_lt_table;
+int lsq_lt_index_build(const lsq_annotation *a, lsq_lt_index **out);
+void lsq_lt_index_free(lsq_lt_index *ix);
+int64_t lsq_lt_index_num_chroms(const lsq_lt_index *ix);
+const char *lsq_lt_index_chrom_name(const lsq_lt_index *ix, int64_t chrom);
+lsq_events *lsq_lt_index_dictionaries(lsq_lt_index *ix);
+int64_t lsq_lt_index_num_intervals(const lsq_lt_index *ix);
+int64_t lsq_lt_index_unplaced_genes(const lsq_lt_index *ix);
+int lsq_lt_host(lsq_lt_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, int n_threads, lsq_lt_table **out);
+int lsq_lt_host_reads(lsq_lt_index *ix, const lsq_reads *r, int n_threads, lsq_lt_table **out);
+int lsq_lt_device(lsq_ctx *c, lsq_lt_index *ix, const char *read_format, const char *path, lsq_lt_table **out);
+void lsq_lt_table_free(lsq_lt_table *t);
+int lsq_lt_table_counts(const lsq_lt_table *t, uint64_t counts[11]);
+int lsq_lt_table_times(const lsq_lt_table *t, float ms[3]);
+int lsq_lt_table_verdict(const lsq_lt_table *t, double *forward_fraction, int *has_fraction, const char **library);
+int lsq_lt_format(const lsq_lt_table *t, char **out_text);
 
 /* ------------------------------------------------------------------------------------
  * Junction reads per event form of a read file: the junction counts of rMATS, the junction-read PSI of MISO and
@@ -914,6 +965,16 @@ int lsq_xb_format_bins(const lsq_xb_index *ix, char **interval_text, char **map_
 typedef struct lsq_ps_index lsq_ps_index;       /* the dictionaries, the forms event-major, per chromosome the informative introns with their forms */
 typedef struct lsq_ps_table lsq_ps_table;
 int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out);
+/* Stranded counting, as lsq_xb_index_build_library: the library type belongs to the index, a read has the transcript
+ * strand of its first block, and the table is, row by row, the unstranded table of the plus events alone on the reads with t = +
+ * and that of the minus events alone on the reads with t = -, in the rows' usual order; introns and --psi's columns follow from
+ * the same integers.  Every event needs a strand of its own: LSQ_E_UNSUPPORTED otherwise, naming the first and their number.  The
+ * report keeps its eight entries: reads, blocks, occurrences, pairs below the overhang and pairs with a block on no chromosome are
+ * those of the unstranded run on the whole annotation; occurrences found, reads counted and reads counted for several events
+ * count matches among the events of the read's own strand.  lsq_ps_table_library_report: as lsq_xb_table_library_report. */
+int lsq_ps_index_build_library(const lsq_annotation *a, int library, lsq_ps_index **out);
+int lsq_ps_index_library(const lsq_ps_index *ix);
+int lsq_ps_table_library_report(const lsq_ps_table *t, uint64_t report[5]);
 void lsq_ps_index_free(lsq_ps_index *ix);
 int64_t lsq_ps_index_num_chroms(const lsq_ps_index *ix);
 int64_t lsq_ps_index_num_events(const lsq_ps_index *ix);
@@ -987,6 +1048,14 @@ int lsq_ps_format(const lsq_ps_table *t, int with_psi, char **out_text);
 typedef struct lsq_fe_index lsq_fe_index;       /* an lsq_ps_index, the regions form-major, per chromosome the cells with the regions that cover them */
 typedef struct lsq_fe_table lsq_fe_table;
 int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out);
+/* Stranded counting, as lsq_xb_index_build_library and lsq_ps_index_build_library: junction and body evidence are
+ * sought among the events of the read's transcript strand alone; introns, body, positions and the regions do not change.  The
+ * report keeps its eleven entries: reads, blocks, occurrences, pairs below the overhang, pairs with a block on no chromosome and
+ * blocks skipped are those of the unstranded run on the whole annotation; occurrences found, body hits, reads counted, counted
+ * for several events and counted by body alone count matches among the events of the read's own strand. */
+int lsq_fe_index_build_library(const lsq_annotation *a, int library, lsq_fe_index **out);
+int lsq_fe_index_library(const lsq_fe_index *ix);
+int lsq_fe_table_library_report(const lsq_fe_table *t, uint64_t report[5]);
 void lsq_fe_index_free(lsq_fe_index *ix);
 int64_t lsq_fe_index_num_chroms(const lsq_fe_index *ix);
 int64_t lsq_fe_index_num_events(const lsq_fe_index *ix);

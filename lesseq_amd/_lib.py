@@ -289,6 +289,24 @@ _sig("lsq_cov_format", C.c_int, vp, u32, P(vp))
 _sig("lsq_cov_format_regions", C.c_int, vp, P(vp))
 _sig("lsq_cov_sort_tile", C.c_int)
 _sig("lsq_xb_index_build", C.c_int, vp, P(vp))
+_sig("lsq_lt_index_build", C.c_int, vp, P(vp))
+_sig("lsq_lt_index_free", None, vp)
+_sig("lsq_lt_index_num_chroms", i64, vp)
+_sig("lsq_lt_index_chrom_name", cs, vp, i64)
+_sig("lsq_lt_index_dictionaries", vp, vp)
+_sig("lsq_lt_index_num_intervals", i64, vp)
+_sig("lsq_lt_index_unplaced_genes", i64, vp)
+_sig("lsq_lt_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, C.c_int, P(vp))
+_sig("lsq_lt_host_reads", C.c_int, vp, vp, C.c_int, P(vp))
+_sig("lsq_lt_device", C.c_int, vp, vp, cs, cs, P(vp))
+_sig("lsq_lt_table_free", None, vp)
+_sig("lsq_lt_table_counts", C.c_int, vp, P(u64))
+_sig("lsq_lt_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_lt_table_verdict", C.c_int, vp, P(C.c_double), P(C.c_int), P(cs))
+_sig("lsq_lt_format", C.c_int, vp, P(vp))
+_sig("lsq_xb_index_build_library", C.c_int, vp, C.c_int, P(vp))
+_sig("lsq_xb_index_library", C.c_int, vp)
+_sig("lsq_xb_table_library_report", C.c_int, vp, P(u64))
 _sig("lsq_xb_index_free", None, vp)
 _sig("lsq_xb_index_num_chroms", i64, vp)
 _sig("lsq_xb_index_num_genes", i64, vp)
@@ -308,6 +326,9 @@ _sig("lsq_xb_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_xb_format", C.c_int, vp, P(vp))
 _sig("lsq_xb_format_bins", C.c_int, vp, P(vp), P(vp))
 _sig("lsq_ps_index_build", C.c_int, vp, P(vp))
+_sig("lsq_ps_index_build_library", C.c_int, vp, C.c_int, P(vp))
+_sig("lsq_ps_index_library", C.c_int, vp)
+_sig("lsq_ps_table_library_report", C.c_int, vp, P(u64))
 _sig("lsq_ps_index_free", None, vp)
 _sig("lsq_ps_index_num_chroms", i64, vp)
 _sig("lsq_ps_index_num_events", i64, vp)
@@ -328,6 +349,9 @@ _sig("lsq_ps_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_ps_table_psi", C.c_int, vp, P(C.c_double))
 _sig("lsq_ps_format", C.c_int, vp, C.c_int, P(vp))
 _sig("lsq_fe_index_build", C.c_int, vp, P(vp))
+_sig("lsq_fe_index_build_library", C.c_int, vp, C.c_int, P(vp))
+_sig("lsq_fe_index_library", C.c_int, vp)
+_sig("lsq_fe_table_library_report", C.c_int, vp, P(u64))
 _sig("lsq_fe_index_free", None, vp)
 _sig("lsq_fe_index_num_chroms", i64, vp)
 _sig("lsq_fe_index_num_events", i64, vp)

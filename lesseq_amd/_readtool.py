@@ -5,7 +5,10 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import lib, check, vp, u64
+from ._lib import lib, check, vp, u64, _b
+
+LIBRARIES = ("unstranded", "forward", "reverse")
+LIBRARY_REPORT = ("plus", "minus", "no_strand", "plus_counted", "minus_counted")
 
 
 def copied(ptr, n, dtype):
@@ -43,14 +46,36 @@ class Table(_Handle):
         check(self._entry("times")(h, ms))
         self.times = dict(zip(phases, (float(v) for v in ms)))
 
+    def library_report(self):
+        """lsq_*_table_library_report of a stranded table: reads with transcript strand +, with -, without one, and of the first two
+        those that counted for a gene or event.  LsqError (LSQ_E_STATE) for the table of an unstranded index."""
+        rep = (u64 * len(LIBRARY_REPORT))()
+        check(self._entry("library_report")(self.h, rep))
+        return dict(zip(LIBRARY_REPORT, (int(v) for v in rep)))
+
 
 class Index(_Handle):
     KIND = "index"
 
-    def __init__(self, annotation):
+    def __init__(self, annotation, library="unstranded"):
+        """library: "unstranded" (the default), "forward" or "reverse" -- stranded counting (lsq_*_index_build_library), for the
+        tools that have it"""
         h = vp()
-        check(self._entry("build")(annotation.h, C.byref(h)))
+        if library == "unstranded":
+            check(self._entry("build")(annotation.h, C.byref(h)))
+        else:
+            code = lib.lsq_library_from_name(_b(library))
+            if code < 0:
+                raise ValueError("library is 'unstranded', 'forward' or 'reverse', not %r" % (library,))
+            if not hasattr(lib, "%s_index_build_library" % self.PREFIX):
+                raise ValueError("%s counts without regard to strand: it takes no library type" % type(self).__name__)
+            check(self._entry("build_library")(annotation.h, code, C.byref(h)))
         self.h = h
+
+    @property
+    def library(self):
+        """the index's library type; "unstranded" for the tools that have no stranded counting"""
+        return LIBRARIES[self._entry("library")(self.h)] if hasattr(lib, "%s_index_library" % self.PREFIX) else "unstranded"
 
     @property
     def num_chroms(self):

@@ -38,8 +38,8 @@ void intersect(const std::vector<Iv> &a, const std::vector<Iv> &b, std::vector<I
 
 inline int32_t clamped(int64_t x) { return (int32_t)std::max<int64_t>(-FE_LIM, std::min<int64_t>(FE_LIM, x)); }
 
-// the first cell of chromosome c that ends behind s (chrom_first_cell[c + 1]: none)
-inline uint32_t first_cell(const lsq_fe_index &ix, uint32_t c, int32_t s) {
+// the first cell of chromosome (stranded index: table) c that ends behind s (chrom_first_cell[c + 1]: none)
+inline uint32_t first_cell(const lsq_fe_index &ix, size_t c, int32_t s) {
 	uint32_t lo = ix.chrom_first_cell[c], hi = ix.chrom_first_cell[c + 1];
 	while (lo < hi) {
 		const uint32_t mid = lo + ((hi - lo) >> 1);
@@ -148,33 +148,39 @@ void lsq::fe_start_table(const lsq_fe_index &ix, uint32_t min_overhang, uint32_t
 	t.event_name = P.event_name; t.form_name = P.form_name; t.event_first_form = P.event_first_form; t.form_introns = P.form_introns;
 	t.form_body = ix.form_body; t.G = ix.G; t.min_overhang = min_overhang; t.min_body = min_body;
 	t.reads.assign(P.form_name.size(), 0); t.total.assign(P.event_name.size(), 0);
+	t.library = ix.E.library;
 	for (uint64_t &v : t.report) v = 0;
+	for (uint64_t &v : t.lib) v = 0;
 	for (float &m : t.ms) m = 0;
 }
 
 // A thread a stretch of reads, counters of its own: the forms of every informative intron a read's block pairs meet (psi's walk) and
 // of every region a block hits (the cells' walk: a region is taken at the first of its cells the block overlaps) are listed per
 // read, sorted and made distinct (a read counts once a form); the events are the distinct form_event of that list (forms are
-// event-major: they ascend)
+// event-major: they ascend).  Under a stranded index a read looks in the tables of its transcript strand t alone;
+// one without t finds nothing, behind the tallies of its pairs and blocks.
 int lsq::fe_host_reads(const lsq_fe_index &ix, const ParsedReads &R, uint32_t min_overhang, uint32_t min_body, int n_threads, lsq_fe_table &t) {
 	const lsq_ps_index &P = *ix.P;
 	const FeGeometry &G = *ix.G;
 	const int T = read_slices(R.n_reads, n_threads);
-	const size_t nf = P.form_name.size(), ne = P.event_name.size(), nc = ix.E.covered.size();
+	const size_t nf = P.form_name.size(), ne = P.event_name.size(), nc = ix.E.n_table_chroms();
+	const bool stranded = ix.E.stranded();
+	constexpr int NT = 9 + LIB_REPORT;
 	fe_start_table(ix, min_overhang, min_body, t);
 	std::vector<std::vector<uint64_t>> part((size_t)T);
 	// occurrences, below the overhang, no chromosome, found, skipped blocks, body hits, reads on an event, on several, by body alone
-	std::vector<uint64_t> tally((size_t)T * 9, 0);
+	std::vector<uint64_t> tally((size_t)T * NT, 0);      // (behind the nine: the library report)
 	const int rc = for_read_slices(R.n_reads, T, [&](int k, uint64_t r0, uint64_t r1) {
 		std::vector<uint64_t> &cnt = part[(size_t)k];
 		cnt.assign(nf + ne, 0);
-		uint64_t *n = &tally[(size_t)k * 9];
+		uint64_t *n = &tally[(size_t)k * NT];
 		std::vector<uint32_t> hit;
 		for (uint64_t r = r0; r < r1; ++r) {
 			hit.clear();
 			const uint64_t found_before = n[3];
+			const unsigned tr = !stranded ? 0u : R.blk_off[r] < R.blk_off[r + 1] ? read_transcript(ix.E, R.bst[R.blk_off[r]]) : 2u;
 			for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
-				const uint32_t i = ps_host_pair(P, R, b, min_overhang, n);
+				const uint32_t i = ps_host_pair(P, R, b, min_overhang, n, tr);
 				if (i == PS_NONE) continue;
 				++n[3];
 				hit.insert(hit.end(), P.intron_forms.begin() + P.intron_off[i], P.intron_forms.begin() + P.intron_off[i + 1]);
@@ -183,8 +189,10 @@ int lsq::fe_host_reads(const lsq_fe_index &ix, const ParsedReads &R, uint32_t mi
 				const unsigned c = R.bc[b];
 				const int32_t s = R.bs[b], e = R.be[b];
 				if (c == NO_CHROM || c >= nc || e <= s) { ++n[4]; continue; }
-				const uint32_t first = first_cell(ix, c, s);
-				for (uint32_t i = first; i < ix.chrom_first_cell[c + 1] && ix.cell_start[i] < e; ++i)
+				if (tr == 2u) continue;
+				const size_t tb = ix.E.table_of(c, tr);
+				const uint32_t first = first_cell(ix, tb, s);
+				for (uint32_t i = first; i < ix.chrom_first_cell[tb + 1] && ix.cell_start[i] < e; ++i)
 					for (uint32_t q = ix.cell_off[i]; q < ix.cell_off[i + 1]; ++q) {
 						const uint32_t g = ix.cell_regions[q];
 						if (i != first && G.region_start[g] != ix.cell_start[i]) continue;      // met in an earlier cell of this walk
@@ -203,6 +211,7 @@ int lsq::fe_host_reads(const lsq_fe_index &ix, const ParsedReads &R, uint32_t mi
 			if (events > 0) ++n[6];
 			if (events > 1) ++n[7];
 			if (events > 0 && n[3] == found_before) ++n[8];
+			if (stranded) lib_note(n + 9, tr, events > 0);
 		}
 	});
 	if (rc) return rc;
@@ -210,27 +219,32 @@ int lsq::fe_host_reads(const lsq_fe_index &ix, const ParsedReads &R, uint32_t mi
 	for (int k = 0; k < T; ++k) {
 		for (size_t f = 0; f < nf; ++f) t.reads[f] += part[(size_t)k][f];
 		for (size_t e = 0; e < ne; ++e) t.total[e] += part[(size_t)k][nf + e];
-		for (int q = 0; q < 9; ++q) t.report[2 + q] += tally[(size_t)k * 9 + q];
+		for (int q = 0; q < 9; ++q) t.report[2 + q] += tally[(size_t)k * NT + q];
+		for (int q = 0; q < LIB_REPORT; ++q) t.lib[q] += tally[(size_t)k * NT + 9 + q];
 	}
 	return LSQ_OK;
 }
 
 extern "C" {
 
-int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out) LSQ_API_TRY {
+int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out) { return lsq_fe_index_build_library(a, LSQ_LIBRARY_UNSTRANDED, out); }
+
+int lsq_fe_index_build_library(const lsq_annotation *a, int library, lsq_fe_index **out) LSQ_API_TRY {
 	if (!a || !out) return fail(LSQ_E_ARG, "null argument");
 	std::unique_ptr<lsq_fe_index> ix(new lsq_fe_index);
 	int rc;
-	if ((rc = annotation_dictionaries(*a, ix->E))) return rc;
+	if ((rc = annotation_dictionaries(*a, ix->E, library))) return rc;
 	lsq_ps_index *p = nullptr;
-	if ((rc = lsq_ps_index_build(a, &p))) return rc;
+	if ((rc = ps_index_build(a, library, "evidence", &p))) return rc;      // (a stranded index: every event has a strand of its own, or this fails)
 	ix->P.reset(p);
 	ix->G = std::make_shared<FeGeometry>();
 	FeGeometry &G = *ix->G;
 	std::vector<Iv> ex, common, both;
 	std::vector<std::vector<Iv>> of_form;
 	G.form_first_iv.push_back(0); G.form_first_region.push_back(0);
+	size_t event = 0;
 	for (const Gene &g : a->selected) {
+		const unsigned e_minus = p->event_strand[event++] == "-" ? 1u : 0u;      // (the tables of the event: a stranded index's alone)
 		// every form's exon union, and the bases all forms of the event hold: none where two forms lie on different chromosomes
 		of_form.assign(g.isos.size(), std::vector<Iv>());
 		bool one_chrom = true;
@@ -253,7 +267,7 @@ int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out) LSQ_API_TRY 
 				// the gap behind interval i: an intron where line_introns makes it one, informative where psi's lookup lists this form
 				bool informative = false;
 				if (i + 1 < U.size() && U[i].second > -FE_LIM && U[i + 1].first < FE_LIM) {
-					const uint32_t in = ps_find_intron(*p, c, jn_key(U[i].second, U[i + 1].first));
+					const uint32_t in = ps_find_intron(*p, p->E.table_of(c, e_minus), jn_key(U[i].second, U[i + 1].first));
 					informative = in != PS_NONE && std::binary_search(p->intron_forms.begin() + p->intron_off[in], p->intron_forms.begin() + p->intron_off[in + 1], f);
 				}
 				G.iv_start.push_back(U[i].first); G.iv_end.push_back(U[i].second); G.iv_gap_informative.push_back(informative ? 1 : 0);
@@ -278,7 +292,10 @@ int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out) LSQ_API_TRY 
 	}
 	if (ix->form_chrom.size() != p->form_name.size()) return fail(LSQ_E_INTERNAL, "the evidence index and the psi index differ in their forms");
 	std::vector<uint32_t> region_chrom(ix->region_form.size());
-	for (size_t r = 0; r < region_chrom.size(); ++r) region_chrom[r] = ix->form_chrom[ix->region_form[r]];
+	for (size_t r = 0; r < region_chrom.size(); ++r) {      // (a stranded index: the region's table id)
+		const uint32_t f = ix->region_form[r];
+		region_chrom[r] = (uint32_t)ix->E.table_of(ix->form_chrom[f], p->event_strand[p->form_event[f]] == "-" ? 1u : 0u);
+	}
 	if ((rc = build_cells(ix->E.covered.size(), region_chrom, G.region_start, G.region_end, ix->chrom_first_cell, ix->cell_start, ix->cell_end, ix->cell_off, ix->cell_regions,
 	                      "more than 2^32-1 entries in the region lookup (overlapping events)"))) return rc;
 	*out = ix.release();
@@ -286,6 +303,7 @@ int lsq_fe_index_build(const lsq_annotation *a, lsq_fe_index **out) LSQ_API_TRY 
 } LSQ_API_CATCH
 
 void lsq_fe_index_free(lsq_fe_index *ix) { delete ix; }
+int lsq_fe_index_library(const lsq_fe_index *ix) { return index_library(ix); }
 int64_t lsq_fe_index_num_chroms(const lsq_fe_index *ix) { return index_num_chroms(ix); }
 int64_t lsq_fe_index_num_events(const lsq_fe_index *ix) { return ix ? lsq_ps_index_num_events(ix->P.get()) : 0; }
 int64_t lsq_fe_index_num_forms(const lsq_fe_index *ix) { return ix ? lsq_ps_index_num_forms(ix->P.get()) : 0; }
@@ -331,6 +349,7 @@ int lsq_fe_table_arrays(const lsq_fe_table *t, const uint64_t **reads, const uin
 	return LSQ_OK;
 }
 int lsq_fe_table_report(const lsq_fe_table *t, uint64_t report[11]) { return table_report(t, report); }
+int lsq_fe_table_library_report(const lsq_fe_table *t, uint64_t report[5]) { return table_library_report(t, report); }
 int lsq_fe_table_times(const lsq_fe_table *t, float ms[3]) { return table_times(t, ms); }
 int lsq_fe_table_psi(const lsq_fe_table *t, uint32_t read_length, double *psi) LSQ_API_TRY {
 	if (!t || (!psi && !t->reads.empty())) return fail(LSQ_E_ARG, "null argument");
@@ -372,12 +391,14 @@ int lsq_fe_format(const lsq_fe_table *t, int with_psi, uint32_t read_length, cha
 
 } // extern "C"
 
-// evidence [--host] [--psi --read-length L] [--min-overhang N] [--min-body N] <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
-// The table on standard output (or in <out>; "-": standard output), the report in the log.  Exit status 1, nothing on standard
-// output and no file, for a file that does not open or parse.
+// evidence [--host] [--psi --read-length L] [--min-overhang N] [--min-body N] [--library unstranded|forward|reverse] <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
+// The table on standard output (or in <out>; "-": standard output), the report in the log.  Without --library the library type is
+// LSQ_LIBRARY's (unstranded without either); a stranded run logs its library report behind the report.  Exit status 1, nothing on
+// standard output and no file, for a file that does not open or parse, and for a stranded run over an event without a strand.
 int lsq::run_evidence(int argc, const char *const *argv, std::string &out) {
 	static const char *USAGE = "Usage:\nevidence [--host] [--psi --read-length L] [--min-overhang N] [--min-body N] isoform_format isoforms_path g2i_format g2i_path read_format reads_path [out_path]";
-	bool host = false, with_psi = false, bad = false;
+	bool host = false, with_psi = false, bad = false, lib_given = false;
+	int library = LSQ_LIBRARY_UNSTRANDED;
 	unsigned long min_ov = 1, min_body = 1, L = 0;
 	std::vector<const char *> pos;
 	for (int i = 1; i < argc && !bad; ++i) {
@@ -386,15 +407,20 @@ int lsq::run_evidence(int argc, const char *const *argv, std::string &out) {
 		else if (strcmp(argv[i], "--min-overhang") == 0) bad = !cli_u32_option(argc, argv, i, min_ov);
 		else if (strcmp(argv[i], "--min-body") == 0) bad = !cli_u32_option(argc, argv, i, min_body);
 		else if (strcmp(argv[i], "--read-length") == 0) bad = !cli_u32_option(argc, argv, i, L) || L < 1 || L > FE_MAX_READ_LENGTH;
-		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
+		else if (strcmp(argv[i], "--library") == 0) {
+			if (i + 1 >= argc) bad = true;
+			else if (!cli_library_option(argc, argv, i, library)) return 1;
+			lib_given = true;
+		} else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
 		else pos.push_back(argv[i]);
 	}
 	if (bad || pos.size() < 6 || pos.size() > 7 || min_ov < 1 || min_body < 1 || (with_psi && L == 0)) { cli_log(0, USAGE); return 1; }
+	if (!lib_given && !cli_library_env(library)) return 1;
 	CliFrame F(pos);
 	CliOwned<lsq_fe_index, lsq_fe_index_free> ix;
 	CliOwned<lsq_fe_table, lsq_fe_table_free> t;
 	int st = F.load_annotation();
-	if (!st) st = lsq_fe_index_build(F.a, &ix.p);
+	if (!st) st = lsq_fe_index_build_library(F.a, library, &ix.p);
 	if (st) return cli_failed(st);
 	if (host) {
 		if (!(st = F.host_parse(&ix.p->E))) st = lsq_fe_host_reads(ix.p, F.reads, (uint32_t)min_ov, (uint32_t)min_body, 0, &t.p);
@@ -411,5 +437,6 @@ int lsq::run_evidence(int argc, const char *const *argv, std::string &out) {
 	         (long long)lsq_fe_index_num_introns(ix.p), (long long)lsq_fe_index_num_regions(ix.p), (long long)lsq_fe_index_num_forms(ix.p), (long long)lsq_fe_index_num_events(ix.p),
 	         (unsigned long long)rep[5], (unsigned long long)rep[7], (unsigned long long)rep[8], (unsigned long long)rep[9], (unsigned long long)rep[10], min_ov, min_body);
 	cli_log(2, msg);
+	if (library != LSQ_LIBRARY_UNSTRANDED) cli_log_library("evidence", library, t.p->lib);
 	return F.deliver(F.text[0], out);
 }

@@ -38,7 +38,8 @@ struct lsq_fe_index {
 	std::shared_ptr<lsq::FeGeometry> G;
 	std::vector<uint32_t> form_chrom, region_form;
 	std::vector<uint64_t> form_body;           // the bases of B(f)
-	// the lookup (build_cells): the cells of every chromosome with the regions that cover them
+	// the lookup (build_cells): the cells of every chromosome with the regions that cover them; a stranded index (E.library, and
+	// P->E.library): of every table 2 * chromosome + (the event's strand is "-"), 2 * chromosomes + 1 offsets
 	std::vector<uint32_t> chrom_first_cell;
 	std::vector<int32_t> cell_start, cell_end;
 	std::vector<uint32_t> cell_off, cell_regions;
@@ -52,6 +53,8 @@ struct lsq_fe_table {
 	uint32_t min_overhang = 1, min_body = 1;             // what the counts were made under: positions use the same
 	std::vector<uint64_t> reads, total;        // per form, per event
 	uint64_t report[lsq::FE_REPORT] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+	int library = LSQ_LIBRARY_UNSTRANDED;      // the index's
+	uint64_t lib[lsq::LIB_REPORT] = {0, 0, 0, 0, 0};       // a stranded table's library report
 	float ms[lsq::FE_PHASES] = {0, 0, 0};
 };
 

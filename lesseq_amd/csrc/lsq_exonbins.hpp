@@ -27,6 +27,8 @@ struct lsq_xb_index {
 	// empty there and in no cell).  A chromosome cut at every bin boundary: the cells that at least one bin covers, ascending and
 	// disjoint, chromosome c's are chrom_first_cell[c] .. chrom_first_cell[c + 1]; the bins that cover cell i, ascending, are
 	// cell_bins[cell_off[i] .. cell_off[i + 1]].  A bin covers every cell between its start and its end: they are neighbours.
+	// A stranded index (E.library) keeps the lookup per table id 2 * c + (the gene's strand is "-") instead of per
+	// chromosome c: chrom_first_cell has 2 * chromosomes + 1 entries, and a cell holds bins of one strand only.
 	std::vector<int32_t> c_bin_start, c_bin_end;
 	std::vector<uint32_t> chrom_first_cell;
 	std::vector<int32_t> cell_start, cell_end;
@@ -38,6 +40,8 @@ struct lsq_xb_table {
 	std::vector<uint32_t> gene_first_bin;
 	std::vector<uint64_t> reads, total;        // per bin, per gene
 	uint64_t report[lsq::XB_REPORT] = {0, 0, 0, 0, 0, 0};
+	int library = LSQ_LIBRARY_UNSTRANDED;      // the index's
+	uint64_t lib[lsq::LIB_REPORT] = {0, 0, 0, 0, 0};       // a stranded table's library report
 	float ms[lsq::XB_PHASES] = {0, 0, 0};
 };
 

@@ -14,7 +14,7 @@ using namespace lsq;
 
 namespace {
 
-typedef std::pair<uint32_t, uint64_t> Intron;        // (chromosome index, jn_key): pairs compare as the lookup is ordered
+typedef std::pair<uint32_t, uint64_t> Intron;        // (chromosome index -- a stranded index: table id --, jn_key): pairs compare as the lookup is ordered
 
 // psi per form from the integers, NaN for NA: x_f = reads_f / introns_f, den the sum of x_g over the event's forms in row order,
 // psi_f = x_f / den; NA for every form of an event that has a form without an informative intron or whose den is 0
@@ -38,28 +38,34 @@ void psi_of(const lsq_ps_table &t, std::vector<double> &psi) {
 void lsq::ps_start_table(const lsq_ps_index &ix, lsq_ps_table &t) {
 	t.event_name = ix.event_name; t.form_name = ix.form_name; t.event_first_form = ix.event_first_form; t.form_introns = ix.form_introns;
 	t.reads.assign(ix.form_name.size(), 0); t.total.assign(ix.event_name.size(), 0);
+	t.library = ix.E.library;
 	for (uint64_t &v : t.report) v = 0;
+	for (uint64_t &v : t.lib) v = 0;
 	for (float &m : t.ms) m = 0;
 }
 
 // A thread a stretch of reads, counters of its own: the forms of every informative intron a read's block pairs meet are listed
 // per read, sorted and made distinct (a read counts once a form); the events are the distinct form_event of that list (forms are
-// event-major: they ascend)
+// event-major: they ascend).  Under a stranded index a read looks in the tables of its transcript strand t alone;
+// one without t finds nothing, behind the tallies of its pairs.
 int lsq::ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t min_overhang, int n_threads, lsq_ps_table &t) {
 	const int T = read_slices(R.n_reads, n_threads);
 	const size_t nf = ix.form_name.size(), ne = ix.event_name.size();
 	ps_start_table(ix, t);
 	std::vector<std::vector<uint64_t>> part((size_t)T);
-	std::vector<uint64_t> tally((size_t)T * 6, 0);       // occurrences, below the overhang, no chromosome, found, reads on an event, on several
+	const bool stranded = ix.E.stranded();
+	constexpr int NT = 6 + LIB_REPORT;
+	std::vector<uint64_t> tally((size_t)T * NT, 0);      // occurrences, below the overhang, no chromosome, found, reads on an event, on several; the library report
 	const int rc = for_read_slices(R.n_reads, T, [&](int k, uint64_t r0, uint64_t r1) {
 		std::vector<uint64_t> &cnt = part[(size_t)k];
 		cnt.assign(nf + ne, 0);
-		uint64_t *n = &tally[(size_t)k * 6];
+		uint64_t *n = &tally[(size_t)k * NT];
 		std::vector<uint32_t> hit;
 		for (uint64_t r = r0; r < r1; ++r) {
 			hit.clear();
+			const unsigned tr = !stranded ? 0u : R.blk_off[r] < R.blk_off[r + 1] ? read_transcript(ix.E, R.bst[R.blk_off[r]]) : 2u;
 			for (uint64_t b = R.blk_off[r]; b + 1 < R.blk_off[r + 1]; ++b) {
-				const uint32_t i = ps_host_pair(ix, R, b, min_overhang, n);
+				const uint32_t i = ps_host_pair(ix, R, b, min_overhang, n, tr);
 				if (i == PS_NONE) continue;
 				++n[3];
 				hit.insert(hit.end(), ix.intron_forms.begin() + ix.intron_off[i], ix.intron_forms.begin() + ix.intron_off[i + 1]);
@@ -73,6 +79,7 @@ int lsq::ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t mi
 			}
 			if (events > 0) ++n[4];
 			if (events > 1) ++n[5];
+			if (stranded) lib_note(n + 6, tr, events > 0);
 		}
 	});
 	if (rc) return rc;
@@ -80,18 +87,38 @@ int lsq::ps_host_reads(const lsq_ps_index &ix, const ParsedReads &R, uint32_t mi
 	for (int k = 0; k < T; ++k) {
 		for (size_t f = 0; f < nf; ++f) t.reads[f] += part[(size_t)k][f];
 		for (size_t e = 0; e < ne; ++e) t.total[e] += part[(size_t)k][nf + e];
-		for (int q = 0; q < 6; ++q) t.report[2 + q] += tally[(size_t)k * 6 + q];
+		for (int q = 0; q < 6; ++q) t.report[2 + q] += tally[(size_t)k * NT + q];
+		for (int q = 0; q < LIB_REPORT; ++q) t.lib[q] += tally[(size_t)k * NT + 6 + q];
 	}
 	return LSQ_OK;
 }
 
 extern "C" {
 
-int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out) LSQ_API_TRY {
+int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out) { return lsq_ps_index_build_library(a, LSQ_LIBRARY_UNSTRANDED, out); }
+
+int lsq_ps_index_build_library(const lsq_annotation *a, int library, lsq_ps_index **out) LSQ_API_TRY {
+	return ps_index_build(a, library, "psi", out);
+} LSQ_API_CATCH
+
+} // extern "C"
+
+int lsq::ps_index_build(const lsq_annotation *a, int library, const char *tool, lsq_ps_index **out) {
 	if (!a || !out) return fail(LSQ_E_ARG, "null argument");
 	std::unique_ptr<lsq_ps_index> ix(new lsq_ps_index);
 	int rc;
-	if ((rc = annotation_dictionaries(*a, ix->E))) return rc;
+	if ((rc = annotation_dictionaries(*a, ix->E, library))) return rc;
+	// an event's strand: the one its lines share (a stranded index needs "+" or "-": checked once all are known, so that the message counts them)
+	for (const Gene &g : a->selected) {
+		std::string strand = g.isos.empty() ? "." : g.isos[0]->strand;
+		for (const IsoRec *r : g.isos) if (r->strand != strand) strand = ".";
+		ix->event_strand.push_back(strand);
+	}
+	if (ix->E.stranded()) {
+		std::vector<std::string> names;
+		for (const Gene &g : a->selected) names.push_back(g.name);
+		if ((rc = require_strands(names, ix->event_strand, "event", tool))) return rc;
+	}
 	struct Entry { Intron in; uint32_t form; };
 	std::vector<Entry> entries;
 	std::vector<std::pair<int64_t, int64_t>> ex, gaps;
@@ -104,7 +131,7 @@ int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out) LSQ_API_TRY 
 		of_form.assign(g.isos.size(), std::vector<Intron>());
 		for (size_t j = 0; j < g.isos.size(); ++j) {
 			const IsoRec &r = *g.isos[j];
-			const uint32_t c = (uint32_t)ix->E.chroms.find(r.chrom);
+			const uint32_t c = (uint32_t)ix->E.table_of((size_t)ix->E.chroms.find(r.chrom), ix->event_strand[ix->event_name.size()] == "-" ? 1u : 0u);
 			gaps.clear();
 			line_introns(r, ex, gaps);
 			for (const auto &gap : gaps) of_form[j].emplace_back(c, jn_key(gap.first, gap.second));
@@ -141,9 +168,12 @@ int lsq_ps_index_build(const lsq_annotation *a, lsq_ps_index **out) LSQ_API_TRY 
 	for (size_t c = 0; c < nc; ++c) ix->chrom_first_intron[c + 1] += ix->chrom_first_intron[c];
 	*out = ix.release();
 	return LSQ_OK;
-} LSQ_API_CATCH
+}
+
+extern "C" {
 
 void lsq_ps_index_free(lsq_ps_index *ix) { delete ix; }
+int lsq_ps_index_library(const lsq_ps_index *ix) { return index_library(ix); }
 int64_t lsq_ps_index_num_chroms(const lsq_ps_index *ix) { return index_num_chroms(ix); }
 int64_t lsq_ps_index_num_events(const lsq_ps_index *ix) { return ix ? (int64_t)ix->event_name.size() : 0; }
 int64_t lsq_ps_index_num_forms(const lsq_ps_index *ix) { return ix ? (int64_t)ix->form_name.size() : 0; }
@@ -184,6 +214,7 @@ int lsq_ps_table_arrays(const lsq_ps_table *t, const uint64_t **reads, const uin
 	return LSQ_OK;
 }
 int lsq_ps_table_report(const lsq_ps_table *t, uint64_t report[8]) { return table_report(t, report); }
+int lsq_ps_table_library_report(const lsq_ps_table *t, uint64_t report[5]) { return table_library_report(t, report); }
 int lsq_ps_table_times(const lsq_ps_table *t, float ms[3]) { return table_times(t, ms); }
 int lsq_ps_table_psi(const lsq_ps_table *t, double *psi) LSQ_API_TRY {
 	if (!t || (!psi && !t->reads.empty())) return fail(LSQ_E_ARG, "null argument");
@@ -219,27 +250,34 @@ int lsq_ps_format(const lsq_ps_table *t, int with_psi, char **out_text) LSQ_API_
 
 } // extern "C"
 
-// psi [--host] [--psi] [--min-overhang N] <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
-// The table on standard output (or in <out>; "-": standard output), the report in the log.  Exit status 1, nothing on standard
-// output and no file, for a file that does not open or parse.
+// psi [--host] [--psi] [--min-overhang N] [--library unstranded|forward|reverse] <isoform_format> <isoforms_path> <g2i_format> <g2i_path> <read_format> <reads_path> [<out>]
+// The table on standard output (or in <out>; "-": standard output), the report in the log.  Without --library the library type is
+// LSQ_LIBRARY's (unstranded without either); a stranded run logs its library report behind the report.  Exit status 1, nothing on
+// standard output and no file, for a file that does not open or parse, and for a stranded run over an event without a strand.
 int lsq::run_psi(int argc, const char *const *argv, std::string &out) {
 	static const char *USAGE = "Usage:\npsi [--host] [--psi] [--min-overhang N] isoform_format isoforms_path g2i_format g2i_path read_format reads_path [out_path]";
-	bool host = false, with_psi = false, bad = false;
+	bool host = false, with_psi = false, bad = false, lib_given = false;
+	int library = LSQ_LIBRARY_UNSTRANDED;
 	unsigned long min_ov = 1;
 	std::vector<const char *> pos;
 	for (int i = 1; i < argc && !bad; ++i) {
 		if (strcmp(argv[i], "--host") == 0) host = true;
 		else if (strcmp(argv[i], "--psi") == 0) with_psi = true;
 		else if (strcmp(argv[i], "--min-overhang") == 0) bad = !cli_u32_option(argc, argv, i, min_ov);
-		else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
+		else if (strcmp(argv[i], "--library") == 0) {
+			if (i + 1 >= argc) bad = true;
+			else if (!cli_library_option(argc, argv, i, library)) return 1;
+			lib_given = true;
+		} else if (argv[i][0] == '-' && argv[i][1] == '-') bad = true;
 		else pos.push_back(argv[i]);
 	}
 	if (bad || pos.size() < 6 || pos.size() > 7 || min_ov < 1) { cli_log(0, USAGE); return 1; }
+	if (!lib_given && !cli_library_env(library)) return 1;
 	CliFrame F(pos);
 	CliOwned<lsq_ps_index, lsq_ps_index_free> ix;
 	CliOwned<lsq_ps_table, lsq_ps_table_free> t;
 	int st = F.load_annotation();
-	if (!st) st = lsq_ps_index_build(F.a, &ix.p);
+	if (!st) st = lsq_ps_index_build_library(F.a, library, &ix.p);
 	if (st) return cli_failed(st);
 	if (host) {
 		if (!(st = F.host_parse(&ix.p->E))) st = lsq_ps_host_reads(ix.p, F.reads, (uint32_t)min_ov, 0, &t.p);
@@ -255,5 +293,6 @@ int lsq::run_psi(int argc, const char *const *argv, std::string &out) {
 	         (long long)lsq_ps_index_num_introns(ix.p), (long long)lsq_ps_index_num_forms(ix.p), (long long)lsq_ps_index_num_events(ix.p),
 	         (unsigned long long)rep[5], (unsigned long long)rep[6], (unsigned long long)rep[7]);
 	cli_log(2, msg);
+	if (library != LSQ_LIBRARY_UNSTRANDED) cli_log_library("psi", library, t.p->lib);
 	return F.deliver(F.text[0], out);
 }

@@ -17,6 +17,7 @@
 #include "lsq_sites.hpp"
 #include "lsq_psi.hpp"
 #include "lsq_evidence.hpp"
+#include "lsq_libtype.hpp"
 
 namespace {
 
@@ -327,7 +328,8 @@ int ingest_text(lsq_ctx *c, int method, const ReadFormat *fmt, lsq_text &T, unsi
 
 // A read file parsed as lsq_mrf_parse_device parses it, against dictionaries that are not the context's events' (table_of_file:
 // an index's chromosomes and strand table): for the length of the call E stands where the context's events do,
-// so every parser finds its chromosomes, its strand table and its library type (unstranded) where it always looks.  The text is
+// so every parser finds its chromosomes, its strand table and its library type where it always looks -- unstranded, or, under a
+// stranded index, a stranded one: the parsers then deliver the strand of a fragment's first mate, as for stranded events.  The text is
 // freed once it has been read (its room is the caller's sort's); the context's events, reads and counters are not touched.
 int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const char *path, DevParsed &P) {
 	HIP_TRY(hipSetDevice(c->device));
@@ -532,6 +534,12 @@ int lsq_fe_device(lsq_ctx *c, lsq_fe_index *ix, const char *read_format, const c
 	if (min_overhang < 1) return fail(LSQ_E_ARG, "min_overhang must be at least 1");
 	if (min_body < 1) return fail(LSQ_E_ARG, "min_body must be at least 1");
 	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_fe_table &t) { return fe_device_reads(c, *ix, R, min_overhang, min_body, t); });
+} LSQ_API_CATCH
+
+// Which library type a read file is (include/lesseq_hip.h): the device arrays handed to lsq_libtype.hip
+int lsq_lt_device(lsq_ctx *c, lsq_lt_index *ix, const char *read_format, const char *path, lsq_lt_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_lt_table &t) { return lt_device_reads(c, *ix, R, t); });
 } LSQ_API_CATCH
 
 int lsq_last_sam_paths(const lsq_ctx *c, uint32_t *lines_listed, uint32_t *all_slow) {

@@ -38,12 +38,46 @@ std::vector<size_t> lsq::rows_by_chrom_name(const std::vector<std::string> &name
 	return from;
 }
 
-int lsq::annotation_dictionaries(const lsq_annotation &a, lsq_events &E) {
-	E.strands.intern("+"); E.strands.intern("-");
+int lsq::annotation_dictionaries(const lsq_annotation &a, lsq_events &E, int library) {
+	if (library != LSQ_LIBRARY_UNSTRANDED && library != LSQ_LIBRARY_FORWARD && library != LSQ_LIBRARY_REVERSE) return fail(LSQ_E_ARG, "unknown library type %d", library);
+	E.library = library;
+	E.strand_plus = E.strands.intern("+"); E.strand_minus = E.strands.intern("-");
 	for (const auto &rp : a.recs) if (E.chroms.intern(rp->chrom) >= (int)NO_CHROM) return fail(LSQ_E_RANGE, "more than 65 535 chromosomes");
-	E.covered.resize(E.chroms.names.size());
+	E.covered.resize(E.table_of(E.chroms.names.size(), 0));
 	for (IntervalList &il : E.covered) il.add(-((int64_t)1 << 40), (int64_t)1 << 40);
 	return LSQ_OK;
+}
+
+int lsq::require_strands(const std::vector<std::string> &names, const std::vector<std::string> &strands, const char *noun, const char *tool) {
+	size_t first_bad = names.size(), n_bad = 0;
+	for (size_t i = 0; i < names.size(); ++i) if (strands[i] != "+" && strands[i] != "-") { if (!n_bad) first_bad = i; ++n_bad; }
+	if (!n_bad) return LSQ_OK;
+	return fail(LSQ_E_UNSUPPORTED, "%s %s has no strand of its own (its isoforms do not all carry the same one of + / -): a stranded %s index cannot place it; %zu such %s(s)",
+	            noun, names[first_bad].c_str(), tool, n_bad, noun);
+}
+
+const char *lsq::library_name(int library) { return library == LSQ_LIBRARY_FORWARD ? "forward" : library == LSQ_LIBRARY_REVERSE ? "reverse" : "unstranded"; }
+
+bool lsq::cli_library_option(int argc, const char *const *argv, int &i, int &library) {
+	if (i + 1 >= argc) return false;
+	library = lsq_library_from_name(argv[++i]);
+	if (library >= 0) return true;
+	cli_log(0, (std::string("--library ") + argv[i] + ": the library type is unstranded, forward or reverse").c_str());
+	return false;
+}
+bool lsq::cli_library_env(int &library) {
+	const char *e = getenv("LSQ_LIBRARY");
+	if (!e || !*e) return true;
+	library = lsq_library_from_name(e);
+	if (library >= 0) return true;
+	cli_log(0, (std::string("LSQ_LIBRARY=") + e + ": the library type is unstranded, forward or reverse").c_str());
+	return false;
+}
+void lsq::cli_log_library(const char *tool, int library, const uint64_t *lib) {
+	char msg[320];
+	snprintf(msg, sizeof msg, "%s: %s library: %llu reads of the + strand, %llu retained; %llu of the - strand, %llu retained; %llu without a strand", tool, library_name(library),
+	         (unsigned long long)lib[0], (unsigned long long)lib[3], (unsigned long long)lib[1], (unsigned long long)lib[4], (unsigned long long)lib[2]);
+	cli_log(2, msg);
 }
 
 int lsq::host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r) {

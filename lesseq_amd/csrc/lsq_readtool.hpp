@@ -26,8 +26,30 @@ inline ParsedReads host_view(const lsq_reads &r) {
 }
 
 // The dictionaries a read file is parsed against without events (an index's `lsq_events E`): "+" and "-" as strands 0 and 1, the
-// distinct chromosome strings of the annotation's isoform lines in file order, one whole-line interval a chromosome
-int annotation_dictionaries(const lsq_annotation &a, lsq_events &E);
+// distinct chromosome strings of the annotation's isoform lines in file order, one whole-line interval a chromosome.
+// A library type other than unstranded makes them a stranded job's dictionaries (lsq_events::library): the parsers
+// deliver the strand of a fragment's first mate as the strand id, and `covered` holds a whole-line interval per TABLE id
+// 2 * chromosome + (strand == "-"), so n_table_chroms() stays the number of chromosomes.
+int annotation_dictionaries(const lsq_annotation &a, lsq_events &E, int library = LSQ_LIBRARY_UNSTRANDED);
+// A stranded index needs a strand of its own for every gene or event (strands[i]: "+", "-", or anything else where the isoform
+// lines differ or carry neither): LSQ_E_UNSUPPORTED naming the first that has none and how many there are
+int require_strands(const std::vector<std::string> &names, const std::vector<std::string> &strands, const char *noun, const char *tool);
+// a stranded table's library report: reads with t = +, with t = -, without t; of the first two, those that counted for a gene or event
+constexpr int LIB_REPORT = 5;
+// The transcript strand of a read under an index's dictionaries from the strand id of its first block: 0 plus,
+// 1 minus, 2 none (the strand string is neither "+" nor "-")
+inline unsigned read_transcript(const lsq_events &E, unsigned strand_id) {
+	return strand_id == (unsigned)E.strand_plus ? E.transcript_minus(false, false) : strand_id == (unsigned)E.strand_minus ? E.transcript_minus(true, false) : 2u;
+}
+// what a host thread notes of one read (t: 0, 1, or 2 for none) in its LIB_REPORT tallies
+inline void lib_note(uint64_t *lib, unsigned t, bool counted) { ++lib[t]; if (t < 2u && counted) ++lib[3 + t]; }
+const char *library_name(int library);         // "unstranded", "forward", "reverse"
+// --library of an executable: the value behind argv[i] (i moves on to it); where the option is not given, LSQ_LIBRARY of the
+// environment (unset or empty: `library` stays).  false, with the message logged, for anything but unstranded, forward or reverse
+bool cli_library_option(int argc, const char *const *argv, int &i, int &library);
+bool cli_library_env(int &library);
+// the library report of a stranded table as the executables log it
+void cli_log_library(const char *tool, int library, const uint64_t *lib);
 // A read file through the host parser of its format, against dictionaries E; verify: a BAM file's CRC32s and end-of-file marker checked
 int host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r);
 // ... under LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (the executables' --host)
@@ -75,9 +97,16 @@ std::vector<X> merge_folded(std::vector<std::vector<X>> &parts, Less less, Fold 
 }
 
 // ---- the bodies of the entry points that differ by the type alone (every index begins with `lsq_events E`)
-template <class IX> int64_t index_num_chroms(const IX *ix) { return ix ? (int64_t)ix->E.covered.size() : 0; }
+template <class IX> int64_t index_num_chroms(const IX *ix) { return ix ? (int64_t)ix->E.n_table_chroms() : 0; }
 template <class IX> const char *index_chrom_name(const IX *ix, int64_t chrom) {
-	return ix && chrom >= 0 && (size_t)chrom < ix->E.covered.size() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
+	return ix && chrom >= 0 && (size_t)chrom < ix->E.n_table_chroms() ? ix->E.chroms.names[(size_t)chrom].c_str() : nullptr;
+}
+template <class IX> int index_library(const IX *ix) { return ix ? ix->E.library : LSQ_LIBRARY_UNSTRANDED; }
+// the library report of a table (its `lib`, under its index's `library`): all zeros and LSQ_E_STATE for an unstranded one
+template <class T> int table_library_report(const T *t, uint64_t *report) {
+	if (!t || !report) return fail(LSQ_E_ARG, "null argument");
+	memcpy(report, t->lib, sizeof(t->lib));
+	return t->library != LSQ_LIBRARY_UNSTRANDED ? LSQ_OK : fail(LSQ_E_STATE, "the table is unstranded: there is no library report");
 }
 template <class IX> lsq_events *index_dictionaries(IX *ix) { return ix ? &ix->E : nullptr; }
 template <class T> int table_report(const T *t, uint64_t *report) {

@@ -4,6 +4,7 @@
 #pragma once
 
 #include "lsq_device.hpp"
+#include "lsq_route.hpp"       // (the library word of a stranded kernel and what it says of a strand id)
 
 constexpr unsigned NO_ID = 0xFFFFFFFFu;        // a lane that holds no id; a free slot of WgCounters
 
@@ -78,6 +79,35 @@ __device__ inline void wave_add_ids(WgCounters<SLOTS> &local, unsigned long long
 	}
 	if (mine) local.add(counter, id, mine);
 }
+
+// ---- the stranded form of a count kernel (exonbins, psi, evidence).  It takes, as a parameter pack that is empty in
+// the unstranded form, the word of lsq_route.hpp's route_lib_word and the five counters of the table's library report.
+__device__ inline unsigned lib_word() { return 0u; }
+__device__ inline unsigned lib_word(unsigned word, unsigned long long *) { return word; }
+__device__ inline unsigned long long *lib_counters() { return nullptr; }
+__device__ inline unsigned long long *lib_counters(unsigned, unsigned long long *counters) { return counters; }
+// The library report: per lane, in registers, what its reads came to -- t plus, t minus, no t, and of the first two those that
+// counted for a gene or event -- summed over the workgroup when it has done all its reads: one atomic a workgroup and counter
+// that is not zero (DESIGN 4.11 records what an atomic a wave on five addresses costs).
+struct LibLane {
+	unsigned long long plus = 0, minus = 0, none = 0, kept_plus = 0, kept_minus = 0;
+	__device__ inline void note(const unsigned t, const bool counted) {
+		plus += (unsigned)(t == 0u); minus += (unsigned)(t == 1u); none += (unsigned)(t >= ROUTE_NO_STRAND);
+		kept_plus += (unsigned)(t == 0u && counted); kept_minus += (unsigned)(t == 1u && counted);
+	}
+	// (every lane of the workgroup comes here, outside the kernel's loops; the LDS is this call's own: another tally may follow at once)
+	__device__ inline void flush(unsigned long long *out) const {
+		__shared__ unsigned long long part_a[4][4], part_b[4][4];
+		unsigned long long v[4] = {plus, minus, none, kept_plus}, w[4] = {kept_minus, 0ull, 0ull, 0ull};
+		workgroup_tally<false>(v, part_a);
+		workgroup_tally<false>(w, part_b);
+		if (threadIdx.x == 0) {
+#pragma unroll
+			for (unsigned q = 0; q < 4; ++q) if (v[q]) atomicAdd(&out[q], v[q]);
+			if (w[0]) atomicAdd(&out[4], w[0]);
+		}
+	}
+};
 
 // workgroups of a kernel that strides over the reads, a lane a read: eight a compute unit at most (the environment's `env_name`:
 // another bound -- tests: the stride on a small file)

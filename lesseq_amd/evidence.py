@@ -52,8 +52,8 @@ class EvidenceIndex(Index):
     """lsq_fe_index_build: psi's index (events, forms, informative introns) and the informative body's regions with their lookup"""
     PREFIX = "lsq_fe"
 
-    def __init__(self, annotation):
-        super().__init__(annotation)
+    def __init__(self, annotation, library="unstranded"):
+        super().__init__(annotation, library)
         first, introns, body = P(u32)(), P(u32)(), P(u64)()
         check(lib.lsq_fe_index_arrays(self.h, C.byref(first), C.byref(introns), C.byref(body)))
         self.event_first_form = copied(first, self.num_events + 1, np.uint32)

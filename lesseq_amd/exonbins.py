@@ -41,11 +41,12 @@ class ExonBins(Table):
 
 
 class ExonBinIndex(Index):
-    """lsq_xb_index_build: the annotation's chromosomes, every gene's bins, the lookup of the bins that overlap a block"""
+    """lsq_xb_index_build: the annotation's chromosomes, every gene's bins, the lookup of the bins that overlap a block.
+    library "forward" / "reverse" (lsq_xb_index_build_library): a read counts for the genes of its transcript strand alone"""
     PREFIX = "lsq_xb"
 
-    def __init__(self, annotation):
-        super().__init__(annotation)
+    def __init__(self, annotation, library="unstranded"):
+        super().__init__(annotation, library)
         nb, ng = self.num_bins, self.num_genes
         ptrs = [P(i64)(), P(i64)(), P(u32)(), P(u32)(), P(u32)()]
         check(lib.lsq_xb_index_arrays(self.h, *[C.byref(p) for p in ptrs]))

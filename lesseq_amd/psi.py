@@ -44,11 +44,12 @@ class Psi(Table):
 
 
 class PsiIndex(Index):
-    """lsq_ps_index_build: the annotation's chromosomes, every event's forms, the informative introns with the forms that hold them"""
+    """lsq_ps_index_build: the annotation's chromosomes, every event's forms, the informative introns with the forms that hold them.
+    library "forward" / "reverse" (lsq_ps_index_build_library): a read counts for the events of its transcript strand alone"""
     PREFIX = "lsq_ps"
 
-    def __init__(self, annotation):
-        super().__init__(annotation)
+    def __init__(self, annotation, library="unstranded"):
+        super().__init__(annotation, library)
         first, introns = P(u32)(), P(u32)()
         check(lib.lsq_ps_index_arrays(self.h, C.byref(first), C.byref(introns)))
         self.event_first_form = copied(first, self.num_events + 1, np.uint32)

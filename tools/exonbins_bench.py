@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Reads per exon bin and per gene of a read file on the GPU box (lsq_xb_device against the parse ahead of it and against
 lsq_xb_host_reads):
-    python tools/exonbins_bench.py [--reads N] [--sam-reads N] [--events N] [--reps K] [--step-timeout S] [--orders sorted,shuffled]
+    python tools/exonbins_bench.py [--reads N] [--sam-reads N] [--events N] [--reps K] [--step-timeout S] [--orders sorted,shuffled] [--library unstranded|forward|reverse]
                                    [--formats MRF_SINGLE,SAM_SINGLE] [--out FILE]
 The generator's library (SynthSpec: --reads reads over --events events, Zipf depth, 8 chromosomes) against its own gene annotation,
 written coordinate-sorted and shuffled, as MRF and as SAM (--sam-reads: a SAM text is seven times its MRF text; default: --reads,
@@ -10,7 +10,7 @@ or what half of the free room of the temporary directory holds).  Every file's d
 Per file: the report, the bins and the genes; the device milliseconds of each phase (lsq_xb_table_times) beside the same run's copy
 and parse (lsq_last_mrf_timing), best of --reps by the count phase; the peak of the device's used memory during the call, sampled;
 and, for the MRF files, lsq_xb_host_reads from already-parsed arrays on 1 and on 16 threads, its table compared with the device's.
-Prints one JSON object, and writes it to --out after every file.  At most 16 host threads."""
+--library: stranded counting in this tool's own index; the runs reported for comparison stay unstranded.  Prints one JSON object, and writes it to --out after every file.  At most 16 host threads."""
 import argparse
 import hashlib
 import json
@@ -33,7 +33,7 @@ def digest(t):
 def child(a):
     import torch
     import lesseq_amd as L
-    ix = L.ExonBinIndex(L.Annotation(a.interval, a.map))
+    ix = L.ExonBinIndex(L.Annotation(a.interval, a.map), a.library)
     ctx = L.Context(0)
     free0 = torch.cuda.mem_get_info(0)[0]
     low = [free0]
@@ -57,15 +57,15 @@ def child(a):
         stop.set()
         th.join()
     best = min(runs, key=lambda r: r["phases_ms"]["count"])
-    out = {"format": a.child, "text_bytes": os.path.getsize(a.reads_path), "report": t.report, "bins": ix.num_bins, "genes": ix.num_genes,
+    out = {"format": a.child, "text_bytes": os.path.getsize(a.reads_path), "report": t.report, "library_report": t.library_report() if a.library != "unstranded" else None, "bins": ix.num_bins, "genes": ix.num_genes,
            "largest_bin": int(t.reads.max()) if len(t) else 0, "largest_gene": int(t.total.max()) if len(t.total) else 0, "bins_hit": int((t.reads > 0).sum()),
            "sums_agree": int(t.reads.sum()) == t.report["bin_hits"], "table_digest": digest(t), "best": best, "runs": runs, "peak_device_bytes_sampled": free0 - low[0]}
     ctx.close()
     print("RESULT " + json.dumps(out))
 
 
-def host_runs(L, d, stem):
-    ix = L.ExonBinIndex(L.Annotation(os.path.join(d, stem + ".interval"), os.path.join(d, stem + ".map")))
+def host_runs(L, d, stem, library):
+    ix = L.ExonBinIndex(L.Annotation(os.path.join(d, stem + ".interval"), os.path.join(d, stem + ".map")), library)
     t0 = time.perf_counter()
     reads = ix.parse_host("MRF_SINGLE", os.path.join(d, stem + ".mrf"), n_threads=16)
     out = {"host_parse_16_threads_s": time.perf_counter() - t0}
@@ -95,13 +95,14 @@ def main():
     ap.add_argument("--interval")
     ap.add_argument("--map")
     ap.add_argument("--reads-path")
+    ap.add_argument("--library", default="unstranded", choices=("unstranded", "forward", "reverse"))
     a = ap.parse_args()
     if a.child:
         return child(a)
     os.environ.setdefault("LSQ_NO_TORCH", "1")      # (the parent touches no GPU)
     import lesseq_amd as L
     d = tempfile.mkdtemp(prefix="lsq_xb_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
-    out = {"n_reads": a.reads, "n_events": a.events, "files": []}
+    out = {"n_reads": a.reads, "n_events": a.events, "library": a.library, "files": []}
 
     def save():
         if a.out:
@@ -128,7 +129,7 @@ def main():
                 path = os.path.join(d, stem + (".mrf" if fmt == "MRF_SINGLE" else ".sam"))
                 rec = {"order": order, "format": fmt, "n_reads": n, "write_s": round(time.time() - t0, 2)}
                 print("written %s %s" % (order, fmt), file=sys.stderr, flush=True)
-                argv = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", fmt, "--reps", str(a.reps),
+                argv = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", fmt, "--reps", str(a.reps), "--library", a.library,
                         "--interval", os.path.join(d, stem + ".interval"), "--map", os.path.join(d, stem + ".map"), "--reads-path", path]
                 env = dict(os.environ)
                 env.pop("LSQ_NO_TORCH", None)
@@ -144,7 +145,7 @@ def main():
                 print("device runs done %s %s" % (order, fmt), file=sys.stderr, flush=True)
                 save()
                 if fmt == "MRF_SINGLE":
-                    rec["host"] = host_runs(L, d, stem)
+                    rec["host"] = host_runs(L, d, stem, a.library)
                     rec["host_equals_device"] = rec["host"]["table_digest"] == rec["table_digest"]
                 out["files"].append(rec)
                 os.remove(path)

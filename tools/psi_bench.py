@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
 """Junction reads per event form of a read file on the GPU box (lsq_ps_device against the parse ahead of it, against the other two
 tools' passes over the same file and against lsq_ps_host_reads):
-    python tools/psi_bench.py [--reads N] [--events N] [--reps K] [--step-timeout S] [--orders sorted,shuffled] [--out FILE]
+    python tools/psi_bench.py [--reads N] [--events N] [--reps K] [--step-timeout S] [--orders sorted,shuffled] [--library unstranded|forward|reverse] [--out FILE]
 The generator's library (SynthSpec: --reads reads over --events events, Zipf depth, 8 chromosomes; the build of
 tools/exonbins_bench.py) against the generator's own events, written coordinate-sorted and shuffled as MRF.  Every file's device run
 is a child process of its own under `timeout`, and the first one that fails ends the run.  Per file: the report, the events, forms
 and informative introns; the device milliseconds of each phase (lsq_ps_table_times) beside the same run's copy and parse
 (lsq_last_mrf_timing), best of --reps by the count phase; in the same process and on the same file the phases of lsq_jn_device and
 of lsq_xb_device, best of --reps by their sum; and lsq_ps_host_reads from already-parsed arrays on 1 and on 16 threads, its table
-compared with the device's.  Prints one JSON object, and writes it to --out after every file.  At most 16 host threads."""
+compared with the device's.  --library: stranded counting in this tool's own index; the runs reported for comparison stay unstranded.  Prints one JSON object, and writes it to --out after every file.  At most 16 host threads."""
 import argparse
 import hashlib
 import json
@@ -30,7 +30,7 @@ def digest(t):
 def child(a):
     import lesseq_amd as L
     ann = L.Annotation(a.interval, a.map)
-    ix = L.PsiIndex(ann)
+    ix = L.PsiIndex(ann, a.library)
     ctx = L.Context(0)
     runs = []
     for _ in range(a.reps):
@@ -40,7 +40,7 @@ def child(a):
         tm = ctx.mrf_timing()
         runs.append({"wall_s": wall, "copy_ms": tm["h2d_ms"], "parse_ms": tm["parse_ms"], "phases_ms": t.times})
     best = min(runs, key=lambda r: r["phases_ms"]["count"])
-    out = {"text_bytes": os.path.getsize(a.reads_path), "report": t.report, "events": ix.num_events, "forms": ix.num_forms, "introns": ix.num_introns,
+    out = {"text_bytes": os.path.getsize(a.reads_path), "report": t.report, "library_report": t.library_report() if a.library != "unstranded" else None, "events": ix.num_events, "forms": ix.num_forms, "introns": ix.num_introns,
            "largest_form": int(t.reads.max()) if len(t) else 0, "forms_hit": int((t.reads > 0).sum()), "psi_rows_not_na": int((t.psi() == t.psi()).sum()),
            "table_digest": digest(t), "best": best, "runs": runs}
     # the other two tools' passes behind the same parse, for the comparison
@@ -59,8 +59,8 @@ def child(a):
     print("RESULT " + json.dumps(out))
 
 
-def host_runs(L, d, stem):
-    ix = L.PsiIndex(L.Annotation(os.path.join(d, stem + ".interval"), os.path.join(d, stem + ".map")))
+def host_runs(L, d, stem, library):
+    ix = L.PsiIndex(L.Annotation(os.path.join(d, stem + ".interval"), os.path.join(d, stem + ".map")), library)
     t0 = time.perf_counter()
     reads = ix.parse_host("MRF_SINGLE", os.path.join(d, stem + ".mrf"), n_threads=16)
     out = {"host_parse_16_threads_s": time.perf_counter() - t0}
@@ -88,13 +88,14 @@ def main():
     ap.add_argument("--interval")
     ap.add_argument("--map")
     ap.add_argument("--reads-path")
+    ap.add_argument("--library", default="unstranded", choices=("unstranded", "forward", "reverse"))
     a = ap.parse_args()
     if a.child:
         return child(a)
     os.environ.setdefault("LSQ_NO_TORCH", "1")      # (the parent touches no GPU)
     import lesseq_amd as L
     d = tempfile.mkdtemp(prefix="lsq_ps_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
-    out = {"n_reads": a.reads, "n_events": a.events, "files": []}
+    out = {"n_reads": a.reads, "n_events": a.events, "library": a.library, "files": []}
 
     def save():
         if a.out:
@@ -111,7 +112,7 @@ def main():
             path = os.path.join(d, stem + ".mrf")
             rec = {"order": order, "n_reads": a.reads, "write_s": round(time.time() - t0, 2)}
             print("written %s" % order, file=sys.stderr, flush=True)
-            argv = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps),
+            argv = ["timeout", "-k", "10", str(a.step_timeout), sys.executable, os.path.abspath(__file__), "--child", "--reps", str(a.reps), "--library", a.library,
                     "--interval", os.path.join(d, stem + ".interval"), "--map", os.path.join(d, stem + ".map"), "--reads-path", path]
             env = dict(os.environ)
             env.pop("LSQ_NO_TORCH", None)
@@ -125,7 +126,7 @@ def main():
                 break
             rec.update(json.loads(got[0][7:]))
             print("device runs done %s" % order, file=sys.stderr, flush=True)
-            rec["host"] = host_runs(L, d, stem)
+            rec["host"] = host_runs(L, d, stem, a.library)
             rec["host_equals_device"] = rec["host"]["table_digest"] == rec["table_digest"]
             out["files"].append(rec)
             os.remove(path)
