@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*), "sites" (lsq_ss_*) or "libtype" (lsq_lt_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*), "sites" (lsq_ss_*), "retention" (lsq_ir_*) or "libtype" (lsq_lt_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -757,6 +757,64 @@ int lsq_ss_table_times(const lsq_ss_table *t, float ms[4]);
 /* The text of the rows with reads >= min_reads and, with novel_only, ann '.'; malloc'd, NUL-terminated (lsq_free). */
 int lsq_ss_format(const lsq_ss_table *t, uint32_t min_reads, int novel_only, int ratios, char **out_text);
 int lsq_ss_lds_slots(void);      /* boundary ids a workgroup of the device count keeps in LDS (tests place their cases around it) */
+
+/* ------------------------------------------------------------------------------------
+ * Intron retention of a read file: per intron of the annotation its splice-site counts and the depth over the
+ * bases of its body that belong to no exon, summarised by order statistics that a local pile-up cannot move -- the integers behind
+ * IRFinder's IR ratio (Middleton et al. 2017)
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition; inputs, coordinates, chromosomes and columns 1-9 are the sites table's above, the depth is the coverage table's below.
+ *   rows           one per distinct intron of the annotation: the rows of lsq_ss_*'s table under the same min_overhang whose ann is
+ *                  not '.', in that table's order.  A novel junction makes no row; it counts in the spliced sums of the sites it shares.
+ *   body           an intron (a, b) -- the end of the left exon interval, the start of the right one -- has the body [a, b).
+ *   clean bases    the bases of [a, b) in no exon of any isoform line on that chromosome, on either strand (exons with end > start,
+ *                  the first exonCount of a line, coordinates clamped to +-2^30).  They form maximal intervals, the intron's pieces;
+ *                  an intron wholly covered by other lines' exons has none.
+ *   depth          d(x) of lsq_cov_* with strand 0: every counted block on its own, 0 where no row lies.
+ *   clean          n, the number of clean bases; covered: those with d >= 1; depth_sum: the sum of d over them (64 bits).
+ *   q25 q50 q75    the n clean bases' depths sorted ascending, zeros included, d(1) <= ... <= d(n): column q (1, 2, 3) is d(k) with
+ *                  k = (q n + 3) div 4 = ceil(q n / 4); all three 0 when n is 0.  No interpolation: exact integers.
+ *   text           the sites row's nine columns, then TAB clean TAB covered TAB depth_sum TAB q25 TAB q50 TAB q75 NL; no header.  With
+ *                  ratios three more columns: mean = depth_sum / clean, coverage = covered / clean, ir_ratio = q50 / (q50 +
+ *                  max(left_spliced, right_spliced)) -- on the host in double from the integers, %.6f, NA where the denominator is
+ *                  0; with clean 0 all three are NA.
+ *   report         thirteen: lsq_ss_table_report's eight, then the rows (introns), the rows with clean 0, the pieces, the depth rows
+ *                  of the file, and lsq_cov_table_report's bases.
+ * Limits: lsq_ss_*'s and lsq_cov_*'s, and 2^32-2 pieces.  Beyond a limit: LSQ_E_RANGE. */
+typedef struct lsq_ir_index lsq_ir_index;       /* an lsq_ss_index and every chromosome's exon union */
+typedef struct lsq_ir_table lsq_ir_table;
+int lsq_ir_index_build(const lsq_annotation *a, lsq_ir_index **out);
+void lsq_ir_index_free(lsq_ir_index *ix);
+int64_t lsq_ir_index_num_chroms(const lsq_ir_index *ix);
+const char *lsq_ir_index_chrom_name(const lsq_ir_index *ix, int64_t chrom);      /* NULL when out of range */
+int64_t lsq_ir_index_num_introns(const lsq_ir_index *ix);
+lsq_events *lsq_ir_index_dictionaries(lsq_ir_index *ix);                  /* as lsq_jn_index_dictionaries */
+/* Host-only, threaded: the table from the host parsers' arrays; read_format, skip_flags, min_mapq, statuses and messages as for
+ * lsq_jn_host (the name-keyed formats included).  min_overhang is lsq_ss_host's, 0 included; the depth does not depend on it.
+ * lsq_ir_host_reads: from arrays parsed against the index. */
+int lsq_ir_host(lsq_ir_index *ix, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, uint32_t min_overhang, int n_threads,
+                lsq_ir_table **out);
+int lsq_ir_host_reads(lsq_ir_index *ix, const lsq_reads *r, uint32_t min_overhang, int n_threads, lsq_ir_table **out);
+/* Device (HIP, gfx950): "MRF_SINGLE", "SAM_SINGLE" or "BAM_SINGLE", parsed once exactly as lsq_jn_device parses it; on those arrays
+ * lsq_ss_device's passes, then lsq_cov_device's extract, sort, reduce and scan, emit -- the depth rows stay on the device -- the
+ * pieces put together on the host and uploaded, and the selection: a wave an intron, the order statistics by bisection on the
+ * depth.  One entry an intron of five arrays comes back.  The context needs no events, and its events, reads and counters are as
+ * they were afterwards.  LSQ_IR_GRID in the environment bounds the selection's workgroups (tests). */
+int lsq_ir_device(lsq_ctx *c, lsq_ir_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ir_table **out);
+void lsq_ir_table_free(lsq_ir_table *t);
+int64_t lsq_ir_table_rows(const lsq_ir_table *t);
+/* The rows' arrays (they live as long as the table; any pointer may be null): chrom indexes lsq_ir_index_chrom_name. */
+int lsq_ir_table_arrays(const lsq_ir_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint8_t **ann, const uint64_t **reads,
+                        const uint64_t **left_spliced, const uint64_t **left_through, const uint64_t **right_spliced, const uint64_t **right_through,
+                        const uint64_t **clean, const uint64_t **covered, const uint64_t **depth_sum, const uint32_t **q25, const uint32_t **q50, const uint32_t **q75);
+int lsq_ir_table_report(const lsq_ir_table *t, uint64_t report[13]);
+/* Device milliseconds per phase of the lsq_ir_device call that made the table -- sites (the sum of lsq_ss_table_times' four), depth
+ * (the sum of lsq_cov_table_times' extract, sort, reduce and scan, emit), index (host work and upload), select, copy-back -- from
+ * HIP events on the library's stream (zeros from the host path). */
+int lsq_ir_table_times(const lsq_ir_table *t, float ms[5]);
+/* The text of all rows; malloc'd, NUL-terminated (lsq_free). */
+int lsq_ir_format(const lsq_ir_table *t, int ratios, char **out_text);
 
 /* ------------------------------------------------------------------------------------
  * Per-base read depth of a read file: what `bedtools genomecov -bg -split` prints, and the depth of every

@@ -267,6 +267,22 @@ _sig("lsq_ss_table_report", C.c_int, vp, P(u64))
 _sig("lsq_ss_table_times", C.c_int, vp, P(C.c_float))
 _sig("lsq_ss_format", C.c_int, vp, u32, C.c_int, C.c_int, P(vp))
 _sig("lsq_ss_lds_slots", C.c_int)
+_sig("lsq_ir_index_build", C.c_int, vp, P(vp))
+_sig("lsq_ir_index_free", None, vp)
+_sig("lsq_ir_index_num_chroms", i64, vp)
+_sig("lsq_ir_index_chrom_name", cs, vp, i64)
+_sig("lsq_ir_index_num_introns", i64, vp)
+_sig("lsq_ir_index_dictionaries", vp, vp)
+_sig("lsq_ir_host", C.c_int, vp, cs, cs, C.c_uint, C.c_uint, u32, C.c_int, P(vp))
+_sig("lsq_ir_host_reads", C.c_int, vp, vp, u32, C.c_int, P(vp))
+_sig("lsq_ir_device", C.c_int, vp, vp, cs, cs, u32, P(vp))
+_sig("lsq_ir_table_free", None, vp)
+_sig("lsq_ir_table_rows", i64, vp)
+_sig("lsq_ir_table_arrays", C.c_int, vp, P(P(u32)), P(P(i32)), P(P(i32)), P(P(u8)), P(P(u64)), P(P(u64)), P(P(u64)), P(P(u64)), P(P(u64)), P(P(u64)), P(P(u64)), P(P(u64)),
+     P(P(u32)), P(P(u32)), P(P(u32)))
+_sig("lsq_ir_table_report", C.c_int, vp, P(u64))
+_sig("lsq_ir_table_times", C.c_int, vp, P(C.c_float))
+_sig("lsq_ir_format", C.c_int, vp, C.c_int, P(vp))
 _sig("lsq_cov_index_build", C.c_int, vp, P(vp))
 _sig("lsq_cov_index_free", None, vp)
 _sig("lsq_cov_index_num_chroms", i64, vp)

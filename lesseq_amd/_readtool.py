@@ -1,4 +1,4 @@
-"""What the tools that take an annotation and a read file share (junctions, coverage, exonbins, psi, evidence, sites): the handle of an index with its
+"""What the tools that take an annotation and a read file share (junctions, coverage, exonbins, psi, evidence, sites, retention): the handle of an index with its
 chromosome dictionary and host parse, the handle of a table with its report and phase times.  A subclass names its entry points'
 prefix (`lsq_jn`: lsq_jn_index_build, lsq_jn_table_report, ...) and keeps what is its own."""
 import ctypes as C

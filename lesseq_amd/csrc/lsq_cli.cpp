@@ -27,6 +27,7 @@
 #include "lsq_psi.hpp"
 #include "lsq_evidence.hpp"
 #include "lsq_sites.hpp"
+#include "lsq_retention.hpp"
 #include "lsq_team.hpp"
 
 using namespace lsq;
@@ -923,6 +924,7 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
 	else if (tool && strcmp(tool, "psi") == 0) rc = run_psi(argc, argv, out);
 	else if (tool && strcmp(tool, "evidence") == 0) rc = run_evidence(argc, argv, out);
 	else if (tool && strcmp(tool, "sites") == 0) rc = run_sites(argc, argv, out);
+	else if (tool && strcmp(tool, "retention") == 0) rc = run_retention(argc, argv, out);
 	else if (tool && strcmp(tool, "libtype") == 0) rc = run_libtype(argc, argv, out);
 	else { fail(LSQ_E_ARG, "unknown tool"); return 2; }
 	if (out_text) *out_text = dup_text(out);

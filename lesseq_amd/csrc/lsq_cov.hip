@@ -8,7 +8,7 @@
 #include "lsq_wave.hpp"
 #include "lsq_scan.hpp"
 #include "lsq_sort.hpp"
-#include "lsq_cov.hpp"
+#include "lsq_cov_dev.hpp"
 
 namespace {
 
@@ -79,7 +79,6 @@ __global__ void __launch_bounds__(256) lsq_cov_piece_flags_kernel(const unsigned
 	const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
 	if (i < n) flag[i] = cov_piece_depth(w0, w1, S, i) ? 1u : 0u;
 }
-struct CovPieces { unsigned *chrom; int *start, *end; unsigned *depth; };
 __global__ void __launch_bounds__(256) lsq_cov_pieces_kernel(const unsigned long long *w0, const unsigned long long *w1, const unsigned long long *S, unsigned long long n,
                                                              const unsigned *flag, const unsigned long long *at, CovPieces P) {
 	const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
@@ -159,28 +158,16 @@ __global__ void __launch_bounds__(256) lsq_cov_regions_kernel(CovIntervals I, Co
 	if (sum) atomicAdd(&depth_sum[line], sum);
 }
 
-struct DevPieces {
-	DevBuf<unsigned> chrom, depth;
-	DevBuf<int> start, end;
-	int alloc(size_t n) { int rc; if ((rc = chrom.alloc(n)) || (rc = start.alloc(n)) || (rc = end.alloc(n)) || (rc = depth.alloc(n))) return rc; return LSQ_OK; }
-	CovPieces view() const { return CovPieces{chrom.p, start.p, end.p, depth.p}; }
-};
-
 } // namespace
 
-int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, lsq_cov_table &t) {
+// extract, sort, reduce and scan, emit: the rows left on the device (lsq_cov_dev.hpp), for the regions and the copy-back below and
+// for lsq_retention.hip's selection
+int lsq::cov_device_rows(lsq_ctx *c, const ParsedReads &R, int strand, PhaseClock<COV_PHASES> &PC, DevPieces &rows, unsigned &n_rows, uint64_t *report) {
 	hipStream_t st = c->stream;
 	int rc;
-	PhaseClock<COV_PHASES> PC;
-	if ((rc = PC.make())) return rc;
-	if (R.n_reads > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 reads");
-	const size_t n_regions = ix.name.size();
-	t.resize(0);
-	t.r_covered.assign(n_regions, 0); t.r_depth_sum.assign(n_regions, 0);
-	for (uint64_t &v : t.report) v = 0;
-	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
-	for (float &m : t.ms) m = 0;
-	if (!R.n_reads) return LSQ_OK;
+	n_rows = 0;
+	for (int k = 0; k < COV_REPORT; ++k) report[k] = 0;
+	report[0] = R.n_reads; report[1] = R.n_blocks;
 	const unsigned strand_id = strand == '+' ? 0u : strand == '-' ? 1u : 0xFFFFFFFFu;
 
 	// ---- extract
@@ -213,10 +200,8 @@ int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads
 	HIP_TRY(PC.mark(1, st));
 	HIP_TRY(hipStreamSynchronize(st));
 	d_cnt.alloc(0); d_off.alloc(0);
-	t.report[2] = n_counted; t.report[3] = acc.nochrom; t.report[4] = acc.empty; t.report[5] = acc.other; t.report[6] = acc.bases;
+	report[2] = n_counted; report[3] = acc.nochrom; report[4] = acc.empty; report[5] = acc.other; report[6] = acc.bases;
 
-	unsigned n_rows = 0;
-	DevPieces rows;
 	if (n) {
 		// ---- sort: the digits of the position, then the chromosome's; those on which every record agrees are left out
 		static const unsigned ALL_DIGITS[6] = {0, 8, 16, 24, 64 + 32, 64 + 40};
@@ -269,6 +254,26 @@ int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads
 		HIP_TRY(PC.mark(4, st));
 		HIP_TRY(hipStreamSynchronize(st));      // (the pieces, the flags and the places are freed on leaving the block)
 	} else { for (int k = 2; k <= 4; ++k) HIP_TRY(PC.mark(k, st)); }
+	return LSQ_OK;
+}
+
+int lsq::cov_device_reads(lsq_ctx *c, const lsq_cov_index &ix, const ParsedReads &R, int strand, uint32_t min_depth, lsq_cov_table &t) {
+	hipStream_t st = c->stream;
+	int rc;
+	PhaseClock<COV_PHASES> PC;
+	if ((rc = PC.make())) return rc;
+	if (R.n_reads > 0xFFFFFFFFull) return fail(LSQ_E_RANGE, "more than 2^32 reads");
+	const size_t n_regions = ix.name.size();
+	t.resize(0);
+	t.r_covered.assign(n_regions, 0); t.r_depth_sum.assign(n_regions, 0);
+	for (uint64_t &v : t.report) v = 0;
+	t.report[0] = R.n_reads; t.report[1] = R.n_blocks;
+	for (float &m : t.ms) m = 0;
+	if (!R.n_reads) return LSQ_OK;
+	unsigned n_rows = 0;
+	DevPieces rows;
+	ScanScratch SS;
+	if ((rc = cov_device_rows(c, R, strand, PC, rows, n_rows, t.report))) return rc;
 
 	// ---- regions
 	DevBuf<unsigned long long> d_cov, d_sum;

@@ -2,8 +2,8 @@
 // (ReadSource), and the entry points that take one -- through the chain (lsq_ingest.hip) for count and solve, into the arrays of
 // lsq_mrf_parse for tests and tools, or over its records alone (lsq_bam_check).  The parsers themselves are lsq_mrf_device.hpp,
 // lsq_sam_device.hpp and lsq_bam_device.hpp; this unit and the chain's meet through lsq_ingest.hpp only.  The tools that take a
-// read file against an index's dictionaries (junctions, coverage, exonbins, psi, evidence, sites) enter through table_of_file: their passes
-// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip, lsq_evidence.hip, lsq_sites.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
+// read file against an index's dictionaries (junctions, coverage, exonbins, psi, evidence, sites, retention) enter through table_of_file: their passes
+// (lsq_junc.hip, lsq_cov.hip, lsq_exonbins.hip, lsq_psi.hip, lsq_evidence.hip, lsq_sites.hip, lsq_retention.hip) take the device arrays as lsq_readtool.hpp's ParsedReads.
 #include <fcntl.h>
 #include <unistd.h>
 
@@ -15,6 +15,7 @@
 #include "lsq_cov.hpp"
 #include "lsq_exonbins.hpp"
 #include "lsq_sites.hpp"
+#include "lsq_retention.hpp"
 #include "lsq_psi.hpp"
 #include "lsq_evidence.hpp"
 #include "lsq_libtype.hpp"
@@ -342,7 +343,7 @@ int parse_file_against(lsq_ctx *c, lsq_events &E, const char *read_format, const
 	return parse_staged_text(c, fmt, T, P);
 }
 
-// lsq_jn_device, lsq_ss_device, lsq_cov_device, lsq_xb_device, lsq_ps_device, lsq_fe_device behind their argument checks: the file parsed against the index's dictionaries, a
+// lsq_jn_device, lsq_ss_device, lsq_ir_device, lsq_cov_device, lsq_xb_device, lsq_ps_device, lsq_fe_device behind their argument checks: the file parsed against the index's dictionaries, a
 // new table filled from the device arrays by the tool's passes (fill(reads, table)) and handed out
 template <class IX, class T, class F>
 int table_of_file(lsq_ctx *c, IX *ix, const char *read_format, const char *path, T **out, F fill) {
@@ -501,6 +502,12 @@ int lsq_jn_device(lsq_ctx *c, lsq_jn_index *ix, const char *read_format, const c
 int lsq_ss_device(lsq_ctx *c, lsq_ss_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ss_table **out) LSQ_API_TRY {
 	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
 	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_ss_table &t) { return ss_device_reads(c, *ix, R, min_overhang, t); });
+} LSQ_API_CATCH
+
+// Intron retention of a read file (include/lesseq_hip.h): the device arrays handed to lsq_retention.hip
+int lsq_ir_device(lsq_ctx *c, lsq_ir_index *ix, const char *read_format, const char *path, uint32_t min_overhang, lsq_ir_table **out) LSQ_API_TRY {
+	if (!c || !ix || !read_format || !path || !out) return fail(LSQ_E_ARG, "null argument");
+	return table_of_file(c, ix, read_format, path, out, [&](const ParsedReads &R, lsq_ir_table &t) { return ir_device_reads(c, *ix, R, min_overhang, t); });
 } LSQ_API_CATCH
 
 // The per-base depth of a read file (include/lesseq_hip.h): the device arrays handed to lsq_cov.hip

@@ -1,4 +1,4 @@
-// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi, evidence, sites):
+// What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi, evidence, sites, retention):
 // the view of parsed reads their passes take, the dictionaries a read file is parsed against without events, a line's exon
 // union and its introns, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
 // the frame of the six executables.  lsq_readtool.cpp defines what is no template.

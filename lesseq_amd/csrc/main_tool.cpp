@@ -6,7 +6,7 @@
 // junctions, the splice junctions of a read file (lsq_junc.cpp); coverage, its per-base depth (lsq_cov.cpp); exonbins, its reads
 // per exon bin and per gene (lsq_exonbins.cpp); psi, its junction reads per event form (lsq_psi.cpp); evidence, its junction and
 // exon-body reads per event form (lsq_evidence.cpp); sites, its splice-site usage and read-through per junction (lsq_sites.cpp);
-// libtype, which library type it is (lsq_libtype.cpp).
+// retention, its depth quartiles and IR ratio per intron (lsq_retention.cpp); libtype, which library type it is (lsq_libtype.cpp).
 // The tool is chosen by the program name.
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +17,6 @@
 int main(int argc, char **argv) {
 	const char *base = strrchr(argv[0], '/');
 	base = base ? base + 1 : argv[0];
-	const char *tool = strstr(base, "libtype") ? "libtype" : strstr(base, "sites") ? "sites" : strstr(base, "evidence") ? "evidence" : strstr(base, "psi") ? "psi" : strstr(base, "exonbins") ? "exonbins" : strstr(base, "coverage") ? "coverage" : strstr(base, "junctions") ? "junctions" : strstr(base, "sam2mrf") ? "sam2mrf" : strstr(base, "bam2mrf") ? "bam2mrf" : strstr(base, "bamcheck") ? "bamcheck" : strstr(base, "parseGencode") ? "parseGencode" : strstr(base, "gencodeIsoformMap") ? "gencodeIsoformMap" : strstr(base, "events") ? "events" : strstr(base, "test_as") ? "test_as" : strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
+	const char *tool = strstr(base, "libtype") ? "libtype" : strstr(base, "retention") ? "retention" : strstr(base, "sites") ? "sites" : strstr(base, "evidence") ? "evidence" : strstr(base, "psi") ? "psi" : strstr(base, "exonbins") ? "exonbins" : strstr(base, "coverage") ? "coverage" : strstr(base, "junctions") ? "junctions" : strstr(base, "sam2mrf") ? "sam2mrf" : strstr(base, "bam2mrf") ? "bam2mrf" : strstr(base, "bamcheck") ? "bamcheck" : strstr(base, "parseGencode") ? "parseGencode" : strstr(base, "gencodeIsoformMap") ? "gencodeIsoformMap" : strstr(base, "events") ? "events" : strstr(base, "test_as") ? "test_as" : strstr(base, "solve") ? "solve" : (strstr(base, "classify") ? "classify" : "count");
 	return lsq_cli_main(tool, argc, argv);
 }
