@@ -41,6 +41,12 @@ int lsq_debug_slot_offsets(lsq_ctx *c, int method, unsigned long long *out, unsi
 int lsq_debug_plan_shares(const unsigned long long *slot_off, const unsigned char *packed, const unsigned long long *n1, const unsigned long long *n2,
                           const unsigned *look1, const unsigned *look2, unsigned long long n_buckets, unsigned long long grid,
                           const double *costs4, int weighted, int snap, unsigned long long *cuts);
+/* The compact pool record of a block, through the library's own pack and unpack helpers (host only, no device).  which = 0: a
+ * block that starts `off` bases from the record's origin and is `len` long -- returns 0 when it does not fit a compact record,
+ * else 1 with the record and the (start, end) it unpacks to; which = 1 / 2: the padding record of the one- / two-block pool
+ * (block 1 of it) that is number `off` of its group and number `len` of its half group (1 to 15 each) -- returns 1 likewise:
+ * padding unpacks to an empty block.  Negative: an error code. */
+int lsq_debug_compact_record(int which, long long off, long long len, uint32_t *rec, int32_t *start, int32_t *end);
 /* An offset table of a method -- which = 0: slots per bucket, 1 / 2: the one- / two-block pool per bucket (n_buckets + 1
  * values each), 3: the share bounds of the count launch's streaming workgroups (their number + 1), 4 / 5: the ingest's
  * estimate of the one- / two-block reads per bucket that the streaming loops leave to the general walk; *n = values written. */

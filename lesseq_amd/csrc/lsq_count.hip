@@ -73,13 +73,15 @@ struct CountArgs {
 
 // compact records to coordinates; base = the bucket's first base minus COMPACT_BIAS
 __device__ inline int2 unpack_one_block(const unsigned a, const int base) {
-	const int s = base + (int)(a & lsq::COMPACT_OFF_MASK);
-	return make_int2(s, s + (int)(a >> lsq::COMPACT_OFF_BITS));
+	int off, end;
+	lsq::compact_unpack(a, off, end);
+	return make_int2(base + off, base + end);
 }
 __device__ inline int4 unpack_two_block(const unsigned a, const unsigned b, const int base) {
-	const int s1 = base + (int)(a & lsq::COMPACT_OFF_MASK), e1 = s1 + (int)(a >> lsq::COMPACT_OFF_BITS);
-	const int s2 = e1 + (int)(b & lsq::COMPACT_OFF_MASK);
-	return make_int4(s1, e1, s2, s2 + (int)(b >> lsq::COMPACT_OFF_BITS));
+	int off, end, gap, reach;
+	lsq::compact_unpack<true>(a, off, end);
+	lsq::compact_unpack<true>(b, gap, reach);
+	return make_int4(base + off, base + end, base + end + gap, base + end + reach);
 }
 // a read of bucket `lo`'s slice of the pools (the slow paths: exception pass, recount, generic buckets)
 __device__ inline int2 pool1_read(const CountArgs &A, const unsigned long long g, const int lo) {
@@ -818,23 +820,25 @@ __device__ inline void stream_pool_wide(FastCtx &C, const uint4 *bins, const uin
 // records).  They lean on the pools' layout, which the ingest establishes with the kernel's own look at the tables and
 // lsq_debug_check_pool_layout verifies in the tests:
 //   one-block pool: the records of an aligned group of eight (P1_GROUP_PAD) start in ONE cell -- the cell of the group's
-//     first record -- or all in none; padding records are empty (length 0) and sit at the tail of a cell's records;
+//     first record -- or all in none; padding records (COMPACT_PAD | ranks) sit at the tail of a cell's records;
 //   two-block pool: an aligned quadruple (P2_GROUP_PAD) lies in ONE junction group -- block 1 starts in the same one-owner cell and ends
 //     on the end of that owner's segment, block 2 starts on the same first base of a later segment of that event -- or in
-//     the bucket's last group (everything else); padding (length 0) never comes first in such a group.
+//     the bucket's last group (everything else); padding (block 1 = ranks << 10, block 2 = 0) never comes first in such a group.
 // So a lane looks at the tables once, for its first record, and every further record only has to show where it ENDS.
 
-// One-block reads, NR = 4 or 8 per lane and step (one or two 16-byte loads).  Records stay in their own terms (offset
-// from `base`, length); the cell's bounds are brought into those terms once per lane.  Per record: its end against the
-// two thresholds of the cell (e1: inside the owner's segment; e2: inside the segment that abuts it / the farther owner's),
-// count and bases summed per lane in one word each (count << 24 | bases), one LDS atomic per class at the end.  Whether
-// anything is left for the general walk falls out of the sums (records counted against records settled): no per-record
-// flag, no scalar mask logic in the loop.
+// One-block reads, NR = 4 or 8 per lane and step (one or two 16-byte loads).  Records stay as they are stored (end from
+// `base` << 10 | length); the cell's bounds are brought into those terms once per lane, as threshold words.  Per record: the
+// whole record against the two threshold words of the cell (e1: inside the owner's segment; e2: inside the segment that
+// abuts it / the farther owner's), count and bases summed per lane in one word each (count << 24 | bases), one LDS atomic
+// per class at the end.  Whether anything is left for the general walk falls out of the sums (records counted against
+// records settled): no per-record flag, no scalar mask logic in the loop.  Padding lies above every threshold word; how
+// many of a lane's records it is, the lane's last record says (lsq_device.hpp COMPACT_PAD).
 template <int NR>
 __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const uint4 *cells, const uint4 *cellx, const unsigned n_cells, const BucketDesc &d,
                                             const CountArgs &A, uint4 *queue, const void *pool, const unsigned long long g0, const unsigned long long g1) {
 	static_assert(NR == 4 || NR == 8, "one or two 16-byte words of four compact records");
-	static_assert((unsigned)NR <= P1_GROUP_PAD, "a lane's records of a step lie in one cell group");
+	static_assert((unsigned)NR == P1_GROUP_PAD || 2u * (unsigned)NR == P1_GROUP_PAD, "a lane's records of a step are a cell group or an aligned half of one (the padding's ranks)");
+	static_assert(P1_GROUP_PAD <= 16u, "a padding rank takes four bits");
 	constexpr int CW = NR / 4;                     // 16-byte loads a lane issues per step
 	constexpr unsigned TILE = 64u * NR;            // records per wave step
 	C.pool = 0u;
@@ -861,6 +865,10 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 	R.q = queue;
 	const unsigned t_begin = min(wave * TILE, n);
 	if (t_begin < n) fetch(t_begin);
+	// (the two constants of a record's share of the loop's sums, count << 24 | bases, held in registers: as literals they
+	// cost an AND and an OR a record, from registers the two are one instruction)
+	unsigned len_mask = lsq::COMPACT_LEN_MASK, one_read = 1u << 24;
+	asm volatile("" : "+v"(len_mask), "+s"(one_read));       // (one vector, one scalar: an instruction reads one scalar register at most)
 	for (unsigned t = t_begin; t < n; t += WAVES * TILE) {
 		unsigned rec[NR];
 #pragma unroll
@@ -872,7 +880,9 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 			continue;
 		}
 		// ---- one look at the tables: the cell of the lane's first record
-		const int p0 = (int)(rec[0] & lsq::COMPACT_OFF_MASK) + base;
+		// (a lane that takes half a cell group may hold nothing but padding: its look goes to the bucket's first base)
+		int p0 = (int)(rec[0] >> lsq::COMPACT_LEN_BITS) - (int)(rec[0] & lsq::COMPACT_LEN_MASK) + base;
+		if ((unsigned)NR < P1_GROUP_PAD) p0 = lsq::compact_is_pad1(rec[0]) ? d.lo : p0;
 		const int rel0 = p0 - d.lo;
 		const unsigned bin = rel0 <= 0 ? 0u : ((unsigned)rel0 >> d.shift);
 		const uint4 br = bins[min(bin, d.n_bins - 1u)];     // first cell | first event << 16, ends of that cell and the next two
@@ -886,25 +896,30 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 		// the lane's records start in this cell (layout) -- if it is one: the bucket's last group holds the reads of no cell
 		const bool has = ci < n_cells && (int)cw.x <= p0 && p0 < (int)cw.y && !ABL(A, 8u);
 		const bool both = has && (cx.z & CELLX_BOTH) != 0;   // two owners: e1 / e2 the ends of their segments, slot 1 / slot 2 theirs
-		// thresholds in the records' terms; without a cell nothing is settled here
+		// thresholds in the records' terms, as words a whole record is compared with; without a cell nothing is settled here
 		const int e1 = has ? (int)cw.z - base : -1, e2 = has ? (int)cw.w - base : -1;
+		const unsigned t1 = lsq::compact_ends_by(e1), t2 = lsq::compact_ends_by(e2);
 		// every step but the first and last of a workgroup's range lies wholly inside it: no per-record range test there
 		const bool interior = t + TILE <= n && t >= first_rel;
-		unsigned accN = 0, accA = 0, accL = 0;          // all records / those that end by e1 / by e2: count << 24 | bases
+		unsigned accN = 0, accA = 0, accL = 0;          // all records / those that end by e1 / by e2: count << 24 | bases (accN: the count alone)
 		// (one_threshold: no lane's cell has a second one -- nothing abuts the owner's segment, no second owner: most waves)
 		auto decide = [&](auto whole_step, auto one_threshold) {
+			if (decltype(whole_step)::value) {
+				// the padding of a cell's group lies above every threshold; how many of the lane's records it is, its last record says
+				const unsigned last = rec[NR - 1];
+				const unsigned ranks = (unsigned)NR < P1_GROUP_PAD ? (last >> 4) & 15u : last & 15u;
+				accN = ((unsigned)NR - (lsq::compact_is_pad1(last) ? ranks : 0u)) << 24;
+			}
 #pragma unroll
 			for (int j = 0; j < NR; ++j) {
-				const unsigned len = rec[j] >> lsq::COMPACT_OFF_BITS;
-				const int e = (int)(rec[j] & lsq::COMPACT_OFF_MASK) + (int)len;
-				unsigned p = len | (min(len, 1u) << 24);           // (an empty record -- the padding of a cell's group -- counts for nothing)
+				unsigned p = (rec[j] & len_mask) | one_read;
 				if (!decltype(whole_step)::value) {
 					const unsigned idx = t + lane * (unsigned)NR + (unsigned)j;
-					p = (idx < n && idx - first_rel < n_rel) ? p : 0u;
+					p = (idx < n && idx - first_rel < n_rel && !lsq::compact_is_pad1(rec[j])) ? p : 0u;
+					accN += p;
 				}
-				accN += p;
-				accA += e <= e1 ? p : 0u;
-				if (!decltype(one_threshold)::value) accL += e <= e2 ? p : 0u;
+				accA += rec[j] <= t1 ? p : 0u;
+				if (!decltype(one_threshold)::value) accL += rec[j] <= t2 ? p : 0u;
 			}
 			if (decltype(one_threshold)::value) accL = accA;
 		};
@@ -936,8 +951,8 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 				unsigned open = 0;
 #pragma unroll
 				for (int j = h; j < h + 2; ++j) {
-					const unsigned len = rec[j] >> lsq::COMPACT_OFF_BITS;
-					const int so = (int)(rec[j] & lsq::COMPACT_OFF_MASK), e = so + (int)len;
+					const unsigned len = rec[j] & lsq::COMPACT_LEN_MASK;
+					const int e = (int)(rec[j] >> lsq::COMPACT_LEN_BITS), so = e - (int)len;
 					const unsigned idx = t + lane * (unsigned)NR + (unsigned)j, rel = idx - first_rel;
 					const bool in = idx < n && rel < n_rel;
 					// two owners: past the end of an owner's segment with no segment abutting it the read matches that owner up to the
@@ -945,7 +960,7 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 					const bool gone_near = both && (cx.z & CELLX_NEAR_NO_ABUT) != 0u && e > e1 && 50 * (e - e1) >= (int)len;
 					const bool gone_far = both && (cx.z & CELLX_FAR_NO_ABUT) != 0u && e > e2 && 50 * (e - e2) >= (int)len;
 					const bool done_near = e <= e1 || gone_near, done_far = e <= e2 || gone_far;          // (one owner: e1 plays no part below)
-					const bool op = in && len != 0u && !(both ? (done_near && done_far) : e <= e2);
+					const bool op = in && !lsq::compact_is_pad1(rec[j]) && !(both ? (done_near && done_far) : e <= e2);
 					open |= op ? 1u << (j - h) : 0u;
 					// the one event to look at: one owner -- that owner; two owners -- the one that is not done with the read; both open: all
 					const unsigned hint = !has ? PARK_EVENT_UNKNOWN : (!both ? (cx.w | PARK_ONE_EVENT) :
@@ -965,20 +980,21 @@ __device__ inline void stream_pool1_compact(FastCtx &C, const uint4 *bins, const
 	if (R.live() && !ABL(A, 32u)) walk_parked<1, false>(C, R, true, base);
 }
 
-// Two-block reads, NR = 2 or 4 per lane and step (8-byte records: block 1 as offset | length, block 2 as gap | length).
+// Two-block reads, NR = 2 or 4 per lane and step (8-byte records: block 1 as end << 10 | length, block 2 as reach << 10 | length).
 // The lane's first record gets the full look -- cell of block 1, the owner's packed record, the segment block 2 starts --
 // and is settled as before: J (block 1 to the end of its segment, block 2 from the first base of a later segment and
 // ending inside it: the two-segment class, matched == total), S (block 2 cannot continue the match: block 1's segment
 // alone, if that is more than 98 % of the read) or parked.  When it crosses a junction, the other records of the quadruple
-// cross the same one (layout): each only shows that block 2 ends inside that segment -- gap + length against one
-// threshold -- and adds its bases; one that runs on is parked for the general walk.  Behind a first record that crosses no
+// cross the same one (layout): each only shows that block 2 ends inside that segment -- its record against one
+// threshold word -- and adds its bases; one that runs on is parked for the general walk.  Behind a first record that crosses no
 // junction a record gets no look of its own: it is settled only as "nothing" (block 1 alone cannot carry it: `nothing`
 // below, which the first record is put through as well) and parked otherwise -- also where it would be S or a start
 // cell's drop as a first record (tests/test_count_paths_gpu.py holds the parked counts of both places).
 template <int NR>
 __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const uint4 *cells, const uint4 *cellx, const unsigned n_cells, const BucketDesc &d,
                                             const CountArgs &A, uint4 *queue, const void *pool, const unsigned long long g0, const unsigned long long g1) {
-	static_assert((NR == 2 || NR == 4 || NR == 8) && (unsigned)NR <= P2_GROUP_PAD, "whole 16-byte words of two compact records, inside one junction group");
+	static_assert((NR == 2 || NR == 4 || NR == 8) && ((unsigned)NR == P2_GROUP_PAD || 2u * (unsigned)NR == P2_GROUP_PAD) && P2_GROUP_PAD <= 16u,
+	              "whole 16-byte words of two compact records: a junction group or an aligned half of one (the padding's ranks, four bits each)");
 	constexpr int CW = NR / 2;
 	constexpr unsigned TILE = 64u * NR;
 	C.pool = 1u;
@@ -1003,7 +1019,7 @@ __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const
 	const unsigned t_begin = min(wave * TILE, n);
 	if (t_begin < n) fetch(t_begin);
 	for (unsigned t = t_begin; t < n; t += WAVES * TILE) {
-		unsigned ra[NR], rb[NR];           // block 1: offset | length << 22; block 2: gap | length << 22
+		unsigned ra[NR], rb[NR];           // block 1: end << 10 | length; block 2: reach << 10 | length (lsq_device.hpp COMPACT_*)
 #pragma unroll
 		for (int cq = 0; cq < CW; ++cq) { ra[2 * cq] = nxt[cq].x; rb[2 * cq] = nxt[cq].y; ra[2 * cq + 1] = nxt[cq].z; rb[2 * cq + 1] = nxt[cq].w; }
 		if (t + WAVES * TILE < n) fetch(t + WAVES * TILE);
@@ -1050,7 +1066,7 @@ __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const
 		const unsigned k1e = ends1b ? k1 + 1u : k1;          // the last segment of block 1's run
 		const bool junction = (ends1 || ends1b) && k2 > k1e;
 		const bool J = junction && rd.w <= end2, Jb = junction && rd.w > end2 && rd.w <= end2b;
-		const unsigned len1 = ra[0] >> lsq::COMPACT_OFF_BITS, total = len1 + (rb[0] >> lsq::COMPACT_OFF_BITS);
+		const unsigned len1 = ra[0] & lsq::COMPACT_LEN_MASK, total = len1 + (rb[0] & lsq::COMPACT_LEN_MASK);
 		const unsigned long long tbl = ((unsigned long long)w0r.w << 32) | w0r.z;
 		const unsigned mask1 = (1u << (k1 & 3u)) | (ends1b ? 2u << (k1 & 3u) : 0u), maskA = mask1 | (1u << k2), maskB = maskA | (2u << k2);
 		const unsigned clsA = (unsigned)(tbl >> (4u * (maskA & 15u))) & 0xFu, clsB = abut2 ? (unsigned)(tbl >> (4u * (maskB & 15u))) & 0xFu : 0u;
@@ -1078,12 +1094,13 @@ __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const
 			near_free = (cx1.z & CELLX_NEAR_NO_ABUT) != 0u; far_free = (cx1.z & CELLX_FAR_NO_ABUT) != 0u;
 		}
 		auto nothing = [&](const unsigned a, const unsigned b2) __attribute__((always_inline)) {      // a record (block 1, block 2) of this cell that counts for nobody
-			const unsigned l1 = a >> lsq::COMPACT_OFF_BITS, l2 = b2 >> lsq::COMPACT_OFF_BITS, gap = b2 & lsq::COMPACT_OFF_MASK;
-			const int y = (int)(a & lsq::COMPACT_OFF_MASK) + (int)l1;
-			const bool weak = gap != 0u && 50u * l1 <= 49u * (l1 + l2);                 // (touching blocks: the exception pass decides)
+			const unsigned l1 = a & lsq::COMPACT_LEN_MASK, l2 = b2 & lsq::COMPACT_LEN_MASK;
+			const int y = (int)(a >> lsq::COMPACT_LEN_BITS);
+			const bool weak = (b2 >> lsq::COMPACT_LEN_BITS) != l2 && 50u * l1 <= 49u * (l1 + l2);      // (touching blocks -- reach == length: the exception pass decides)
 			const bool one_ok = y <= e2c;                                                  // one owner: inside its segment or the one abutting it
 			const bool two_ok = y != e1c && y != e2c && (y < e1c || near_free) && (y < e2c || far_free);
-			return empty || (weak && (two ? two_ok : (v1 && !start1 && one_ok)));
+			// (the padding of a group behind such a record, block 2 == 0, is nobody's either: nothing here tells it from a read otherwise)
+			return empty || b2 == 0u || (weak && (two ? two_ok : (v1 && !start1 && one_ok)));
 		};
 		bool none[NR];
 #pragma unroll
@@ -1097,29 +1114,42 @@ __device__ inline void stream_pool2_compact(FastCtx &C, const uint4 *bins, const
 		if (ABL(A, 256u) && park[0]) atomicAdd(&A.dbg[8 + (v1 ? 1 : 0)], 1ull);       // parked: block 1 in no one-owner cell / in one
 		unsigned nA = (in0 && J && slotA != CELL_NONE) ? 1u : 0u, sA = nA ? total : 0u, nB = (in0 && Jb && slotB != CELL_NONE) ? 1u : 0u, sB = nB ? total : 0u;
 		// ---- the other records: block 2 must end inside the junction's second segment (gap + length <= lim) or inside the one
-		// that abuts it (<= limb)
+		// that abuts it (<= limb).  Both as words a whole block-2 record is compared with: it ends by lim when it lies below
+		// pastA, by limb when below pastB.  The
+		// padding of a junction group (block 2 == 0, no bases) lies below them too: in a whole step it passes as one more read of
+		// the junction -- never parked, nothing to test per record -- and the lane takes its padding off the count afterwards
+		// (how many of its records are padding, its last record says; the first record of a lane at a junction never is).
 		const int lim = junction ? end2 - rd.y : -1, limb = junction ? end2b - rd.y : -1;
+		const unsigned pastA = lsq::compact_past(lim), pastB = lsq::compact_past(limb);
 		bool any_park = park[0];
 		const bool any_b = __any(limb > lim) || ABL(A, 8388608u);
+		// (whole_step: every step but the first and last of a range -- no per-record range test, and the padding is taken off afterwards)
+		auto followers = [&](auto whole_step) {
 #pragma unroll
-		for (int j = 1; j < NR; ++j) {
-			const unsigned l1 = ra[j] >> lsq::COMPACT_OFF_BITS, l2 = rb[j] >> lsq::COMPACT_OFF_BITS;
-			const int reach = (int)(rb[j] & lsq::COMPACT_OFF_MASK) + (int)l2;         // from the end of block 1 to the end of block 2
-			bool in = l1 != 0u;                                                          // (padding of a junction group: an empty record)
-			if (!interior) { const unsigned idx = idx0 + (unsigned)j; in = in && idx < n && idx - first_rel < n_rel; }
-			const bool sameA = in && reach <= lim;
-			bool sameB = false;
-			const bool cA = sameA && slotA != CELL_NONE;
-			nA += cA ? 1u : 0u; sA += cA ? l1 + l2 : 0u;
-			if (any_b) {          // (wave-uniform: some lane's junction leads into a segment that another abuts)
-				sameB = in && reach > lim && reach <= limb;
-				const bool cB = sameB && slotB != CELL_NONE;
-				nB += cB ? 1u : 0u; sB += cB ? l1 + l2 : 0u;
+			for (int j = 1; j < NR; ++j) {
+				const unsigned l12 = (ra[j] & lsq::COMPACT_LEN_MASK) + (rb[j] & lsq::COMPACT_LEN_MASK);
+				bool in = true;
+				if (!decltype(whole_step)::value) { const unsigned idx = idx0 + (unsigned)j; in = rb[j] != 0u && idx < n && idx - first_rel < n_rel; }
+				const bool sameA = in && rb[j] < pastA;
+				bool sameB = false;
+				const bool cA = sameA && slotA != CELL_NONE;
+				nA += cA ? 1u : 0u; sA += cA ? l12 : 0u;
+				if (any_b) {          // (wave-uniform: some lane's junction leads into a segment that another abuts)
+					sameB = in && rb[j] >= pastA && rb[j] < pastB;
+					const bool cB = sameB && slotB != CELL_NONE;
+					nB += cB ? 1u : 0u; sB += cB ? l12 : 0u;
+				}
+				park[j] = in && !(sameA || sameB || none[j]) && !ABL(A, 17u | 1048576u | 2097152u);
+				if (ABL(A, 256u) && park[j]) atomicAdd(&A.dbg[junction ? 14 : 13], 1ull);       // parked followers: block 2 runs past the junction's segments / the first record crosses no junction
+				any_park = any_park || park[j];
 			}
-			park[j] = in && !(sameA || sameB || none[j]) && !ABL(A, 17u | 1048576u | 2097152u);
-			if (ABL(A, 256u) && park[j]) atomicAdd(&A.dbg[junction ? 14 : 13], 1ull);       // parked followers: block 2 runs past the junction's segments / the first record crosses no junction
-			any_park = any_park || park[j];
-		}
+			if (decltype(whole_step)::value) {
+				const unsigned ranks = ra[NR - 1] >> lsq::COMPACT_LEN_BITS;
+				const unsigned pads = rb[NR - 1] != 0u ? 0u : ((unsigned)NR < P2_GROUP_PAD ? (ranks >> 4) & 15u : ranks & 15u);
+				nA -= (junction && slotA != CELL_NONE) ? pads : 0u;
+			}
+		};
+		if (interior) followers(std::true_type{}); else followers(std::false_type{});
 		if (!ABL(A, 1u)) {
 			if (addS) atomicAdd(&C.hist[sa], (1ull << 40) | len1);
 			if (nA) atomicAdd(&C.hist[slotA], ((unsigned long long)nA << 40) | sA);
@@ -1868,6 +1898,21 @@ int lsq_debug_plan_shares(const unsigned long long *slot_off, const unsigned cha
 	pc.two_block = costs4[0]; pc.walk_look = costs4[1]; pc.visit = costs4[2]; pc.taper = costs4[3];
 	lsq::plan_share_cuts(slot_off, packed, n1, n2, look1, look2, (size_t)n_buckets, grid, pc, cuts);
 	return LSQ_OK;
+} LSQ_API_CATCH
+
+// developer aid (include/lesseq_hip_dev.h): a block through the compact record's pack and unpack helpers (host only).
+// which = 0: the block (off, len) -- returns 1 and the record with what it unpacks to when compact_block_fits holds, else 0;
+// which = 1 / 2: the padding of the one- / two-block pool (its block 1) with the ranks (off, len) -- returns 1 likewise
+int lsq_debug_compact_record(int which, long long off, long long len, uint32_t *rec, int32_t *start, int32_t *end) LSQ_API_TRY {
+	if (!rec || !start || !end || which < 0 || which > 2) return fail(LSQ_E_ARG, "bad argument");
+	if (which == 0 && !lsq::compact_block_fits(off, len)) return 0;
+	if (which != 0 && (off < 1 || off > 15 || len < 1 || len > 15)) return fail(LSQ_E_ARG, "padding ranks are 1 to 15");
+	const unsigned r = which == 0 ? lsq::compact_pack((unsigned)off, (unsigned)len) :
+	                   (which == 1 ? lsq::compact_pad1((unsigned)off, (unsigned)len) : lsq::compact_pad2_a((unsigned)off, (unsigned)len));
+	int s, e;
+	if (which == 2) lsq::compact_unpack<true>(r, s, e); else lsq::compact_unpack(r, s, e);
+	*rec = r; *start = s; *end = e;
+	return 1;
 } LSQ_API_CATCH
 
 // developer aid (include/lesseq_hip_dev.h): per-bucket slot offsets of a method (n_buckets + 1 values)

@@ -42,13 +42,41 @@ constexpr int EM_LANES = 4;          // lanes that share one event in the EM ker
 
 namespace lsq {
 
-// Compact pool records.  A block is (offset | length << 22): 22 bits of offset, 10 bits of length.  The offset of a read's
-// first block counts from the bucket's first base minus COMPACT_BIAS (the first bin of a bucket also holds reads that start
-// before it), that of its second block from the end of the first (the bases between them).  One-block reads take one
-// such word, two-block reads two.  Reads with a longer block or a larger offset are kept with the many-block reads.
-constexpr unsigned COMPACT_OFF_BITS = 22, COMPACT_OFF_MASK = (1u << COMPACT_OFF_BITS) - 1u, COMPACT_MAX_LEN = 1u << 10;
+// Compact pool records.  A block is (end << 10 | length): 22 bits for where it ENDS, 10 bits of length, so that an unsigned
+// compare of whole records orders blocks by their end -- all that the count kernel's loops ask of most records.  The end of a
+// read's first block counts from the bucket's first base minus COMPACT_BIAS (the first bin of a bucket also holds reads that
+// start before it), that of its second block from the end of the first (the bases between them plus its length: the
+// "reach").  One-block reads take one such word, two-block reads two.  Reads with a longer block or a farther end are kept
+// with the many-block reads.  The largest end value is kept for the padding of the one-block pool (COMPACT_PAD).
+constexpr unsigned COMPACT_END_BITS = 22, COMPACT_LEN_BITS = 10, COMPACT_LEN_MASK = (1u << COMPACT_LEN_BITS) - 1u, COMPACT_MAX_LEN = 1u << COMPACT_LEN_BITS;
+constexpr unsigned COMPACT_END_MAX = (1u << COMPACT_END_BITS) - 2u;      // the farthest end of a block
 constexpr int COMPACT_BIAS = 1 << 21;
-__host__ __device__ inline bool compact_block_fits(long long off, long long len) { return off >= 0 && off <= (long long)COMPACT_OFF_MASK && len > 0 && len < (long long)COMPACT_MAX_LEN; }
+__host__ __device__ inline bool compact_block_fits(long long off, long long len) {
+	return off >= 0 && len > 0 && len < (long long)COMPACT_MAX_LEN && off + len <= (long long)COMPACT_END_MAX;
+}
+// a block that starts `off` bases in and is `len` long (compact_block_fits holds), and back: where it starts and ends
+__host__ __device__ inline unsigned compact_pack(const unsigned off, const unsigned len) { return ((off + len) << COMPACT_LEN_BITS) | len; }
+// Padding of a group.  One-block pool: COMPACT_PAD | ranks, above every block and every threshold; two-block pool: block 1 =
+// ranks << 10 (an empty block), block 2 = 0, below every block and every threshold but "nothing".  ranks: which padding record of
+// its aligned group this is, counted from 1 (bits 0-3), and which of its aligned half group (bits 4-7): the last record a
+// lane holds tells it how many of its records are padding, whether it takes a whole group per step or half of one.
+constexpr unsigned COMPACT_PAD = ((1u << COMPACT_END_BITS) - 1u) << COMPACT_LEN_BITS;
+__host__ __device__ inline bool compact_is_pad1(const unsigned rec) { return rec >= COMPACT_PAD; }
+__host__ __device__ inline unsigned compact_pad_ranks(const unsigned in_group, const unsigned in_half) { return in_group | (in_half << 4); }
+__host__ __device__ inline unsigned compact_pad1(const unsigned in_group, const unsigned in_half) { return COMPACT_PAD | compact_pad_ranks(in_group, in_half); }
+__host__ __device__ inline unsigned compact_pad2_a(const unsigned in_group, const unsigned in_half) { return compact_pad_ranks(in_group, in_half) << COMPACT_LEN_BITS; }
+// (padding unpacks to an empty block: of the one-block pool by the test here, of the two-block pool -- POOL2: no test -- by its own bits)
+template <bool POOL2 = false>
+__host__ __device__ inline void compact_unpack(const unsigned rec, int &off, int &end) {
+	end = (int)(rec >> COMPACT_LEN_BITS);
+	off = end - ((!POOL2 && compact_is_pad1(rec)) ? 0 : (int)(rec & COMPACT_LEN_MASK));
+}
+// "ends by e" for a whole record.  One-block pool: rec <= compact_ends_by(e) -- no block for e < 0, no padding ever.
+// Two-block pool: rec < compact_past(e) -- no block and no padding for e < 0, blocks and the padding (0) for e >= 0.
+__host__ __device__ inline unsigned compact_ends_by(const int e) {
+	return e < 0 ? 0u : ((((unsigned)e < COMPACT_END_MAX ? (unsigned)e : COMPACT_END_MAX) << COMPACT_LEN_BITS) | COMPACT_LEN_MASK);
+}
+__host__ __device__ inline unsigned compact_past(const int e) { return e < 0 ? 0u : compact_ends_by(e) + 1u; }
 
 // A (read, event) pair the fast kernel does not settle itself: span-start ties that need the
 // strand/name order, two-block reads whose blocks touch, second looks that did not fit the LDS

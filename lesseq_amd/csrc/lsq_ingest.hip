@@ -328,12 +328,12 @@ __global__ void __launch_bounds__(256) lsq_ingest_offsets_kernel(const unsigned 
 
 // a read into the pool: the wide record as it is, or the compact one (CountArgs)
 template <bool COMPACT> __device__ inline void pool_store(void *out, const unsigned long long at, const int2 r, const int base) {
-	if (COMPACT) reinterpret_cast<unsigned *>(out)[at] = (unsigned)(r.x - base) | ((unsigned)(r.y - r.x) << lsq::COMPACT_OFF_BITS);
+	if (COMPACT) reinterpret_cast<unsigned *>(out)[at] = lsq::compact_pack((unsigned)(r.x - base), (unsigned)(r.y - r.x));
 	else reinterpret_cast<int2 *>(out)[at] = r;
 }
 template <bool COMPACT> __device__ inline void pool_store(void *out, const unsigned long long at, const int4 r, const int base) {
-	if (COMPACT) reinterpret_cast<uint2 *>(out)[at] = make_uint2((unsigned)(r.x - base) | ((unsigned)(r.y - r.x) << lsq::COMPACT_OFF_BITS),
-	                                                              (unsigned)(r.z - r.y) | ((unsigned)(r.w - r.z) << lsq::COMPACT_OFF_BITS));
+	if (COMPACT) reinterpret_cast<uint2 *>(out)[at] = make_uint2(lsq::compact_pack((unsigned)(r.x - base), (unsigned)(r.y - r.x)),
+	                                                              lsq::compact_pack((unsigned)(r.z - r.y), (unsigned)(r.w - r.z)));
 	else reinterpret_cast<int4 *>(out)[at] = r;
 }
 
@@ -427,9 +427,10 @@ __global__ void __launch_bounds__(256) lsq_ingest_nblock_kernel(NbOut O) {
 	}
 }
 
-// The padding of the groups (up to seven one-block, three two-block records each): empty reads.  A one-block one starts on its cell's first base, so
-// that the count kernel's loop sees it as inside the cell and adding nothing; a two-block one never comes first among a
-// lane's records and is passed over there.
+// The padding of the groups (up to seven one-block, three two-block records each).  Wide pools: empty reads -- a one-block one
+// starts on its cell's first base, so that the count kernel's loop sees it as inside the cell and adding nothing; a two-block
+// one never comes first in a group and is passed over there.  Compact pools: the padding values of lsq_device.hpp
+// (COMPACT_PAD), which the loops' compares settle and which unpack to empty blocks.
 __global__ void __launch_bounds__(256) lsq_ingest_pad_kernel(const BucketDesc *buckets, const unsigned *cell_base, const unsigned *jgroup_base, unsigned n_buckets,
                                                              unsigned n_groups1, unsigned n_groups2, const unsigned *cnt1, const unsigned long long *off1,
                                                              const unsigned *cnt2, const unsigned long long *off2, const unsigned char *images,
@@ -444,11 +445,13 @@ __global__ void __launch_bounds__(256) lsq_ingest_pad_kernel(const BucketDesc *b
 		unsigned lo_b = 0, hi_b = n_buckets;                 // bucket of the group: last b with gbase[b] <= g
 		while (hi_b - lo_b > 1) { const unsigned mid = (lo_b + hi_b) >> 1; if (gbase[mid] <= g) lo_b = mid; else hi_b = mid; }
 		const BucketDesc &d = buckets[lo_b];
-		const int base = d.lo - lsq::COMPACT_BIAS;
+		// compact pools: a padding record says which one of its aligned group and of its half group it is (COMPACT_PAD)
+		const unsigned first_pad = n & (gp - 1u), half = gp / 2u;
+		auto in_half = [&](const unsigned q) { const unsigned k = first_pad + q, h0 = k & ~(half - 1u); return k - (first_pad > h0 ? first_pad : h0) + 1u; };
 		if (!one) {
 			for (unsigned q = 0; q < pad; ++q) {
 				const unsigned long long w = off2[g] + n + q;
-				if (compact) reinterpret_cast<uint2 *>(p2)[w] = make_uint2((unsigned)lsq::COMPACT_BIAS, 0u);
+				if (compact) reinterpret_cast<uint2 *>(p2)[w] = make_uint2(lsq::compact_pad2_a(q + 1u, in_half(q)), 0u);
 				else reinterpret_cast<int4 *>(p2)[w] = make_int4(d.lo, d.lo, d.lo, d.lo);
 				p2_strand[w] = 0; p2_line[w] = 0;
 			}
@@ -457,10 +460,9 @@ __global__ void __launch_bounds__(256) lsq_ingest_pad_kernel(const BucketDesc *b
 		const unsigned cell = g - cell_base[lo_b];
 		int at = d.lo;
 		if (d.kind == 1u && cell < (d.iso_off & 0xFFFFu)) at = reinterpret_cast<const lsq::Cell *>(images + d.img_off + d.seg_off)[cell].lo;
-		if (compact && !lsq::compact_block_fits((long long)at - base, 1)) at = base;       // (a cell 2 Mi bases into its bucket: the loop then parks nothing for it all the same, the record is empty)
 		for (unsigned q = 0; q < pad; ++q) {
 			const unsigned long long w = off1[g] + n + q;
-			if (compact) reinterpret_cast<unsigned *>(p1)[w] = (unsigned)(at - base);
+			if (compact) reinterpret_cast<unsigned *>(p1)[w] = lsq::compact_pad1(q + 1u, in_half(q));
 			else reinterpret_cast<int2 *>(p1)[w] = make_int2(at, at);
 			p1_strand[w] = 0; p1_line[w] = 0;
 		}

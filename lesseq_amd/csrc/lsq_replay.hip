@@ -205,12 +205,16 @@ int fetch_bucket(const lsq::MethodReads &mr, size_t b, int32_t lo, BucketReads &
 	if (mr.compact) {         // to wide records (lsq_device.hpp COMPACT_*)
 		std::vector<int32_t> a(2 * n1), b2(4 * n2);
 		const int32_t base = lo - lsq::COMPACT_BIAS;
-		auto off = [](int32_t w) { return (int32_t)((uint32_t)w & lsq::COMPACT_OFF_MASK); };
-		auto len = [](int32_t w) { return (int32_t)((uint32_t)w >> lsq::COMPACT_OFF_BITS); };
-		for (size_t i = 0; i < n1; ++i) { a[2 * i] = base + off(R.p1[i]); a[2 * i + 1] = a[2 * i] + len(R.p1[i]); }
+		for (size_t i = 0; i < n1; ++i) {
+			int off, end;
+			lsq::compact_unpack((uint32_t)R.p1[i], off, end);
+			a[2 * i] = base + off; a[2 * i + 1] = base + end;
+		}
 		for (size_t i = 0; i < n2; ++i) {
-			const int32_t s1 = base + off(R.p2[2 * i]), e1 = s1 + len(R.p2[2 * i]), s2 = e1 + off(R.p2[2 * i + 1]);
-			b2[4 * i] = s1; b2[4 * i + 1] = e1; b2[4 * i + 2] = s2; b2[4 * i + 3] = s2 + len(R.p2[2 * i + 1]);
+			int off1, end1, gap, reach;
+			lsq::compact_unpack<true>((uint32_t)R.p2[2 * i], off1, end1);
+			lsq::compact_unpack<true>((uint32_t)R.p2[2 * i + 1], gap, reach);
+			b2[4 * i] = base + off1; b2[4 * i + 1] = base + end1; b2[4 * i + 2] = base + end1 + gap; b2[4 * i + 3] = base + end1 + reach;
 		}
 		R.p1.swap(a); R.p2.swap(b2);
 	}
