@@ -582,7 +582,8 @@ int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_
  * count / solve run leaves the process (_exit) as soon as its table is written and flushed -- the pools, the helper
  * threads and the runtime are the operating system's to reclaim, which takes it a fraction of the time an orderly
  * teardown of several gigabytes of HBM takes (0.1-0.2 s of a 0.7 s run); LSQ_CLI_TEARDOWN=1 in the environment keeps
- * the orderly way.  Not for use inside a host process: call lsq_cli_run there. */
+ * the orderly way.  A null tool means "choose by argv[0]": the first tool, in the precedence of the library's table of tools, whose
+ * name is a substring of the program's base name, else count.  Not for use inside a host process: call lsq_cli_run there. */
 int lsq_cli_main(const char *tool, int argc, const char *const *argv);
 
 /* ------------------------------------------------------------------------------------

@@ -7,7 +7,7 @@
  * lesseq_hip.h has the host side (lsq_shard_bounds, lsq_events_set_shard, lsq_results_pack_device,
  * lsq_gathered_unpack); this library (liblesseq_rccl.so, the only part that links librccl) has the
  * collective.  lesseq_amd/bin/{count,solve} drive it with LSQ_GPUS=N, one host thread per GPU
- * (lesseq_amd/csrc/lsq_cli.cpp); examples and the call order are in INTEGRATION.md.
+ * (lesseq_amd/csrc/lsq_cli_shard.cpp); examples and the call order are in INTEGRATION.md.
  *
  * Conventions as in lesseq_hip.h: plain C, 0 or a negative lsq_status, message via lsq_rccl_last_error().
  */

@@ -312,7 +312,8 @@ int plan_device(lsq_events &E);
 int compile_events(const lsq_annotation *a, int n_methods, const char *const *read_types, const uint64_t *expected_read_lengths, bool device_plan, int library, lsq_events **out);
 int host_threads(int requested);
 void cli_log(int level, const char *text);                                   // lsq_cli.cpp: the executables' stderr log
-char *dup_text(const std::string &s);                                        // lsq_readtool.cpp: a malloc'd copy for lsq_free (nullptr: out of memory)
+constexpr const char *LEXICAL_CAST_ERROR = "Lexical_cast error when converting arguments to numeric values";      // the reference's line for a field that fails the cast: behind the text of every LSQ_E_PARSE an executable reports
+char *dup_text(const std::string &s);                                       // lsq_readtool.cpp: a malloc'd copy for lsq_free (nullptr: out of memory)
 int cli_device();                                                            // lsq_cli.cpp: the GPU the environment picks for an executable (default 0)
 int run_test_as(int argc, const char *const *argv, std::string &out);        // lsq_as.cpp: the test_as executable
 int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out);      // lsq_sam.cpp: the sam2mrf and bam2mrf executables

@@ -65,9 +65,9 @@ bool lsq::cli_library_option(int argc, const char *const *argv, int &i, int &lib
 	cli_log(0, (std::string("--library ") + argv[i] + ": the library type is unstranded, forward or reverse").c_str());
 	return false;
 }
-bool lsq::cli_library_env(int &library) {
+bool lsq::cli_library_env(int &library, bool empty_is_unset) {
 	const char *e = getenv("LSQ_LIBRARY");
-	if (!e || !*e) return true;
+	if (!e || (!*e && empty_is_unset)) return true;
 	library = lsq_library_from_name(e);
 	if (library >= 0) return true;
 	cli_log(0, (std::string("LSQ_LIBRARY=") + e + ": the library type is unstranded, forward or reverse").c_str());
@@ -86,15 +86,22 @@ int lsq::host_parse_reads(lsq_events *E, const char *read_format, const char *pa
 	return lsq_reads_parse(read_format, path, E, n_threads, r);
 }
 
-int lsq::cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r) {
-	unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
+int lsq::cli_read_option_env(const std::function<int(int, unsigned long)> &use) {
 	const char *names[3] = {"LSQ_SAM_SKIP_FLAGS", "LSQ_SAM_MIN_MAPQ", "LSQ_BAM_VERIFY"};
 	for (int k = 0; k < 3; ++k) if (const char *e = getenv(names[k])) {
 		char *end = nullptr;
-		opt[k] = strtoul(e, &end, 0);
+		const unsigned long v = strtoul(e, &end, 0);
 		if (end == e || *end) return fail(LSQ_E_ARG, "%s=%s is not a number", names[k], e);
+		const int st = use(k, v);
+		if (st) return st;
 	}
-	return host_parse_reads(E, read_format, path, (unsigned)opt[0], (unsigned)opt[1], opt[2] != 0, 0, r);
+	return LSQ_OK;
+}
+
+int lsq::cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r) {
+	unsigned long opt[3] = {LSQ_SAM_DEFAULT_SKIP_FLAGS, LSQ_SAM_DEFAULT_MIN_MAPQ, 0};
+	const int st = cli_read_option_env([&](int k, unsigned long v) { opt[k] = v; return LSQ_OK; });
+	return st ? st : host_parse_reads(E, read_format, path, (unsigned)opt[0], (unsigned)opt[1], opt[2] != 0, 0, r);
 }
 
 void lsq::exon_union(const IsoRec &r, std::vector<std::pair<int64_t, int64_t>> &sorted_exons) {
@@ -165,7 +172,7 @@ bool lsq::cli_u32_option(int argc, const char *const *argv, int &i, unsigned lon
 
 int lsq::cli_failed(int st) {
 	cli_log(0, lsq_last_error());
-	if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values");
+	if (st == LSQ_E_PARSE) cli_log(0, LEXICAL_CAST_ERROR);
 	return st == LSQ_E_DEVICE || st == LSQ_E_INTERNAL ? 2 : 1;
 }
 

@@ -1,11 +1,13 @@
 // What the tools that take an annotation and a read file share on the host (junctions, coverage, exonbins, psi, evidence, sites, retention):
 // the view of parsed reads their passes take, the dictionaries a read file is parsed against without events, a line's exon
 // union and its introns, the split of the reads over host threads, the entry points that differ by the index's or the table's type alone, and
-// the frame of the six executables.  lsq_readtool.cpp defines what is no template.
+// the frame of their executables, whose owned handles (CliOwned), library type and read options of the environment count, solve,
+// classify and bamcheck take too (lsq_cli.cpp, lsq_cli_job.cpp).  lsq_readtool.cpp defines what is no template.
 #pragma once
 
 #include <algorithm>
 #include <cstring>
+#include <functional>
 #include <utility>
 
 #include "lsq_internal.hpp"
@@ -47,14 +49,19 @@ const char *library_name(int library);         // "unstranded", "forward", "reve
 // --library of an executable: the value behind argv[i] (i moves on to it); where the option is not given, LSQ_LIBRARY of the
 // environment (unset or empty: `library` stays).  false, with the message logged, for anything but unstranded, forward or reverse
 bool cli_library_option(int argc, const char *const *argv, int &i, int &library);
-bool cli_library_env(int &library);
+// (count and solve, which have no --library, take an LSQ_LIBRARY that is set and empty for a wrong name: empty_is_unset false)
+bool cli_library_env(int &library, bool empty_is_unset = true);
 // the library report of a stranded table as the executables log it
 void cli_log_library(const char *tool, int library, const uint64_t *lib);
 // A read file through the host parser of its format, against dictionaries E; verify: a BAM file's CRC32s and end-of-file marker checked
 int host_parse_reads(lsq_events *E, const char *read_format, const char *path, unsigned skip_flags, unsigned min_mapq, bool verify, int n_threads, lsq_reads **r);
-// ... under LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (the executables' --host)
+// The one parse of LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ and LSQ_BAM_VERIFY of the environment (k = 0, 1, 2; as strtoul reads them in
+// base 0): use(k, value) for every one that is set, in this order; a value that is no number (LSQ_E_ARG) or a status of use ends it.
+// A variable that is not set is the caller's default.
+int cli_read_option_env(const std::function<int(int, unsigned long)> &use);
+// ... over the host parsers' defaults (LSQ_SAM_DEFAULT_*, no verification): the executables' --host
 int cli_host_parse(lsq_events *E, const char *read_format, const char *path, lsq_reads **r);
-int cli_env_options(lsq_ctx *c);               // lsq_cli.cpp: LSQ_SAM_SKIP_FLAGS, LSQ_SAM_MIN_MAPQ, LSQ_BAM_VERIFY, LSQ_OPTIONS
+int cli_env_options(lsq_ctx *c);               // lsq_cli.cpp: ... as options of a context, which keeps its own defaults; then LSQ_OPTIONS
 // rows ascending in chromosome index -> where each row of the tables' order (chromosome names bytewise) comes from
 std::vector<size_t> rows_by_chrom_name(const std::vector<std::string> &names, const std::vector<uint32_t> &chrom);
 // The exons of a line that are not empty (no more than exonCount of them) merged into `sorted_exons` (empty, or other lines'

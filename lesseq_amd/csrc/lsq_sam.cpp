@@ -79,7 +79,7 @@ int run_sam2mrf(bool bam, int argc, const char *const *argv, std::string &out) {
 	std::string bytes;
 	if (read_all(path, bytes)) { cli_log(0, lsq_last_error()); return 1; }
 	const int st = bam ? bam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out, verify, library) : sam_to_mrf(bytes.data(), bytes.size(), skip_flags, min_mapq, out, library);
-	if (st) { out.clear(); cli_log(0, lsq_last_error()); if (st == LSQ_E_PARSE) cli_log(0, "Lexical_cast error when converting arguments to numeric values"); return 1; }
+	if (st) { out.clear(); cli_log(0, lsq_last_error()); if (st == LSQ_E_PARSE) cli_log(0, LEXICAL_CAST_ERROR); return 1; }
 	return 0;
 }
 

@@ -1,4 +1,4 @@
-// The host threads of one job over several GPUs (lsq_cli.cpp): a thread per slice, every slice's status and error text, and
+// The host threads of one job over several GPUs (lsq_cli_shard.cpp): a thread per slice, every slice's status and error text, and
 // the points where the slices meet before a collective.  std, and lsq_internal.hpp for ThreadGroup and the status codes; no
 // lsq_* or HIP call: tests/host/slice_team_check.cpp drives it without a device.
 #pragma once

@@ -445,6 +445,22 @@ def test_slice_team_alone_under_sanitizers(tmp_path):
         assert p.returncode == 0 and p.stdout == "slice team ok\n" and p.stderr == "", (sanitizers, p.returncode, p.stdout, p.stderr[-2000:])
 
 
+def test_job_args_alone_under_sanitizers(tmp_path):
+    """lesseq_amd/csrc/lsq_jobargs.hpp -- the argv of count and solve, read without environment, log or device -- called by
+    tests/host/job_args_check.cpp on the accepted shapes (one and two read files, --fim, --bootstrap with and without --seed, a path
+    spelled like an option), with every field checked, and on every shape that ends in the usage text, the abort, the Lexical_cast
+    line or "too many read files", in the reference's order.  Under AddressSanitizer + UBSan, runtimes linked statically, a
+    program of its own: every argv is an allocation of exactly argc words."""
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "job_args_check")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Wextra", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan", "-static-libubsan",
+                    "-I", os.path.join(root, "lesseq_amd", "csrc"), "-o", exe, os.path.join(root, "tests", "host", "job_args_check.cpp")],
+                   check=True, capture_output=True, text=True, timeout=120)
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and p.stdout == "job args ok\n" and p.stderr == "", (p.returncode, p.stdout, p.stderr[-2000:])
+
+
 def test_share_plan_of_a_count_launch():
     """run_count's share plan on made-up buckets (host only, lsq_debug_plan_shares): the bounds rise from 0 to the last slot,
     no share is longer than 2^21 slots, weighted shares are equal in cost where no cut snaps (a two-block record, a walk
