@@ -487,6 +487,37 @@ class Context:
         check(lib.lsq_reads_pool_format(self.h, method, C.byref(a), C.byref(n), k))
         return bool(a.value), n.value, tuple(int(x) for x in k)
 
+    POOL_NAMES = (None, "one", "two", "many")
+
+    def pool_reads(self, method=0):
+        """every read in the pools of the latest read set of `method`, the groups' padding left out, whichever format the
+        pools have (a developer entry: lsq_debug_pool_reads): a list of (line_no, bucket, strand id, pool, blocks) -- pool
+        "one", "two" or "many", blocks the merged (start, end) pairs as wide coordinates"""
+        nr, nb = u64(), u64()
+        check(lib.lsq_debug_pool_reads(self.h, method, C.byref(nr), C.byref(nb), None, None, None, None, None, None, None, 0, 0))
+        n, m = nr.value, nb.value
+        line, bucket = np.zeros(max(n, 1), np.uint32), np.zeros(max(n, 1), np.uint32)
+        strand, pool = np.zeros(max(n, 1), np.uint8), np.zeros(max(n, 1), np.uint8)
+        off = np.zeros(max(n, 1), np.uint64)
+        s, e = np.zeros(max(m, 1), np.int64), np.zeros(max(m, 1), np.int64)
+        check(lib.lsq_debug_pool_reads(self.h, method, C.byref(nr), C.byref(nb), _ptr(line, u32), _ptr(bucket, u32), _ptr(strand, u8), _ptr(pool, u8),
+                                       _ptr(off, u64), _ptr(s, i64), _ptr(e, i64), max(n, 1), max(m, 1)))
+        if (nr.value, nb.value) != (n, m):
+            raise RuntimeError("the pools changed between two calls")
+        ends = [int(x) for x in off[1:n]] + [m]
+        return [(int(line[r]), int(bucket[r]), int(strand[r]), self.POOL_NAMES[pool[r]],
+                 tuple((int(s[q]), int(e[q])) for q in range(int(off[r]), ends[r]))) for r in range(n)]
+
+    def locator(self):
+        """the locator grid of the uploaded events (a developer entry: lsq_debug_locator): {"shift": the bins are 2^shift
+        bases wide, "tables": per chromosome table (loc_base -- the first base of bin 0, loc_nb -- its bins; 0: no record)}.
+        Table of a chromosome: Events.chrom_id(name), or 2 * that + (1 for the minus strand) for stranded events."""
+        shift, n = C.c_uint(), u64()
+        check(lib.lsq_debug_locator(self.h, C.byref(shift), C.byref(n), None, None, 0))
+        base, nb = (i64 * max(n.value, 1))(), (u64 * max(n.value, 1))()
+        check(lib.lsq_debug_locator(self.h, C.byref(shift), C.byref(n), base, nb, n.value))
+        return {"shift": int(shift.value), "tables": [(int(base[q]), int(nb[q])) for q in range(n.value)]}
+
     def retained_blocks(self, method):
         return lib.lsq_reads_retained_blocks(self.h, method)
 

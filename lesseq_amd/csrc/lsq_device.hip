@@ -430,6 +430,21 @@ int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
+// Developer view of the locator grid as uploaded (tests): its shift, the number of chromosome tables, and of the first `cap` of them
+// the first base of bin 0 and the number of bins (0: a table without a record)
+int lsq_debug_locator(lsq_ctx *c, unsigned *shift, unsigned long long *n_tables, int64_t *loc_base, unsigned long long *loc_nb, unsigned long long cap) LSQ_API_TRY {
+	if (!c || !shift || !n_tables || (cap && (!loc_base || !loc_nb))) return fail(LSQ_E_ARG, "bad argument");
+	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
+	HIP_TRY(hipSetDevice(c->device));
+	*shift = c->loc_shift;
+	*n_tables = c->n_chrom_tables;
+	const size_t n = (size_t)std::min<unsigned long long>(cap, c->n_chrom_tables);
+	std::vector<RouteChrom> chrom(n);
+	if (n) HIP_TRY(hipMemcpy(chrom.data(), c->route_chrom.p, n * sizeof(RouteChrom), hipMemcpyDeviceToHost));
+	for (size_t q = 0; q < n; ++q) { loc_base[q] = chrom[q].loc_base; loc_nb[q] = chrom[q].loc_nb; }
+	return LSQ_OK;
+} LSQ_API_CATCH
+
 int lsq_count(lsq_ctx *c) LSQ_API_TRY {
 	if (!c) return fail(LSQ_E_ARG, "null context");
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");

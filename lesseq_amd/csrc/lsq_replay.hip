@@ -558,4 +558,44 @@ int lsq_debug_check_pool_layout(lsq_ctx *c, int method, unsigned long long *out)
 	return LSQ_OK;
 } LSQ_API_CATCH
 
+// Developer view of the pools (tests): every read the pools of the latest read set of `method` hold, bucket by bucket, the groups'
+// padding left out -- per read its line number, bucket, strand id, pool (1 one-block, 2 two-block, 3 the many-block reads'), and
+// from blk_off[r] on (to the next read's, or to n_blocks) its merged blocks as wide coordinates, whichever format the pools have.  n_reads / n_blocks: what
+// there is; the arrays are filled when cap_reads / cap_blocks hold all of it (call once with both 0 to size them).
+int lsq_debug_pool_reads(lsq_ctx *c, int method, unsigned long long *n_reads, unsigned long long *n_blocks, uint32_t *line, uint32_t *bucket, uint8_t *strand,
+                         uint8_t *pool, unsigned long long *blk_off, int64_t *blk_start, int64_t *blk_end, unsigned long long cap_reads, unsigned long long cap_blocks) LSQ_API_TRY {
+	if (!c || !c->E || !n_reads || !n_blocks || method < 0 || method >= c->E->n_methods) return fail(LSQ_E_ARG, "bad argument");
+	if ((cap_reads || cap_blocks) && (!line || !bucket || !strand || !pool || !blk_off || !blk_start || !blk_end)) return fail(LSQ_E_ARG, "bad argument");
+	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = lsq::sync_all(c); if (rc) return rc; }
+	const lsq_events &E = *c->E;
+	const lsq::MethodReads &mr = c->reads[method];
+	if (!mr.present) return fail(LSQ_E_STATE, "no reads uploaded for method %d", method);
+	unsigned long long nr = 0, nb = 0;
+	bool room = true;
+	auto put = [&](size_t b, unsigned ln, uint8_t sid, uint8_t pl, const int32_t *se, size_t nblk) {
+		room = room && nr < cap_reads && nb + nblk <= cap_blocks;
+		if (room) {
+			line[nr] = ln; bucket[nr] = (uint32_t)b; strand[nr] = sid; pool[nr] = pl; blk_off[nr] = nb;
+			for (size_t q = 0; q < nblk; ++q) { blk_start[nb + q] = se[2 * q]; blk_end[nb + q] = se[2 * q + 1]; }
+		}
+		++nr; nb += nblk;
+	};
+	for (size_t b = 0; b < E.buckets.size(); ++b) {
+		BucketReads R;
+		{ int rc = fetch_bucket(mr, b, E.buckets[b].lo, R); if (rc) return rc; }
+		for (size_t i = 0; i < R.p1_line.size(); ++i)
+			if (R.p1[2 * i] != R.p1[2 * i + 1]) put(b, R.p1_line[i], R.p1_strand[i], 1, &R.p1[2 * i], 1);          // (an empty block: padding)
+		for (size_t i = 0; i < R.p2_line.size(); ++i)
+			if (R.p2[4 * i] != R.p2[4 * i + 1]) put(b, R.p2_line[i], R.p2_strand[i], 2, &R.p2[4 * i], 2);
+		for (size_t i = 0; i < R.pn_line.size(); ++i) {
+			if (R.pn_blk_off[i] < R.pnb0 || (unsigned long long)R.pn_blk_off[i] + R.pn_nblk[i] > R.pnb1)
+				return fail(LSQ_E_STATE, "bucket %zu: block offsets of a multi-block read lie outside its bucket", b);
+			put(b, R.pn_line[i], R.pn_strand[i], 3, R.pn_se.data() + 2 * (size_t)(R.pn_blk_off[i] - R.pnb0), R.pn_nblk[i]);
+		}
+	}
+	*n_reads = nr; *n_blocks = nb;
+	return LSQ_OK;
+} LSQ_API_CATCH
+
 } // extern "C"
