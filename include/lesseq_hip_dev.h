@@ -143,6 +143,33 @@ int64_t lsq_debug_bucket_cells(const lsq_events *e, int64_t bucket, int32_t *lo,
  * Returns their number and writes at most `capacity`; -1 for a bad argument. */
 int64_t lsq_debug_bucket_events(const lsq_events *e, int64_t bucket, int *kind, int64_t *events, int64_t capacity);
 
+/* The locator grid as uploaded, read back from the device: its shift, the number of chromosome tables, and of the first `cap` of
+ * them the first base of bin 0 and the number of bins (0: a table without a record). */
+int lsq_debug_locator(lsq_ctx *c, unsigned *shift, unsigned long long *n_tables, int64_t *loc_base, unsigned long long *loc_nb, unsigned long long cap);
+/* The tables lsq_events_upload makes of compiled events (csrc/lsq_upload_tables.hpp), as the host works them out: no context, no
+ * device.  Writes at most `cap` values of table `which` to `out` (may be NULL with cap 0) and their number to *n.  Values are 32-bit
+ * words unless said otherwise; records are laid out field by field.  tests/test_upload_tables_host.py holds each table against its
+ * definition. */
+enum {
+	LSQ_UT_EM_ORDER = 0,        /* device event per EM place, 0xFFFFFFFF padding */
+	LSQ_UT_EM_PLACES = 1,       /* places of the lean group, all places */
+	LSQ_UT_PACK_CLS = 2, LSQ_UT_PACK_ISO = 3, LSQ_UT_PACK_EV = 4,      /* lsq_results_pack_device's lists, output order */
+	LSQ_UT_START_WEIGHTS = 5,   /* G = 1 / ARS, doubles, [read file][device isoform] */
+	LSQ_UT_ROUTE_CHROM = 6,     /* per table id: loc_first, loc_nb, loc_base (signed), cov0, cov1, clu0, clu1, 0 */
+	LSQ_UT_ROUTE_COV = 7,       /* covered regions: start, end (signed) */
+	LSQ_UT_ROUTE_CLU = 8,       /* cluster records: start, end, bucket, the bucket's first base (signed) */
+	LSQ_UT_ROUTE_LOC = 9,       /* locator entries: lower bound among the covered starts, among the cluster starts */
+	LSQ_UT_ROUTE_SHIFT = 10,    /* the locator's shift, the number of table ids */
+	LSQ_UT_BIN_BASE = 11, LSQ_UT_CELL_BASE = 12, LSQ_UT_JGROUP_BASE = 13,      /* per bucket, n_buckets + 1 values each */
+	LSQ_UT_GROUP_TOTALS = 14,   /* bins, one-block groups, two-block groups */
+	LSQ_UT_GENE_NAMES = 15,     /* bytes: the gene names in device event order, back to back */
+	LSQ_UT_GENE_NAME_OFF = 16,  /* their offsets, n_events + 1 */
+	/* two inputs of the group bases, straight from the compiled events: what the test sums up itself */
+	LSQ_UT_BUCKET_BINS = 17,    /* per bucket: its bins (BucketDesc::n_bins) */
+	LSQ_UT_JG_BASE = 18         /* per bucket: the first of its junction-group keys (lsq_events::jg_base), n_buckets + 1 */
+};
+int lsq_debug_upload_tables(const lsq_events *e, int which, void *out, unsigned long long cap, unsigned long long *n);
+
 /* The read bootstrap's draws one by one (host only, no device; csrc/lsq_philox.hpp): the classes (1-based) that the draws
  * first_draw .. first_draw + n_draws - 1 of replicate b take for read file m (< 256) and event e (the generator's event
  * number) whose n_cls classes hold class_count reads -- so that a test can look at the first draws of an event of 2^40

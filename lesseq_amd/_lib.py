@@ -138,6 +138,7 @@ _sig("lsq_debug_scan", C.c_int, vp, C.c_int, vp, u64, P(u64))
 _sig("lsq_debug_sort", C.c_int, vp, P(u64), P(u64), u64, P(C.c_uint), C.c_uint, C.c_int, P(C.c_uint))
 _sig("lsq_debug_pool_reads", C.c_int, vp, C.c_int, P(u64), P(u64), P(u32), P(u32), P(u8), P(u8), P(u64), P(i64), P(i64), u64, u64)
 _sig("lsq_debug_locator", C.c_int, vp, P(C.c_uint), P(u64), P(i64), P(u64), u64)
+_sig("lsq_debug_upload_tables", C.c_int, vp, C.c_int, vp, u64, P(u64))
 _sig("lsq_bam_check", C.c_int, vp, cs, P(BamReportStruct))
 _sig("lsq_reads_retained", u64, vp, C.c_int)
 _sig("lsq_last_library_report", C.c_int, vp, C.c_int, P(u64))

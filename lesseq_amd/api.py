@@ -80,6 +80,29 @@ class Events:
         lib.lsq_debug_bucket_events(self.h, bucket, None, out, n)
         return kind.value, [int(out[q]) for q in range(n)]
 
+    # lsq_debug_upload_tables: name -> (table number, element type, columns of a record)
+    UPLOAD_TABLES = {"em_order": (0, np.uint32, 1), "em_places": (1, np.uint32, 1), "pack_cls": (2, np.uint32, 1), "pack_iso": (3, np.uint32, 1),
+                     "pack_ev": (4, np.uint32, 1), "G": (5, np.float64, 1), "route_chrom": (6, np.int32, 8), "cov": (7, np.int32, 2), "clu": (8, np.int32, 4),
+                     "loc": (9, np.uint32, 2), "route_shift": (10, np.uint32, 1), "bin_base": (11, np.uint32, 1), "cell_base": (12, np.uint32, 1),
+                     "jgroup_base": (13, np.uint32, 1), "group_totals": (14, np.uint32, 1), "gene_names": (15, np.uint8, 1), "gene_name_off": (16, np.uint32, 1),
+                     "bucket_bins": (17, np.uint32, 1), "jg_base": (18, np.uint32, 1)}
+
+    def upload_tables(self, *names):
+        """the tables lsq_events_upload makes of these events, as the host works them out (a developer entry:
+        lsq_debug_upload_tables; csrc/lsq_upload_tables.hpp says what each holds): {name: numpy array}, records as rows
+        (route_chrom: loc_first, loc_nb, loc_base, cov0, cov1, clu0, clu1, 0; bucket_bins and jg_base are no tables of the upload
+        but the events' own figures that bin_base and jgroup_base are summed from).  No names: every table.  No GPU."""
+        out = {}
+        for name in names or self.UPLOAD_TABLES:
+            which, dtype, cols = self.UPLOAD_TABLES[name]
+            n = u64()
+            check(lib.lsq_debug_upload_tables(self.h, which, None, 0, C.byref(n)))
+            a = np.zeros(max(n.value, 1), dtype)
+            check(lib.lsq_debug_upload_tables(self.h, which, a.ctypes.data_as(vp), n.value, C.byref(n)))
+            a = a[:n.value]
+            out[name] = a.reshape(-1, cols) if cols > 1 else a
+        return out
+
     def bucket_cells(self, bucket):
         """the shortcut table of a packed bucket as compiled: a list of (lo, hi, e1, e2, info, flags) per cell, in start
         order (a developer entry: lsq_debug_bucket_cells; csrc/lsq_internal.hpp says what the fields hold).  No GPU."""

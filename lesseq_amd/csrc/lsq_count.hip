@@ -1516,7 +1516,6 @@ namespace lsq {
 // and junction group: where a hot bucket is cut into many shares it matters WHICH of its groups are the walk's); anything else
 // (kind 2: many-block reads, buckets the kernel does not visit) next to nothing; staging + flush of a visited bucket `visit`.
 // x == null: every slot weighs 1.
-struct SharePlanCosts { bool weighted = true, snap = true; double two_block = 4.3, walk_look = 9.0, visit = 7000.0, taper = 0.5, hot = 0.0; };
 void plan_share_cuts_seg(const unsigned long long *so, const unsigned char *visited_kind, const size_t B, const unsigned long long *x, const unsigned char *kind,
                          const unsigned *looks, const unsigned *bseg, const size_t S, const unsigned long long grid, const SharePlanCosts &pc, unsigned long long *cut) {
 	const unsigned long long total_slots = B ? so[B] : 0;
@@ -1608,33 +1607,40 @@ void plan_share_cuts(const unsigned long long *so, const unsigned char *visited_
 	plan_share_cuts_seg(so, visited_kind, B, x.data(), kind.data(), looks.data(), bseg.data(), kind.size(), grid, pc, cut);
 }
 
-int run_count(lsq_ctx *c) {
-	const lsq_events &E = *c->E;
-	const size_t n_cls = E.n_cls_total;
-	const int M = E.n_methods;
-	hipStream_t st_em = nullptr;
-	// Count k takes the lanes in turn (two) and the counter sets in turn (`opt_counter_sets`: three, or two).  The set of the count
-	// before is zeroed now, on that count's lane -- its result stream carries that step's exception pass, EM and hand-off, and by now
-	// every call that can ever read that set has been queued there, whether a solve came or not -- and its mark recorded behind the
-	// zeroing.  This count waits for the mark of its own set: with three sets that one was zeroed when count k-2 was submitted, behind
-	// the readers of step k-3, so nothing of step k-1's or k-2's result chain stands in front of this count; with two it
-	// was zeroed when count k-1 was submitted, behind the readers of step k-2.
+// ---- run_count's steps, in the order it takes them ----
+
+struct CountTurn { int lane, set; hipStream_t st, st_em; };      // the lane, counter set and streams of this count
+struct LaunchShape {
+	unsigned tables_bytes, lds_bytes, per_cu;      // LDS of the bucket tables, of a workgroup, resident workgroups a compute unit
+	int p1w;                                       // one-block records a lane takes per look, in words of two
+	const void *fn_wide, *fn_compact;              // the streaming kernel for wide and for compact pools
+};
+struct Cleanup { CountArgs A; int m; };            // a read file whose streaming kernel ran: what its exception pass works on
+
+// Count k takes the lanes in turn (two) and the counter sets in turn (`counter_sets`: three, or two).  The set of the count
+// before is zeroed now, on that count's lane -- its result stream carries that step's exception pass, EM and hand-off, and by now
+// every call that can ever read that set has been queued there, whether a solve came or not -- and its mark recorded behind the
+// zeroing.  This count waits for the mark of its own set: with three sets that one was zeroed when count k-2 was submitted, behind
+// the readers of step k-3, so nothing of step k-1's or k-2's result chain stands in front of this count; with two it
+// was zeroed when count k-1 was submitted, behind the readers of step k-2.
+static int rotate_counter_sets(lsq_ctx *c, CountTurn &T) {
 	const int prev_lane = c->lane, prev_set = c->set;
-	const int lane = prev_lane ^ 1, set = (prev_set + 1) % c->opt_counter_sets;
-	hipStream_t st = c->opt_two_count_streams ? c->stream_count2[lane] : c->stream;      // (lsq_device.hpp: a count stream per lane)
-	if (c->mark_recorded2[set]) HIP_TRY(hipStreamWaitEvent(st, c->ev_mark2[set], 0));
+	T.lane = prev_lane ^ 1; T.set = (prev_set + 1) % c->count_opt.counter_sets;
+	T.st = c->count_opt.two_count_streams ? c->stream_count2[T.lane] : c->stream;      // (lsq_device.hpp: a count stream per lane)
+	if (c->mark_recorded2[T.set]) HIP_TRY(hipStreamWaitEvent(T.st, c->ev_mark2[T.set], 0));
 	HIP_TRY(hipMemsetAsync(c->counters.p + (size_t)prev_set * c->counters_per_set, 0, c->counters_per_set * sizeof(unsigned long long), c->stream_em2[prev_lane]));
 	HIP_TRY(hipEventRecord(c->ev_mark2[prev_set], c->stream_em2[prev_lane]));
 	c->mark_recorded2[prev_set] = true;
-	select_counter_set(c, lane, set);
-	st_em = c->stream_em;
-	c->fast_launched = 0;
-	struct Cleanup { CountArgs A; unsigned long long n_pn; int m; };
-	std::vector<Cleanup> cleanups;
-	bool counted_signalled = false;
-	if (c->time_events) HIP_TRY(hipEventRecord(c->ev0, st));      // ev0..ev1 brackets the count kernel launches only
-	const unsigned generic_tables_bytes = (std::max<unsigned>(E.max_lds_bytes, 16) + 15u) & ~15u;
-	const unsigned tables_bytes = generic_tables_bytes;
+	select_counter_set(c, T.lane, T.set);
+	T.st_em = c->stream_em;
+	return LSQ_OK;
+}
+
+// The shape every launch of this count has: LDS bytes, kernel, resident workgroups a compute unit.
+static int launch_shape(lsq_ctx *c, LaunchShape &S) {
+	const lsq_events &E = *c->E;
+	const int M = E.n_methods;
+	S.tables_bytes = (std::max<unsigned>(E.max_lds_bytes, 16) + 15u) & ~15u;
 	// Five workgroups a compute unit, not the six that registers and tables would allow: 5 x 80 registers a SIMD leave
 	// room for a wave of the EM kernel (104) beside them, so the EM of the step before runs without displacing count waves
 	// (measured with LDS padding at the same tables: 6 -> 0.1429, 5 -> 0.1366, 4 -> 0.1433 ms per step on C3).  The LDS
@@ -1645,9 +1651,9 @@ int run_count(lsq_ctx *c) {
 	// fit, n = n.
 	double max_skew = 0.0;
 	for (int m = 0; m < M; ++m) max_skew = std::max(max_skew, c->reads[m].skew);
-	const unsigned cap = c->opt_wg_per_cu >= 0 ? (unsigned)c->opt_wg_per_cu : (c->em.small_places >= c->em.opt_flat_min && max_skew < 4.0 ? 5u : 0u);
-	const unsigned lds_bytes = std::max(tables_bytes + WAVES * WAVE_QUEUE_WORDS * 16, cap ? 160u * 1024u / (cap + 1u) + 16u : 0u);
-	if (lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables + read tile exceed the CU's LDS");
+	const unsigned cap = c->count_opt.wg_per_cu >= 0 ? (unsigned)c->count_opt.wg_per_cu : (c->em.small_places >= c->em.opt_flat_min && max_skew < 4.0 ? 5u : 0u);
+	S.lds_bytes = std::max(S.tables_bytes + WAVES * WAVE_QUEUE_WORDS * 16, cap ? 160u * 1024u / (cap + 1u) + 16u : 0u);
+	if (S.lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables + read tile exceed the CU's LDS");
 	// (That is how the rule was found, with the 80-register kernel.  The launches it holds to five now run the 96-register
 	// kernel below, which fills the SIMD's registers at five waves by itself and still gains: fewer instructions per read.)
 	// Eight reads per look (lsq_count_fast_kernel<true, 4>) where the launch is held to five workgroups a compute unit anyway
@@ -1655,185 +1661,231 @@ int run_count(lsq_ctx *c) {
 	// workgroups: 0.189 -> 0.191).  Option "reads_per_look": 0 = this rule, 4, 8.
 	bool all_compact = true;
 	for (int m = 0; m < M; ++m) if (c->reads[m].total_slots && !c->reads[m].compact) all_compact = false;
-	const int p1w = !all_compact ? 2 : (c->opt_reads_per_look ? (c->opt_reads_per_look == 8 ? 4 : 2) : (cap != 0 && cap <= 5 ? 4 : 2));
-	const void *const fn_wide = (const void *)lsq_count_fast_kernel<false, 2>;
-	const void *const fn_compact = p1w == 4 ? (const void *)lsq_count_fast_kernel<true, 4> : (const void *)lsq_count_fast_kernel<true, 2>;
-	c->last_reads_per_look = 2u * (unsigned)p1w;
-	if (lds_bytes > 64 * 1024) {
-		HIP_TRY(hipFuncSetAttribute(fn_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-		HIP_TRY(hipFuncSetAttribute(fn_compact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-		HIP_TRY(hipFuncSetAttribute((const void *)lsq_count_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+	const int rpl = c->count_opt.reads_per_look;
+	S.p1w = !all_compact ? 2 : (rpl ? (rpl == 8 ? 4 : 2) : (cap != 0 && cap <= 5 ? 4 : 2));
+	S.fn_wide = (const void *)lsq_count_fast_kernel<false, 2>;
+	S.fn_compact = S.p1w == 4 ? (const void *)lsq_count_fast_kernel<true, 4> : (const void *)lsq_count_fast_kernel<true, 2>;
+	CountLaunch &L = c->launch;
+	L.last_reads_per_look = 2u * (unsigned)S.p1w;
+	if (S.lds_bytes > 64 * 1024) {
+		HIP_TRY(hipFuncSetAttribute(S.fn_wide, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes));
+		HIP_TRY(hipFuncSetAttribute(S.fn_compact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes));
+		HIP_TRY(hipFuncSetAttribute((const void *)lsq_count_generic_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S.lds_bytes));
 	}
 	// resident workgroups per CU as the runtime sees them (registers, LDS, wave slots): the grid is a whole number of rounds
-	unsigned per_cu = std::max(1u, std::min(2048u / COUNT_BLOCK, (160u * 1024u) / lds_bytes));
+	S.per_cu = std::max(1u, std::min(2048u / COUNT_BLOCK, (160u * 1024u) / S.lds_bytes));
+	if (L.occ_lds_bytes != S.lds_bytes || L.occ_p1w != S.p1w) {             // asked once per table size and kernel
+		int nb = 0;
+		int nb2 = 0;
+		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, S.fn_wide, (int)COUNT_BLOCK, (size_t)S.lds_bytes));
+		HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, S.fn_compact, (int)COUNT_BLOCK, (size_t)S.lds_bytes));
+		L.occ_lds_bytes = S.lds_bytes; L.occ_p1w = S.p1w; L.occ_blocks = all_compact ? nb2 : std::min(nb, nb2);
+	}
+	if (L.occ_blocks >= 1) S.per_cu = std::min(S.per_cu, (unsigned)L.occ_blocks);
+	L.last_wg_per_cu = S.per_cu;
+	return LSQ_OK;
+}
+
+// Workgroups of one read file's launch.
+static unsigned long long count_grid(const lsq_ctx *c, const MethodReads &mr, const LaunchShape &S) {
+	// workgroups per resident slot: 2 for even read depth (fewest table stagings), more when a few buckets hold most of the
+	// reads and shares differ in cost.  Measured with a count stream per lane, where the next count fills the tail of this
+	// one (before that the tail made more and smaller shares pay: 3 and 8): C3 1 -> 0.150, 2 -> 0.143, 3 -> 0.148, 4 ->
+	// 0.151 ms per step; the skewed c5s 3 -> 0.179, 4 -> 0.176, 6 -> 0.178, 8 -> 0.183; C2 1 -> 0.046, 2 -> 0.044, 3 -> 0.044.
+	// The five-wave kernel's steps are twice as long, and its shares pay for being smaller: C3 1.6 -> 0.137, 2 -> 0.133,
+	// 2.4 -> 0.1335, 3 -> 0.129, 3.5 -> 0.132, 4 -> 0.133, 5 -> 0.137, 6 -> 0.1355.
+	// With three counter sets two counts are co-resident throughout; same box, one process: C3 2 -> 0.0985, 3 -> 0.0992, 4 -> 0.1040
+	// (share_taper 0.25 / 0.5 / 1: 0.0991 / 0.0986 / 0.1004; six workgroups a compute unit 0.1131 against 0.0995 with five): the rules stay.
+	// lsq_ctx_set_option "grid_multiplier" overrides
+	const double mult = c->count_opt.grid_mult > 0 ? c->count_opt.grid_mult : (mr.skew >= 32.0 ? 4.0 : (mr.skew >= 4.0 || S.p1w == 4 ? 3.0 : 2.0));
+	unsigned long long grid = (unsigned long long)((double)c->n_cu * S.per_cu * mult);
+	// one workgroup's share must keep the packed LDS counters (24-bit count, 40-bit bases) exact
+	grid = std::max(grid, mr.total_slots / (1ull << 21) + 1);
+	grid = std::min<unsigned long long>(grid, std::max<unsigned long long>(mr.total_slots / 64, 1));
+#ifdef LSQ_DEV
+	if (const char *e = getenv("LSQ_GRID_WGS")) { const long v = atol(e); if (v >= 1) grid = (unsigned long long)v; }      // timing experiments
+#endif
+	return grid;
+}
+
+// The workgroups' shares of one read file's launch of `grid` workgroups, made and uploaded when the grid has changed.
+static int plan_shares(lsq_ctx *c, MethodReads &mr, const unsigned long long grid, hipStream_t st) {
+	// The workgroups' shares: equal in COST, with a cut moved onto a bucket boundary when one lies within 30 % of a share
+	// of it -- a workgroup that owns whole buckets stages, drains and flushes each once, where a cut through the middle
+	// makes two workgroups do it (the planner's buckets of an evenly deep read set are about a share long).
+	// Cost (round 3; the workgroup trace of the developer build, tools/kbench.py, fitted over C3's 3 840 shares: with shares
+	// equal in reads a workgroup took 11 to 72 us, median 31, and the wave slots of the launch were 68 % used -- the last
+	// third of the launch was a thinning tail of late, long shares): a two-block record costs what 4.3 one-block records
+	// do, a look of the general walk at a read that the streaming loops leave to it what 9 do (the ingest counts those looks
+	// per bucket as it pools the reads: plan_park*), a bucket's staging and flush what 7 000 do.  And the shares get smaller towards the end
+	// of the grid ("share_taper": the last is that fraction of the first), so that what is still running when the slots
+	// start to empty is short.
+	const lsq_events &E = *c->E;
+	const std::vector<unsigned long long> &so = mr.slot_off_host;
+	const size_t B = E.buckets.size();
+	std::vector<unsigned long long> cut((size_t)grid + 1, 0);
+	std::vector<unsigned> first((size_t)grid, 0);
+	// (the pipelined step on one box, taper 1 / 0.5 / 0.25: C3 0.1189 / 0.1165 / 0.1193 ms -- the next count's first workgroups fill this
+	// launch's tail there, and smaller last shares cost more stagings than they still save; the skewed c5s 0.1364 / 0.1358 / 0.1300,
+	// from 0.1607 with shares equal in reads; C2 0.0404 / 0.0389 / 0.0389 from 0.0400)
+	SharePlanCosts pc = c->count_opt.share;
+	pc.weighted = pc.weighted && mr.plan_n1.size() == B && mr.plan_park1.size() == B;
+	if (!(pc.taper > 0)) pc.taper = mr.skew >= 4.0 ? 0.25 : 0.5;
+	const bool weighted = pc.weighted;
+	std::vector<unsigned char> visited(B, 0);
+	for (size_t q = 0; q < B; ++q) visited[q] = E.buckets[q].kind == 1u ? 1 : 0;
+	if (weighted && mr.plan_seg_x.size() >= 2 && mr.plan_seg_first.size() == B + 1)
+		plan_share_cuts_seg(so.data(), visited.data(), B, mr.plan_seg_x.data(), mr.plan_seg_kind.data(), mr.plan_seg_looks.data(), mr.plan_seg_first.data(),
+		                    mr.plan_seg_kind.size(), grid, pc, cut.data());
+	else
+		plan_share_cuts(so.data(), visited.data(), weighted ? mr.plan_n1.data() : nullptr, weighted ? mr.plan_n2.data() : nullptr,
+		                weighted ? mr.plan_park1.data() : nullptr, weighted ? mr.plan_park2.data() : nullptr, B, grid, pc, cut.data());
+	// the first packed bucket that holds slots of the share [cut[g], cut[g + 1]) (the kernel follows the visit
+	// records' links from there); B when there is none
+	size_t bb = 0;
+	for (unsigned long long g = 0; g < grid; ++g) {
+		while (bb + 1 < B && so[bb + 1] <= cut[(size_t)g]) ++bb;
+		const unsigned f = mr.next_packed_host[bb];
+		first[(size_t)g] = (f < B && so[f] < cut[(size_t)g + 1]) ? f : (unsigned)B;
+	}
+	int rc = mr.wg_first.upload(first.data(), first.size(), st);
+	if (!rc) rc = mr.wg_cut.upload(cut.data(), cut.size(), st);
+	if (rc) return rc;
 	{
-		if (c->occ_lds_bytes != lds_bytes || c->occ_p1w != p1w) {             // asked once per table size and kernel
-			int nb = 0;
-			int nb2 = 0;
-			HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn_wide, (int)COUNT_BLOCK, (size_t)lds_bytes));
-			HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb2, fn_compact, (int)COUNT_BLOCK, (size_t)lds_bytes));
-			c->occ_lds_bytes = lds_bytes; c->occ_p1w = p1w; c->occ_blocks = all_compact ? nb2 : std::min(nb, nb2);
+		std::vector<WgPlan> plan((size_t)grid);
+		for (unsigned long long g = 0; g < grid; ++g) {
+			WgPlan &w = plan[(size_t)g];
+			w.s_begin = cut[(size_t)g]; w.s_end = cut[(size_t)g + 1];
+			w.first = mr.visits_host[std::min<size_t>(first[(size_t)g], B)];
 		}
-		if (c->occ_blocks >= 1) per_cu = std::min(per_cu, (unsigned)c->occ_blocks);
+		if ((rc = mr.wg_plan.upload(plan.data(), plan.size(), st))) return rc;
+		HIP_TRY(hipStreamSynchronize(st));          // the host vector goes out of scope
 	}
-	c->last_wg_per_cu = per_cu;
-	for (int m = 0; m < M; ++m) {
-		MethodReads &mr = c->reads[m];
-		if (mr.total_slots == 0 || E.buckets.empty()) continue;
-		// workgroups per resident slot: 2 for even read depth (fewest table stagings), more when a few buckets hold most of the
-		// reads and shares differ in cost.  Measured with a count stream per lane, where the next count fills the tail of this
-		// one (before that the tail made more and smaller shares pay: 3 and 8): C3 1 -> 0.150, 2 -> 0.143, 3 -> 0.148, 4 ->
-		// 0.151 ms per step; the skewed c5s 3 -> 0.179, 4 -> 0.176, 6 -> 0.178, 8 -> 0.183; C2 1 -> 0.046, 2 -> 0.044, 3 -> 0.044.
-		// The five-wave kernel's steps are twice as long, and its shares pay for being smaller: C3 1.6 -> 0.137, 2 -> 0.133,
-		// 2.4 -> 0.1335, 3 -> 0.129, 3.5 -> 0.132, 4 -> 0.133, 5 -> 0.137, 6 -> 0.1355.
-		// With three counter sets two counts are co-resident throughout; same box, one process: C3 2 -> 0.0985, 3 -> 0.0992, 4 -> 0.1040
-		// (share_taper 0.25 / 0.5 / 1: 0.0991 / 0.0986 / 0.1004; six workgroups a compute unit 0.1131 against 0.0995 with five): the rules stay.
-		// lsq_ctx_set_option "grid_multiplier" overrides
-		const double mult = c->opt_grid_mult > 0 ? c->opt_grid_mult : (mr.skew >= 32.0 ? 4.0 : (mr.skew >= 4.0 || p1w == 4 ? 3.0 : 2.0));
-		unsigned long long grid = (unsigned long long)((double)c->n_cu * per_cu * mult);
-		// one workgroup's share must keep the packed LDS counters (24-bit count, 40-bit bases) exact
-		grid = std::max(grid, mr.total_slots / (1ull << 21) + 1);
-		grid = std::min<unsigned long long>(grid, std::max<unsigned long long>(mr.total_slots / 64, 1));
+	HIP_TRY(hipStreamSynchronize(st));          // the host vectors go out of scope
+	mr.wg_grid = grid;
+	return LSQ_OK;
+}
+
+// The argument record of read file m's kernels, for the counter set the context has selected.
+static CountArgs count_args(const lsq_ctx *c, const int m, const int set, const LaunchShape &S) {
+	const lsq_events &E = *c->E;
+	const MethodReads &mr = c->reads[m];
+	const size_t n_cls = E.n_cls_total;
+	CountArgs A{};
+	A.buckets = c->buckets.p; A.images = c->images.p; A.ties = c->ties.p; A.strand_rank = c->strand_rank.p;
+	A.wg_first = mr.wg_first.p; A.wg_cut = mr.wg_cut.p; A.wg_plan = mr.wg_plan.p; A.visits = mr.visits.p;
+	A.read_names = mr.named ? mr.names.p : nullptr; A.read_name_off = mr.named ? mr.name_off.p : nullptr;
+	A.gene_names = c->gene_names.p; A.gene_name_off = c->gene_name_off.p;
+	A.n_buckets = (unsigned)E.buckets.size();
+	A.tables_lds_bytes = S.tables_bytes;
+	A.ablate = c->launch.dev_ablate;
+	A.compact = mr.compact ? 1u : 0u;
+	A.p1 = mr.p1.p; A.p1_strand = mr.p1_strand.p; A.p1_line = mr.p1_line.p;
+	A.p2 = mr.p2.p; A.p2_strand = mr.p2_strand.p; A.p2_line = mr.p2_line.p;
+	A.pn_blk_off = mr.pn_blk_off.p; A.pn_nblk = mr.pn_nblk.p; A.pn_se = reinterpret_cast<const int2 *>(mr.pn_se.p);
+	A.pn_strand = mr.pn_strand.p; A.pn_line = mr.pn_line.p; A.pn_bucket = mr.pn_bucket.p;
+	A.p1_off = mr.p1_off.p; A.p2_off = mr.p2_off.p; A.pn_off = mr.pn_off.p; A.slot_off = mr.slot_off.p;
+	A.total_slots = mr.total_slots;
+	A.cnt = c->cnt.p + (size_t)m * n_cls; A.bases = c->bases.p + (size_t)m * n_cls;
+	A.exc = mr.exc.p + (size_t)set * mr.exc_cap; A.exc_count = c->exc_count.p + 2 * m; A.exc_cap = (unsigned)mr.exc_cap;
+	A.dbg = c->dbg.p; A.bar = c->dbg.p + 16 + m;
+	A.wg_trace = nullptr;
+	// pool-n workers: one workgroup per CU at most, one lane per read and pass
+	A.n_pn = mr.pn_strand.n;
+	const unsigned workers_per_cu = 2;          // 1, 4 and 8 measured within 2 % of each other
+	A.n_workers = (unsigned)std::min<unsigned long long>((A.n_pn + COUNT_BLOCK - 1) / COUNT_BLOCK, (unsigned long long)c->n_cu * workers_per_cu);
 #ifdef LSQ_DEV
-		if (const char *e = getenv("LSQ_GRID_WGS")) { const long v = atol(e); if (v >= 1) grid = (unsigned long long)v; }      // timing experiments
+	if (c->launch.dev_ablate & 32768u) A.n_workers = 0;          // timing experiment: no pool-n workers (their reads go uncounted)
 #endif
-		if (mr.wg_grid != grid) {
-			// The workgroups' shares: equal in COST, with a cut moved onto a bucket boundary when one lies within 30 % of a share
-			// of it -- a workgroup that owns whole buckets stages, drains and flushes each once, where a cut through the middle
-			// makes two workgroups do it (the planner's buckets of an evenly deep read set are about a share long).
-			// Cost (round 3; the workgroup trace of the developer build, tools/kbench.py, fitted over C3's 3 840 shares: with shares
-			// equal in reads a workgroup took 11 to 72 us, median 31, and the wave slots of the launch were 68 % used -- the last
-			// third of the launch was a thinning tail of late, long shares): a two-block record costs what 4.3 one-block records
-			// do, a look of the general walk at a read that the streaming loops leave to it what 9 do (the ingest counts those looks
-			// per bucket as it pools the reads: plan_park*), a bucket's staging and flush what 7 000 do.  And the shares get smaller towards the end
-			// of the grid ("share_taper": the last is that fraction of the first), so that what is still running when the slots
-			// start to empty is short.
-			const std::vector<unsigned long long> &so = mr.slot_off_host;
-			const size_t B = E.buckets.size();
-			std::vector<unsigned long long> cut((size_t)grid + 1, 0);
-			std::vector<unsigned> first((size_t)grid, 0);
-			const bool weighted = c->opt_share_weighted && mr.plan_n1.size() == B && mr.plan_park1.size() == B;
-			// (the pipelined step on one box, taper 1 / 0.5 / 0.25: C3 0.1189 / 0.1165 / 0.1193 ms -- the next count's first workgroups fill this
-			// launch's tail there, and smaller last shares cost more stagings than they still save; the skewed c5s 0.1364 / 0.1358 / 0.1300,
-			// from 0.1607 with shares equal in reads; C2 0.0404 / 0.0389 / 0.0389 from 0.0400)
-			SharePlanCosts pc;
-			pc.weighted = weighted; pc.snap = c->opt_snap_shares;
-			pc.two_block = c->opt_share_cost_p2; pc.walk_look = c->opt_share_cost_park; pc.visit = c->opt_share_cost_visit;
-			pc.taper = c->opt_share_taper > 0 ? c->opt_share_taper : (mr.skew >= 4.0 ? 0.25 : 0.5);
-			pc.hot = c->opt_share_cost_hot;
-			std::vector<unsigned char> visited(B, 0);
-			for (size_t q = 0; q < B; ++q) visited[q] = E.buckets[q].kind == 1u ? 1 : 0;
-			if (weighted && mr.plan_seg_x.size() >= 2 && mr.plan_seg_first.size() == B + 1)
-				plan_share_cuts_seg(so.data(), visited.data(), B, mr.plan_seg_x.data(), mr.plan_seg_kind.data(), mr.plan_seg_looks.data(), mr.plan_seg_first.data(),
-				                    mr.plan_seg_kind.size(), grid, pc, cut.data());
-			else
-				plan_share_cuts(so.data(), visited.data(), weighted ? mr.plan_n1.data() : nullptr, weighted ? mr.plan_n2.data() : nullptr,
-				                weighted ? mr.plan_park1.data() : nullptr, weighted ? mr.plan_park2.data() : nullptr, B, grid, pc, cut.data());
-			// the first packed bucket that holds slots of the share [cut[g], cut[g + 1]) (the kernel follows the visit
-			// records' links from there); B when there is none
-			size_t bb = 0;
-			for (unsigned long long g = 0; g < grid; ++g) {
-				while (bb + 1 < B && so[bb + 1] <= cut[(size_t)g]) ++bb;
-				const unsigned f = mr.next_packed_host[bb];
-				first[(size_t)g] = (f < B && so[f] < cut[(size_t)g + 1]) ? f : (unsigned)B;
-			}
-			int rc = mr.wg_first.upload(first.data(), first.size(), st);
-			if (!rc) rc = mr.wg_cut.upload(cut.data(), cut.size(), st);
-			if (rc) return rc;
-			{
-				std::vector<WgPlan> plan((size_t)grid);
-				for (unsigned long long g = 0; g < grid; ++g) {
-					WgPlan &w = plan[(size_t)g];
-					w.s_begin = cut[(size_t)g]; w.s_end = cut[(size_t)g + 1];
-					w.first = mr.visits_host[std::min<size_t>(first[(size_t)g], B)];
-				}
-				if ((rc = mr.wg_plan.upload(plan.data(), plan.size(), st))) return rc;
-				HIP_TRY(hipStreamSynchronize(st));          // the host vector goes out of scope
-			}
-			HIP_TRY(hipStreamSynchronize(st));          // the host vectors go out of scope
-			mr.wg_grid = grid;
-		}
-		CountArgs A{};
-		A.buckets = c->buckets.p; A.images = c->images.p; A.ties = c->ties.p; A.strand_rank = c->strand_rank.p;
-		A.wg_first = mr.wg_first.p; A.wg_cut = mr.wg_cut.p; A.wg_plan = mr.wg_plan.p; A.visits = mr.visits.p;
-		A.read_names = mr.named ? mr.names.p : nullptr; A.read_name_off = mr.named ? mr.name_off.p : nullptr;
-		A.gene_names = c->gene_names.p; A.gene_name_off = c->gene_name_off.p;
-		A.n_buckets = (unsigned)E.buckets.size();
-		A.tables_lds_bytes = tables_bytes;
-		A.ablate = c->dev_ablate;
-		A.compact = mr.compact ? 1u : 0u;
-		A.p1 = mr.p1.p; A.p1_strand = mr.p1_strand.p; A.p1_line = mr.p1_line.p;
-		A.p2 = mr.p2.p; A.p2_strand = mr.p2_strand.p; A.p2_line = mr.p2_line.p;
-		A.pn_blk_off = mr.pn_blk_off.p; A.pn_nblk = mr.pn_nblk.p; A.pn_se = reinterpret_cast<const int2 *>(mr.pn_se.p);
-		A.pn_strand = mr.pn_strand.p; A.pn_line = mr.pn_line.p; A.pn_bucket = mr.pn_bucket.p;
-		A.p1_off = mr.p1_off.p; A.p2_off = mr.p2_off.p; A.pn_off = mr.pn_off.p; A.slot_off = mr.slot_off.p;
-		A.total_slots = mr.total_slots;
-		A.cnt = c->cnt.p + (size_t)m * n_cls; A.bases = c->bases.p + (size_t)m * n_cls;
-		A.exc = mr.exc.p + (size_t)set * mr.exc_cap; A.exc_count = c->exc_count.p + 2 * m; A.exc_cap = (unsigned)mr.exc_cap;
-		A.dbg = c->dbg.p; A.bar = c->dbg.p + 16 + m;
-		A.wg_trace = nullptr;
-		const unsigned long long n_pn = mr.pn_strand.n;
-		// pool-n workers: one workgroup per CU at most, one lane per read and pass
-		A.n_pn = n_pn;
-		const unsigned workers_per_cu = 2;          // 1, 4 and 8 measured within 2 % of each other
-		A.n_workers = (unsigned)std::min<unsigned long long>((n_pn + COUNT_BLOCK - 1) / COUNT_BLOCK, (unsigned long long)c->n_cu * workers_per_cu);
+	return A;
+}
+
+// Read file m's kernels on the count stream: the streaming kernel over the packed buckets, the generic one over the others.
+static int launch_counts(lsq_ctx *c, const CountTurn &T, const LaunchShape &S, const int m, const unsigned long long grid, CountArgs &A,
+                         std::vector<Cleanup> &cleanups, bool &counted_signalled) {
+	const MethodReads &mr = c->reads[m];
+	if (c->has_fast) {
+		if (c->time_events) HIP_TRY(hipEventRecord(c->evf0[m], T.st));
+		// the last streaming kernel of the step carries ev_counted as its own completion signal: a separate
+		// event record is one more packet between this kernel and the next count's (measured ~5 us each)
+		const bool last_streaming = m == c->E->n_methods - 1 && !c->has_generic && !c->time_events;
+		const dim3 fgrid((unsigned)grid + A.n_workers);
 #ifdef LSQ_DEV
-		if (c->dev_ablate & 32768u) A.n_workers = 0;          // timing experiment: no pool-n workers (their reads go uncounted)
-#endif
-		if (c->has_fast) {
-			if (c->time_events) HIP_TRY(hipEventRecord(c->evf0[m], st));
-			// the last streaming kernel of the step carries ev_counted as its own completion signal: a separate
-			// event record is one more packet between this kernel and the next count's (measured ~5 us each)
-			const bool last_streaming = m == M - 1 && !c->has_generic && !c->time_events;
-			const dim3 fgrid((unsigned)grid + A.n_workers);
-#ifdef LSQ_DEV
-			if (c->dev_ablate & 4194304u) {
-				if (c->wg_trace.n < 4ull * fgrid.x) { int rc = c->wg_trace.alloc(4ull * fgrid.x); if (rc) return rc; }
-				HIP_TRY(hipMemsetAsync(c->wg_trace.p, 0, 4ull * fgrid.x * sizeof(unsigned long long), st));
-				c->wg_trace_n = fgrid.x; c->wg_trace_workers = A.n_workers;
-				A.wg_trace = c->wg_trace.p;
-			}
-#endif
-			void *kargs[] = {(void *)&A};
-			HIP_TRY(hipExtLaunchKernel(mr.compact ? fn_compact : fn_wide, fgrid, dim3(COUNT_BLOCK), kargs, lds_bytes, st, nullptr, last_streaming ? c->ev_counted2[lane] : nullptr, 0));
-			if (last_streaming) counted_signalled = true;
-			if (c->time_events) HIP_TRY(hipEventRecord(c->evf1[m], st));
-			c->fast_launched |= 1 << m;
-			cleanups.push_back({A, n_pn, m});
+		if (c->launch.dev_ablate & 4194304u) {
+			CountLaunch &L = c->launch;
+			if (L.wg_trace.n < 4ull * fgrid.x) { int rc = L.wg_trace.alloc(4ull * fgrid.x); if (rc) return rc; }
+			HIP_TRY(hipMemsetAsync(L.wg_trace.p, 0, 4ull * fgrid.x * sizeof(unsigned long long), T.st));
+			L.wg_trace_n = fgrid.x; L.wg_trace_workers = A.n_workers;
+			A.wg_trace = L.wg_trace.p;
 		}
-		if (c->has_generic) {
-			hipLaunchKernelGGL(lsq_count_generic_kernel, dim3((unsigned)grid), dim3(COUNT_BLOCK), generic_tables_bytes, st, A);
-			HIP_TRY(hipGetLastError());
-		}
+#endif
+		void *kargs[] = {(void *)&A};
+		HIP_TRY(hipExtLaunchKernel(mr.compact ? S.fn_compact : S.fn_wide, fgrid, dim3(COUNT_BLOCK), kargs, S.lds_bytes, T.st, nullptr, last_streaming ? c->ev_counted2[T.lane] : nullptr, 0));
+		if (last_streaming) counted_signalled = true;
+		if (c->time_events) HIP_TRY(hipEventRecord(c->evf1[m], T.st));
+		c->launch.fast_launched |= 1 << m;
+		cleanups.push_back({A, m});
 	}
-	if (c->time_events) HIP_TRY(hipEventRecord(c->ev1, st));
-	c->count_timed = c->time_events;
-	// the exception pass, and everything that reads the counts, on the result stream behind the streaming kernels;
-	// (it turns into the recount where the exception list overflowed)
-	if (!counted_signalled) HIP_TRY(hipEventRecord(c->ev_counted2[lane], st));
-	HIP_TRY(hipStreamWaitEvent(st_em, c->ev_counted2[lane], 0));
+	if (c->has_generic) {
+		hipLaunchKernelGGL(lsq_count_generic_kernel, dim3((unsigned)grid), dim3(COUNT_BLOCK), S.tables_bytes, T.st, A);
+		HIP_TRY(hipGetLastError());
+	}
+	return LSQ_OK;
+}
+
+// The exception pass, and everything that reads the counts, on the result stream behind the streaming kernels
+// (it turns into the recount where the exception list overflowed).
+static int exception_pass(lsq_ctx *c, const CountTurn &T, const std::vector<Cleanup> &cleanups, const bool counted_signalled) {
+	if (!counted_signalled) HIP_TRY(hipEventRecord(c->ev_counted2[T.lane], T.st));
+	HIP_TRY(hipStreamWaitEvent(T.st_em, c->ev_counted2[T.lane], 0));
 	// One workgroup a compute unit: the launch normally finds a handful of pairs to settle beside the next count's kernel (C3: a step
 	// takes 0.107-0.109 ms with 16, 64, 128 or 256 of them, profiles/r04_recount_c3.json), and when the list has overflowed the same
 	// workgroups count every read again -- 14 ms per C3 step on 256, 37 on 64, 90-108 on the 16 of round 3.  No workgroup waits for another.
 	const unsigned rgrid = std::max(16u, (unsigned)c->n_cu);
-	if (c->recount_args.n < (size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs)) {
-		int rc = c->recount_args.alloc((size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs));
+	CountLaunch &L = c->launch;
+	const size_t all_args = (size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs);
+	if (L.recount_args.n < all_args) {
+		int rc = L.recount_args.alloc(all_args);
 		if (rc) return rc;
-		c->recount_args_host.assign((size_t)LSQ_COUNTER_SETS * LSQ_MAX_METHODS * sizeof(CountArgs), 0);
+		L.recount_args_host.assign(all_args, 0);
 	}
 	for (const Cleanup &u : cleanups) {
 		// the arguments of these two kernels live in device memory, one record per (counter set, read file); rewritten only when they change
-		const size_t slot = ((size_t)set * LSQ_MAX_METHODS + (size_t)u.m) * sizeof(CountArgs);
-		if (memcmp(c->recount_args_host.data() + slot, &u.A, sizeof(CountArgs)) != 0) {
-			memcpy(c->recount_args_host.data() + slot, &u.A, sizeof(CountArgs));
-			HIP_TRY(hipMemcpyAsync(c->recount_args.p + slot, c->recount_args_host.data() + slot, sizeof(CountArgs), hipMemcpyHostToDevice, st_em));
+		const size_t slot = ((size_t)T.set * LSQ_MAX_METHODS + (size_t)u.m) * sizeof(CountArgs);
+		if (memcmp(L.recount_args_host.data() + slot, &u.A, sizeof(CountArgs)) != 0) {
+			memcpy(L.recount_args_host.data() + slot, &u.A, sizeof(CountArgs));
+			HIP_TRY(hipMemcpyAsync(L.recount_args.p + slot, L.recount_args_host.data() + slot, sizeof(CountArgs), hipMemcpyHostToDevice, T.st_em));
 		}
-		const CountArgs *dA = reinterpret_cast<const CountArgs *>(c->recount_args.p + slot);
-		hipLaunchKernelGGL(lsq_count_cleanup_kernel, dim3(c->opt_cleanup_grid ? c->opt_cleanup_grid : rgrid), dim3(256), 0, st_em, dA, c->opt_recount ? 1 : 0, u.n_pn,
+		const CountArgs *dA = reinterpret_cast<const CountArgs *>(L.recount_args.p + slot);
+		hipLaunchKernelGGL(lsq_count_cleanup_kernel, dim3(c->count_opt.cleanup_grid ? c->count_opt.cleanup_grid : rgrid), dim3(256), 0, T.st_em, dA, c->count_opt.recount ? 1 : 0, u.A.n_pn,
 		                   (const ExcEntry *)u.A.exc, (const unsigned *)u.A.exc_count, u.A.exc_cap);
 		HIP_TRY(hipGetLastError());
 	}
 	return LSQ_OK;
+}
+
+int run_count(lsq_ctx *c) {
+	const lsq_events &E = *c->E;
+	int rc;
+	CountTurn T{};
+	if ((rc = rotate_counter_sets(c, T))) return rc;
+	c->launch.fast_launched = 0;
+	std::vector<Cleanup> cleanups;
+	bool counted_signalled = false;
+	if (c->time_events) HIP_TRY(hipEventRecord(c->ev0, T.st));      // ev0..ev1 brackets the count kernel launches only
+	LaunchShape S{};
+	if ((rc = launch_shape(c, S))) return rc;
+	for (int m = 0; m < E.n_methods; ++m) {
+		MethodReads &mr = c->reads[m];
+		if (mr.total_slots == 0 || E.buckets.empty()) continue;
+		const unsigned long long grid = count_grid(c, mr, S);
+		if (mr.wg_grid != grid && (rc = plan_shares(c, mr, grid, T.st))) return rc;
+		CountArgs A = count_args(c, m, T.set, S);
+		if ((rc = launch_counts(c, T, S, m, grid, A, cleanups, counted_signalled))) return rc;
+	}
+	if (c->time_events) HIP_TRY(hipEventRecord(c->ev1, T.st));
+	c->count_timed = c->time_events;
+	return exception_pass(c, T, cleanups, counted_signalled);
 }
 
 } // namespace lsq
@@ -1860,8 +1912,8 @@ int lsq_count_status(lsq_ctx *c, uint32_t *exceptions, uint32_t *recounted) LSQ_
 int lsq_count_launch_info(lsq_ctx *c, uint32_t *reads_per_look, uint32_t *workgroups_per_cu) LSQ_API_TRY {
 	if (!c) return fail(LSQ_E_ARG, "null context");
 	if (!c->counted) return fail(LSQ_E_STATE, "lsq_count must come first");
-	if (reads_per_look) *reads_per_look = c->last_reads_per_look;
-	if (workgroups_per_cu) *workgroups_per_cu = c->last_wg_per_cu;
+	if (reads_per_look) *reads_per_look = c->launch.last_reads_per_look;
+	if (workgroups_per_cu) *workgroups_per_cu = c->launch.last_wg_per_cu;
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -1881,9 +1933,9 @@ int lsq_debug_counters(lsq_ctx *c, unsigned long long *out8) LSQ_API_TRY {
 int lsq_debug_wg_trace(lsq_ctx *c, unsigned long long *out, unsigned long long cap, unsigned long long *n, unsigned long long *n_workers) LSQ_API_TRY {
 	HIP_TRY(hipSetDevice(c->device));
 	{ int rc = sync_all(c); if (rc) return rc; }
-	const unsigned long long k = std::min<unsigned long long>(cap, c->wg_trace_n);
-	if (k) HIP_TRY(hipMemcpy(out, c->wg_trace.p, 4 * k * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-	*n = k; *n_workers = c->wg_trace_workers;
+	const unsigned long long k = std::min<unsigned long long>(cap, c->launch.wg_trace_n);
+	if (k) HIP_TRY(hipMemcpy(out, c->launch.wg_trace.p, 4 * k * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+	*n = k; *n_workers = c->launch.wg_trace_workers;
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -1893,7 +1945,7 @@ int lsq_debug_plan_shares(const unsigned long long *slot_off, const unsigned cha
                           const unsigned *look1, const unsigned *look2, unsigned long long n_buckets, unsigned long long grid,
                           const double *costs4, int weighted, int snap, unsigned long long *cuts) LSQ_API_TRY {
 	if (!slot_off || !packed || !costs4 || !cuts || grid == 0) return fail(LSQ_E_ARG, "null argument");
-	lsq::SharePlanCosts pc;
+	SharePlanCosts pc;
 	pc.weighted = weighted != 0; pc.snap = snap != 0;
 	pc.two_block = costs4[0]; pc.walk_look = costs4[1]; pc.visit = costs4[2]; pc.taper = costs4[3];
 	lsq::plan_share_cuts(slot_off, packed, n1, n2, look1, look2, (size_t)n_buckets, grid, pc, cuts);

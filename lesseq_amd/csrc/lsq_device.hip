@@ -1,7 +1,9 @@
 // Device group of the C ABI: context, event tables, count / solve entry points, result fetch (gfx950).
 // The kernels live in lsq_count.hip, lsq_em.hip, lsq_ingest.hip and lsq_readfile.hip.
 #include "lsq_device.hpp"
+#include "lsq_upload_tables.hpp"
 #include <chrono>
+#include <cstddef>
 #include <thread>
 
 namespace lsq {
@@ -71,7 +73,7 @@ void note_overflow(lsq_ctx *c, const std::vector<unsigned> &h) {
 	for (int m = 0; m < c->E->n_methods; ++m) {
 		if (!h[2 * (size_t)m + 1] || c->overflow_logged[m]) continue;
 		c->overflow_logged[m] = true;
-		if (c->opt_recount) continue;            // asked for (option recount_every_read): nothing to report
+		if (c->count_opt.recount) continue;            // asked for (option recount_every_read): nothing to report
 		warn("read file %d: the exception list overflowed (%u pairs for %zu entries); every read of the file was counted again on the device. "
 		     "Tables are complete; raise lsq_ctx_set_option \"exception_capacity\" to avoid the second pass", m, h[2 * (size_t)m], c->reads[m].exc_cap);
 	}
@@ -79,24 +81,32 @@ void note_overflow(lsq_ctx *c, const std::vector<unsigned> &h) {
 
 } // namespace lsq
 
+namespace {
+// developer aid: LSQ_CLI_TIMING=1 prints where the start-up goes (stderr) -- a line per mark, with the time since the mark before
+struct CliClock {
+	const bool on = getenv("LSQ_CLI_TIMING") != nullptr;
+	const int digits;
+	std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+	explicit CliClock(int digits_) : digits(digits_) {}
+	void mark(const char *what) {
+		if (!on) return;
+		const auto t = std::chrono::steady_clock::now();
+		fprintf(stderr, "[timing]     %-32s %.*f s\n", what, digits, std::chrono::duration<double>(t - t_last).count());
+		t_last = t;
+	}
+};
+} // namespace
+
 extern "C" {
 
 int lsq_ctx_create(int device_id, lsq_ctx **out) { return lsq_ctx_create_with(device_id, 0u, out); }
 
 int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TRY {
 	if (!out) return fail(LSQ_E_ARG, "null argument");
-	// developer aid: LSQ_CLI_TIMING=1 prints where the start-up goes (stderr)
-	const bool timing = getenv("LSQ_CLI_TIMING") != nullptr;
-	auto t_last = std::chrono::steady_clock::now();
-	auto mark = [&](const char *what) {
-		if (!timing) return;
-		const auto t = std::chrono::steady_clock::now();
-		fprintf(stderr, "[timing]     %-32s %.3f s\n", what, std::chrono::duration<double>(t - t_last).count());
-		t_last = t;
-	};
+	CliClock clock(3);
 	int n = 0;
 	hipError_t e = hipGetDeviceCount(&n);
-	mark("context: runtime start-up");
+	clock.mark("context: runtime start-up");
 	if (e != hipSuccess || n <= 0) return fail(LSQ_E_DEVICE, "no HIP device available (%s)", e == hipSuccess ? "device count 0" : hipGetErrorString(e));
 	if (device_id < 0 || device_id >= n) return fail(LSQ_E_ARG, "device %d out of range (%d devices)", device_id, n);
 	HIP_TRY(hipSetDevice(device_id));
@@ -104,7 +114,7 @@ int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TR
 	HIP_TRY(hipGetDeviceProperties(&prop, device_id));
 	if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
 		return fail(LSQ_E_DEVICE, "device %d is %s; this library carries gfx950 code only", device_id, prop.gcnArchName);
-	mark("context: device selected");
+	clock.mark("context: device selected");
 	std::unique_ptr<lsq_ctx> c(new lsq_ctx);
 	c->device = device_id;
 	c->n_cu = prop.multiProcessorCount;
@@ -138,12 +148,12 @@ int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TR
 	if (lanes_first) {
 		const int rc = make_lanes();
 		if (rc) return rc;
-		mark("context: lanes");
+		clock.mark("context: lanes");
 	} else
-		c->opt_counter_sets = 2;          // (on shared queues three sets are slower than two, 0.153 against 0.119 ms per C3 step; "counter_sets" still asks for them)
+		c->count_opt.counter_sets = 2;          // (on shared queues three sets are slower than two, 0.153 against 0.119 ms per C3 step; "counter_sets" still asks for them)
 	HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
 	HIP_TRY(hipEventCreate(&c->evt0)); HIP_TRY(hipEventCreate(&c->evt1));
-	mark("context: upload stream");
+	clock.mark("context: upload stream");
 	if (flags & LSQ_CTX_LANES_IN_BACKGROUND) {
 		c->lanes_thread = std::thread([cp, make_lanes]() noexcept {
 			try { cp->lanes_status = make_lanes(); if (cp->lanes_status) cp->lanes_error = lsq_last_error(); }
@@ -152,7 +162,7 @@ int lsq_ctx_create_with(int device_id, unsigned flags, lsq_ctx **out) LSQ_API_TR
 	} else if (!lanes_first) {
 		const int rc = make_lanes();
 		if (rc) return rc;
-		mark("context: lanes");
+		clock.mark("context: lanes");
 	}
 	*out = c.release();
 	return LSQ_OK;
@@ -209,224 +219,125 @@ int lsq_ctx_synchronize_for(lsq_ctx *c, double seconds) LSQ_API_TRY {
 	return LSQ_OK;
 } LSQ_API_CATCH
 
-int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
-	if (!c || !E) return fail(LSQ_E_ARG, "null argument");
-	HIP_TRY(hipSetDevice(c->device));
-	{ int rc = sync_all(c); if (rc) return rc; }        // the buffers below may still be read by a solve in flight
-	if (E->max_lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables exceed the CU's LDS");
-	c->E = E;
-	c->counted = c->solved = false;
-	c->boot.done = false;
-	c->has_fast = c->has_generic = c->has_host = false;
-	for (const BucketDesc &bd : E->buckets) { if (bd.kind == 1) c->has_fast = true; else if (bd.kind == 0) c->has_generic = true; else c->has_host = true; }
-	std::vector<bool> host_event(E->dev2out.size(), false);
-	for (const BucketDesc &bd : E->buckets) if (bd.kind == 2) for (uint32_t q = 0; q < bd.n_events; ++q) host_event[bd.ev_base + q] = true;
-	for (auto &r : c->reads) r.present = false;
+} // extern "C"
+
+namespace {
+
+// lsq_events_upload's steps.  Each builds its tables on the host (lsq_upload_tables.hpp) and queues them on the upload stream.
+int upload_images_em_pack(lsq_ctx *c, const lsq_events &E) {
 	int rc;
-	const bool timing = getenv("LSQ_CLI_TIMING") != nullptr;
-	auto t_last = std::chrono::steady_clock::now();
-	auto mark = [&](const char *what) {
-		if (!timing) return;
-		const auto t = std::chrono::steady_clock::now();
-		fprintf(stderr, "[timing]     %-32s %.4f s\n", what, std::chrono::duration<double>(t - t_last).count());
-		t_last = t;
-	};
-	if ((rc = c->buckets.upload(E->buckets.data(), E->buckets.size(), c->stream))) return rc;
-	if ((rc = c->images.upload(E->images.data(), E->images.size(), c->stream))) return rc;
-	if ((rc = c->ties.upload(E->ties.data(), E->ties.size(), c->stream))) return rc;
-	if ((rc = c->dK.upload(E->dev_K.data(), E->dev_K.size(), c->stream))) return rc;
-	if ((rc = c->cls_base.upload(E->dev_cls_base.data(), E->dev_cls_base.size(), c->stream))) return rc;
-	if ((rc = c->iso_base.upload(E->dev_iso_base.data(), E->dev_iso_base.size(), c->stream))) return rc;
-	{
-		// EM places: events with at most two isoforms and one (method, class) pair per lane first, then
-		// the others; each group padded to whole waves (16 events) so that a wave runs one loop shape
-		const size_t n_dev = E->dev2out.size();
-		std::vector<uint32_t> order;
-		order.reserve(n_dev + 32);
-		for (int pass = 0; pass < 2; ++pass) {
-			for (size_t d = 0; d < n_dev; ++d) {
-				const int K = E->dev_K[d];
-				if (host_event[d]) continue;            // solved on the host (host_solve)
-				// (an isoform with ONE accessible start, G = 1: the general kernel's loop with the reference's own quotients,
-				// lsq_em.hip em_quad_body)
-				bool unit_g = false;
-				for (int m = 0; m < E->n_methods; ++m) for (int j = 0; j < K; ++j) unit_g = unit_g || E->ev[E->dev2out[d]].ars[m][j] == 1;
-				const bool small = K <= 2 && E->n_methods * ((1 << K) - 1) <= EM_LANES && !unit_g;
-				if (small == (pass == 0)) order.push_back((uint32_t)d);
-			}
-			while (order.size() % (64 / EM_LANES)) order.push_back(0xFFFFFFFFu);
-			if (pass == 0) c->em.small_places = (unsigned)order.size();
-		}
-		c->em.places = (unsigned)order.size();
-		for (EmLane &l : c->em.lane) l.order_valid = false;
-		if ((rc = c->em.tail_count.alloc(4))) return rc;
-		HIP_TRY(hipMemsetAsync(c->em.tail_count.p, 0, 4 * sizeof(uint32_t), c->stream));
-		if ((rc = c->em.reserve_tails(c->em.small_places))) return rc;
-		if (c->em.split.n != EM_SPLIT_WORDS) { if ((rc = c->em.split.alloc(EM_SPLIT_WORDS))) return rc; }
-		HIP_TRY(hipMemsetAsync(c->em.split.p, 0xFF, EM_SPLIT_WORDS * sizeof(uint32_t), c->stream));
-		c->em.last = {};
-		if ((rc = c->em.order.upload(order.data(), order.size(), c->stream))) return rc;
-		// gene names for span-start ties against named reads
-		std::string blob;
-		std::vector<uint32_t> goff(n_dev + 1, 0);
-		for (size_t d = 0; d < n_dev; ++d) { blob += E->ev[E->dev2out[d]].gname; goff[d + 1] = (uint32_t)blob.size(); }
-		if ((rc = c->gene_names.upload(blob.data(), blob.size(), c->stream))) return rc;
-		if ((rc = c->gene_name_off.upload(goff.data(), goff.size(), c->stream))) return rc;
-	}
-	{
-		// lsq_results_pack_device: where every class slot, isoform and event of the shard sits in the device arrays,
-		// listed in output order (the shard is a contiguous run of output-ordered events)
-		const size_t n_dev = E->dev2out.size();
-		std::vector<uint32_t> order(n_dev);
-		std::iota(order.begin(), order.end(), 0u);
-		std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return E->dev2out[a] < E->dev2out[b]; });
-		std::vector<uint32_t> pc, pi, pe;
-		for (uint32_t dd : order) {
-			const int K = E->dev_K[dd];
-			for (uint32_t k = 0; k < (1u << K) - 1u; ++k) pc.push_back(E->dev_cls_base[dd] + k);
-			for (int j = 0; j < K; ++j) pi.push_back(E->dev_iso_base[dd] + (uint32_t)j);
-			pe.push_back(dd);
-		}
-		if ((rc = c->pack_cls.upload(pc.data(), pc.size(), c->stream))) return rc;
-		if ((rc = c->pack_iso.upload(pi.data(), pi.size(), c->stream))) return rc;
-		if ((rc = c->pack_ev.upload(pe.data(), pe.size(), c->stream))) return rc;
-	}
-	mark("events: images, EM order, pack lists");
-	// G = 1/ARS (common/read.h:331-340), device isoform order, per method
-	const size_t n_iso = E->n_iso_total, M = (size_t)E->n_methods;
-	std::vector<double> G(std::max<size_t>(M * n_iso, 1), 0.0);
-	for (size_t d = 0; d < E->dev2out.size(); ++d) {
-		const Event &ev = E->ev[E->dev2out[d]];
-		for (size_t m = 0; m < M; ++m)
-			for (int j = 0; j < ev.K; ++j) {
-				double nd = (double)ev.ars[m][j];
-				G[m * n_iso + E->dev_iso_base[d] + j] = nd <= 0 ? 0.0 : (double)1.0 / nd;
-			}
-	}
-	if ((rc = c->G.upload(G.data(), M * n_iso, c->stream))) return rc;
-	const size_t n_cls = E->n_cls_total, n_ev = E->dev2out.size();
-	{
-		const size_t per = std::max<size_t>(M, 1) * n_cls;
-		c->counters_per_set = 2 * per + LSQ_MAX_METHODS + 16 + LSQ_MAX_METHODS;          // cnt | bases | exc_count (two words a read file) | dbg | one barrier word a read file (lsq_count_cleanup_kernel)
-		if ((rc = c->counters.alloc(LSQ_COUNTER_SETS * c->counters_per_set))) return rc;
-		c->cnt.n = per; c->bases.n = per; c->exc_count.n = 2 * LSQ_MAX_METHODS; c->dbg.n = 16;
-		for (bool &r : c->mark_recorded2) r = false;
-		c->fim_uploaded = false; c->fim_done = false;
-		select_counter_set(c, 0, 0);
-		HIP_TRY(hipMemsetAsync(c->counters.p, 0, c->counters.n * sizeof(unsigned long long), c->stream));      // every set starts out zero
-	}
+	if ((rc = c->buckets.upload(E.buckets.data(), E.buckets.size(), c->stream))) return rc;
+	if ((rc = c->images.upload(E.images.data(), E.images.size(), c->stream))) return rc;
+	if ((rc = c->ties.upload(E.ties.data(), E.ties.size(), c->stream))) return rc;
+	if ((rc = c->dK.upload(E.dev_K.data(), E.dev_K.size(), c->stream))) return rc;
+	if ((rc = c->cls_base.upload(E.dev_cls_base.data(), E.dev_cls_base.size(), c->stream))) return rc;
+	if ((rc = c->iso_base.upload(E.dev_iso_base.data(), E.dev_iso_base.size(), c->stream))) return rc;
+	const EmPlacement P = em_placement(E);
+	c->em.small_places = P.small_places;
+	c->em.places = P.places;
+	for (EmLane &l : c->em.lane) l.order_valid = false;
+	if ((rc = c->em.tail_count.alloc(4))) return rc;
+	HIP_TRY(hipMemsetAsync(c->em.tail_count.p, 0, 4 * sizeof(uint32_t), c->stream));
+	if ((rc = c->em.reserve_tails(c->em.small_places))) return rc;
+	if (c->em.split.n != EM_SPLIT_WORDS) { if ((rc = c->em.split.alloc(EM_SPLIT_WORDS))) return rc; }
+	HIP_TRY(hipMemsetAsync(c->em.split.p, 0xFF, EM_SPLIT_WORDS * sizeof(uint32_t), c->stream));
+	c->em.last = {};
+	if ((rc = c->em.order.upload(P.order.data(), P.order.size(), c->stream))) return rc;
+	const GeneNames N = gene_names(E);
+	if ((rc = c->gene_names.upload(N.blob.data(), N.blob.size(), c->stream))) return rc;
+	if ((rc = c->gene_name_off.upload(N.off.data(), N.off.size(), c->stream))) return rc;
+	const PackLists L = pack_lists(E);
+	if ((rc = c->pack_cls.upload(L.cls.data(), L.cls.size(), c->stream))) return rc;
+	if ((rc = c->pack_iso.upload(L.iso.data(), L.iso.size(), c->stream))) return rc;
+	return c->pack_ev.upload(L.ev.data(), L.ev.size(), c->stream);
+}
+
+// G (the caller's vector: it lives until lsq_events_upload has waited for the stream), the counter sets (every set starts out zero)
+// and the two lanes' EM outputs
+int upload_weights_counters_outputs(lsq_ctx *c, const lsq_events &E, const std::vector<double> &G) {
+	int rc;
+	if ((rc = c->G.upload(G.data(), G.size(), c->stream))) return rc;
+	const size_t n_iso = E.n_iso_total, n_cls = E.n_cls_total, n_ev = E.dev2out.size();
+	const size_t per = std::max<size_t>((size_t)E.n_methods, 1) * n_cls;
+	c->counters_per_set = 2 * per + LSQ_MAX_METHODS + 16 + LSQ_MAX_METHODS;          // cnt | bases | exc_count (two words a read file) | dbg | one barrier word a read file (lsq_count_cleanup_kernel)
+	if ((rc = c->counters.alloc(LSQ_COUNTER_SETS * c->counters_per_set))) return rc;
+	c->cnt.n = per; c->bases.n = per; c->exc_count.n = 2 * LSQ_MAX_METHODS; c->dbg.n = 16;
+	for (bool &r : c->mark_recorded2) r = false;
+	c->fim.uploaded = false; c->fim.done = false;
+	select_counter_set(c, 0, 0);
+	HIP_TRY(hipMemsetAsync(c->counters.p, 0, c->counters.n * sizeof(unsigned long long), c->stream));
 	for (int l = 0; l < 2; ++l) {
 		if ((rc = c->theta2[l].alloc(n_iso)) || (rc = c->logll2[l].alloc(n_ev)) || (rc = c->iters2[l].alloc(n_ev)) || (rc = c->flags2[l].alloc(n_ev))) return rc;
 		HIP_TRY(hipMemsetAsync(c->flags2[l].p, 0, std::max<size_t>(n_ev, 1), c->stream));
 	}
 	select_counter_set(c, 0, 0);
-	mark("events: G, counters, EM outputs");
-	{
-		// ingest tables (lsq_device.hpp: RouteChrom): per chromosome id the covered regions (count/count.cpp:244) as (start, end)
-		// pairs, the spans of the planned events ("clusters") with the bucket each lies in, and the locator grid over both
-		const size_t nc = E->covered.size();
-		std::vector<RouteChrom> chrom(std::max<size_t>(nc, 1));
-		std::vector<int2> cov;
-		std::vector<int4> clu;
-		for (size_t ch = 0; ch < nc; ++ch) {
-			RouteChrom &R = chrom[ch];
-			memset(&R, 0, sizeof(R));
-			R.cov0 = (unsigned)cov.size();
-			for (size_t q = 0; q < E->covered[ch].s.size(); ++q) cov.push_back(make_int2((int)E->covered[ch].s[q], (int)E->covered[ch].e[q]));
-			R.cov1 = (unsigned)cov.size();
-			R.clu0 = (unsigned)clu.size();
-			// A cluster with the bucket of its bases.  Buckets are cut where no span crosses, so a cluster lies in one; the records are
-			// cut at the bucket cuts all the same, and a stretch left of the chromosome's first cut (in no bucket) gets none: a
-			// look-up of "the last record that starts at or left of p" then IS the bucket search and the cluster test of p.
-			const int first = ch < E->chrom_first_bucket.size() ? E->chrom_first_bucket[ch] : -1;
-			if (first >= 0 && ch < E->clu_s.size() && ch < E->cut_lo.size()) {
-				const std::vector<int32_t> &cuts = E->cut_lo[ch];
-				for (size_t q = 0; q < E->clu_s[ch].size(); ++q) {
-					long long s = E->clu_s[ch][q];
-					const long long e = E->clu_e[ch][q];           // (inclusive: a read whose first base is e is still inside)
-					while (s <= e) {
-						const size_t ub = (size_t)(std::upper_bound(cuts.begin(), cuts.end(), (int32_t)s) - cuts.begin());
-						const long long next_cut = ub < cuts.size() ? (long long)cuts[ub] : e + 1;
-						const long long stop = std::min(e, next_cut - 1);
-						if (ub > 0) {
-							const unsigned b = (unsigned)first + (unsigned)(ub - 1);
-							clu.push_back(make_int4((int)s, (int)std::min<long long>(stop, E->buckets[b].hi), (int)b, E->buckets[b].lo));
-						}
-						s = stop + 1;
-					}
-				}
-			}
-			R.clu1 = (unsigned)clu.size();
-		}
-		c->n_chrom_tables = (unsigned)nc;
-		{
-			// the locator: bins of 2^shift bases over each chromosome's range of starts (covered regions and cluster records), the
-			// shift raised until all chromosomes together take at most 2^22 entries.  Entry k of a chromosome, for the bin's first
-			// base x and the next bin's first base y: lower bounds of x and of y among the covered starts (.x, .y) and among the
-			// cluster starts: entry k holds the lower bounds of x (.x covered, .y clusters), entry k + 1 those of y -- read as one
-			// 16-byte pair, a search starts one load away from a handful of candidates; eight bytes a bin keep the bins of the
-			// events (where the reads are) inside the L2.
-			unsigned shift = 10;
-			std::vector<long long> lo(nc, 0), hi(nc, -1);
-			for (size_t ch = 0; ch < nc; ++ch) {
-				bool any = false;
-				auto see = [&](long long v) { if (!any) { lo[ch] = hi[ch] = v; any = true; } lo[ch] = std::min(lo[ch], v); hi[ch] = std::max(hi[ch], v); };
-				for (unsigned q = chrom[ch].cov0; q < chrom[ch].cov1; ++q) see(cov[q].x);
-				for (unsigned q = chrom[ch].clu0; q < chrom[ch].clu1; ++q) see(clu[q].x);
-			}
-			for (;; ++shift) {
-				unsigned long long total = 0;
-				for (size_t ch = 0; ch < nc; ++ch) if (hi[ch] >= lo[ch]) total += (unsigned long long)(((hi[ch] >> shift) - (lo[ch] >> shift)) + 2);
-				if (total <= (1ull << 22) || shift >= 30) break;
-			}
-			std::vector<uint2> loc;
-			for (size_t ch = 0; ch < nc; ++ch) {
-				RouteChrom &R = chrom[ch];
-				R.loc_first = (unsigned)loc.size();
-				if (hi[ch] < lo[ch]) continue;
-				const long long base = (lo[ch] >> shift) << shift;          // (arithmetic shift: rounds towards minus infinity)
-				const long long nb = ((hi[ch] - base) >> shift) + 1;
-				R.loc_base = (int)base; R.loc_nb = (unsigned)nb;
-				unsigned a = R.cov0, u = R.clu0;
-				for (long long k = 0; k <= nb; ++k) {               // (nb + 1 entries: a bin's upper bounds are the next entry's lower bounds)
-					const long long x = base + (k << shift);
-					while (a < R.cov1 && cov[a].x < x) ++a;
-					while (u < R.clu1 && clu[u].x < x) ++u;
-					loc.push_back(make_uint2(a, u));
-				}
-			}
-			loc.push_back(make_uint2(0, 0)); loc.push_back(make_uint2(0, 0));      // (an entry is read as a pair with its successor)
-			if (cov.empty()) cov.push_back(make_int2(0, 0));
-			if (clu.empty()) clu.push_back(make_int4(0, 0, 0, 0));
-			c->loc_shift = shift;
-			if ((rc = c->loc.upload(loc.data(), loc.size(), c->stream))) return rc;
-			if ((rc = c->route_chrom.upload(chrom.data(), chrom.size(), c->stream))) return rc;
-			if ((rc = c->cov.upload(cov.data(), cov.size(), c->stream))) return rc;
-			if ((rc = c->clu.upload(clu.data(), clu.size(), c->stream))) return rc;
-			HIP_TRY(hipStreamSynchronize(c->stream));          // the host vectors go out of scope
-		}
-		mark("events: loader tables + locator");
-		std::vector<unsigned> bb(E->buckets.size() + 1, 0);
-		for (size_t b = 0; b < E->buckets.size(); ++b) bb[b + 1] = bb[b] + E->buckets[b].n_bins;
-		c->n_fine = bb.back();
-		if ((rc = c->bin_base.upload(bb.data(), bb.size(), c->stream))) return rc;
-		std::vector<unsigned> cb(E->buckets.size() + 1, 0);
-		for (size_t b = 0; b < E->buckets.size(); ++b) cb[b + 1] = cb[b] + (E->buckets[b].kind == 1 ? (E->buckets[b].iso_off & 0xFFFFu) : 0u) + 1u;
-		c->n_cell_groups = cb.back();
-		if ((rc = c->cell_base.upload(cb.data(), cb.size(), c->stream))) return rc;
-		std::vector<unsigned> jb(E->buckets.size() + 1, 0);
-		// the bucket's junction groups, then -- round 3 -- one group per cell (and one for "no cell") for the two-block reads
-		// that cross no junction of the annotation: a quadruple of those shares the cell of its first record too
-		for (size_t b = 0; b <= E->buckets.size(); ++b) jb[b] = E->jg_base[b] + cb[b];
-		c->n_junction_groups = jb.back();
-		const unsigned long long none = 0;
-		if ((rc = c->jg_keys.upload(E->jg_keys.empty() ? &none : (const unsigned long long *)E->jg_keys.data(), std::max<size_t>(E->jg_keys.size(), 1), c->stream))) return rc;
-		if ((rc = c->jg_base.upload(E->jg_base.data(), E->jg_base.size(), c->stream))) return rc;
-		if ((rc = c->jgroup_base.upload(jb.data(), jb.size(), c->stream))) return rc;
-	}
+	return LSQ_OK;
+}
+
+// the host's records of the loader's tables are the device's vector types, field for field
+static_assert(sizeof(CovRec) == sizeof(int2) && offsetof(CovRec, y) == 4, "CovRec is uploaded as int2");
+static_assert(sizeof(LocRec) == sizeof(uint2) && offsetof(LocRec, y) == 4, "LocRec is uploaded as uint2");
+static_assert(sizeof(CluRec) == sizeof(int4) && offsetof(CluRec, y) == 4 && offsetof(CluRec, z) == 8 && offsetof(CluRec, w) == 12, "CluRec is uploaded as int4");
+
+int upload_loader_tables(lsq_ctx *c, const lsq_events &E) {
+	int rc;
+	LoaderTables &L = c->loader;
+	const RouteHostTables T = route_host_tables(E);
+	L.n_chrom_tables = T.n_chrom;
+	L.loc_shift = T.shift;
+	if ((rc = L.loc.upload(reinterpret_cast<const uint2 *>(T.loc.data()), T.loc.size(), c->stream))) return rc;
+	if ((rc = L.route_chrom.upload(T.chrom.data(), T.chrom.size(), c->stream))) return rc;
+	if ((rc = L.cov.upload(reinterpret_cast<const int2 *>(T.cov.data()), T.cov.size(), c->stream))) return rc;
+	if ((rc = L.clu.upload(reinterpret_cast<const int4 *>(T.clu.data()), T.clu.size(), c->stream))) return rc;
+	HIP_TRY(hipStreamSynchronize(c->stream));          // the host vectors go out of scope
+	return LSQ_OK;
+}
+
+int upload_group_bases(lsq_ctx *c, const lsq_events &E) {
+	int rc;
+	LoaderTables &L = c->loader;
+	const GroupBases G = group_bases(E);
+	L.n_fine = G.n_fine;
+	if ((rc = L.bin_base.upload(G.bin_base.data(), G.bin_base.size(), c->stream))) return rc;
+	L.n_cell_groups = G.n_cell_groups;
+	if ((rc = L.cell_base.upload(G.cell_base.data(), G.cell_base.size(), c->stream))) return rc;
+	L.n_junction_groups = G.n_junction_groups;
+	const unsigned long long none = 0;
+	if ((rc = L.jg_keys.upload(E.jg_keys.empty() ? &none : (const unsigned long long *)E.jg_keys.data(), std::max<size_t>(E.jg_keys.size(), 1), c->stream))) return rc;
+	if ((rc = L.jg_base.upload(E.jg_base.data(), E.jg_base.size(), c->stream))) return rc;
+	if ((rc = L.jgroup_base.upload(G.jgroup_base.data(), G.jgroup_base.size(), c->stream))) return rc;
 	if ((rc = upload_strand_ranks(c))) return rc;
 	HIP_TRY(hipStreamSynchronize(c->stream));
-	mark("events: group bases, strand ranks");
+	return LSQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int lsq_events_upload(lsq_ctx *c, lsq_events *E) LSQ_API_TRY {
+	if (!c || !E) return fail(LSQ_E_ARG, "null argument");
+	HIP_TRY(hipSetDevice(c->device));
+	{ int rc = sync_all(c); if (rc) return rc; }        // the buffers below may still be read by a solve in flight
+	if (E->max_lds_bytes > 160 * 1024) return fail(LSQ_E_UNSUPPORTED, "bucket tables exceed the CU's LDS");
+	// what the context knew of the events and reads before
+	c->E = E;
+	c->counted = c->solved = false;
+	c->boot.done = false;
+	c->has_fast = c->has_generic = c->has_host = false;
+	for (const BucketDesc &bd : E->buckets) { if (bd.kind == 1) c->has_fast = true; else if (bd.kind == 0) c->has_generic = true; else c->has_host = true; }
+	for (auto &r : c->reads) r.present = false;
+	int rc;
+	CliClock clock(4);
+	if ((rc = upload_images_em_pack(c, *E))) return rc;
+	clock.mark("events: images, EM order, pack lists");
+	const std::vector<double> G = start_weights(*E);
+	if ((rc = upload_weights_counters_outputs(c, *E, G))) return rc;
+	clock.mark("events: G, counters, EM outputs");
+	if ((rc = upload_loader_tables(c, *E))) return rc;
+	clock.mark("events: loader tables + locator");
+	if ((rc = upload_group_bases(c, *E))) return rc;
+	clock.mark("events: group bases, strand ranks");
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -436,11 +347,11 @@ int lsq_debug_locator(lsq_ctx *c, unsigned *shift, unsigned long long *n_tables,
 	if (!c || !shift || !n_tables || (cap && (!loc_base || !loc_nb))) return fail(LSQ_E_ARG, "bad argument");
 	if (!c->E) return fail(LSQ_E_STATE, "lsq_events_upload must come first");
 	HIP_TRY(hipSetDevice(c->device));
-	*shift = c->loc_shift;
-	*n_tables = c->n_chrom_tables;
-	const size_t n = (size_t)std::min<unsigned long long>(cap, c->n_chrom_tables);
+	*shift = c->loader.loc_shift;
+	*n_tables = c->loader.n_chrom_tables;
+	const size_t n = (size_t)std::min<unsigned long long>(cap, c->loader.n_chrom_tables);
 	std::vector<RouteChrom> chrom(n);
-	if (n) HIP_TRY(hipMemcpy(chrom.data(), c->route_chrom.p, n * sizeof(RouteChrom), hipMemcpyDeviceToHost));
+	if (n) HIP_TRY(hipMemcpy(chrom.data(), c->loader.route_chrom.p, n * sizeof(RouteChrom), hipMemcpyDeviceToHost));
 	for (size_t q = 0; q < n; ++q) { loc_base[q] = chrom[q].loc_base; loc_nb[q] = chrom[q].loc_nb; }
 	return LSQ_OK;
 } LSQ_API_CATCH
@@ -451,8 +362,8 @@ int lsq_count(lsq_ctx *c) LSQ_API_TRY {
 	HIP_TRY(hipSetDevice(c->device));
 	for (int m = 0; m < c->E->n_methods; ++m) if (!c->reads[m].present) return fail(LSQ_E_STATE, "reads of method %d were not uploaded", m);
 #ifdef LSQ_DEV
-	if (const char *e = getenv("LSQ_ABLATE")) c->dev_ablate = (unsigned)atoi(e); else c->dev_ablate = 0;
-	if (const char *e = getenv("LSQ_GRID_MULT")) { const int v = atoi(e); if (v >= 1 && v <= 64) c->opt_grid_mult = v; }
+	if (const char *e = getenv("LSQ_ABLATE")) c->launch.dev_ablate = (unsigned)atoi(e); else c->launch.dev_ablate = 0;
+	if (const char *e = getenv("LSQ_GRID_MULT")) { const int v = atoi(e); if (v >= 1 && v <= 64) c->count_opt.grid_mult = v; }
 #endif
 	int rc = run_count(c);
 	if (rc) return rc;
@@ -473,7 +384,7 @@ int lsq_solve(lsq_ctx *c) LSQ_API_TRY {
 	if (c->has_host && c->counts_external) return fail(LSQ_E_UNSUPPORTED, "genes beyond the kernels' limits are solved from their reads, which counts set from outside do not come with");
 	if (c->has_host && (rc = host_solve(c))) return rc;
 	c->solved = true;
-	c->fim_done = false;
+	c->fim.done = false;
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -484,7 +395,7 @@ int lsq_fim(lsq_ctx *c) LSQ_API_TRY {
 	HIP_TRY(hipSetDevice(c->device));
 	const lsq_events &E = *c->E;
 	const size_t n_ev = E.dev2out.size(), M = (size_t)E.n_methods;
-	if (!c->fim_uploaded) {
+	if (!c->fim.uploaded) {
 		std::vector<uint32_t> sb(n_ev + 1, 0), mb(n_ev + 1, 0);
 		for (size_t d = 0; d < n_ev; ++d) {
 			const lsq::Event &e = E.ev[(size_t)E.dev2out[d]];
@@ -492,25 +403,25 @@ int lsq_fim(lsq_ctx *c) LSQ_API_TRY {
 			sb[d + 1] = sb[d] + (uint32_t)((size_t)e.K * (((size_t)1 << e.K) - 1));
 			mb[d + 1] = mb[d] + (uint32_t)((e.K - 1) * (e.K - 1));
 		}
-		c->fim_starts_total = sb[n_ev]; c->fim_mat_total = mb[n_ev];
-		std::vector<uint32_t> st(std::max<size_t>(M * c->fim_starts_total, 1), 0);
+		c->fim.starts_total = sb[n_ev]; c->fim.mat_total = mb[n_ev];
+		std::vector<uint32_t> st(std::max<size_t>(M * c->fim.starts_total, 1), 0);
 		for (size_t m = 0; m < M; ++m)
 			for (size_t d = 0; d < n_ev; ++d) {
 				const lsq::Event &e = E.ev[(size_t)E.dev2out[d]];
-				std::copy(e.fim_starts[m].begin(), e.fim_starts[m].end(), st.begin() + (ptrdiff_t)(m * c->fim_starts_total + sb[d]));
+				std::copy(e.fim_starts[m].begin(), e.fim_starts[m].end(), st.begin() + (ptrdiff_t)(m * c->fim.starts_total + sb[d]));
 			}
 		int rc;
-		if ((rc = c->fim_start_base.upload(sb.data(), sb.size(), c->stream))) return rc;
-		if ((rc = c->fim_mat_base.upload(mb.data(), mb.size(), c->stream))) return rc;
-		if ((rc = c->fim_starts.upload(st.data(), st.size(), c->stream))) return rc;
-		if ((rc = c->fim.alloc(std::max<size_t>(M * c->fim_mat_total, 1)))) return rc;
-		if ((rc = c->fim_var.alloc(std::max<size_t>(M * n_ev * 2, 1)))) return rc;
+		if ((rc = c->fim.start_base.upload(sb.data(), sb.size(), c->stream))) return rc;
+		if ((rc = c->fim.mat_base.upload(mb.data(), mb.size(), c->stream))) return rc;
+		if ((rc = c->fim.starts.upload(st.data(), st.size(), c->stream))) return rc;
+		if ((rc = c->fim.mat.alloc(std::max<size_t>(M * c->fim.mat_total, 1)))) return rc;
+		if ((rc = c->fim.var.alloc(std::max<size_t>(M * n_ev * 2, 1)))) return rc;
 		HIP_TRY(hipStreamSynchronize(c->stream));
-		c->fim_uploaded = true;
+		c->fim.uploaded = true;
 	}
 	int rc = run_fim(c);
 	if (rc) return rc;
-	c->fim_done = true;
+	c->fim.done = true;
 	return LSQ_OK;
 } LSQ_API_CATCH
 
@@ -531,17 +442,17 @@ int lsq_results_fim_offsets(const lsq_ctx *c, uint64_t *fim_off) LSQ_API_TRY {
 
 int lsq_results_fim(lsq_ctx *c, double *fim, double *var_by_diag, double *var_by_inverse) LSQ_API_TRY {
 	if (!c || !fim || !var_by_diag || !var_by_inverse) return fail(LSQ_E_ARG, "null argument");
-	if (!c->fim_done || !c->solved) return fail(LSQ_E_STATE, "lsq_fim must come first");
+	if (!c->fim.done || !c->solved) return fail(LSQ_E_STATE, "lsq_fim must come first");
 	HIP_TRY(hipSetDevice(c->device));
 	{ int rc = sync_all(c); if (rc) return rc; }
 	const lsq_events &E = *c->E;
 	const size_t n_ev = E.dev2out.size(), n_out = E.ev.size(), M = (size_t)E.n_methods;
-	std::vector<double> hf(std::max<size_t>(M * c->fim_mat_total, 1)), hv(std::max<size_t>(M * n_ev * 2, 1));
+	std::vector<double> hf(std::max<size_t>(M * c->fim.mat_total, 1)), hv(std::max<size_t>(M * n_ev * 2, 1));
 	std::vector<uint32_t> mb(n_ev + 1, 0);
 	if (n_ev) {
-		HIP_TRY(hipMemcpy(hf.data(), c->fim.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(hv.data(), c->fim_var.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost));
-		HIP_TRY(hipMemcpy(mb.data(), c->fim_mat_base.p, mb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(hf.data(), c->fim.mat.p, hf.size() * sizeof(double), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(hv.data(), c->fim.var.p, hv.size() * sizeof(double), hipMemcpyDeviceToHost));
+		HIP_TRY(hipMemcpy(mb.data(), c->fim.mat_base.p, mb.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
 	}
 	std::vector<uint64_t> off(n_out + 1);
 	lsq_results_fim_offsets(c, off.data());
@@ -552,7 +463,7 @@ int lsq_results_fim(lsq_ctx *c, double *fim, double *var_by_diag, double *var_by
 		const size_t o = (size_t)E.dev2out[d];
 		const size_t nn = (size_t)(E.ev[o].K - 1) * (size_t)(E.ev[o].K - 1);
 		for (size_t m = 0; m < M; ++m) {
-			for (size_t i = 0; i < nn; ++i) fim[m * total + off[o] + i] = hf[m * c->fim_mat_total + mb[d] + i];
+			for (size_t i = 0; i < nn; ++i) fim[m * total + off[o] + i] = hf[m * c->fim.mat_total + mb[d] + i];
 			var_by_diag[m * n_out + o] = hv[(m * n_ev + d) * 2];
 			var_by_inverse[m * n_out + o] = hv[(m * n_ev + d) * 2 + 1];
 		}
@@ -911,22 +822,22 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 	const std::string n(name);
 	if (n == "grid_multiplier") {
 		if (!(value >= 0 && value <= 64)) return fail(LSQ_E_ARG, "grid_multiplier must lie in 0..64 (0 = automatic)");
-		c->opt_grid_mult = value;
+		c->count_opt.grid_mult = value;
 		for (auto &r : c->reads) r.wg_grid = 0;
 	} else if (n == "exception_capacity") {
 		if (!(value >= 0 && value <= 4e9)) return fail(LSQ_E_ARG, "exception_capacity must lie in 0..4e9 (0 = automatic)");
 		c->opt_exc_cap = (size_t)value;          // takes effect with the next upload of a read set
 	} else if (n == "snap_shares") {
-		c->opt_snap_shares = value != 0;
+		c->count_opt.share.snap = value != 0;
 		for (auto &r : c->reads) r.wg_grid = 0;
 	} else if (n == "share_weighted" || n == "share_cost_two_block" || n == "share_cost_parked" || n == "share_cost_visit" || n == "share_taper" || n == "share_cost_hot") {
 		if (!(value >= 0 && value <= 1e6)) return fail(LSQ_E_ARG, "%s must lie in 0..1e6", name);
-		if (n == "share_weighted") c->opt_share_weighted = value != 0;
-		else if (n == "share_cost_two_block") c->opt_share_cost_p2 = value;
-		else if (n == "share_cost_parked") c->opt_share_cost_park = value;
-		else if (n == "share_cost_visit") c->opt_share_cost_visit = value;
-		else if (n == "share_cost_hot") c->opt_share_cost_hot = value;
-		else c->opt_share_taper = value;
+		if (n == "share_weighted") c->count_opt.share.weighted = value != 0;
+		else if (n == "share_cost_two_block") c->count_opt.share.two_block = value;
+		else if (n == "share_cost_parked") c->count_opt.share.walk_look = value;
+		else if (n == "share_cost_visit") c->count_opt.share.visit = value;
+		else if (n == "share_cost_hot") c->count_opt.share.hot = value;
+		else c->count_opt.share.taper = value;
 		for (auto &r : c->reads) r.wg_grid = 0;
 	} else if (n == "sam_skip_flags") {
 		if (!(value >= 0 && value <= 65535)) return fail(LSQ_E_ARG, "sam_skip_flags must lie in 0..65535");
@@ -941,14 +852,14 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 		c->opt_compact_pools = value != 0;        // takes effect with the next upload of a read set
 	} else if (n == "workgroups_per_cu") {
 		if (!(value >= -1 && value <= 32)) return fail(LSQ_E_ARG, "workgroups_per_cu must lie in -1..32 (-1 = automatic, 0 = as many as fit)");
-		c->opt_wg_per_cu = (int)value;
-		c->occ_lds_bytes = 0;          // the occupancy is asked again
+		c->count_opt.wg_per_cu = (int)value;
+		c->launch.occ_lds_bytes = 0;          // the occupancy is asked again
 	} else if (n == "reads_per_look") {
 		if (!(value == 0 || value == 4 || value == 8)) return fail(LSQ_E_ARG, "reads_per_look must be 0 (automatic), 4 or 8");
-		c->opt_reads_per_look = (int)value;
+		c->count_opt.reads_per_look = (int)value;
 	} else if (n == "count_streams") {
 		{ int rc = sync_all(c); if (rc) return rc; }
-		c->opt_two_count_streams = value >= 2;
+		c->count_opt.two_count_streams = value >= 2;
 	} else if (n == "counter_sets") {
 		// (the rotation of run_count; every set but the latest count's is zero at any time, so either number may follow the other --
 		// but only between steps: a count in flight has its successor's set and mark chosen by the number it was submitted under)
@@ -960,7 +871,7 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 			if (e == hipErrorNotReady) return fail(LSQ_E_STATE, "counter_sets may only be set while nothing is in flight (lsq_ctx_synchronize first)");
 			if (e != hipSuccess) return fail(LSQ_E_DEVICE, "hipStreamQuery: %s", hipGetErrorString(e));
 		}
-		c->opt_counter_sets = (int)value;
+		c->count_opt.counter_sets = (int)value;
 	} else if (n == "em_flat_min_events") {
 		if (!(value >= 0 && value <= 4e9)) return fail(LSQ_E_ARG, "em_flat_min_events must lie in 0..4e9");
 		c->em.opt_flat_min = (unsigned)value;
@@ -977,10 +888,10 @@ int lsq_ctx_set_option(lsq_ctx *c, const char *name, double value) LSQ_API_TRY {
 		c->em.opt_regroup = value != 0;
 		for (EmLane &l : c->em.lane) l.order_valid = false;
 	} else if (n == "recount_every_read") {
-		c->opt_recount = value != 0;
+		c->count_opt.recount = value != 0;
 	} else if (n == "cleanup_workgroups") {
 		if (value < 0 || value > 4096) return fail(LSQ_E_ARG, "cleanup_workgroups out of range");
-		c->opt_cleanup_grid = (unsigned)value;
+		c->count_opt.cleanup_grid = (unsigned)value;
 	} else if (n == "em_guard_band") {
 		return lsq_set_em_guard_band(c, value);
 	} else
@@ -1000,7 +911,7 @@ int lsq_last_fast_kernel_ms(lsq_ctx *c, float *ms) LSQ_API_TRY {
 	HIP_TRY(hipSetDevice(c->device));
 	{ int rc = sync_all(c); if (rc) return rc; }
 	*ms = 0;
-	for (int m = 0; m < LSQ_MAX_METHODS; ++m) if (c->fast_launched >> m & 1) { float t = 0; HIP_TRY(hipEventElapsedTime(&t, c->evf0[m], c->evf1[m])); *ms += t; }
+	for (int m = 0; m < LSQ_MAX_METHODS; ++m) if (c->launch.fast_launched >> m & 1) { float t = 0; HIP_TRY(hipEventElapsedTime(&t, c->evf0[m], c->evf1[m])); *ms += t; }
 	return LSQ_OK;
 } LSQ_API_CATCH
 

@@ -38,7 +38,6 @@ constexpr unsigned P1_GROUP_PAD = LSQ_P1_PAD;      // records a cell's group of 
 constexpr int LSQ_INGEST_STAGES = 7;     // newline count, route, partition count, partition scatter, group classify, group offsets, group place
 constexpr int LSQ_INGEST_PASS_MAX = 16;  // ... and room for the passes a read file clocks ahead of its route (a BAM file: inflate, CRC32s, record starts)
 constexpr int LSQ_COUNTER_SETS = 3;  // counter sets a context holds (lsq_ctx::set)
-constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
 
 namespace lsq {
 
@@ -129,15 +128,6 @@ inline unsigned grid_for(int n_cu, unsigned long long items, unsigned per_block,
 	const unsigned long long want = (items + per_block - 1) / per_block, cap = (unsigned long long)n_cu * per_cu;
 	return (unsigned)std::max<unsigned long long>(1, std::min(want, cap));
 }
-
-// what the loader's routing pass knows about one chromosome: its stretch of the locator grid, of the covered regions and of the clusters
-struct RouteChrom {
-	unsigned loc_first, loc_nb;              // its bins of the grid
-	int loc_base;                            // first base of bin 0
-	unsigned cov0, cov1, clu0, clu1;
-	unsigned pad;
-};
-static_assert(sizeof(RouteChrom) == 32, "RouteChrom is staged in LDS as two 16-byte words");
 
 // What a workgroup of the count kernel needs to know about one visit to a bucket, in one 128-byte record per (read file,
 // bucket), written once per read set (ingest): the bucket's description, where its slots and its one- and two-block
@@ -268,6 +258,79 @@ struct BootState {
 	bool timed = false;
 };
 
+// The loader's tables of a context, as lsq_events_upload made them (written in lsq_device.hip, read by lsq_ingest.hip: route_tables and
+// the ingest chain).  Per table id a RouteChrom; the covered regions as (start, end) pairs; the clusters (spans of the planned
+// events) as (start, end, bucket, bucket's first base), cut at the bucket cuts; and the locator grid over both (lsq_upload_tables.hpp
+// says how each is made)
+struct LoaderTables {
+	lsq::DevBuf<lsq::RouteChrom> route_chrom;
+	lsq::DevBuf<int2> cov;
+	lsq::DevBuf<int4> clu;
+	lsq::DevBuf<uint2> loc;
+	unsigned loc_shift = 10;
+	unsigned n_chrom_tables = 0;
+	lsq::DevBuf<unsigned> bin_base;        // per bucket: first of its bins among all bins (n_buckets + 1)
+	size_t n_fine = 0;
+	// The one-block pool is laid out by cell (lsq_internal.hpp: Cell), not by bin: per bucket its cells in order and one more
+	// group for the reads that start in no cell, every group padded to eight records (P1_GROUP_PAD) -- a lane of the count kernel takes four or eight
+	// neighbouring records and decides them against one cell.  cell_base: per bucket the first of its groups (n_buckets + 1).
+	lsq::DevBuf<unsigned> cell_base;
+	size_t n_cell_groups = 0;
+	// The two-block pool is laid out by junction group (lsq_events::jg_keys), every group padded to four records, and per
+	// bucket one more group for the reads that cross no known junction.  jgroup_base: per bucket the first of its groups.
+	lsq::DevBuf<unsigned long long> jg_keys;
+	lsq::DevBuf<unsigned> jg_base, jgroup_base;
+	size_t n_junction_groups = 0;
+};
+
+// lsq_fim (fim.h / linalg.h) of a context (lsq_device.hip: lsq_fim and its results; lsq_em.hip: run_fim): per device event the offset
+// of its accessible-start class counts and of its (K-1) x (K-1) matrix; counts per method; results
+struct FimState {
+	lsq::DevBuf<uint32_t> start_base, mat_base, starts;
+	lsq::DevBuf<double> mat, var;
+	size_t starts_total = 0, mat_total = 0;
+	bool uploaded = false, done = false;
+};
+
+// The costs of a count launch's share plan (lsq_count.hip: plan_share_cuts_seg says what each weighs).  The defaults here are
+// those of a bare plan, which lsq_debug_plan_shares fills from its arguments; a context's are CountOptions::share, below.
+struct SharePlanCosts { bool weighted = true, snap = true; double two_block = 4.3, walk_look = 9.0, visit = 7000.0, taper = 0.5, hot = 0.0; };
+
+// What lsq_ctx_set_option keeps for run_count alone (lsq_count.hip; "recount_every_read" is also read where an overflow is reported)
+struct CountOptions {
+	// "count_streams": a lane's counts run on a stream of the lane's own (lsq_ctx::stream_count2); 1: every count on `stream`, one after the other
+	bool two_count_streams = true;
+	int wg_per_cu = -1;                     // "workgroups_per_cu": resident workgroups of the count kernel per compute unit
+	int counter_sets = LSQ_COUNTER_SETS;    // "counter_sets": 2 or 3 (set only while nothing is in flight)
+	int reads_per_look = 0;                 // "reads_per_look": 0 = by the launch, 4, 8
+	double grid_mult = 0;                   // "grid_multiplier" (fractions allowed; 0 = by the read set's skew)
+	bool recount = false;                   // "recount_every_read": recount every read with the one-lane-per-read kernel (self-check)
+	unsigned cleanup_grid = 0;              // "cleanup_workgroups": workgroups of the exception pass (0: one a compute unit)
+	// "share_weighted" (the shares equal in cost, not in reads), "snap_shares" (cut on bucket boundaries where one is near),
+	// "share_cost_two_block" (a two-block record, in one-block records), "share_cost_parked" (one look of the general walk at a
+	// parked read), "share_cost_visit" (staging + flush of a bucket), "share_taper" (the last share of the grid as a fraction of the
+	// first; 0 = automatic, run_count's rule), "share_cost_hot" (extra cost a record of a group of 8 192 records or more)
+	// A context's defaults differ from a bare plan's in two costs, and these are the two:
+	SharePlanCosts share;
+	CountOptions() {
+		share.taper = 0.0;                  // 0 = automatic (0.25 or 0.5 by the read set's skew), where a bare plan has 0.5
+		share.hot = 0.5;                    // where a bare plan has none
+	}
+};
+
+// What run_count keeps between launches and reports of the latest one (lsq_count.hip; lsq_device.hip reads fast_launched for
+// lsq_last_fast_kernel_ms, drops the occupancy answer with "workgroups_per_cu" and sets dev_ablate in the developer build)
+struct CountLaunch {
+	unsigned occ_lds_bytes = 0; int occ_p1w = 0, occ_blocks = 0;      // the runtime's occupancy answer for the fast kernel at that LDS size
+	unsigned last_reads_per_look = 4, last_wg_per_cu = 0;       // what the latest lsq_count ran with
+	int fast_launched = 0;                  // bit m: read file m's streaming kernel ran (evf0 / evf1 bracket it)
+	lsq::DevBuf<unsigned char> recount_args;      // the recount kernels' argument records, and the host's copy of what was last written
+	std::vector<unsigned char> recount_args_host;
+	lsq::DevBuf<unsigned long long> wg_trace;     // developer build (LSQ_ABLATE 4194304): lsq_debug_wg_trace
+	unsigned long long wg_trace_n = 0, wg_trace_workers = 0;
+	unsigned dev_ablate = 0;                // developer build only (LSQ_ABLATE)
+};
+
 struct lsq_ctx {
 	// lsq_ctx_create_with(LSQ_CTX_LANES_IN_BACKGROUND): the helper thread that makes the lanes' streams and events, and how it ended
 	std::thread lanes_thread;
@@ -293,27 +356,21 @@ struct lsq_ctx {
 	// what they read, so the next count's workgroups may fill the compute units the tail of this one leaves idle, and no
 	// dispatch waits for the kernel before it (option "count_streams" 1: every count on `stream`, one after the other).
 	hipStream_t stream_count2[2] = {nullptr, nullptr};
-	bool opt_two_count_streams = true;
-	int opt_wg_per_cu = -1;                 // "workgroups_per_cu": resident workgroups of the count kernel per compute unit (lsq_count.hip)
 	// LANE and COUNTER SET are two things.  The lanes stay two -- streams, ev_counted2, the EM's outputs -- and consecutive
 	// counts take them in turn.  The counter sets (counters, exception lists, the exception pass's argument records, ev_mark2) are
-	// LSQ_COUNTER_SETS, of which counts take the first `opt_counter_sets` in turn: with three, count k+1 waits for the readers of step k-2
+	// LSQ_COUNTER_SETS, of which counts take the first `count_opt.counter_sets` in turn: with three, count k+1 waits for the readers of step k-2
 	// and not for those of step k-1, whose chain (exception pass, EM, hand-off, zeroing) otherwise stands between two counts of a lane.
 	// Every set but the latest count's is zero or has its zeroing queued, its mark recorded behind that: whichever comes next may be taken.
 	hipEvent_t ev_counted2[2] = {nullptr, nullptr}, ev_mark2[LSQ_COUNTER_SETS] = {};
 	bool mark_recorded2[LSQ_COUNTER_SETS] = {};
 	int lane = 0;                           // lane of the latest count
 	int set = 0;                            // counter set of the latest count
-	int opt_counter_sets = LSQ_COUNTER_SETS;      // "counter_sets": 2 or 3 (set only while nothing is in flight)
 	size_t counters_per_set = 0;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr, ev3 = nullptr;
 	hipEvent_t evt0 = nullptr, evt1 = nullptr;      // around a text copy (lsq_text_stage may run beside other host work)
 	hipEvent_t evf0[LSQ_MAX_METHODS] = {}, evf1[LSQ_MAX_METHODS] = {};   // around each method's lsq_count_fast_kernel launch
-	int fast_launched = 0;
-	int occ_p1w = 0;
-	int opt_reads_per_look = 0;             // "reads_per_look": 0 = by the launch (lsq_count.hip), 4, 8
-	unsigned last_reads_per_look = 4, last_wg_per_cu = 0;       // what the latest lsq_count ran with
-	unsigned occ_lds_bytes = 0; int occ_blocks = 0;      // the runtime's occupancy answer for the fast kernel at that LDS size
+	CountOptions count_opt;
+	CountLaunch launch;
 	bool time_events = false;               // lsq_set_timing: event records around the kernels cost ~4 us each in the queue
 	bool count_timed = false, solve_timed = false;      // the last lsq_count / lsq_solve ran with them
 	lsq_events *E = nullptr;                // must outlive the uploads made from it (its strand dictionary grows with the reads)
@@ -331,57 +388,14 @@ struct lsq_ctx {
 	DevView<double> theta, logll;           // the latest count's lane
 	DevView<uint32_t> iters;
 	DevView<uint8_t> flags;
-	// lsq_fim (fim.h / linalg.h): per device event the offset of its accessible-start class counts and of its
-	// (K-1) x (K-1) matrix; counts per method; results
-	DevBuf<uint32_t> fim_start_base, fim_mat_base, fim_starts;
-	DevBuf<double> fim, fim_var;
-	size_t fim_starts_total = 0, fim_mat_total = 0;
-	bool fim_uploaded = false, fim_done = false;
+	FimState fim;
 	DevBuf<unsigned long long> counters;   // LSQ_COUNTER_SETS sets of cnt | bases | exc_count | dbg (one memset per count); the views below are the latest count's
 	DevView<unsigned long long> cnt, bases, dbg;
-	DevBuf<unsigned long long> wg_trace;   // developer build (LSQ_ABLATE 4194304): lsq_debug_wg_trace
-	unsigned long long wg_trace_n = 0, wg_trace_workers = 0;
 	DevView<unsigned> exc_count;           // per method: [2m] appended, [2m+1] overflow flag
-	// ingest tables (round 4 form): per chromosome id a RouteChrom; the covered regions as (start, end) pairs; the clusters (spans of
-	// the planned events) as (start, end, bucket, bucket's first base), cut at the bucket cuts; and the locator grid over both:
-	// per chromosome bins of 2^loc_shift bases, entry k = lower bounds of the bin's first base among the covered starts (.x) and
-	// the cluster starts (.y); entries k and k + 1, one 16-byte load, bound a search to a handful of neighbouring records
-	DevBuf<RouteChrom> route_chrom;
-	DevBuf<int2> cov;
-	DevBuf<int4> clu;
-	DevBuf<uint2> loc;
-	unsigned loc_shift = 10;
-	DevBuf<unsigned> bin_base;             // per bucket: first of its bins among all bins (n_buckets + 1)
-	size_t n_fine = 0;
-	// The one-block pool is laid out by cell (lsq_internal.hpp: Cell), not by bin: per bucket its cells in order and one more
-	// group for the reads that start in no cell, every group padded to eight records (P1_GROUP_PAD) -- a lane of the count kernel takes four or eight
-	// neighbouring records and decides them against one cell.  cell_base: per bucket the first of its groups (n_buckets + 1).
-	DevBuf<unsigned> cell_base;
-	size_t n_cell_groups = 0;
-	// The two-block pool is laid out by junction group (lsq_events::jg_keys), every group padded to four records, and per
-	// bucket one more group for the reads that cross no known junction.  jgroup_base: per bucket the first of its groups.
-	DevBuf<unsigned long long> jg_keys;
-	DevBuf<unsigned> jg_base, jgroup_base;
-	size_t n_junction_groups = 0;
-	unsigned n_chrom_tables = 0;
-	// lsq_ctx_set_option: grid multiplier (0 = by the read set's skew), entries of a method's exception list
-	// (0 = a quarter of its reads, at least 64 Ki), recount every read with the one-lane-per-read kernel (self-check)
-	double opt_grid_mult = 0;               // "grid_multiplier" (fractions allowed)
-	size_t opt_exc_cap = 0;
+	LoaderTables loader;
+	size_t opt_exc_cap = 0;                 // "exception_capacity": entries of a method's exception list (0 = a quarter of its reads, at least 64 Ki)
 	bool opt_compact_pools = true;          // "compact_pools": 0 keeps wide pool records whatever the reads look like
-	bool opt_recount = false;
-	unsigned opt_cleanup_grid = 0;          // "cleanup_workgroups": workgroups of the exception pass (0: one a compute unit)
 	bool overflow_logged[LSQ_MAX_METHODS] = {};      // the warning about an overflowed exception list has been written for the latest count
-	bool opt_snap_shares = true;            // workgroup shares cut on bucket boundaries where one is near
-	bool opt_share_weighted = true;         // "share_weighted": the shares equal in cost, not in reads (run_count's plan)
-	double opt_share_cost_p2 = 4.3;         // "share_cost_two_block": a two-block record, in one-block records
-	double opt_share_cost_park = 9.0;       // "share_cost_parked": one look of the general walk at a parked read
-	double opt_share_cost_visit = 7000.0;   // "share_cost_visit": staging + flush of a bucket
-	double opt_share_cost_hot = 0.5;        // "share_cost_hot": extra cost a record of a group of 8 192 records or more
-	double opt_share_taper = 0;             // "share_taper": the last share of the grid as a fraction of the first (0 = automatic)
-	unsigned dev_ablate = 0;                // developer build only (LSQ_ABLATE)
-	DevBuf<unsigned char> recount_args;     // the recount kernels' argument records (lsq_count.hip), and the host's copy of what was last written
-	std::vector<unsigned char> recount_args_host;
 	MethodReads reads[LSQ_MAX_METHODS];
 	bool counted = false, solved = false;
 	bool counts_external = false;           // lsq_results_set_counts: the counts are sums the reads here do not explain

@@ -888,9 +888,9 @@ int run_fim(lsq_ctx *c) {
 	if (!n_ev) return LSQ_OK;
 	FimArgs A{};
 	A.n_events = n_ev; A.n_methods = (unsigned)E.n_methods; A.n_iso = E.n_iso_total;
-	A.K = c->dK.p; A.iso_base = c->iso_base.p; A.start_base = c->fim_start_base.p; A.mat_base = c->fim_mat_base.p;
-	A.starts = c->fim_starts.p; A.starts_total = c->fim_starts_total; A.mat_total = c->fim_mat_total;
-	A.theta = c->theta.p; A.G = c->G.p; A.fim = c->fim.p; A.var = c->fim_var.p;
+	A.K = c->dK.p; A.iso_base = c->iso_base.p; A.start_base = c->fim.start_base.p; A.mat_base = c->fim.mat_base.p;
+	A.starts = c->fim.starts.p; A.starts_total = c->fim.starts_total; A.mat_total = c->fim.mat_total;
+	A.theta = c->theta.p; A.G = c->G.p; A.fim = c->fim.mat.p; A.var = c->fim.var.p;
 	const unsigned n = n_ev * (unsigned)E.n_methods;
 	hipLaunchKernelGGL(lsq_fim_kernel, dim3((n + 63) / 64), dim3(64), 0, c->stream_em, A);      // behind the solve
 	HIP_TRY(hipGetLastError());

@@ -491,7 +491,7 @@ unsigned lsq::route_lib(const lsq_ctx *c) {
 }
 RouteTables lsq::route_tables(lsq_ctx *c) {
 	RouteTables T{};
-	T.chrom = c->route_chrom.p; T.cov = c->cov.p; T.clu = c->clu.p; T.loc = c->loc.p; T.loc_shift = c->loc_shift; T.n_chrom = c->n_chrom_tables;
+	T.chrom = c->loader.route_chrom.p; T.cov = c->loader.cov.p; T.clu = c->loader.clu.p; T.loc = c->loader.loc.p; T.loc_shift = c->loader.loc_shift; T.n_chrom = c->loader.n_chrom_tables;
 	return T;
 }
 
@@ -513,8 +513,8 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	HIP_TRY(hipStreamSynchronize(c->stream_em2[1]));
 	HIP_TRY(hipStreamSynchronize(c->stream_count2[0]));      // ... and a count of an earlier read set on a lane's count stream
 	HIP_TRY(hipStreamSynchronize(c->stream_count2[1]));
-	const size_t FC = c->n_cell_groups;          // one-block groups of all buckets
-	const size_t FJ = c->n_junction_groups;      // two-block groups of all buckets
+	const size_t FC = c->loader.n_cell_groups;          // one-block groups of all buckets
+	const size_t FJ = c->loader.n_junction_groups;      // two-block groups of all buckets
 	// counters, one allocation (zeroed per attempt): part_cnt[2B] | part_cur[2B] | piece_cnt[2B] | cntn[B] | cntnb[B] | curn[B] | curnb[B] |
 	// cnt1[FC] | cnt2[FJ] | cur1[FC] | cur2[FJ] | park1[FC] | park2[FJ]
 	const size_t n_cnt = 10 * (size_t)B + 3 * (FC + FJ);
@@ -638,7 +638,7 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	if (n_pieces) {
 		StageClock k(c, st, "group_classify");
 		GroupTables GT{};
-		GT.buckets = c->buckets.p; GT.images = c->images.p; GT.cell_base = c->cell_base.p; GT.jg_keys = c->jg_keys.p; GT.jg_base = c->jg_base.p; GT.jgroup_base = c->jgroup_base.p;
+		GT.buckets = c->buckets.p; GT.images = c->images.p; GT.cell_base = c->loader.cell_base.p; GT.jg_keys = c->loader.jg_keys.p; GT.jg_base = c->loader.jg_base.p; GT.jgroup_base = c->loader.jgroup_base.p;
 		GT.B = B; GT.lds_img = (unsigned)img_max; GT.lds_keys = (unsigned)keys_lds;
 		hipLaunchKernelGGL(lsq_group_classify_kernel, dim3((unsigned)n_pieces), dim3(256), group_lds, st, GT, GA);
 		HIP_TRY(hipGetLastError());
@@ -648,7 +648,7 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 	{
 		StageClock k(c, st, "group_offsets");
 		if ((rc = device_scan<P1_GROUP_PAD>(SS, cnt1, FC, d_off1.p, st)) || (rc = device_scan<P2_GROUP_PAD>(SS, cnt2, FJ, d_off2.p, st))) return rc;      // groups padded to eight records, and to four
-		hipLaunchKernelGGL(lsq_ingest_offsets_kernel, dim3(B / 256 + 1), dim3(256), 0, st, c->cell_base.p, c->jgroup_base.p, B, d_off1.p, d_off2.p, mr.pn_off.p,
+		hipLaunchKernelGGL(lsq_ingest_offsets_kernel, dim3(B / 256 + 1), dim3(256), 0, st, c->loader.cell_base.p, c->loader.jgroup_base.p, B, d_off1.p, d_off2.p, mr.pn_off.p,
 		                   mr.p1_off.p, mr.p2_off.p, mr.slot_off.p);
 		HIP_TRY(hipGetLastError());
 		k.end(12ull * (FC + FJ));
@@ -674,13 +674,13 @@ int lsq::ingest_device(lsq_ctx *c, int method, Front &F) {
 			PlaceArgs P{};
 			P.pieces = d_pieces.p; P.part_off1 = d_part_off1.p; P.part_off2 = d_part_off2.p; P.part1 = d_part1.p; P.part2 = d_part2.p;
 			P.fine1 = d_fine1.p; P.fine2 = d_fine2.p; P.off1 = d_off1.p; P.off2 = d_off2.p; P.cur1 = cur1; P.cur2 = cur2;
-			P.buckets = c->buckets.p; P.cell_base = c->cell_base.p; P.jg_base = c->jg_base.p; P.jgroup_base = c->jgroup_base.p; P.B = B; P.compact = compact;
+			P.buckets = c->buckets.p; P.cell_base = c->loader.cell_base.p; P.jg_base = c->loader.jg_base.p; P.jgroup_base = c->loader.jgroup_base.p; P.B = B; P.compact = compact;
 			P.p1 = mr.p1.p; P.p1_strand = mr.p1_strand.p; P.p1_line = mr.p1_line.p; P.p2 = mr.p2.p; P.p2_strand = mr.p2_strand.p; P.p2_line = mr.p2_line.p;
 			hipLaunchKernelGGL(lsq_group_place_kernel, dim3((unsigned)n_pieces), dim3(256), place_lds, st, P);
 		}
 		if (FC + FJ) {
 			const unsigned pgrid = (unsigned)std::min<size_t>((FC + FJ) / 256 + 1, (size_t)c->n_cu * 8);
-			hipLaunchKernelGGL(lsq_ingest_pad_kernel, dim3(pgrid), dim3(256), 0, st, c->buckets.p, c->cell_base.p, c->jgroup_base.p, B, (unsigned)FC, (unsigned)FJ,
+			hipLaunchKernelGGL(lsq_ingest_pad_kernel, dim3(pgrid), dim3(256), 0, st, c->buckets.p, c->loader.cell_base.p, c->loader.jgroup_base.p, B, (unsigned)FC, (unsigned)FJ,
 			                   (const unsigned *)cnt1, (const unsigned long long *)d_off1.p, (const unsigned *)cnt2, (const unsigned long long *)d_off2.p, c->images.p,
 			                   (void *)mr.p1.p, (void *)mr.p2.p, compact, mr.p1_strand.p, mr.p1_line.p, mr.p2_strand.p, mr.p2_line.p);
 		}

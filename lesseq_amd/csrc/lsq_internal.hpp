@@ -215,6 +215,17 @@ struct TieRec {            // global memory, device event order; read only on st
 };
 static_assert(sizeof(TieRec) == 24, "TieRec layout");
 
+// what the loader's routing pass knows about one chromosome: its stretch of the locator grid, of the covered regions and of the clusters
+struct RouteChrom {
+	unsigned loc_first, loc_nb;              // its bins of the grid
+	int loc_base;                            // first base of bin 0
+	unsigned cov0, cov1, clu0, clu1;
+	unsigned pad;
+};
+static_assert(sizeof(RouteChrom) == 32, "RouteChrom is staged in LDS as two 16-byte words");
+
+constexpr int EM_LANES = 4;          // lanes that share one event in the EM kernel (and one place of its grid)
+
 struct Dict {              // string interning (chromosomes, strands)
 	std::vector<std::string> names;
 	std::unordered_map<std::string, int> ids;
