@@ -575,7 +575,7 @@ void lsq_free(void *p);
 
 /* Whole executables in-process: argv as the reference's (argv[0] ignored).  tool is
  * "count", "solve", "classify", "test_as" (bin/Test_AS.r; lsq_as_* below), "events" (bin/Events.r; lsq_le_*), "parseGencode" or
- * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*), "sites" (lsq_ss_*), "retention" (lsq_ir_*) or "libtype" (lsq_lt_*).  stdout text is returned in *out_text (malloc'd), the
+ * "gencodeIsoformMap" (lsq_gtf_*; one optional argument names a file to read instead of standard input), "sam2mrf", "bam2mrf", "bamcheck", "junctions" (lsq_jn_*), "coverage" (lsq_cov_*), "exonbins" (lsq_xb_*), "psi" (lsq_ps_*), "evidence" (lsq_fe_*), "sites" (lsq_ss_*), "retention" (lsq_ir_*), "clusters" (lsq_cl_*) or "libtype" (lsq_lt_*).  stdout text is returned in *out_text (malloc'd), the
  * return value is the process exit status the reference would give (0, 1). */
 int lsq_cli_run(const char *tool, int argc, const char *const *argv, char **out_text);
 /* The same for an executable's main(): writes the table to stdout itself and returns the exit status.  A successful
@@ -816,6 +816,78 @@ int lsq_ir_table_report(const lsq_ir_table *t, uint64_t report[13]);
 int lsq_ir_table_times(const lsq_ir_table *t, float ms[5]);
 /* The text of all rows; malloc'd, NUL-terminated (lsq_free). */
 int lsq_ir_format(const lsq_ir_table *t, int ratios, char **out_text);
+
+/* ------------------------------------------------------------------------------------
+ * Intron clusters of several read files: the junctions of all samples pooled, introns that share a splice site
+ * joined into clusters, a count table per sample with the same rows in every one -- LeafCutter's clustering, applied once; the
+ * rows `test_as lrt --tables` and `test_as betabin --tables` read
+ * ------------------------------------------------------------------------------------ */
+
+/* The definition.  A sample is the rows of one junction table (lsq_jn_*: chromosome index, start, end, reads; 0-based half-open),
+ * all samples under one index.
+ *   pooled introns the distinct (chromosome, start, end) over all samples.  r_k(j): the reads of intron j in sample k (rows of one
+ *                  sample with one intron add up; 0 without a row), reads(j) their sum over k in 64 bits, samples(j) the number of
+ *                  k with r_k(j) > 0, ann from the index as lsq_jn_* gives it.
+ *   row filters    long: max_intron != 0 and end - start > max_intron.  weak: reads(j) < min_reads.  A row that is both is long.
+ *                  The others are kept.
+ *   links          two kept rows on one chromosome with the same start, or with the same end.  A start equal to another row's
+ *                  end, and equal coordinates on two chromosomes, are no link; strand plays no part.
+ *   clusters       the connected components of the kept rows.  One row: a singleton.  Two or more whose reads sum below
+ *                  min_cluster_reads: weak.  The others are printed, numbered 1, 2, ... by the table order of their first row.
+ *   status         per distinct intron: 0 printed, 1 weak row, 2 long row, 3 singleton, 4 weak cluster; cluster: its number, 0
+ *                  unless status is 0.
+ *   rows           every distinct intron, ascending in chromosome name (bytewise), start, end.  counts: [rows][samples], r_k(j).
+ *   text           the printed rows by (cluster number, table order).  lsq_cl_format: clu_<n> TAB chrom TAB start+1 TAB end TAB ann
+ *                  TAB reads TAB samples NL.  lsq_cl_format_sample (sample: 0-based, the order the samples were added in): clu_<n>
+ *                  TAB total TAB chrom:start+1:end TAB r_k(j) NL, total the sum of r_k over the cluster's rows -- the four columns of
+ *                  a count table of one read file; the same rows for every sample, zeros included.  No header.
+ *   report         eleven: samples, pooled input rows, distinct introns, long rows, weak rows, kept rows, components, singletons,
+ *                  weak clusters, printed clusters, printed rows.
+ * Limits: 65 535 samples, 2^32-1 pooled rows, 2^32-1 for the sum of one sample's reads, rows x samples at most 2^31.  Beyond a
+ * limit: LSQ_E_RANGE. */
+typedef struct lsq_cl_pool lsq_cl_pool;         /* the samples' rows, and the chromosomes and introns of the index it was made from (copied) */
+typedef struct lsq_cl_table lsq_cl_table;
+int lsq_cl_pool_create(const lsq_jn_index *ix, lsq_cl_pool **out);
+void lsq_cl_pool_free(lsq_cl_pool *p);
+int64_t lsq_cl_pool_samples(const lsq_cl_pool *p);
+int64_t lsq_cl_pool_rows(const lsq_cl_pool *p);      /* pooled input rows */
+/* One more sample; a call that fails adds nothing.  lsq_cl_pool_add_table: the rows of a junction table of the same index
+ * (LSQ_E_ARG for another dictionary of chromosomes).  lsq_cl_pool_add_rows: from arrays -- LSQ_E_ARG for a chromosome that is no
+ * index of the dictionary or a row with start >= end, LSQ_E_RANGE for a coordinate outside (-2^30, 2^30); n may be 0.
+ * lsq_cl_pool_add_text: a file as lsq_jn_format printed it (any min_reads, novel or not); the chromosome is looked up by name and
+ * ann is not taken from the file -- LSQ_E_IO for a file that does not open, LSQ_E_PARSE with "<path>: #<line>:<text>" for a name
+ * the index lacks or a line that is not eight columns of the right kinds. */
+int lsq_cl_pool_add_table(lsq_cl_pool *p, const lsq_jn_table *t);
+int lsq_cl_pool_add_rows(lsq_cl_pool *p, uint64_t n, const uint32_t *chrom, const int32_t *start, const int32_t *end, const uint32_t *reads);
+int lsq_cl_pool_add_text(lsq_cl_pool *p, const char *path);
+/* Host-only, the sort threaded: a sort of the pooled rows, then a union-find over the kept rows.  The pool may be solved again,
+ * under other thresholds or with more samples.  max_intron < 2^31. */
+int lsq_cl_host(const lsq_cl_pool *p, uint64_t min_reads, uint32_t max_intron, uint64_t min_cluster_reads, int n_threads, lsq_cl_table **out);
+/* Device (HIP, gfx950): the pooled rows uploaded as two-word records and sorted (the library's radix sort), equal keys reduced to
+ * the distinct introns and the count matrix, the row filters and the compaction of the kept rows, the links to a kept row's
+ * predecessor by start and by end, connected components by hooking onto the smaller label with pointer jumping -- a round is two
+ * launches, the host reads one word a round, no workgroup waits for another --, and per component its size, its reads and its
+ * sums per sample.  Statuses, numbering and texts are made on the host as for lsq_cl_host; both give the same table.  The
+ * context needs no events, and its events, reads and counters are as they were afterwards. */
+int lsq_cl_device(lsq_ctx *c, const lsq_cl_pool *p, uint64_t min_reads, uint32_t max_intron, uint64_t min_cluster_reads, lsq_cl_table **out);
+void lsq_cl_table_free(lsq_cl_table *t);
+int64_t lsq_cl_table_rows(const lsq_cl_table *t);             /* distinct introns */
+int64_t lsq_cl_table_samples(const lsq_cl_table *t);
+const char *lsq_cl_table_chrom_name(const lsq_cl_table *t, int64_t chrom);      /* NULL when out of range */
+/* The rounds of the components loop of the lsq_cl_device call that made the table, the last one -- which changes nothing --
+ * included; it grows with the logarithm of the longest chain of links.  0 from the host path, and where no row is kept. */
+int64_t lsq_cl_table_rounds(const lsq_cl_table *t);
+/* The rows' arrays (they live as long as the table; any pointer may be null): chrom indexes lsq_cl_table_chrom_name. */
+int lsq_cl_table_arrays(const lsq_cl_table *t, const uint32_t **chrom, const int32_t **start, const int32_t **end, const uint8_t **ann, const uint64_t **reads,
+                        const uint32_t **samples, const uint32_t **cluster, const uint8_t **status);
+int lsq_cl_table_counts(const lsq_cl_table *t, const uint32_t **counts);      /* [rows][samples] */
+int lsq_cl_table_report(const lsq_cl_table *t, uint64_t report[11]);
+/* Device milliseconds per phase of the lsq_cl_device call that made the table -- upload, sort, reduce, filter, links, components,
+ * totals, copy-back -- from HIP events on the library's stream (zeros from the host path). */
+int lsq_cl_table_times(const lsq_cl_table *t, float ms[8]);
+/* The two texts; malloc'd, NUL-terminated (lsq_free).  LSQ_E_ARG for a sample out of range. */
+int lsq_cl_format(const lsq_cl_table *t, char **out_text);
+int lsq_cl_format_sample(const lsq_cl_table *t, int64_t sample, char **out_text);
 
 /* ------------------------------------------------------------------------------------
  * Per-base read depth of a read file: what `bedtools genomecov -bg -split` prints, and the depth of every

@@ -1,7 +1,7 @@
 """lesseq_amd -- MI355X-native count + solve path of LESSeq.
 
 The product is the C-ABI library `liblesseq_hip.so` (include/lesseq_hip.h: host logic in C++,
-hand-written HIP kernels for gfx950) and the `count` / `solve` / `classify` / `test_as` / `events` / `parseGencode` / `gencodeIsoformMap` / `sam2mrf` / `bam2mrf` / `bamcheck` / `junctions` / `coverage` / `exonbins` / `psi` / `evidence` / `sites` / `retention` / `libtype` executables built
+hand-written HIP kernels for gfx950) and the `count` / `solve` / `classify` / `test_as` / `events` / `parseGencode` / `gencodeIsoformMap` / `sam2mrf` / `bam2mrf` / `bamcheck` / `junctions` / `coverage` / `exonbins` / `psi` / `evidence` / `sites` / `retention` / `clusters` / `libtype` executables built
 from it.  This package is only the ctypes binding used by the tests and bench.py; it holds
 no compute of its own and refuses to import without the built library.
 """
@@ -29,7 +29,9 @@ from . import sites  # noqa: F401
 from .sites import SiteIndex, Sites  # noqa: F401
 from . import retention  # noqa: F401
 from .retention import RetentionIndex, Retention  # noqa: F401
+from . import clusters  # noqa: F401
+from .clusters import ClusterPool, Clusters  # noqa: F401
 
 __all__ = ["lib", "LsqError", "check", "Annotation", "Events", "Reads", "Context", "SynthSpec",
            "cli_run", "synth_write", "synth_write_sam", "sam_to_mrf", "bam_to_mrf", "bam_check_host", "SAM_DEFAULT_SKIP_FLAGS", "format_count", "format_solve", "EVENT_TYPES",
-           "fisher", "lrt", "wilcox", "adjust", "betabin", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex", "exonbins", "ExonBinIndex", "ExonBins", "libtype", "LibTypeIndex", "LibType", "psi", "PsiIndex", "Psi", "evidence", "EvidenceIndex", "Evidence", "sites", "SiteIndex", "Sites", "retention", "RetentionIndex", "Retention", "bootstrap_resample_host", "bootstrap_draws"]
+           "fisher", "lrt", "wilcox", "adjust", "betabin", "localevents", "gencode", "parse_gtf", "isoform_map", "junctions", "JunctionIndex", "coverage", "CoverageIndex", "exonbins", "ExonBinIndex", "ExonBins", "libtype", "LibTypeIndex", "LibType", "psi", "PsiIndex", "Psi", "evidence", "EvidenceIndex", "Evidence", "sites", "SiteIndex", "Sites", "retention", "RetentionIndex", "Retention", "clusters", "ClusterPool", "Clusters", "bootstrap_resample_host", "bootstrap_draws"]

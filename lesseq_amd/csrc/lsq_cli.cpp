@@ -17,6 +17,7 @@
 #include "lsq_evidence.hpp"
 #include "lsq_sites.hpp"
 #include "lsq_retention.hpp"
+#include "lsq_clusters.hpp"
 
 using namespace lsq;
 
@@ -173,7 +174,7 @@ int run_bamcheck(int argc, const char *const *argv, std::string &out) {
 // name is a substring of the program's, else the last one, count.
 typedef int (*ToolFn)(int argc, const char *const *argv, std::string &out);
 const struct Tool { const char *name; ToolFn run; } TOOLS[] = {
-	{"libtype", run_libtype}, {"retention", run_retention}, {"sites", run_sites}, {"evidence", run_evidence}, {"psi", run_psi},
+	{"libtype", run_libtype}, {"clusters", run_clusters}, {"retention", run_retention}, {"sites", run_sites}, {"evidence", run_evidence}, {"psi", run_psi},
 	{"exonbins", run_exonbins}, {"coverage", run_coverage}, {"junctions", run_junctions},
 	{"sam2mrf", [](int n, const char *const *v, std::string &o) { return run_sam2mrf(false, n, v, o); }},
 	{"bam2mrf", [](int n, const char *const *v, std::string &o) { return run_sam2mrf(true, n, v, o); }},

@@ -1,6 +1,6 @@
 // What the tools that take an annotation and a read file share on the host (lsq_readtool.hpp): the dictionaries of an index, a
 // read file through its host parser, a line's exon union and introns, the cells of an interval lookup, the tables' row order,
-// and the frame of the junctions, coverage, exonbins, psi, evidence, sites and retention executables -- arguments, owned handles, the log on failure, the output file.
+// and the frame of the junctions, coverage, exonbins, psi, evidence, sites, retention and clusters executables -- arguments, owned handles, the log on failure, the output file.
 #include <cerrno>
 #include <cstdlib>
 #include <numeric>
